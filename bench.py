@@ -6,8 +6,15 @@ forward (train mode, dropout 0.1) -> BCEWithLogits - 0.01*beta-reg -> backward -
 over RCCL.  N=1 workload = BASELINE.json configs[1]: d=768, T_a=400, T_t=128, N_e=6, batch 64, bf16.
 For N>1 launch with torch.distributed.run (one rank per GPU); per-GPU batch stays 64 (weak scaling).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the launch stream inside
-libhriemo.so) and, at N=1, `cpu_baseline` (the CPU oracle timed on this box's host cores, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports them (`value`,
+`ms_per_step`); the secondary measurements need runs of their own and come with --full only: ragged / packed masks,
+optimizer, host -> device hand-over, cross-attention cores, `roofline` (dominant kernel, HIP-event timed on the launch
+stream inside libhriemo.so) and, at N=1, `cpu_baseline` (the CPU oracle timed on this box's host cores, bounded sample).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as .npy files
+(float32): `loss.npy` (shape (1,)) and `grads.npy`, a fixed seeded sample of every parameter's gradient (the gradients
+concatenated in `named_parameters()` order, GRAD_SAMPLE positions drawn uniformly with generator seed 0, sorted).
+The inputs, weights and dropout seeds are fixed, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes
@@ -42,6 +49,7 @@ FLOP_PER_UTT_FWD_BWD = 65.378e9           # SURVEY.md 8(d), closed form == FlopC
 PEAK_BF16_TFLOPS = 2500.0                 # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0                  # dense MX-fp8 (scaled MFMA 16x16x128)
 PEAK_HBM_GBS = 8000.0
+GRAD_SAMPLE = 1 << 22                     # --dump-outputs: gradient entries kept (16 MB of float32; cfg 2 has 54.6 M)
 
 
 def log(msg):
@@ -63,7 +71,32 @@ def parse():
     ap.add_argument("--dropout", type=float, default=0.1, help="dropout probability of the benchmark model (0.1 = the reference default)")
     ap.add_argument("--captured-exchange", action="store_true",
                     help="N>1: also probe the replay whose graph holds the gradient exchange (capture(collectives=True)) as a third mode")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: ragged / packed masks, optimizer, host -> device "
+                         "copy, cross-attention cores, per-kernel-class roofline (--no-roofline drops these) and the CPU baseline "
+                         "(--no-cpu-baseline drops it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and a seeded sample of the gradients of the last timed step to DIR/*.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(out_dir, loss, model):
+    """what the last timed step handed its caller: the loss it returned and the parameters' gradients (sampled, see the module
+    docstring).  Called right after the timed region, before anything else runs a step."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    grads = [p.grad.reshape(-1) for p in model.parameters() if p.requires_grad]
+    n = sum(g.numel() for g in grads)
+    flat = torch.cat(grads).float()
+    if n > GRAD_SAMPLE:
+        idx = torch.randint(0, n, (GRAD_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "grads.npy"), flat.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: loss.npy, grads.npy ({flat.numel()} of {n} gradient entries)")
 
 
 def synth(B, rank, device):
@@ -270,7 +303,7 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for k in range(a.steps):
-        dp.step(*batch)
+        loss = dp.step(*batch)
         evs[k + 1].record()
     host_ms = (time.perf_counter() - t0) / a.steps * 1e3       # time to ENQUEUE a step (diagnostic)
     sync()
@@ -285,12 +318,14 @@ def main():
     ms = dt / a.steps * 1e3
     value = B * world / (ms * 1e-3)
     log(f"{ms:.3f} ms/step -> {value:.1f} utt/s (host enqueue {host_ms:.3f} ms/step)")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
 
     # secondary number: the same step with ragged key-padding masks, valid length ~U[0.5 L, L] per sample and
     # modality.  PAD keys are masked, PAD query rows are still computed (as in the reference), so the first number mainly shows
     # that masks cost nothing; the second is the packed (varlen) encoder, which computes the valid rows only.
     ragged = None
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if a.full and rank == 0 and world == 1 and not a.no_roofline:
         g = torch.Generator().manual_seed(4321)
         la = torch.randint(T_A // 2, T_A + 1, (B,), generator=g)
         lt = torch.randint(T_T // 2, T_T + 1, (B,), generator=g)
@@ -353,7 +388,7 @@ def main():
     # flat fp32 parameter buffer with the gradients of the last step (train_fusion_seq_level_decoder.py:332-334).
     # Never in `value`.
     opt_ms = None
-    if rank == 0:
+    if a.full and rank == 0:
         snap = opt.flat_p.clone()
         for i in range(6):
             if i == 1:
@@ -369,7 +404,7 @@ def main():
     # host -> device hand-over of one batch (features + masks + labels from pinned host memory), timed separately: `value` is
     # quoted with the inputs resident in HBM; this is the PCIe-inclusive rate DESIGN.md notes (copy not overlapped with compute)
     h2d = None
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         host = [t.cpu().pin_memory() for t in batch]
         dst = [torch.empty_like(t) for t in batch]
         for i in range(6):
@@ -410,7 +445,7 @@ def main():
     # algorithmic FLOPs (fwd 4*B*H*Lq*Lk*hd, bwd 2x) over the kernels' own time, against the dense bf16 MFMA peak and
     # against the attention roofline min(MFMA peak, AI * HBM) with AI = Lq*Lk/(Lq+Lk) flop/B
     xattn = None
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         from hri_emo_amd import _ops
         Hh, hd = CFG["n_heads"], CFG["d_model"] // CFG["n_heads"]
         pd = CFG["dropout"]
@@ -454,7 +489,7 @@ def main():
             f"{100 * xattn['frac_of_attention_roofline']:.1f} % of the attention roofline")
 
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         L = _lib.lib()
         from hri_emo_amd import _ops
         two = _ops.side_stream(device) is not None
@@ -520,7 +555,7 @@ def main():
                "model_mfma_frac": round(value * FLOP_PER_UTT_FWD_BWD / 1e12 / world / PEAK_BF16_TFLOPS, 4)}
         if roof is not None:
             out["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

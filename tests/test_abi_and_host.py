@@ -275,6 +275,25 @@ def test_bench_becomes_its_own_launcher_for_several_gpus(monkeypatch):
     assert os.path.basename(cmd[-7]) == "bench.py" and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    """bench.py: the secondary measurements are behind --full (off by default), --dump-outputs takes a directory, and a run
+    that would time no step is refused before anything touches the GPU."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_step_context_is_per_step_and_restored():
     """_ops.StepContext: the capture flag / capture stream / packed plan / join scope / half-gradient bookkeeping of a step in
     flight live in the context its DataParallelStep owns, installed by use_context and restored on the way out (re-entrant), so

@@ -1009,7 +1009,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HRIEMO_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "8"]
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "8", "--full"]
     r = subprocess.run(cmd, env=env, cwd=repo, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1017,6 +1017,34 @@ def test_bench_two_rank_control_flow_rehearsal():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 16 and d["config"]["launch"] == "eager" and d["value"] > 0
     assert "roofline" in d and d["roofline"]["frac"] > 0 and d["cross_attention"] is not None
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, carries none of the secondary legs, and with
+    --dump-outputs writes the last timed step's loss and gradient sample as float32 .npy files that a second run with the
+    same arguments reproduces (fixed inputs, weights and dropout seeds)."""
+    import json, subprocess, sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-per-gpu", "8",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "utterances/s"
+        assert "roofline" not in d and "cpu_baseline" not in d and d["cross_attention"] is None and d["ragged_masks"] is None
+        loss, grads = np.load(out / "loss.npy"), np.load(out / "grads.npy")
+        assert loss.dtype == np.float32 and loss.shape == (1,) and np.isfinite(loss).all()
+        assert grads.dtype == np.float32 and grads.ndim == 1 and 0 < grads.size <= 1 << 22 and np.isfinite(grads).all()
+        assert np.abs(grads).max() > 0
+        got.append((loss, grads))
+    np.testing.assert_allclose(got[1][0], got[0][0], rtol=1e-5)
+    np.testing.assert_allclose(got[1][1], got[0][1], rtol=1e-4, atol=1e-6 * float(np.abs(got[0][1]).max()))
 
 
 def _nccl_worker(rank, world, port, q):
