@@ -14,6 +14,10 @@ the fp32 kernels drop where the bf16 ones do -- attention weights, sub-layer out
 hidden layer -- from the same counter hash with the same (seed, site, offset) keys, so a model draws the same masks in either
 precision; the backward replays them, nothing is stored.
 
+Packed (varlen) sequences: the sub-layers take the Seq of _ops.pack_pair in the kpm slot, as the bf16 Functions do -- attention on
+cu_seqlens (hriemo_attn_*_f32_varlen), LayerNorm on the gathered rows with the dropout keyed by the padded row (*_f32_rows), every
+Linear on the N packed rows (the bucket's surplus rows carry zero gradients, so the weight-gradient GEMMs need no PAD mask).
+
 Reference arithmetic: models/cross_modal_block_tacfn.py:70-125, models/beta_gate_tacfn.py:68-118, models/emotion_decoder.py:30-64,
 116-162 (all fp32 nn.Modules)."""
 import torch
@@ -67,16 +71,16 @@ def _ws(nbytes, dev):
 
 
 # ----------------------------------------------------------------------------- operand splits and the three GEMMs of a Linear
-def split(x32, form, relu=False, mask=None):
+def split(x32, form, relu=False, mask=None, out=None):
     """x32 [M,K] fp32 (row stride free) -> bf16 split operand, form 0 / 1: [M,3K] = [hi|mid|hi] / [hi|hi|mid] (contraction along
     the columns), form 2 / 3: [3M,K] = [hi;mid;hi] / [hi;hi;mid] (contraction along the rows); forms 4 / 5 and 6 / 7: the same with
     the exact three-way split x = hi + mid + lo and six blocks ([hi|mid|lo|hi|mid|hi] / [hi|hi|hi|mid|mid|lo]: what this module
-    uses); relu: max(x, 0) first; mask (fp32 [M,K]): x * (mask > 0) first"""
+    uses); relu: max(x, 0) first; mask (fp32 [M,K]): x * (mask > 0) first; out: a bf16 tensor of that shape to write into"""
     M, K = x32.shape
     if K % 8:
         raise ValueError(f"fp32 mode: width {K} must be a multiple of 8")
     shape = {0: (M, 3 * K), 1: (M, 3 * K), 2: (3 * M, K), 3: (3 * M, K), 4: (M, 6 * K), 5: (M, 6 * K), 6: (6 * M, K), 7: (6 * M, K)}[form]
-    y = _new(shape, x32, BF16)
+    y = out if out is not None and tuple(out.shape) == shape else _new(shape, x32, BF16)
     _lib.call("hriemo_split3_f32", _ops._p(x32), x32.stride(0), M, K, _ops._p(y), form, int(relu), _ops._p(mask),
               mask.stride(0) if mask is not None else 0, _ops._stream())
     return y
@@ -93,7 +97,8 @@ def _weight_split(sh, w, form, rows=None, kp=None):
     key = ("x3", id(w), form, rows, kp)
     ent = sh._d.get(key)
     ver = (w._version, w.data_ptr(), _ops.WEIGHTS_EPOCH)
-    if ent is None or ent[0] != ver or ent[1].device != w.device:
+    # inside a capture every step splits again (a replay must honour optimizer updates, as Shadows.get re-casts), once per step
+    if (_ops.CTX.capturing and (ent is None or ent[2] != _ops.STEP_ID)) or ent is None or ent[0] != ver or ent[1].device != w.device:
         _ops._require_gpu(w)
         _ops._require_fp32_master(w)
         src = _c(w.detach())
@@ -103,7 +108,8 @@ def _weight_split(sh, w, form, rows=None, kp=None):
             pad = torch.zeros((src.shape[0], kp), dtype=F32, device=src.device)
             pad[:, :src.shape[1]].copy_(src)
             src = pad
-        ent = (ver, split(src, form))
+        out = ent[1] if ent is not None and ent[1].device == w.device else None
+        ent = (ver, split(src, form, out=out), _ops.STEP_ID)
         sh._d[key] = ent
     return ent[1]
 
@@ -159,10 +165,16 @@ def colsum(x32, mask=None):
 
 
 # ----------------------------------------------------------------------------- attention cores, LayerNorm
-def attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=False, drop=None):
-    """drop = (p, seed, site, b_offset): dropout on the attention weights (the keys of _ops.attn_fwd)"""
-    o = _new((B * Lq, H * hd), q)
-    lse = _new((B, H, Lq), q) if want_lse else None
+def attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=False, drop=None, cu=None):
+    """drop = (p, seed, site, b_offset): dropout on the attention weights (the keys of _ops.attn_fwd).
+    cu = (cu_seqlens_q, cu_seqlens_k): q / k / v hold packed rows, Lq / Lk are the longest sequences, kpm is None (the masks the
+    packed launch draws are those of the padded one: a mask log stays with the padded path)"""
+    o = _new((q.shape[0], H * hd), q)
+    lse = _new((B, H, Lq), q) if (want_lse or cu is not None) else None
+    if cu is not None:
+        _lib.call("hriemo_attn_fwd_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(v), v.stride(0), _ops._p(o),
+                  H * hd, _ops._p(cu[0]), _ops._p(cu[1]), _ops._p(lse), B, H, Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
+        return o, lse
     if _on(drop) and _ops.DROP_LOG is not None:
         _ops.DROP_LOG.append(("attn", drop[1], drop[2], B, H, Lq, Lk, float(drop[0]), drop[3]))
     _lib.call("hriemo_attn_fwd_f32", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(v), v.stride(0), _ops._p(o), H * hd,
@@ -170,8 +182,14 @@ def attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=False, drop=None):
     return o, lse
 
 
-def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None):
+def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None, cu=None):
     delta = _new((B, H, Lq), q)
+    if cu is not None:
+        _lib.call("hriemo_attn_bwd_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(v), v.stride(0), _ops._p(o),
+                  o.stride(0), _ops._p(do), do.stride(0), _ops._p(cu[0]), _ops._p(cu[1]), _ops._p(lse), _ops._p(dq), dq.stride(0),
+                  _ops._p(dk), dk.stride(0), _ops._p(dv), dv.stride(0), _ops._p(delta), B, H, Lq, Lk, hd, *_drop_args(drop, q.device),
+                  _ops._stream())
+        return
     _lib.call("hriemo_attn_bwd_f32", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(v), v.stride(0), _ops._p(o), o.stride(0),
               _ops._p(do), do.stride(0), _ops._p(kpm), _ops._p(lse), _ops._p(dq), dq.stride(0), _ops._p(dk), dk.stride(0), _ops._p(dv),
               dv.stride(0), _ops._p(delta), B, H, Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
@@ -184,12 +202,16 @@ def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None):
     return p
 
 
-def add_ln(g32, x32, gamma, beta, want16=True, drop=None):
+def add_ln(g32, x32, gamma, beta, want16=True, drop=None, rows=None):
     """LayerNorm(x32 + drop(g32)) (x32 may be None) -> (bf16 copy | None, fp32); drop = (p, seed, site, row_offset) as
-    _ops.add_ln_fwd"""
+    _ops.add_ln_fwd; rows: int64 [M] padded row of every (packed) row, keys the dropout hash (Seq.idx)"""
     M, d = g32.shape
     y32 = _new((M, d), g32)
     y16 = _new((M, d), g32, BF16) if want16 else None
+    if rows is not None:
+        _lib.call("hriemo_add_ln_f32_rows", _ops._p(g32), _ops._p(x32), _ops._p(gamma.detach()), _ops._p(beta.detach()), _ops._p(y32),
+                  _ops._p(y16), M, d, _ops._EPS, *_drop_args(drop, g32.device), _ops._p(rows), _ops._stream())
+        return y16, y32
     if _on(drop) and _ops.DROP_LOG is not None:
         _ops.DROP_LOG.append(("rows", drop[1], drop[2], M, d, float(drop[0]), drop[3]))
     _lib.call("hriemo_add_ln_f32", _ops._p(g32), _ops._p(x32), _ops._p(gamma.detach()), _ops._p(beta.detach()), _ops._p(y32),
@@ -197,17 +219,20 @@ def add_ln(g32, x32, gamma, beta, want16=True, drop=None):
     return y16, y32
 
 
-def add_ln_bwd(dy32, g32, x32, gamma, want_dbias=True, drop=None):
+def add_ln_bwd(dy32, g32, x32, gamma, want_dbias=True, drop=None, rows=None):
     """backward of LayerNorm(x32 + drop(g32)): -> (dS [M,d] = gradient of the sum = dX, dG = gradient of g32 (dS itself without
-    dropout), dgamma, dbeta, dbias = colsum(dG) | None)"""
+    dropout), dgamma, dbeta, dbias = colsum(dG) | None); rows as add_ln"""
     M, d = g32.shape
     ds = _new((M, d), g32)
     dg = _new((M, d), g32) if _on(drop) else None
     stats = _new((3, d), g32)
     ws = _ws(_lib.lib().hriemo_add_ln_bwd_f32_workspace_bytes(M, d), g32.device)
-    _lib.call("hriemo_add_ln_bwd_f32", _ops._p(dy32), _ops._p(g32), _ops._p(x32), _ops._p(gamma.detach()), _ops._p(ds), _ops._p(dg),
-              _ops._p(stats[0]), _ops._p(stats[1]), _ops._p(stats[2]) if want_dbias else None, 0, M, d, _ops._EPS,
-              *_drop_args(drop, g32.device), _ops._p(ws), _ops._stream())
+    args = (_ops._p(dy32), _ops._p(g32), _ops._p(x32), _ops._p(gamma.detach()), _ops._p(ds), _ops._p(dg), _ops._p(stats[0]),
+            _ops._p(stats[1]), _ops._p(stats[2]) if want_dbias else None, 0, M, d, _ops._EPS, *_drop_args(drop, g32.device), _ops._p(ws))
+    if rows is not None:
+        _lib.call("hriemo_add_ln_bwd_f32_rows", *args, _ops._p(rows), _ops._stream())
+    else:
+        _lib.call("hriemo_add_ln_bwd_f32", *args, _ops._stream())
     return ds, (dg if dg is not None else ds), stats[0], stats[1], (stats[2] if want_dbias else None)
 
 
@@ -258,25 +283,42 @@ def _drops(p, seed, site, b_off, rows_per_sample):
     return (p, seed, site, b_off), (p, seed, site + 1, b_off * rows_per_sample)
 
 
+def _packing(kpm, B, Lq, Lk, need_w):
+    """the kpm slot -> (kpm | None, attention batch, Lq, Lk, cu | None, rows per padded sample, LayerNorm row index | None).
+    Packed sequences (x is [1, N_valid, d]) carry a Seq there (self-attention) or (Seq of the queries, Seq of the keys)
+    (cross-attention), as in _ops.SelfAttnLN / CrossAttnLN: the attention sees Seq.B samples of up to Seq.Lmax rows, the
+    LayerNorm dropout is keyed by the rows of the padded layout"""
+    if isinstance(kpm, _ops.Seq):
+        kpm = (kpm, kpm)
+    if not isinstance(kpm, tuple):
+        return kpm, B, Lq, Lk, None, Lq, None
+    if need_w:
+        raise ValueError("attention maps are exported by the padded path only")
+    sq, sk = kpm
+    return None, sq.B, sq.Lmax, sk.Lmax, (sq.cu, sk.cu), sq.L, sq.idx
+
+
 def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, need_w, p=0.0, seed=0, site=0, b_off=0):
     _ops._require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
     _ops._require_gpu(x)
     B, L, d = x.shape
     hd = _ops._heads(d, H)
     rec = recording(ctx)
-    d_attn, d_res = _drops(p, seed, site, b_off, L)
+    kpm, AB, AL, _, cu, RL, rows = _packing(kpm, B, L, L, need_w)
+    d_attn, d_res = _drops(p, seed, site, b_off, RL)
     xf = _twin(x, x32).view(B * L, d)
     qkv = linear(xf, sh, w_in, b_in)
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    o, lse = attn(q, k, v, B, H, L, L, hd, kpm, want_lse=need_w or rec, drop=d_attn)
+    o, lse = attn(q, k, v, AB, H, AL, AL, hd, kpm, want_lse=need_w or rec, drop=d_attn, cu=cu)
     g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res)
+    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=rows)
     pr = probs(q, k, B, H, L, L, hd, kpm, lse, drop=d_attn) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, qkv, o, lse, g, kpm)
         ctx.f32_cfg = (B, L, d, H, hd)
+        ctx.f32_packed = (AB, AL, AL, cu, rows)
         ctx.f32_drop = (d_attn, d_res)
         ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
@@ -288,16 +330,17 @@ def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm,
 def self_attn_ln_bwd(ctx, dy, dy32):
     xf, qkv, o, lse, g, kpm = ctx.saved_tensors
     B, L, d, H, hd = ctx.f32_cfg
+    AB, ALq, ALk, cu, rows = ctx.f32_packed
     w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
     M = B * L
     d_attn, d_res = ctx.f32_drop
     dyt = _total(dy, dy32, (M, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xf, gamma, drop=d_res)
+    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=rows)
     dw_out = linear_dw(dg, o)
     do = linear_dx(dg, sh, w_out)
     dqkv = _new((M, 3 * d), xf)
-    attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, H, L, L, hd, kpm,
-             drop=d_attn)
+    attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], AB, H, ALq, ALk, hd,
+             kpm, drop=d_attn, cu=cu)
     dw_in = linear_dw(dqkv, xf)
     db_in = colsum(dqkv)
     dx = linear_dx(dqkv, sh, w_in, into=ds)            # + the residual path's gradient
@@ -312,21 +355,23 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
     Lk = xkv.shape[1]
     hd = _ops._heads(d, H)
     rec = recording(ctx)
-    d_attn, d_res = _drops(p, seed, site, b_off, Lq)
+    kpm, AB, ALq, ALk, cu, RL, rows = _packing(kpm, B, Lq, Lk, need_w)
+    d_attn, d_res = _drops(p, seed, site, b_off, RL)
     xqf = _twin(xq, xq32).view(B * Lq, d)
     xkvf = _c(f32_of(xkv)).view(B * Lk, d)
     q = linear(xqf, sh, w_in, b_in, rows=(0, d))
     kv = linear(xkvf, sh, w_in, b_in, rows=(d, 3 * d))
     k, v = kv[:, :d], kv[:, d:]
-    o, lse = attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=need_w or rec, drop=d_attn)
+    o, lse = attn(q, k, v, AB, H, ALq, ALk, hd, kpm, want_lse=need_w or rec, drop=d_attn, cu=cu)
     g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res)
+    y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res, rows=rows)
     pr = probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=d_attn) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xqf, xkvf, q, kv, o, lse, g, kpm)
         ctx.f32_cfg = (B, Lq, Lk, d, H, hd)
+        ctx.f32_packed = (AB, ALq, ALk, cu, rows)
         ctx.f32_drop = (d_attn, d_res)
         ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype, ctx.f32_kv_dtype = xq32 is not None, xq.dtype, xkv.dtype
@@ -338,15 +383,16 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
 def cross_attn_ln_bwd(ctx, dy, dy32):
     xqf, xkvf, q, kv, o, lse, g, kpm = ctx.saved_tensors
     B, Lq, Lk, d, H, hd = ctx.f32_cfg
+    AB, ALq, ALk, cu, rows = ctx.f32_packed
     w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
     d_attn, d_res = ctx.f32_drop
     dyt = _total(dy, dy32, (B * Lq, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xqf, gamma, drop=d_res)
+    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xqf, gamma, drop=d_res, rows=rows)
     dw_out = linear_dw(dg, o)
     do = linear_dx(dg, sh, w_out)
     dq = _new((B * Lq, d), xqf)
     dkv = _new((B * Lk, 2 * d), xqf)
-    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], B, H, Lq, Lk, hd, kpm, drop=d_attn)
+    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], AB, H, ALq, ALk, hd, kpm, drop=d_attn, cu=cu)
     dw_in = _new((3 * d, d), xqf)
     dw_in[:d].copy_(linear_dw(dq, xqf))
     dw_in[d:].copy_(linear_dw(dkv, xkvf))
@@ -359,12 +405,18 @@ def cross_attn_ln_bwd(ctx, dy, dy32):
     return (gx[0], gx[1], dxkv, dw_in, db_in, dw_out, db_out, dgamma, dbeta) + (None,) * 12
 
 
-def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p=0.0, p_mid=0.0, seed=0, site=0, b_off=0):
+def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p=0.0, p_mid=0.0, seed=0, site=0, b_off=0, seq=None):
+    """seq: the Seq of packed rows (x is [1, N_valid, d]): the LayerNorm dropout is keyed by the rows of the padded layout"""
     _ops._require_fp32_masters(w1, b1, w2, b2, gamma, beta)
     _ops._require_gpu(x)
     shape = x.shape
     d = shape[-1]
     L = shape[1] if len(shape) == 3 else 1
+    rows = None
+    if seq is not None:
+        if p_mid > 0:
+            raise ValueError("FFNLN: packed rows with a mid-FFN dropout are not built (the encoder's FFNs have none)")
+        L, rows = seq.L, seq.idx
     d_res = (p, seed, site + 1, b_off * L) if p > 0 else None
     d_mid = (p_mid, seed, site + 2, b_off * L) if p_mid > 0 else None        # keys of _ops.FFNLN.forward
     xf = _twin(x, x32).view(-1, d)
@@ -373,12 +425,13 @@ def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p=0.0, p_mid=0.0, seed=
         g = linear(dropout(h, d_mid, relu=True), sh, w2, b2)
     else:
         g = linear(h, sh, w2, b2, relu_in=True)      # ReLU applied while the hidden activations are split
-    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res)
+    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=rows)
     ctx.fp32 = True
     if recording(ctx):
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, h, g)
         ctx.f32_cfg = tuple(shape)
+        ctx.f32_rows = rows
         ctx.f32_drop = (d_res, d_mid)
         ctx.f32_params = (w1, b1, w2, b2, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
@@ -392,7 +445,7 @@ def ffn_ln_bwd(ctx, dy, dy32):
     M, d = xf.shape
     d_res, d_mid = ctx.f32_drop
     dyt = _total(dy, dy32, (M, d))
-    ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dyt, g, xf, gamma, drop=d_res)
+    ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=ctx.f32_rows)
     if d_mid is not None:                             # g = drop(relu(h)) . W2^T + b2: the dropped activations are rebuilt, not stored
         dw2 = linear_dw(dg, dropout(h, d_mid, relu=True, log=False))
         da = dropout(linear_dx(dg, sh, w2), d_mid, gate=h, log=False)     # * keep / (1 - p) * relu'(h)

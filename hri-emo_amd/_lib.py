@@ -54,6 +54,10 @@ _SIGS = {
     "hriemo_gate_input_bwd_f32": ("pppppiip", "i"),
     "hriemo_gate_dy_f32": ("ppipppiiiip", "i"),
     "hriemo_rowdot_bwd_f32": ("ppppppiiip", "i"),
+    "hriemo_attn_fwd_f32_varlen": ("plplplplpppiiiiifQpIip", "i"),
+    "hriemo_attn_bwd_f32_varlen": ("plplplplplpppplplplpiiiiifQpIip", "i"),
+    "hriemo_add_ln_f32_rows": ("ppppppiiffQpIlpp", "i"),
+    "hriemo_add_ln_bwd_f32_rows": ("pppppppppiiiffQpIlppp", "i"),
     "hriemo_attn_probs": ("plplpppiiiiifQpIip", "i"),
     "hriemo_add_ln_fwd": ("pppppppppiiffQpIlp", "i"),
     "hriemo_add_ln_fwd_mx8": ("pppppppppiiffQpIlpplp", "i"),

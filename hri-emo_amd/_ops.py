@@ -1800,7 +1800,7 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
     def forward(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq=None):
         """seq: the Seq of packed rows (x is [1, N_valid, d]): keys the LayerNorm dropout by the rows of the padded layout"""
         if precision() == "fp32":
-            return _fp32().ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off)
+            return _fp32().ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq)
         _require_fp32_masters(w1, b1, w2, b2, gamma, beta)
         ctx.set_materialize_grads(False)      # an unused twin output must arrive as None, not as zeros
         _require_gpu(x)

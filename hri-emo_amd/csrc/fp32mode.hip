@@ -129,16 +129,18 @@ extern "C" int hriemo_dropout_f32(const float* X, float* Y, long M, int N, int r
 }
 
 // ------------------------------------------------------------------------------------------- LayerNorm(x + drop(g)), fp32 in and out
-// one wave per row, the row in registers (d <= 64 * 4 * NV4)
-template <int NV4>
+// one wave per row, the row in registers (d <= 64 * 4 * NV4).  ROWS: the rows were gathered from a larger layout (packed varlen
+// sequences) and the dropout hash is keyed by rowmap[row] (the padded row, hriemo_pack_rows) instead of row.
+template <int NV4, bool ROWS>
 __global__ __launch_bounds__(256) void add_ln_f32_kernel(const float* __restrict__ G, const float* __restrict__ X, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ Y32, bf16_t* __restrict__ Y16, int M,
-                                                         int d, float eps, RowDrop dr) {
+                                                         int d, float eps, RowDrop dr, const long long* __restrict__ rowmap) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const int nq = d >> 2;
   const uint32_t dkey = dr.thr16 != 0 ? site_key(eff_seed(dr.seed, dr.seed_dev), dr.site, 0u) : 0u;
+  const uint32_t drow = (uint32_t)((ROWS ? (long)rowmap[row] : row) + dr.row_off);
   f32x4 s[NV4];
   float sum = 0.f;
 #pragma unroll
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256) void add_ln_f32_kernel(const float* __restrict
     s[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (q < nq) {
       s[c] = *(const f32x4*)(G + row * d + q * 4);
-      if (dr.thr16 != 0) s[c] = drop4(s[c], dkey, (uint32_t)(row + dr.row_off), (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
+      if (dr.thr16 != 0) s[c] = drop4(s[c], dkey, drow, (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
       if (X != nullptr) s[c] += *(const f32x4*)(X + row * d + q * 4);
       sum += s[c][0] + s[c][1] + s[c][2] + s[c][3];
     }
@@ -176,19 +178,34 @@ __global__ __launch_bounds__(256) void add_ln_f32_kernel(const float* __restrict
   }
 }
 
-extern "C" int hriemo_add_ln_f32(const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16, int M, int d,
-                                 float eps, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, long row_off,
-                                 hipStream_t st) {
-  HRIEMO_CHECK(M > 0 && d > 0 && d % 4 == 0 && d <= 4096, "add_ln_f32: d=%d must be a multiple of 4, at most 4096", d);
-  HRIEMO_CHECK(p >= 0.f && p < 1.f, "add_ln_f32: dropout p=%f", (double)p);
+template <bool ROWS>
+static int add_ln_f32_launch(const char* who, const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16,
+                             int M, int d, float eps, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
+                             long row_off, const long long* row_index, hipStream_t st) {
+  HRIEMO_CHECK(M > 0 && d > 0 && d % 4 == 0 && d <= 4096, "%s: d=%d must be a multiple of 4, at most 4096", who, d);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "%s: dropout p=%f", who, (double)p);
+  HRIEMO_CHECK(!ROWS || row_index != nullptr, "%s: row_index is required", who);
   const RowDrop dr = make_row_drop(p, seed, seed_dev, site, row_off);
   hriemo_prof_begin(HP_ROWOPS, st);
   const dim3 grid((M + 3) / 4);
-  if (d <= 1024) hipLaunchKernelGGL((add_ln_f32_kernel<4>), grid, dim3(256), 0, st, G, X, gamma, beta, Y32, (bf16_t*)Y16, M, d, eps, dr);
-  else hipLaunchKernelGGL((add_ln_f32_kernel<16>), grid, dim3(256), 0, st, G, X, gamma, beta, Y32, (bf16_t*)Y16, M, d, eps, dr);
+  if (d <= 1024) hipLaunchKernelGGL((add_ln_f32_kernel<4, ROWS>), grid, dim3(256), 0, st, G, X, gamma, beta, Y32, (bf16_t*)Y16, M, d, eps, dr, row_index);
+  else hipLaunchKernelGGL((add_ln_f32_kernel<16, ROWS>), grid, dim3(256), 0, st, G, X, gamma, beta, Y32, (bf16_t*)Y16, M, d, eps, dr, row_index);
   HRIEMO_LAUNCH_CHECK("add_ln_f32_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (double)M * d * 14.0);
   return 0;
+}
+
+extern "C" int hriemo_add_ln_f32(const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16, int M, int d,
+                                 float eps, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, long row_off,
+                                 hipStream_t st) {
+  return add_ln_f32_launch<false>("add_ln_f32", G, X, gamma, beta, Y32, Y16, M, d, eps, p, seed, seed_dev, site, row_off, nullptr, st);
+}
+
+// the same on gathered rows: the dropout hash is keyed by row_index[row] + row_off (hriemo_add_ln_fwd_rows' contract)
+extern "C" int hriemo_add_ln_f32_rows(const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16, int M,
+                                      int d, float eps, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
+                                      long row_off, const long long* row_index, hipStream_t st) {
+  return add_ln_f32_launch<true>("add_ln_f32_rows", G, X, gamma, beta, Y32, Y16, M, d, eps, p, seed, seed_dev, site, row_off, row_index, st);
 }
 
 // ------------------------------------------------------------------------------------------- gate pieces (beta_gate_tacfn.py)
@@ -284,11 +301,15 @@ extern "C" int hriemo_fuse_f32(const float* w, const float* A, int La, const flo
 //   O^T[dim][query] += sum_key V[key][dim] P^T[key][query] : A = V^T (LDS), B = P^T -- lane (i, g) holds P^T[16n + 4g + r][i] in
 //   accumulator register r of sub-tile n, so MFMA step (n, r) contracts over the keys {16n + 4g' + r : g' = 0..3} with both
 //   operands indexed by g: no transpose, no LDS round trip for P.
-template <int HD>
+// PACKED (hriemo_attn_*_f32_varlen): sample b owns rows cu_q[b] .. cu_q[b+1]-1 of Q / O (cu_k of K / V), Lq / Lk arrive as the
+// longest sequences and become this sample's lengths; lse keeps its padded [B, H, Lq max] slots; blocks past the sample's end exit.
+// Queries and keys are indexed within their sample, so the dropout hash sees the padded (batch, query, key) of the padded launch.
+template <int HD, bool PACKED>
 __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
                                                            const float* __restrict__ V, long ldv, float* __restrict__ O, long ldo,
                                                            const uint8_t* __restrict__ kpm, float* __restrict__ lse, int H, int Lq, int Lk,
-                                                           float scale, AttnDrop dr) {
+                                                           float scale, AttnDrop dr, const int* __restrict__ cu_q,
+                                                           const int* __restrict__ cu_k) {
   constexpr int LDR = HD + 4;                 // LDS row stride in floats
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Ks = (float*)smem_raw;               // [64][LDR]
@@ -296,9 +317,16 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   float* pad = Vs + 64 * LDR;                 // [64] additive mask of the key tile: 0 or -inf
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int LqS = Lq;                         // row stride of lse
+  long rq = (long)b * Lq, rk = (long)b * Lk;  // first row of sample b in Q / O and in K / V
+  if (PACKED) {
+    rq = cu_q[b]; rk = cu_k[b];
+    Lq = cu_q[b + 1] - (int)rq; Lk = cu_k[b + 1] - (int)rk;
+    if (blockIdx.x * 64 >= Lq) return;
+  }
   const int q0 = blockIdx.x * 64 + wave * 16;
   const int q = min(q0 + i, Lq - 1);
-  const float* qp = Q + ((long)b * Lq + q) * ldq + h * HD;
+  const float* qp = Q + (rq + q) * ldq + h * HD;
   float qf[HD / 4];
 #pragma unroll
   for (int ks = 0; ks < HD / 4; ++ks) qf[ks] = qp[4 * ks + g] * scale;
@@ -307,8 +335,8 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   for (int t = 0; t < HD / 16; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float mrun = -INFINITY, lrun = 0.f;          // running max (shared by the 4 lanes of a query) and THIS lane's partial sum
   const uint32_t dkey = dr.thr16 != 0 ? site_key(eff_seed(dr.seed, dr.seed_dev), dr.site, (uint32_t)((dr.b_offset + b) * H + h)) : 0u;
-  const float* Kb = K + (long)b * Lk * ldk + h * HD;
-  const float* Vb = V + (long)b * Lk * ldv + h * HD;
+  const float* Kb = K + rk * ldk + h * HD;
+  const float* Vb = V + rk * ldv + h * HD;
   for (int k0 = 0; k0 < Lk; k0 += 64) {
     __syncthreads();
     for (int e = tid; e < 64 * (HD / 4); e += 256) {
@@ -321,7 +349,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
     }
     if (tid < 64) {
       const int key = k0 + tid;
-      pad[tid] = (key < Lk && (kpm == nullptr || kpm[(long)b * Lk + key] == 0)) ? 0.f : -INFINITY;
+      pad[tid] = (key < Lk && (PACKED || kpm == nullptr || kpm[(long)b * Lk + key] == 0)) ? 0.f : -INFINITY;
     }
     __syncthreads();
     f32x4 s[4];
@@ -370,7 +398,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   // a query whose keys are all padding: PyTorch's softmax over -inf gives NaN, and so does this (0 * inf)
   const float inv = (dr.thr16 != 0 ? dr.inv_keep : 1.f) / l;
   if (q0 + i < Lq) {
-    float* op = O + ((long)b * Lq + q0 + i) * ldo + h * HD;
+    float* op = O + (rq + q0 + i) * ldo + h * HD;
 #pragma unroll
     for (int t = 0; t < HD / 16; ++t) {
       f32x4 v = o[t];
@@ -378,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
       if (l == 0.f) v = (f32x4){NAN, NAN, NAN, NAN};
       *(f32x4*)(op + 16 * t + 4 * g) = v;
     }
-    if (g == 0 && lse != nullptr) lse[((long)b * H + h) * Lq + q0 + i] = l == 0.f ? -INFINITY : mrun + logf(l);
+    if (g == 0 && lse != nullptr) lse[((long)b * H + h) * LqS + q0 + i] = l == 0.f ? -INFINITY : mrun + logf(l);
   }
 }
 
@@ -573,10 +601,12 @@ extern "C" int hriemo_colsum_f32(const float* X, long ldx, int M, int N, const f
 // ------------------------------------------------------------------------------------------- LayerNorm(x + g) backward, fp32
 // dS = d loss / d (x + drop(g)) (= dX; = dG too without dropout, else dG = dS * keep / (1 - p) goes to its own matrix); per-block column partials of dgamma = sum dY * xhat, dbeta = sum dY and
 // dbias = sum dG (the bias of the Linear that produced g).  The row statistics are recomputed (the row is in registers anyway).
-template <int NV4>
+// ROWS: dropout keyed by rowmap[row] (gathered rows), as add_ln_f32_kernel
+template <int NV4, bool ROWS>
 __global__ __launch_bounds__(256) void add_ln_bwd_f32_kernel(const float* __restrict__ dY, const float* __restrict__ G, const float* __restrict__ X,
                                                              const float* __restrict__ gamma, float* __restrict__ dS, float* __restrict__ dG,
-                                                             float* __restrict__ part, int M, int d, float eps, RowDrop dr) {
+                                                             float* __restrict__ part, int M, int d, float eps, RowDrop dr,
+                                                             const long long* __restrict__ rowmap) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = (float*)smem_raw;            // [3][d]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -589,13 +619,14 @@ __global__ __launch_bounds__(256) void add_ln_bwd_f32_kernel(const float* __rest
   for (long row = (long)blockIdx.x * 4 + wave; row < M; row += (long)gridDim.x * 4) {
     f32x4 s[NV4], dy[NV4];
     float sum = 0.f;
+    const uint32_t drow = (uint32_t)((ROWS ? (long)rowmap[row] : row) + dr.row_off);
 #pragma unroll
     for (int c = 0; c < NV4; ++c) {
       const int q = lane + 64 * c;
       s[c] = dy[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (q < nq) {
         s[c] = *(const f32x4*)(G + row * d + q * 4);
-        if (dr.thr16 != 0) s[c] = drop4(s[c], dkey, (uint32_t)(row + dr.row_off), (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
+        if (dr.thr16 != 0) s[c] = drop4(s[c], dkey, drow, (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
         if (X != nullptr) s[c] += *(const f32x4*)(X + row * d + q * 4);
         dy[c] = *(const f32x4*)(dY + row * d + q * 4);
         sum += (s[c][0] + s[c][1]) + (s[c][2] + s[c][3]);
@@ -640,7 +671,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_f32_kernel(const float* __rest
         for (int j = 0; j < 4; ++j) ds[j] = rstd * (dy[c][j] - c1 - s[c][j] * c2);
         *(f32x4*)(dS + row * d + q * 4) = ds;
         if (dr.thr16 != 0) {              // the dropped branch's gradient: dG = dS * (keep ? 1 / (1 - p) : 0); the bias sits inside g
-          const f32x4 f = drop4_factor(dkey, (uint32_t)(row + dr.row_off), (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
+          const f32x4 f = drop4_factor(dkey, drow, (uint32_t)(q * 4), dr.thr16, dr.inv_keep);
           ds *= f;
           *(f32x4*)(dG + row * d + q * 4) = ds;
         }
@@ -673,26 +704,44 @@ __global__ __launch_bounds__(256) void add_ln_bwd_f32_kernel(const float* __rest
 }
 static int add_ln_bwd_f32_blocks(int M) { int g = (M + 3) / 4; return g > 512 ? 512 : g; }
 extern "C" long hriemo_add_ln_bwd_f32_workspace_bytes(int M, int d) { return (long)add_ln_bwd_f32_blocks(M) * 3 * d * 4; }
-extern "C" int hriemo_add_ln_bwd_f32(const float* dY, const float* G, const float* X, const float* gamma, float* dS, float* dG, float* dgamma,
-                                     float* dbeta, float* dbias, int accumulate, int M, int d, float eps, float p, uint64_t seed,
-                                     const unsigned long long* seed_dev, uint32_t site, long row_off, float* workspace, hipStream_t st) {
-  HRIEMO_CHECK(M > 0 && d > 0 && d % 4 == 0 && d <= 1024, "add_ln_bwd_f32: d=%d must be a multiple of 4, at most 1024", d);
-  HRIEMO_CHECK(p >= 0.f && p < 1.f, "add_ln_bwd_f32: dropout p=%f", (double)p);
+template <bool ROWS>
+static int add_ln_bwd_f32_launch(const char* who, const float* dY, const float* G, const float* X, const float* gamma, float* dS, float* dG,
+                                 float* dgamma, float* dbeta, float* dbias, int accumulate, int M, int d, float eps, float p, uint64_t seed,
+                                 const unsigned long long* seed_dev, uint32_t site, long row_off, float* workspace,
+                                 const long long* row_index, hipStream_t st) {
+  HRIEMO_CHECK(M > 0 && d > 0 && d % 4 == 0 && d <= 1024, "%s: d=%d must be a multiple of 4, at most 1024", who, d);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "%s: dropout p=%f", who, (double)p);
+  HRIEMO_CHECK(!ROWS || row_index != nullptr, "%s: row_index is required", who);
   const RowDrop dr = make_row_drop(p, seed, seed_dev, site, row_off);
-  HRIEMO_CHECK(dr.thr16 == 0 || dG != nullptr, "add_ln_bwd_f32: with dropout the gradient of g differs from dS and needs its own output (dG)");
+  HRIEMO_CHECK(dr.thr16 == 0 || dG != nullptr, "%s: with dropout the gradient of g differs from dS and needs its own output (dG)", who);
   HRIEMO_CHECK(dY != nullptr && G != nullptr && gamma != nullptr && dS != nullptr && dgamma != nullptr && dbeta != nullptr && workspace != nullptr,
-               "add_ln_bwd_f32: missing operand");
+               "%s: missing operand", who);
   const int nb = add_ln_bwd_f32_blocks(M);
   hriemo_prof_begin(HP_ROWOPS, st);
   // (the row, its gradient and three column accumulators live in registers: 1024 columns -- every BASELINE config -- is what fits
   // without scratch; wider rows are refused above rather than served by a spilling instantiation)
-  hipLaunchKernelGGL((add_ln_bwd_f32_kernel<4>), dim3(nb), dim3(256), 3 * d * 4, st, dY, G, X, gamma, dS, dG, workspace, M, d, eps, dr);
+  hipLaunchKernelGGL((add_ln_bwd_f32_kernel<4, ROWS>), dim3(nb), dim3(256), 3 * d * 4, st, dY, G, X, gamma, dS, dG, workspace, M, d, eps, dr,
+                     row_index);
   HRIEMO_LAUNCH_CHECK("add_ln_bwd_f32_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (double)M * d * 16.0);
   SegOut so; so.o[0] = dgamma; so.o[1] = dbeta; so.o[2] = dbias;
   hipLaunchKernelGGL(colreduce_f32_kernel, dim3((d + 255) / 256, dbias != nullptr ? 3 : 2), dim3(256), 0, st, workspace, nb, d, 3, so, accumulate);
   HRIEMO_LAUNCH_CHECK("colreduce_f32_kernel");
   return 0;
+}
+extern "C" int hriemo_add_ln_bwd_f32(const float* dY, const float* G, const float* X, const float* gamma, float* dS, float* dG, float* dgamma,
+                                     float* dbeta, float* dbias, int accumulate, int M, int d, float eps, float p, uint64_t seed,
+                                     const unsigned long long* seed_dev, uint32_t site, long row_off, float* workspace, hipStream_t st) {
+  return add_ln_bwd_f32_launch<false>("add_ln_bwd_f32", dY, G, X, gamma, dS, dG, dgamma, dbeta, dbias, accumulate, M, d, eps, p, seed,
+                                      seed_dev, site, row_off, workspace, nullptr, st);
+}
+// the same on gathered rows (dropout keyed by row_index[row] + row_off); workspace: hriemo_add_ln_bwd_f32_workspace_bytes
+extern "C" int hriemo_add_ln_bwd_f32_rows(const float* dY, const float* G, const float* X, const float* gamma, float* dS, float* dG,
+                                          float* dgamma, float* dbeta, float* dbias, int accumulate, int M, int d, float eps, float p,
+                                          uint64_t seed, const unsigned long long* seed_dev, uint32_t site, long row_off, float* workspace,
+                                          const long long* row_index, hipStream_t st) {
+  return add_ln_bwd_f32_launch<true>("add_ln_bwd_f32_rows", dY, G, X, gamma, dS, dG, dgamma, dbeta, dbias, accumulate, M, d, eps, p, seed,
+                                     seed_dev, site, row_off, workspace, row_index, st);
 }
 
 // ------------------------------------------------------------------------------------------- attention backward on the fp32 MFMA
@@ -702,12 +751,14 @@ extern "C" int hriemo_add_ln_bwd_f32(const float* dY, const float* G, const floa
 //      the second kernel); dQ^T += K^T . dS^T is the forward's O^T += V^T . P^T with K for V.
 //  dK/dV: block = 64 keys, the keys on the lanes (K, V rows in registers), query tiles of 64 (Q, dO rows, lse, delta) through LDS:
 //      S = Q.K^T and dP = dO.V^T leave [query 16n+4g+r][key i]; dV^T += dO^T . P and dK^T += Q^T . dS contract over the tile's queries.
-template <int HD>
+// PACKED: the cu_seqlens form of the forward kernel (rows of sample b from cu_q / cu_k, lse / delta in their padded slots).
+template <int HD, bool PACKED>
 __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
                                                               const float* __restrict__ V, long ldv, const float* __restrict__ O, long ldo,
                                                               const float* __restrict__ dO, long lddo, const uint8_t* __restrict__ kpm,
                                                               const float* __restrict__ lse, float* __restrict__ dQ, long lddq,
-                                                              float* __restrict__ delta, int H, int Lq, int Lk, float scale, AttnDrop dr) {
+                                                              float* __restrict__ delta, int H, int Lq, int Lk, float scale, AttnDrop dr,
+                                                              const int* __restrict__ cu_q, const int* __restrict__ cu_k) {
   constexpr int LDR = HD + 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Ks = (float*)smem_raw;
@@ -715,11 +766,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
   float* pad = Vs + 64 * LDR;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int LqS = Lq;
+  long rq = (long)b * Lq, rk = (long)b * Lk;
+  if (PACKED) {
+    rq = cu_q[b]; rk = cu_k[b];
+    Lq = cu_q[b + 1] - (int)rq; Lk = cu_k[b + 1] - (int)rk;
+    if (blockIdx.x * 64 >= Lq) return;
+  }
   const int q0 = blockIdx.x * 64 + wave * 16;
   const int q = min(q0 + i, Lq - 1);
-  const float* qp = Q + ((long)b * Lq + q) * ldq + h * HD;
-  const float* dop = dO + ((long)b * Lq + q) * lddo + h * HD;
-  const float* op = O + ((long)b * Lq + q) * ldo + h * HD;
+  const float* qp = Q + (rq + q) * ldq + h * HD;
+  const float* dop = dO + (rq + q) * lddo + h * HD;
+  const float* op = O + (rq + q) * ldo + h * HD;
   float qf[HD / 4], dof[HD / 4];
   float dl = 0.f;
 #pragma unroll
@@ -730,14 +788,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
   }
   dl += __shfl_xor(dl, 16);
   dl += __shfl_xor(dl, 32);
-  const float ls = lse[((long)b * H + h) * Lq + q];
-  if (g == 0 && q0 + i < Lq) delta[((long)b * H + h) * Lq + q0 + i] = dl;
+  const float ls = lse[((long)b * H + h) * LqS + q];
+  if (g == 0 && q0 + i < Lq) delta[((long)b * H + h) * LqS + q0 + i] = dl;
   const uint32_t dkey = dr.thr16 != 0 ? site_key(eff_seed(dr.seed, dr.seed_dev), dr.site, (uint32_t)((dr.b_offset + b) * H + h)) : 0u;
   f32x4 dq[HD / 16];
 #pragma unroll
   for (int t = 0; t < HD / 16; ++t) dq[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float* Kb = K + (long)b * Lk * ldk + h * HD;
-  const float* Vb = V + (long)b * Lk * ldv + h * HD;
+  const float* Kb = K + rk * ldk + h * HD;
+  const float* Vb = V + rk * ldv + h * HD;
   for (int k0 = 0; k0 < Lk; k0 += 64) {
     __syncthreads();
     for (int e = tid; e < 64 * (HD / 4); e += 256) {
@@ -750,7 +808,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
     }
     if (tid < 64) {
       const int key = k0 + tid;
-      pad[tid] = (key < Lk && (kpm == nullptr || kpm[(long)b * Lk + key] == 0)) ? 0.f : -INFINITY;
+      pad[tid] = (key < Lk && (PACKED || kpm == nullptr || kpm[(long)b * Lk + key] == 0)) ? 0.f : -INFINITY;
     }
     __syncthreads();
     f32x4 s[4], dp[4];
@@ -781,7 +839,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
           dq[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ks[(16 * n + 4 * g + r) * LDR + 16 * t + i], s[n][r], dq[t], 0, 0, 0);
   }
   if (q0 + i < Lq) {
-    float* dqp = dQ + ((long)b * Lq + q0 + i) * lddq + h * HD;
+    float* dqp = dQ + (rq + q0 + i) * lddq + h * HD;
 #pragma unroll
     for (int t = 0; t < HD / 16; ++t) {
       f32x4 v = dq[t];
@@ -791,13 +849,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
   }
 }
 
-template <int HD>
+template <int HD, bool PACKED>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
                                                                const float* __restrict__ V, long ldv, const float* __restrict__ dO, long lddo,
                                                                const uint8_t* __restrict__ kpm, const float* __restrict__ lse,
                                                                const float* __restrict__ delta, float* __restrict__ dK, long lddk,
                                                                float* __restrict__ dV, long lddv, int H, int Lq, int Lk, float scale,
-                                                               AttnDrop dr) {
+                                                               AttnDrop dr, const int* __restrict__ cu_q, const int* __restrict__ cu_k) {
   constexpr int LDR = HD + 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Qs = (float*)smem_raw;
@@ -806,21 +864,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __re
   float* dls = lss + 64;               // [64] delta
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int LqS = Lq;
+  long rq = (long)b * Lq, rk = (long)b * Lk;
+  if (PACKED) {
+    rq = cu_q[b]; rk = cu_k[b];
+    Lq = cu_q[b + 1] - (int)rq; Lk = cu_k[b + 1] - (int)rk;
+    if (blockIdx.x * 64 >= Lk) return;
+  }
   const int k0 = blockIdx.x * 64 + wave * 16;
   const int key = min(k0 + i, Lk - 1);
-  const bool kvalid = (k0 + i < Lk) && (kpm == nullptr || kpm[(long)b * Lk + key] == 0);
+  const bool kvalid = (k0 + i < Lk) && (PACKED || kpm == nullptr || kpm[(long)b * Lk + key] == 0);
   const float kpad = kvalid ? 0.f : -INFINITY;
   const uint32_t dkey = dr.thr16 != 0 ? site_key(eff_seed(dr.seed, dr.seed_dev), dr.site, (uint32_t)((dr.b_offset + b) * H + h)) : 0u;
-  const float* kp = K + ((long)b * Lk + key) * ldk + h * HD;
-  const float* vp = V + ((long)b * Lk + key) * ldv + h * HD;
+  const float* kp = K + (rk + key) * ldk + h * HD;
+  const float* vp = V + (rk + key) * ldv + h * HD;
   float kf[HD / 4], vf[HD / 4];
 #pragma unroll
   for (int ks = 0; ks < HD / 4; ++ks) { kf[ks] = kp[4 * ks + g] * scale; vf[ks] = vp[4 * ks + g]; }
   f32x4 dk[HD / 16], dv[HD / 16];
 #pragma unroll
   for (int t = 0; t < HD / 16; ++t) dk[t] = dv[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float* Qb = Q + (long)b * Lq * ldq + h * HD;
-  const float* Db = dO + (long)b * Lq * lddo + h * HD;
+  const float* Qb = Q + rq * ldq + h * HD;
+  const float* Db = dO + rq * lddo + h * HD;
   for (int q0 = 0; q0 < Lq; q0 += 64) {
     __syncthreads();
     for (int e = tid; e < 64 * (HD / 4); e += 256) {
@@ -833,8 +898,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __re
     }
     if (tid < 64) {
       const int qq = q0 + tid;
-      lss[tid] = qq < Lq ? lse[((long)b * H + h) * Lq + qq] : INFINITY;
-      dls[tid] = qq < Lq ? delta[((long)b * H + h) * Lq + qq] : 0.f;
+      lss[tid] = qq < Lq ? lse[((long)b * H + h) * LqS + qq] : INFINITY;
+      dls[tid] = qq < Lq ? delta[((long)b * H + h) * LqS + qq] : 0.f;
     }
     __syncthreads();
     f32x4 s[4], dp[4];
@@ -868,8 +933,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __re
         }
   }
   if (k0 + i < Lk) {
-    float* dkp = dK + ((long)b * Lk + k0 + i) * lddk + h * HD;
-    float* dvp = dV + ((long)b * Lk + k0 + i) * lddv + h * HD;
+    float* dkp = dK + (rk + k0 + i) * lddk + h * HD;
+    float* dvp = dV + (rk + k0 + i) * lddv + h * HD;
 #pragma unroll
     for (int t = 0; t < HD / 16; ++t) {
       f32x4 v = dk[t];
@@ -995,14 +1060,19 @@ extern "C" int hriemo_rowdot_bwd_f32(const float* dl, const float* Z, const floa
     default: hriemo_set_error("attn_f32: head_dim=%d is not built (16, 32, 64, 96, 128)", hd); return 1; \
   }
 
-extern "C" int hriemo_attn_fwd_f32(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, float* O, long ldo,
-                                   const unsigned char* key_padding_mask, float* lse, int B, int H, int Lq, int Lk, int head_dim,
-                                   float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, int b_offset, hipStream_t st) {
-  HRIEMO_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0, "attn_fwd_f32: empty problem");
-  HRIEMO_CHECK(p >= 0.f && p < 1.f, "attn_fwd_f32: dropout p=%f", (double)p);
+// padded (key_padding_mask, cu_q = cu_k = NULL) or packed (cu_q / cu_k, no mask; Lq / Lk = the longest sequences) launch
+template <bool PACKED>
+static int attn_fwd_f32_launch(const char* who, const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, float* O,
+                               long ldo, const unsigned char* key_padding_mask, const int* cu_q, const int* cu_k, float* lse, int B, int H,
+                               int Lq, int Lk, int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
+                               int b_offset, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0, "%s: empty problem", who);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "%s: dropout p=%f", who, (double)p);
+  HRIEMO_CHECK(!PACKED || (cu_q != nullptr && cu_k != nullptr && key_padding_mask == nullptr),
+               "%s: packed sequences need cu_seqlens_q and cu_seqlens_k and carry their lengths (no key_padding_mask)", who);
   const AttnDrop dr = make_attn_drop(p, seed, seed_dev, site, b_offset);
   HRIEMO_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 &&
-                   ((uintptr_t)V % 16) == 0 && ((uintptr_t)O % 16) == 0, "attn_fwd_f32: operands must be 16-byte aligned");
+                   ((uintptr_t)V % 16) == 0 && ((uintptr_t)O % 16) == 0, "%s: operands must be 16-byte aligned", who);
   const float scale = 1.0f / sqrtf((float)head_dim);
   const dim3 grid((Lq + 63) / 64, B * H);
   hriemo_prof_begin(HP_ATTN_FWD, st);
@@ -1010,14 +1080,30 @@ extern "C" int hriemo_attn_fwd_f32(const float* Q, long ldq, const float* K, lon
   {                                                                                                                                      \
     const int lds = (2 * 64 * (HD + 4) + 64) * 4;                                                                                        \
     static bool attr = false;                                                                                                            \
-    if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_f32_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; } \
-    hipLaunchKernelGGL((attn_fwd_f32_kernel<HD>), grid, dim3(256), lds, st, Q, ldq, K, ldk, V, ldv, O, ldo, key_padding_mask, lse, H, Lq, Lk, scale, dr); \
+    if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_f32_kernel<HD, PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; } \
+    hipLaunchKernelGGL((attn_fwd_f32_kernel<HD, PACKED>), grid, dim3(256), lds, st, Q, ldq, K, ldk, V, ldv, O, ldo, key_padding_mask, lse, H, \
+                       Lq, Lk, scale, dr, cu_q, cu_k);                                                                                   \
   }
   DISPATCH_HD_F32(head_dim, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("attn_fwd_f32_kernel");
   hriemo_prof_end(HP_ATTN_FWD, st, 4.0 * B * H * (double)Lq * Lk * head_dim);
   return 0;
+}
+
+extern "C" int hriemo_attn_fwd_f32(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, float* O, long ldo,
+                                   const unsigned char* key_padding_mask, float* lse, int B, int H, int Lq, int Lk, int head_dim,
+                                   float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, int b_offset, hipStream_t st) {
+  return attn_fwd_f32_launch<false>("attn_fwd_f32", Q, ldq, K, ldk, V, ldv, O, ldo, key_padding_mask, nullptr, nullptr, lse, B, H, Lq, Lk,
+                                    head_dim, p, seed, seed_dev, site, b_offset, st);
+}
+
+extern "C" int hriemo_attn_fwd_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, float* O, long ldo,
+                                          const int* cu_seqlens_q, const int* cu_seqlens_k, float* lse, int B, int H, int max_len_q,
+                                          int max_len_k, int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev,
+                                          uint32_t site, int b_offset, hipStream_t st) {
+  return attn_fwd_f32_launch<true>("attn_fwd_f32_varlen", Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, cu_seqlens_q, cu_seqlens_k, lse, B, H,
+                                   max_len_q, max_len_k, head_dim, p, seed, seed_dev, site, b_offset, st);
 }
 
 extern "C" int hriemo_attn_probs_f32(const float* Q, long ldq, const float* K, long ldk, const unsigned char* key_padding_mask,
@@ -1040,17 +1126,21 @@ extern "C" int hriemo_attn_probs_f32(const float* Q, long ldq, const float* K, l
   return 0;
 }
 
-extern "C" int hriemo_attn_bwd_f32(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, const float* O, long ldo,
-                                   const float* dO, long lddo, const unsigned char* key_padding_mask, const float* lse, float* dQ, long lddq,
-                                   float* dK, long lddk, float* dV, long lddv, float* delta, int B, int H, int Lq, int Lk, int head_dim,
-                                   float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, int b_offset, hipStream_t st) {
-  HRIEMO_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0 && lse != nullptr && delta != nullptr, "attn_bwd_f32: empty problem");
-  HRIEMO_CHECK(p >= 0.f && p < 1.f, "attn_bwd_f32: dropout p=%f", (double)p);
+template <bool PACKED>
+static int attn_bwd_f32_launch(const char* who, const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, const float* O,
+                               long ldo, const float* dO, long lddo, const unsigned char* key_padding_mask, const int* cu_q, const int* cu_k,
+                               const float* lse, float* dQ, long lddq, float* dK, long lddk, float* dV, long lddv, float* delta, int B,
+                               int H, int Lq, int Lk, int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev,
+                               uint32_t site, int b_offset, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0 && lse != nullptr && delta != nullptr, "%s: empty problem", who);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "%s: dropout p=%f", who, (double)p);
+  HRIEMO_CHECK(!PACKED || (cu_q != nullptr && cu_k != nullptr && key_padding_mask == nullptr),
+               "%s: packed sequences need cu_seqlens_q and cu_seqlens_k and carry their lengths (no key_padding_mask)", who);
   const AttnDrop dr = make_attn_drop(p, seed, seed_dev, site, b_offset);
   HRIEMO_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && lddo % 4 == 0 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0,
-               "attn_bwd_f32: leading dimensions must be multiples of 4");
+               "%s: leading dimensions must be multiples of 4", who);
   HRIEMO_CHECK(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)V % 16) == 0 && ((uintptr_t)O % 16) == 0 && ((uintptr_t)dO % 16) == 0 &&
-                   ((uintptr_t)dQ % 16) == 0 && ((uintptr_t)dK % 16) == 0 && ((uintptr_t)dV % 16) == 0, "attn_bwd_f32: operands must be 16-byte aligned");
+                   ((uintptr_t)dQ % 16) == 0 && ((uintptr_t)dK % 16) == 0 && ((uintptr_t)dV % 16) == 0, "%s: operands must be 16-byte aligned", who);
   const float scale = 1.0f / sqrtf((float)head_dim);
   hriemo_prof_begin(HP_ATTN_BWD_DQ, st);
 #define CALL(HD)                                                                                                                          \
@@ -1058,18 +1148,36 @@ extern "C" int hriemo_attn_bwd_f32(const float* Q, long ldq, const float* K, lon
     const int lds = (2 * 64 * (HD + 4) + 64) * 4;                                                                                         \
     static bool attr = false;                                                                                                             \
     if (!attr) {                                                                                                                          \
-      hipFuncSetAttribute((const void*)attn_bwd_dq_f32_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                      \
-      hipFuncSetAttribute((const void*)attn_bwd_dkv_f32_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 256);               \
+      hipFuncSetAttribute((const void*)attn_bwd_dq_f32_kernel<HD, PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);              \
+      hipFuncSetAttribute((const void*)attn_bwd_dkv_f32_kernel<HD, PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 256);       \
       attr = true;                                                                                                                        \
     }                                                                                                                                     \
-    hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<HD>), dim3((Lq + 63) / 64, B * H), dim3(256), lds, st, Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, \
-                       key_padding_mask, lse, dQ, lddq, delta, H, Lq, Lk, scale, dr);                                                    \
-    hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<HD>), dim3((Lk + 63) / 64, B * H), dim3(256), lds + 256, st, Q, ldq, K, ldk, V, ldv, dO, lddo, \
-                       key_padding_mask, lse, delta, dK, lddk, dV, lddv, H, Lq, Lk, scale, dr);                                          \
+    hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<HD, PACKED>), dim3((Lq + 63) / 64, B * H), dim3(256), lds, st, Q, ldq, K, ldk, V, ldv, O, ldo, \
+                       dO, lddo, key_padding_mask, lse, dQ, lddq, delta, H, Lq, Lk, scale, dr, cu_q, cu_k);                             \
+    hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<HD, PACKED>), dim3((Lk + 63) / 64, B * H), dim3(256), lds + 256, st, Q, ldq, K, ldk, V, ldv, \
+                       dO, lddo, key_padding_mask, lse, delta, dK, lddk, dV, lddv, H, Lq, Lk, scale, dr, cu_q, cu_k);                   \
   }
   DISPATCH_HD_F32(head_dim, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("attn_bwd_f32 kernels");
   hriemo_prof_end(HP_ATTN_BWD_DQ, st, 14.0 * B * H * (double)Lq * Lk * head_dim);
   return 0;
+}
+
+extern "C" int hriemo_attn_bwd_f32(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, const float* O, long ldo,
+                                   const float* dO, long lddo, const unsigned char* key_padding_mask, const float* lse, float* dQ, long lddq,
+                                   float* dK, long lddk, float* dV, long lddv, float* delta, int B, int H, int Lq, int Lk, int head_dim,
+                                   float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, int b_offset, hipStream_t st) {
+  return attn_bwd_f32_launch<false>("attn_bwd_f32", Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, key_padding_mask, nullptr, nullptr, lse, dQ,
+                                    lddq, dK, lddk, dV, lddv, delta, B, H, Lq, Lk, head_dim, p, seed, seed_dev, site, b_offset, st);
+}
+
+extern "C" int hriemo_attn_bwd_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, const float* O,
+                                          long ldo, const float* dO, long lddo, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                          const float* lse, float* dQ, long lddq, float* dK, long lddk, float* dV, long lddv, float* delta,
+                                          int B, int H, int max_len_q, int max_len_k, int head_dim, float p, uint64_t seed,
+                                          const unsigned long long* seed_dev, uint32_t site, int b_offset, hipStream_t st) {
+  return attn_bwd_f32_launch<true>("attn_bwd_f32_varlen", Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, nullptr, cu_seqlens_q, cu_seqlens_k,
+                                   lse, dQ, lddq, dK, lddk, dV, lddv, delta, B, H, max_len_q, max_len_k, head_dim, p, seed, seed_dev, site,
+                                   b_offset, st);
 }

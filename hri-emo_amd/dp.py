@@ -353,7 +353,7 @@ class DataParallelStep:
         self._static = [None if t is None else t.clone() for t in (h_a, h_t, m_a, m_t, y)]
         self.release_graph()              # a re-capture replaces the old graph(s): their pinned buffers go first
         self._collectives = bool(collectives)
-        if _ops.varlen() and m_a is not None and m_t is not None and _ops.precision() == "bf16":
+        if _ops.varlen() and m_a is not None and m_t is not None:
             if collectives and self.world > 1:
                 raise RuntimeError("capture(collectives=True) in packed (varlen) mode: ranks meet new buckets at different steps and a "
                                    "bucket's capture runs eager warm-up exchanges -- capture without collectives (exchange after the "

@@ -414,6 +414,31 @@ int hriemo_gate_dy_f32(const float* dH, const float* w, int is_a, const float* d
 int hriemo_rowdot_bwd_f32(const float* dl, const float* Z, const float* w, float* dZ, float* dw, float* db, int accumulate, int M, int d,
                           hriemo_stream_t stream);
 
+/* ---- fp32-tolerance mode on packed (varlen) sequences: the encoder on the valid rows only (hriemo_attn_*_varlen's contract).
+ *  - hriemo_attn_fwd_f32_varlen / hriemo_attn_bwd_f32_varlen: hriemo_attn_fwd_f32 / _bwd_f32 with cu_seqlens_q / cu_seqlens_k
+ *    (int32 [B+1], device memory, every length >= 1) in place of the key padding mask: sample b = rows cu[b] .. cu[b+1]-1 of
+ *    Q / O / dO / dQ (cu_seqlens_q) and K / V / dK / dV (cu_seqlens_k); max_len_q / max_len_k are the longest sequences (grid, and
+ *    the row stride of lse / delta, which keep their padded [B, H, max_len_q] slots).  The dropout hash is keyed by position within
+ *    the sequence, i.e. the padded (batch, query, key): a packed launch drops what the padded one drops.
+ *  - hriemo_add_ln_f32_rows / hriemo_add_ln_bwd_f32_rows: hriemo_add_ln_f32 / _bwd_f32 on rows gathered from a larger layout; the
+ *    residual-dropout hash is keyed by row_index[row] + row_offset (int64 [M], the padded row hriemo_pack_rows writes). */
+int hriemo_attn_fwd_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, float* O, long ldo,
+                               const int* cu_seqlens_q, const int* cu_seqlens_k, float* lse, int B, int H, int max_len_q, int max_len_k,
+                               int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
+                               int b_offset, hriemo_stream_t stream);
+int hriemo_attn_bwd_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv, const float* O, long ldo,
+                               const float* dO, long lddo, const int* cu_seqlens_q, const int* cu_seqlens_k, const float* lse, float* dQ,
+                               long lddq, float* dK, long lddk, float* dV, long lddv, float* delta, int B, int H, int max_len_q,
+                               int max_len_k, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
+                               unsigned site, int b_offset, hriemo_stream_t stream);
+int hriemo_add_ln_f32_rows(const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16, int M, int d,
+                           float eps, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
+                           long row_offset, const long long* row_index, hriemo_stream_t stream);
+int hriemo_add_ln_bwd_f32_rows(const float* dY, const float* G, const float* X, const float* gamma, float* dS, float* dG, float* dgamma,
+                               float* dbeta, float* dbias, int accumulate, int M, int d, float eps, float p_drop, unsigned long long seed,
+                               const unsigned long long* seed_dev, unsigned site, long row_offset, float* workspace,
+                               const long long* row_index, hriemo_stream_t stream);
+
 /* ---- per-kernel-class HIP-event timing on the launch stream (bench.py roofline leg) */
 int hriemo_prof_enable(int on);
 int hriemo_prof_nclass(void);
