@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_reference as R
 import hashrng
 
 pytestmark = pytest.mark.gpu
@@ -240,7 +241,8 @@ ATTN_CASES = [  # B, H, Lq, Lk, hd, masked, p
     (3, 8, 32, 16, 16, True, 0.1),
     (1, 2, 200, 200, 128, False, 0.0),
     (1, 4, 50, 1000, 32, True, 0.0),
-    (64, 8, 128, 70, 96, True, 0.1),      # B*H = 512 at L <= 128: the backward picks its 128-row tiles (one round of blocks)
+    (64, 8, 128, 70, 96, True, 0.1),      # B*H = 512 blocks of the key-resident single pass (L_k <= 128) on 256 CUs; the 128-row
+                                          # two-kernel tiles this row reached before that kernel landed: test_gpu_attention_variants.py
     (2, 8, 6, 128, 96, True, 0.1),        # decoder cross-attention: N_e = 6 queries over the fused memory (single-pass backward)
     (2, 4, 100, 128, 128, True, 0.1),     # head_dim 128 (cfg 5), all 128 keys in one block
     (3, 4, 70, 40, 64, True, 0.1),        # L_k <= 64: one 16-key sub-tile per wave
@@ -309,6 +311,13 @@ def test_attention_fwd_bwd(ops, B, H, Lq, Lk, hd, masked, p):
     for name, got, ref in (("dq", dq, dq_ref), ("dk", dkv[:, :d], dk_ref), ("dv", dkv[:, d:], dv_ref)):
         err = (got.float().cpu() - ref).abs().max().item()
         assert err <= 3e-2 * max(1.0, ref.abs().max().item()), (name, err, ref.abs().max().item())
+    # on top of the global limits above: the elementwise and per-tile limits of tests/attn_reference.py (float64 reference,
+    # bf16 yardstick, magnitude of the same products)
+    hs = lambda x2d, L: R.heads(x2d.float().cpu(), B, L, H, hd)
+    ref64, yard, mag = R.all_three(hs(qb, Lq), hs(kvb[:, :d], Lk), hs(kvb[:, d:], Lk), hs(dob, Lq), kpm,
+                                   None if keep is None else keep.bool(), hashrng.inv_keep(p))
+    for name, got, L in (("O", o, Lq), ("dQ", dq, Lq), ("dK", dkv[:, :d], Lk), ("dV", dkv[:, d:], Lk)):
+        R.check(hs(got, L), ref64[name], yard[name], mag[name], name)
     if p > 0:       # mask from the bit words == mask replayed from the hash: same kernels, bit-identical gradients
         dq_h, dkv_h = torch.empty_like(qd), torch.empty_like(kvd)
         ops.attn_bwd(qd, kvd[:, :d], kvd[:, d:], o, dod, dq_h, dkv_h[:, :d], dkv_h[:, d:], lse, B, H, Lq, Lk, hd, kpm_d, p, seed,

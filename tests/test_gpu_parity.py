@@ -9,6 +9,7 @@ gradients: per-parameter relative L2 error bounded by the reference path's own b
 test_fusion_train_step_grads.
 """
 import os
+import time
 
 import pytest
 import torch
@@ -212,19 +213,40 @@ def test_fusion_train_step_grads(H, name, d, ne, init):
     assert _rel(gt_m, gt_r) <= max(3e-2, 1.5 * _rel(gt_y, gt_r)), "d loss / d h_t"
 
 
-def test_fusion_train_step_grads_cfg2_shape(H):
+def _first_wide_batch(n_heads, L, hd):
+    """first batch size whose self-attention backward at length L takes the 128-row dQ tile on this device (the ABI's
+    column-sum row count tells: B * ceil(L / 128) instead of B * ceil(L / 64))"""
+    from hri_emo_amd import _lib
+    L_ = _lib.lib()
+    for B in range(1, 129):
+        if not L_.hriemo_attn_bwd_single_pass_q(B, n_heads, L, L, hd) and \
+                L_.hriemo_attn_bwd_dq_colsum_rows(B, n_heads, L, L, hd) == B * ((L + 127) // 128):
+            return B
+    raise AssertionError(f"no batch size in 1..128 takes the 128-row backward tile at H={n_heads}, L={L}, hd={hd} on this device")
+
+
+@pytest.mark.parametrize("B", [2, "W"])
+def test_fusion_train_step_grads_cfg2_shape(H, B):
     """The same per-parameter gradient bound at the HEADLINE shape (BASELINE configs[1]: d=768, T_a=400, T_t=128, N_e=6,
-    H=8, 2+2 layers; B=2 keeps the CPU oracle and its autocast yardstick within seconds), default torch init, ragged masks."""
+    H=8, 2+2 layers), default torch init, ragged masks.  B=2 keeps the CPU oracle and its autocast yardstick within seconds.
+    B=W is the first batch size at which the self-audio backward runs its 128-row tiles (15 on 256 CUs: the headline batch
+    sharded over 4 GPUs); there M = B*400 >= 1024 rows and the weight-gradient reductions are >= 4096 long, so the encoder's
+    NT / NN / TN GEMMs go to the loader/consumer kernel as well -- neither is under a model-level oracle test at smaller B."""
+    if B == "W":
+        B = _first_wide_batch(8, 400, 96)
+        assert B * 400 >= 1024
     torch.manual_seed(1234)
     kw = dict(d_model=768, num_emotions=6, n_heads=8, dropout=0.0)
     ref = O.FusionWithEmotionDecoder(**kw).train()
     m = H.FusionWithEmotionDecoder(**kw)
     m.load_state_dict(ref.state_dict())
     m.cuda().train()
-    h_a, h_t, m_a, m_t = _rand_batch(2, 400, 128, 768, 41)
-    y = (torch.rand(2, 6, generator=torch.Generator().manual_seed(42)) < 0.3).float()
+    h_a, h_t, m_a, m_t = _rand_batch(B, 400, 128, 768, 41)
+    y = (torch.rand(B, 6, generator=torch.Generator().manual_seed(42)) < 0.3).float()
+    t0 = time.time()
     loss_r, logits_r, ga_r, gt_r, gr = _train_step(ref, h_a, h_t, m_a, m_t, y)
     _, _, ga_y, gt_y, gy = _train_step(ref, h_a, h_t, m_a, m_t, y, autocast_cpu=True)
+    print(f"cfg-2 shape, B={B}: CPU oracle + autocast yardstick took {time.time() - t0:.1f} s")
     loss_m, logits_m, ga_m, gt_m, gm = _train_step(m, cu(h_a), cu(h_t), cu(m_a), cu(m_t), cu(y))
     close(loss_m.reshape(1), loss_r.reshape(1), what="loss"); close(logits_m, logits_r, what="logits")
     assert_per_parameter_grads(gm, gy, gr, what="cfg2 shape")
