@@ -728,21 +728,37 @@ def proj_fwd(xop, sh, w, w16, bias, rows=None, relu=False, out_f32=False, want_q
     return linear_fwd(x, wv, b, relu=relu, out_f32=out_f32)
 
 
-_GEMM_CONTENDED = None
+_GEMM_FLAGS_EXPLICIT = False
 
 
-def gemm_contended(on):
+def gemm_flags():
+    """the tuning word of hriemo_gemm_debug_flags that is in force right now (read back from the library)"""
+    L = _lib.lib()
+    cur = L.hriemo_gemm_debug_flags(0)
+    L.hriemo_gemm_debug_flags(cur)
+    return cur
+
+
+def set_gemm_flags(word):
+    """Set the GEMM tuning word (include/hriemo.h: hriemo_gemm_debug_flags) for good: gemm_contended() then leaves it alone, so a
+    caller's choice of the tile walk (bit 3) is what runs.  None hands bit 3 back to gemm_contended.  Returns the previous word."""
+    global _GEMM_FLAGS_EXPLICIT
+    _GEMM_FLAGS_EXPLICIT = word is not None
+    return _lib.lib().hriemo_gemm_debug_flags(word) if word is not None else gemm_flags()
+
+
+def gemm_contended(on, force=False):
     """Will other kernels (RCCL collectives) hold CUs while the GEMMs run?  True: the loader / consumer GEMM draws its tiles from
     the per-XCD work queue (with 32 CUs held a 25600x3072x768 launch takes 140 us, 184 on the static walk; 118-124 alone); False
     (default): static walk, 5-8 % faster per launch on a chip the kernel has to itself, the same step time
-    (profiles/r04_gemm_ws.log).  Bit 3 of hriemo_gemm_debug_flags.  No-op without a GPU."""
-    global _GEMM_CONTENDED
-    if _GEMM_CONTENDED is on or not torch.cuda.is_available():
+    (profiles/r04_gemm_ws.log).  Bit 3 of hriemo_gemm_debug_flags and nothing else of that word; a word set through
+    set_gemm_flags() is kept as it is unless `force` (DataParallelStep(force_queue=...)).  No-op without a GPU."""
+    if not torch.cuda.is_available() or (_GEMM_FLAGS_EXPLICIT and not force):
         return
-    L = _lib.lib()
-    prev = L.hriemo_gemm_debug_flags(9)
-    L.hriemo_gemm_debug_flags((prev & ~8) if on else (prev | 8))
-    _GEMM_CONTENDED = on
+    cur = gemm_flags()
+    want = (cur & ~8) if on else (cur | 8)
+    if want != cur:
+        _lib.lib().hriemo_gemm_debug_flags(want)
 
 
 FUSE_LN = None             # Linear + bias + dropout + residual + LayerNorm in one launch (csrc/gemm_ln.hip); HRIEMO_FUSE_LN=1

@@ -852,14 +852,42 @@ static int wave_rows(int cfg) {
   static const int waves_m[] = {2, 4, 2, 2, 2, 4, 2, 2, 2, 4};
   return kCfg[cfg].bm / waves_m[cfg];
 }
-static int pick_config(int ta, int tb, int M, int N, int K);
-extern "C" int hriemo_gemm_colsum_rows(int ta, int tb, int M, int N, int K) {
+// The launch plan of one GEMM call: the tile configuration after EVERY fallback, the number of split-K slices and the k of a
+// slice.  gemm_impl launches exactly this; hriemo_gemm_plan reports it (the tests pin which kernel a shape runs on).
+struct GemmPlan { int cfg, splitk, k_per_split; };
+static GemmPlan plan_gemm(int ta, int tb, int M, int N, int K, int c_is_f32, long workspace_bytes) {
   int cfg = pick_config(ta, tb, M, N, K);
   if (cfg == 8 && tb == 1) cfg = 7;
-  if ((cfg == 3 || (cfg >= 6 && cfg <= 8)) && ta == 1) cfg = 0;
-  if (cfg == 5 && ta == 1) cfg = 0;
-  if (K <= (kCfg[cfg].ns - 2) * kCfg[cfg].bk) cfg = 0;
-  const int wr = wave_rows(cfg);
+  if ((cfg == 3 || (cfg >= 6 && cfg <= 8)) && ta == 1) cfg = 0;   // the 64- / 32-row tiles have no K-strided A image (128-B rows cannot hold the swizzle)
+  if (cfg == 5 && (ta == 1 || c_is_f32)) cfg = 0;   // the 320-row tile exists for row-major A and bf16 output only
+  int splitk = 1;
+  if (c_is_f32) {
+    const long tiles = (long)((M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((N + kCfg[cfg].bn - 1) / kCfg[cfg].bn);
+    const int ksteps = (K + 63) / 64;
+    const long slots = (long)hriemo_num_cus() * (kCfg[cfg].lds + kCfg[cfg].threads * 32 <= 80 * 1024 ? 2 : 1);
+    long want = slots / tiles;                         // persistent grid: one work unit per resident block
+    if (want > ksteps / 4) want = ksteps / 4;          // >= 4 K-steps (256 of K) per slice
+    const long fit = workspace_bytes > 0 ? workspace_bytes / ((long)M * N * 4) : 0;
+    if (want > fit) want = fit;
+    if (want > 1) splitk = (int)want;
+  }
+  const int kper = ((K + splitk - 1) / splitk + 63) / 64 * 64;
+  splitk = (K + kper - 1) / kper;
+  // an NS-deep ring streams NS-1 K-steps ahead across work units: every unit needs >= NS-1 K-steps
+  if (K - (splitk - 1) * kper <= (kCfg[cfg].ns - 2) * kCfg[cfg].bk) cfg = 0;
+  return {cfg, splitk, kper};
+}
+// read-only: what hriemo_gemm_bf16 would launch for this call (workspace_bytes <= 0: no workspace)
+extern "C" int hriemo_gemm_plan(int ta, int tb, int M, int N, int K, int c_is_f32, long workspace_bytes, int* cfg, int* splitk,
+                                int* k_per_split) {
+  HRIEMO_CHECK(M > 0 && N > 0 && K > 0 && cfg != nullptr && splitk != nullptr && k_per_split != nullptr, "gemm_plan: bad arguments");
+  HRIEMO_CHECK(!(ta == 1 && tb == 0), "gemm: layout (ta=1,tb=0) is not used by this path and not built");
+  const GemmPlan pl = plan_gemm(ta, tb, M, N, K, c_is_f32, workspace_bytes);
+  *cfg = pl.cfg; *splitk = pl.splitk; *k_per_split = pl.k_per_split;
+  return 0;
+}
+extern "C" int hriemo_gemm_colsum_rows(int ta, int tb, int M, int N, int K) {
+  const int wr = wave_rows(plan_gemm(ta, tb, M, N, K, 0, 0).cfg);
   return (M + wr - 1) / wr;
 }
 
@@ -882,10 +910,8 @@ static int gemm_impl(int ta, int tb, int M, int N, int K, const void* A, long ld
   HRIEMO_CHECK(!(c_is_f32 && epilogue != 0), "gemm: fp32 output has no activation epilogue");
   HRIEMO_CHECK(c_is_f32 || !accumulate, "gemm: accumulate needs fp32 output");
 
-  int cfg = pick_config(ta, tb, M, N, K);
-  if (cfg == 8 && tb == 1) cfg = 7;
-  if ((cfg == 3 || (cfg >= 6 && cfg <= 8)) && ta == 1) cfg = 0;   // the 64- / 32-row tiles have no K-strided A image (128-B rows cannot hold the swizzle)
-  if (cfg == 5 && (ta == 1 || c_is_f32)) cfg = 0;   // the 320-row tile exists for row-major A and bf16 output only
+  const GemmPlan pl = plan_gemm(ta, tb, M, N, K, c_is_f32, workspace != nullptr ? workspace_bytes : 0);
+  const int cfg = pl.cfg, splitk = pl.splitk;
   GemmArgs a = {};
   a.M = M; a.N = N; a.K = K;
   a.A = (const bf16_t*)A; a.lda = lda; a.B = (const bf16_t*)B; a.ldb = ldb;
@@ -895,25 +921,7 @@ static int gemm_impl(int ta, int tb, int M, int N, int K, const void* A, long ld
   a.flags = g_gemm_flags;
   a.cs = colsum_partials;
   HRIEMO_CHECK(colsum_partials == nullptr || (epilogue == 2 && !c_is_f32), "gemm: column sums are built for the masked epilogue (2) with bf16 output");
-  int splitk = 1;
-  if (c_is_f32) {
-    const long tiles = (long)a.tiles_m * a.tiles_n;
-    const int ksteps = (K + 63) / 64;
-    const long slots = (long)hriemo_num_cus() * (kCfg[cfg].lds + kCfg[cfg].threads * 32 <= 80 * 1024 ? 2 : 1);
-    long want = slots / tiles;                         // persistent grid: one work unit per resident block
-    if (want > ksteps / 4) want = ksteps / 4;          // >= 4 K-steps (256 of K) per slice
-    const long fit = workspace ? workspace_bytes / ((long)M * N * 4) : 0;
-    if (want > fit) want = fit;
-    if (want > 1) splitk = (int)want;
-  }
-  int kper = ((K + splitk - 1) / splitk + 63) / 64 * 64;
-  splitk = (K + kper - 1) / kper;
-  if (K - (splitk - 1) * kper <= (kCfg[cfg].ns - 2) * kCfg[cfg].bk) {
-    // an NS-deep ring streams NS-1 K-steps ahead across work units: every unit needs >= NS-1 K-steps
-    cfg = 0;
-    a.tiles_m = (M + kCfg[cfg].bm - 1) / kCfg[cfg].bm; a.tiles_n = (N + kCfg[cfg].bn - 1) / kCfg[cfg].bn;
-  }
-  a.splitk = splitk; a.k_per_split = kper;
+  a.splitk = splitk; a.k_per_split = pl.k_per_split;
   if (C2 != nullptr && splitk == 1) {
     // the split is applied by the split-K reduce; a problem that is not split along K runs as two launches instead
     const char* A2 = (const char*)A + (size_t)split_m * 2;      // ta == 1: A is [K][M], its column m is output row m

@@ -268,8 +268,9 @@ class DataParallelStep:
     _capture_streams = {}         # device index -> the one stream every capture of this process records on
 
     def __init__(self, model, loss_fn, group=None, bucket_bytes=32 << 20, overlap=True, comm_dtype=torch.float32, force_exchange=False,
-                 launch_from="notify"):
+                 launch_from="notify", force_queue=None):
         self.model, self.loss_fn = model, loss_fn
+        self.force_queue = force_queue    # None: the loader / consumer GEMMs draw from the work queue when collectives run beside backward; True / False: always / never
         self._keep = []
         self._exchange_in_graph = False
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -295,7 +296,10 @@ class DataParallelStep:
         # consumer GEMMs then draw their tiles from the work queue (a block whose CU a collective holds late draws fewer); with
         # the chip to itself they walk statically, which is 5-8 % faster per launch alone and equal inside the step
         b = self.buckets
-        _ops.gemm_contended(bool(b._hooks) and not b.suspended and b.world > 1)
+        if self.force_queue is None:
+            _ops.gemm_contended(bool(b._hooks) and not b.suspended and b.world > 1)
+        else:
+            _ops.gemm_contended(bool(self.force_queue), force=True)
         if zero:
             self.buckets.zero_grad()
         logits, beta, _ = self.model(h_a, h_t, m_a, m_t)

@@ -74,6 +74,12 @@ int hriemo_gemm_force_config(int cfg);
  * them from the per-XCD work queue -- faster on a chip the launch has to itself; hri_emo_amd.dp clears it while collectives run
  * beside backward (a block whose CU is held late then draws fewer tiles). */
 int hriemo_gemm_debug_flags(int flags);
+/* Read-only: the launch plan hriemo_gemm_bf16 (and _split / _colsum) takes for this call on the current device, after every
+ * fallback and with the forced configuration and flag word in force: tile configuration (0-9 as hriemo_gemm_force_config), number
+ * of split-K slices (1: no workspace traffic) and the k of one slice.  workspace_bytes <= 0: no workspace.  The split-K launch
+ * writes splitk * M * N floats of the workspace.  Launches nothing. */
+int hriemo_gemm_plan(int ta, int tb, int M, int N, int K, int c_is_f32, long workspace_bytes, int* cfg, int* splitk,
+                     int* k_per_split);
 
 /* ---- MX-fp8 operand path (BASELINE.json configs[4], "fp8 MFMA path"): the same nn.Linear / in-projection / out-projection
  * sites as hriemo_gemm_bf16 in the FORWARD direction (models/cross_modal_block_tacfn.py:24-52, models/emotion_decoder.py:14-27),
