@@ -93,6 +93,8 @@ _SIGS = {
     "hriemo_debug_hog": ("iipp", "i"),
     "hriemo_sumsq_f32": ("plpip", "i"),
     "hriemo_adamw_flat": ("pppplfffffifpp", "i"),
+    "hriemo_optim_finalize": ("pippppp", "i"),
+    "hriemo_adamw_flat_dev": ("pppplppp", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),

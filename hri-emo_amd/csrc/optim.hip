@@ -1,0 +1,94 @@
+// Device-state AdamW (hri-emo_amd/optim.py: DeviceAdamW): clip_grad_norm_ + torch.optim.AdamW with EVERY scalar of the update in
+// device memory, so the whole optimizer step can be recorded into the hipGraph of the trainer step and still follow a learning-
+// rate schedule, a GradScaler and its own step count (scripts/fusion/train_mosei_fusion_seq_level_decoder.py:367-402, 564-584).
+//   hyper[8]  written by the host:   lr, beta1, beta2, eps, weight_decay, max_norm (<= 0: no clipping), 2 spare words
+//   state[8]  written by the device: step, skip, coef, step_size = lr / bc1, 1 / sqrt(bc2), decay = 1 - lr * wd,
+//                                    grad_norm (pre-clip, unscaled), skipped (number of skipped steps)
+// A step is hriemo_sumsq_f32 (rowops.hip) -> hriemo_optim_finalize (one block) -> hriemo_adamw_flat_dev (streaming).
+#include "common.h"
+
+enum { HY_LR = 0, HY_BETA1, HY_BETA2, HY_EPS, HY_WD, HY_MAX_NORM };
+enum { ST_STEP = 0, ST_SKIP, ST_COEF, ST_STEP_SIZE, ST_ISB2, ST_DECAY, ST_GRAD_NORM, ST_SKIPPED };
+
+// One block.  Sums the sumsq_f32 partials in a fixed order (deterministic), forms the unscaled gradient norm, decides whether
+// the step is skipped (GradScaler found an inf / the norm is not finite: torch's GradScaler.step and the reference trainer's
+// NaN guard, without the host reading anything back) and leaves every per-step scalar of the update in state[]: the only
+// powf of the optimizer runs here, once, not per element.
+__global__ __launch_bounds__(256) void optim_finalize_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
+                                                             const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                                                             float* __restrict__ state) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblocks; i += 256) s += partial[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const float sum = red[0] + red[1] + red[2] + red[3];
+  const float gs = grad_scale != nullptr ? grad_scale[0] : 1.f;
+  const float norm = sqrtf(sum) / gs;
+  const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+  const bool skip = !finite || (found_inf != nullptr && !(found_inf[0] == 0.f));
+  state[ST_GRAD_NORM] = norm;
+  if (skip) {
+    state[ST_SKIP] = 1.f;
+    state[ST_SKIPPED] += 1.f;
+    return;
+  }
+  const float lr = hyper[HY_LR], b1 = hyper[HY_BETA1], b2 = hyper[HY_BETA2], wd = hyper[HY_WD], max_norm = hyper[HY_MAX_NORM];
+  const float step = state[ST_STEP] + 1.f;
+  const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
+  float coef = 1.f;
+  if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
+  state[ST_STEP] = step;
+  state[ST_SKIP] = 0.f;
+  state[ST_COEF] = coef / gs;
+  state[ST_STEP_SIZE] = lr / bc1;
+  state[ST_ISB2] = 1.f / sqrtf(bc2);
+  state[ST_DECAY] = 1.f - lr * wd;
+}
+
+// adamw_flat_kernel (rowops.hip) with its scalars read from hyper[] / state[]: torch.optim.AdamW's arithmetic on the clipped,
+// unscaled gradient coef * g.  A skipped step returns before it touches p, m or v.
+__global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, long n, const float* __restrict__ hyper,
+                                                             const float* __restrict__ state) {
+  if (state[ST_SKIP] != 0.f) return;
+  const float b1 = hyper[HY_BETA1], b2 = hyper[HY_BETA2], eps = hyper[HY_EPS];
+  const float coef = state[ST_COEF], step = state[ST_STEP_SIZE], isb2 = state[ST_ISB2], decay = state[ST_DECAY];
+  const long nv = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+    f32x4 pp = *(const f32x4*)(p + i * 4), mm = *(const f32x4*)(m + i * 4), vv = *(const f32x4*)(v + i * 4);
+    const f32x4 gg = *(const f32x4*)(g + i * 4) * coef;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      pp[e] *= decay;
+      mm[e] += (gg[e] - mm[e]) * (1.f - b1);
+      vv[e] = vv[e] * b2 + gg[e] * gg[e] * (1.f - b2);
+      pp[e] -= step * mm[e] / (sqrtf(vv[e]) * isb2 + eps);
+    }
+    *(f32x4*)(p + i * 4) = pp; *(f32x4*)(m + i * 4) = mm; *(f32x4*)(v + i * 4) = vv;
+  }
+}
+
+extern "C" int hriemo_optim_finalize(const float* partial, int nblocks, const float* hyper, const float* grad_scale, const float* found_inf,
+                                     float* state, hipStream_t st) {
+  HRIEMO_CHECK(partial != nullptr && hyper != nullptr && state != nullptr, "optim_finalize: partial, hyper and state are required");
+  HRIEMO_CHECK(nblocks > 0 && nblocks <= 4096, "optim_finalize: nblocks=%d out of range (1..4096)", nblocks);
+  hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, grad_scale, found_inf, state);
+  HRIEMO_LAUNCH_CHECK("optim_finalize_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* state,
+                                     hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0, "adamw_flat_dev: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+               "adamw_flat_dev: unaligned buffer");
+  HRIEMO_CHECK(hyper != nullptr && state != nullptr, "adamw_flat_dev: hyper and state are required");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  hipLaunchKernelGGL(adamw_flat_dev_kernel, dim3((int)gsz), dim3(256), 0, st, p, g, m, v, n, hyper, state);
+  HRIEMO_LAUNCH_CHECK("adamw_flat_dev_kernel");
+  return 0;
+}

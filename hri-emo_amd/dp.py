@@ -263,7 +263,8 @@ class DataParallelStep:
     costs ~10 ms of host time for ~150 launches; a replay costs microseconds).  Dropout stays fresh per
     replay through the device-resident seed word the graph bumps itself (``_ops.seed_word``); bf16 weight
     shadows are re-cast inside the graph so optimizer updates between replays are honoured.  The gradient
-    all-reduce runs after the replay on the flat buffer."""
+    all-reduce runs after the replay on the flat buffer.  ``capture(..., optimizer=opt)`` with an ``optim.DeviceAdamW``
+    records the optimizer's three launches at the end of the graph as well: one ``step()`` is then the whole trainer step."""
 
     _capture_streams = {}         # device index -> the one stream every capture of this process records on
 
@@ -283,6 +284,7 @@ class DataParallelStep:
         self._static_loss = None
         self._pb = None               # packed (varlen) bucket graphs: {(rows audio, rows text): record}, see capture()
         self._pool = None
+        self._optimizer = None        # optim.DeviceAdamW whose update closes the captured step (capture(optimizer=...))
 
     def set_global_batch(self, global_batch):
         lo, hi = shard_bounds(global_batch, self.rank, self.world)
@@ -330,7 +332,7 @@ class DataParallelStep:
         return total
 
     @_in_step_context
-    def capture(self, h_a, h_t, m_a, m_t, y, collectives=False, lengths=None):
+    def capture(self, h_a, h_t, m_a, m_t, y, collectives=False, lengths=None, optimizer=None):
         """Record one step on static copies of the batch tensors; later ``step()`` calls replay it.
 
         collectives=True: the gradient exchange is captured INSIDE the graph -- every bucket's all-reduce is launched from its
@@ -344,8 +346,23 @@ class DataParallelStep:
         rounded up to a bucket (1/64 of the padded rows; the surplus rows form one extra all-zero sequence).  ``step()`` then
         serves EVERY batch of these shapes: a batch whose row counts fall into a bucket not seen yet captures that bucket's
         graph on the spot (same static inputs, one memory pool).  ``lengths`` = (audio lengths, text lengths) as host lists /
-        CPU tensors spares the device -> host read of the masks' row sums (one sync per step otherwise)."""
+        CPU tensors spares the device -> host read of the masks' row sums (one sync per step otherwise).
+
+        optimizer: an ``optim.DeviceAdamW`` built on this step's buckets.  Its three launches (sum of squares, finalize, update) are
+        recorded at the END of the captured step -- behind the captured exchange with collectives=True -- and in no warm-up pass,
+        so capture() itself moves neither parameters nor moments nor the step count.  ``step()`` then uploads the optimizer's
+        hyper-parameters (lr as a scheduler left it) before the replay and is the whole trainer step: no ``opt.step()`` after it.
+        Every scalar of the update is device data, so packed bucket graphs captured later share the one step count.  At world
+        size > 1 this needs collectives=True: an exchange after the replay would run behind the update."""
         from . import _ops
+        if optimizer is not None:
+            from .optim import DeviceAdamW
+            if not isinstance(optimizer, DeviceAdamW) or optimizer.buckets is not self.buckets:
+                raise TypeError("capture(optimizer=...) takes an optim.DeviceAdamW built on this step's buckets (every scalar of its "
+                                "update is device data; FusedClipAdamW passes lr and the step count by value)")
+            if self.world > 1 and not collectives:
+                raise RuntimeError("capture(optimizer=...) at world size > 1 needs collectives=True: the gradient exchange after the "
+                                   "replay would run behind the captured update")
         if collectives and not self.buckets._hooks:
             raise RuntimeError("capture(collectives=True) needs the gradient-ready hooks: GradBuckets(overlap=True) at world size > 1 "
                                "(or force_exchange=True)")
@@ -357,6 +374,7 @@ class DataParallelStep:
         self._static = [None if t is None else t.clone() for t in (h_a, h_t, m_a, m_t, y)]
         self.release_graph()              # a re-capture replaces the old graph(s): their pinned buffers go first
         self._collectives = bool(collectives)
+        self._optimizer = optimizer
         if _ops.varlen() and m_a is not None and m_t is not None:
             if collectives and self.world > 1:
                 raise RuntimeError("capture(collectives=True) in packed (varlen) mode: ranks meet new buckets at different steps and a "
@@ -484,6 +502,8 @@ class DataParallelStep:
                     loss = self._fwd_bwd(*self._static)
                     if collectives:
                         self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
+                    if self._optimizer is not None:
+                        self._optimizer._enqueue()    # recorded, not run: norm, skip / clip / bias corrections, update
             finally:
                 _ops.CTX.capturing = False
                 _ops.CTX.capture_origin = None
@@ -505,6 +525,7 @@ class DataParallelStep:
             self._graph = None
             self._keep = []
             self._pb = None
+            self._optimizer = None
             _ops.GRAPHS_ALIVE = max(0, _ops.GRAPHS_ALIVE - n)
             if _ops.GRAPHS_ALIVE == 0:
                 del _ops._ws_retired[:]   # no graph points into the outgrown workspaces any more
@@ -519,6 +540,8 @@ class DataParallelStep:
     def step(self, h_a, h_t, m_a, m_t, y, lengths=None):
         if self._graph is not None and getattr(self, "_replay", True):
             graph, loss = self._graph, self._static_loss
+            if self._optimizer is not None:
+                self._optimizer._upload_hyper()           # host -> device only; the replay reads lr & co. from that block
             if self._pb is not None:
                 # packed mode: any padding masks of the captured shapes; the lengths travel as device data (cu_seqlens), the row
                 # counts pick the bucket graph (captured now if this bucket was not seen before)
@@ -546,7 +569,13 @@ class DataParallelStep:
             graph.replay()
             if not self._exchange_in_graph:
                 self.buckets.finish()
+            if self._optimizer is not None:
+                from . import _ops
+                _ops.bump_weights_epoch()                 # the replay rewrote the parameters through raw pointers
+                self._optimizer._opt_called = True        # torch's lr schedulers warn about a scheduler.step() before any optimizer step
             return loss
         loss = self._fwd_bwd(h_a, h_t, m_a, m_t, y)
         self.buckets.finish()
+        if self._optimizer is not None:
+            self._optimizer.step()                        # use_graph(False): still the whole trainer step
         return loss

@@ -292,6 +292,22 @@ int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, int is_a, c
 int hriemo_sumsq_f32(const float* x, long n, float* partial, int nblocks, hriemo_stream_t stream);
 int hriemo_adamw_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                       float weight_decay, int step, float max_norm, const float* norm2, hriemo_stream_t stream);
+/* The same trainer step with EVERY scalar in device memory (hri-emo_amd/optim.py: DeviceAdamW), so the update can be recorded
+ * into the hipGraph of the step and still follow torch's LambdaLR, GradScaler and the NaN / Inf batch guard of
+ * scripts/fusion/train_mosei_fusion_seq_level_decoder.py:367-402,564-584 without a host read:
+ *   hyper[8] (host-written fp32):   lr, beta1, beta2, eps, weight_decay, max_norm (<= 0: no clipping), two spare words;
+ *   state[8] (device-written fp32): step, skip, coef, step_size = lr/bc1, 1/sqrt(bc2), decay = 1 - lr*wd, grad_norm (pre-clip,
+ *                                   unscaled), skipped (count of skipped steps); bcN = 1 - betaN^step.
+ * hriemo_optim_finalize (one block) sums the nblocks partials of hriemo_sumsq_f32 in a fixed order, norm = sqrt(sum)/grad_scale,
+ * skip = (found_inf != 0) || !isfinite(norm); a step that is not skipped increments `step` and writes
+ * coef = min(1, max_norm/(norm+1e-6))/grad_scale and the bias-correction terms of the new step; a skipped one increments `skipped`
+ * only.  grad_scale / found_inf (one fp32 each, torch.amp.GradScaler's device tensors) may be NULL: scale 1, nothing found.
+ * hriemo_adamw_flat_dev is hriemo_adamw_flat's arithmetic with its scalars read from hyper / state; a skipped step leaves p, m, v
+ * untouched. */
+int hriemo_optim_finalize(const float* partial, int nblocks, const float* hyper, const float* grad_scale, const float* found_inf,
+                          float* state, hriemo_stream_t stream);
+int hriemo_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* state,
+                          hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
