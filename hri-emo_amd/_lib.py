@@ -36,6 +36,7 @@ _SIGS = {
     "hriemo_attn_bwd_kv_colsum_rows": ("iiiii", "i"),
     "hriemo_attn_bwd_colsum_rows": ("iiii", "i"),
     "hriemo_attn_bwd_dq_colsum_rows": ("iiiii", "i"),
+    "hriemo_attn_plan": ("iiiiiipppppp", "i"),
     "hriemo_split_bf16x3": ("pliipiip", "i"),
     "hriemo_attn_fwd_f32": ("plplplplppiiiiifQpIip", "i"),
     "hriemo_attn_probs_f32": ("plplpppiiiiifQpIip", "i"),

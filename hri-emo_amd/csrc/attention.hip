@@ -18,6 +18,8 @@
 //  * attention dropout is replayed from a counter hash (common.h), nothing is stored.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 struct AttnArgs {
@@ -1066,10 +1068,10 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_hash_kernel(const AttnAr
 // Per query row the Q image's 32 pad bytes carry the row's sideband: {lse', delta', keep-mask dwords [tile][half]}.
 // PACKED: cu_seqlens launch (localize()); a separate instantiation because this kernel runs at the 256-register limit and the
 // per-sample pointers of the packed view cost the padded launch 13 us of 82 (a2t backward at cfg 2) when they share one body
-template <int HD, int NW, int KW, int QT, bool BITS, bool FUSED, bool PAIR = false, bool PACKED = false>
+template <int HD, int NW, int KW, int QT, bool BITS, bool FUSED, bool PACKED = false>
 // two waves per SIMD (256 registers) wherever the kernel fits them without spilling inside its loops (`make check-isa` prints the
 // spill counts per kernel and fails on scratch traffic inside a loop of a default-path kernel)
-__global__ __launch_bounds__(NW * 64 * (PAIR ? 2 : 1), (!FUSED && !PAIR && HD <= 96 && NW == 4 && KW == 1) ? 3 : ((PAIR || (HD <= 96 && NW == 4 && (KW == 1 || (BITS && !FUSED) || FUSED))) ? 2 : 1)) void attn_bwd_dkv_kernel(const AttnArgs a0) {
+__global__ __launch_bounds__(NW * 64, (!FUSED && HD <= 96 && NW == 4 && KW == 1) ? 3 : ((HD <= 96 && NW == 4 && (KW == 1 || (BITS && !FUSED) || FUSED)) ? 2 : 1)) void attn_bwd_dkv_kernel(const AttnArgs a0) {
   using G = AttnGeom<HD>;
   constexpr int KS = G::KS, DT = G::DT, STRIDE = G::STRIDE, NT = NW * 64;
   static_assert(QT == 32, "query tile");
@@ -1083,20 +1085,16 @@ __global__ __launch_bounds__(NW * 64 * (PAIR ? 2 : 1), (!FUSED && !PAIR && HD <=
   constexpr int IMG = 2 * QT * STRIDE;               // Q image + dO image
   constexpr int DSS = QT * 2 + 32;                   // row stride of the dS^T tile ([key][QT queries] bf16)
   constexpr int KT_BYTES = FUSED ? NK * STRIDE : 0, DST_BYTES = FUSED ? NK * DSS : 0;
-  constexpr int LDS_ONE = 2 * IMG + KT_BYTES + 2 * DST_BYTES;
-  // PAIR: one workgroup of 2*NW waves = two independent (batch, head) problems, each with its own NW waves and its own LDS half;
-  // they only share the barriers (same trip counts).  The fused kernel at 128 keys needs half the CU's LDS and a full register
-  // budget per problem; two problems per workgroup keep two waves per SIMD with ONE workgroup per CU (exactly two 80 KB
-  // workgroups would also fit, but a paired one does not depend on the dispatcher co-scheduling them).  (The wrong dS elements
-  // once seen at two waves per SIMD were a packed subtract -- see the (dP - delta') line further down -- not the pairing.)
-  __shared__ __attribute__((aligned(16))) char lds_all[LDS_ONE * (PAIR ? 2 : 1)];
-  const int sub = PAIR ? (int)(threadIdx.x / (NW * 64)) : 0;
-  char* const lds = lds_all + sub * LDS_ONE;
+  // One workgroup per (batch, head) problem.  Round 2 first shipped heads 2j, 2j+1 of a sample in ONE workgroup of 2*NW waves, each
+  // problem with its own LDS half: its block-wide barriers coupled the two problems -- a2t backward 80 us against 66 -- and that
+  // instantiation spilled inside its loops; removed in round 4.  (The wrong dS elements once seen at two waves per SIMD were a
+  // packed subtract -- see the (dP - delta') line further down -- not the pairing.)
+  __shared__ __attribute__((aligned(16))) char lds[2 * IMG + KT_BYTES + 2 * DST_BYTES];
   char* const Ktile = lds + 2 * IMG;
   char* const dSt0 = Ktile + KT_BYTES;
-  const int tid = PAIR ? (int)(threadIdx.x % (NW * 64)) : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
   int tile, bh;
-  tile_and_head((a0.Lk + NK - 1) / NK, a0.B * a0.H, tile, bh, PAIR ? (int)blockIdx.x * 2 + sub : (int)blockIdx.x);
+  tile_and_head((a0.Lk + NK - 1) / NK, a0.B * a0.H, tile, bh);
   const int b = bh / a0.H, h = bh - b * a0.H;
   const AttnArgs a = PACKED ? localize(a0, b, h) : a0;
   float* const cskv_row = a.cskv != nullptr ? a.cskv + (long)(b * gridDim_tiles(a0.Lk, NK) + tile) * (2L * a.H * HD) + h * HD : nullptr;
@@ -1365,7 +1363,7 @@ __global__ __launch_bounds__(NW * 64 * (PAIR ? 2 : 1), (!FUSED && !PAIR && HD <=
   f32x4 csk[DT], csv[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) { csk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; csv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  int tid_e = PAIR ? (int)(threadIdx.x % (NW * 64)) : (int)threadIdx.x;
+  int tid_e = (int)threadIdx.x;
   asm volatile("" : "+v"(tid_e));       // opaque: the epilogue's lane-derived addresses are rebuilt here, not carried through the loop
   const int i_e = tid_e & 15, g_e = (tid_e >> 4) & 3, kbase_e = tile * NK + (tid_e >> 6) * KW * 16;
 #pragma unroll
@@ -1503,26 +1501,149 @@ __global__ __launch_bounds__(64) void attn_probs_kernel(const AttnArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-// Sub-tiles per wave.  Measured on cfg 2 (profiles/): the forward is fastest with two 16-row query sub-tiles
-// per wave (K/V fragment reuse), the backward kernels with one (128 instead of ~220 VGPRs -> twice the
-// waves per SIMD to cover their long VALU chains, and less padding waste at L=400).
-static int attn_wide(int backward) { return backward ? 0 : 1; }      // (the backward's width is chosen per launch: bwd_wide)
-static int check_common(const AttnArgs& a, int hd) {
-  HRIEMO_CHECK(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0, "attn: empty problem");
+static int cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  }
+  return n;
+}
+
+// Backward tile width for a row side of length L (queries for dQ, keys for dK/dV).  Narrow blocks (64 rows, ~160
+// VGPRs, 3 per CU) win in general; but their blocks live as long as the whole key / query loop, so a grid that fills
+// the chip 1.33 times (B*H = 512, L = 128: 1024 blocks on 768 slots) runs a second, mostly empty round.  The wide tile
+// (128 rows, 2 blocks per CU) is picked when it fills its slots >= 90 % and the narrow one < 75 %
+// (scripts_dev/bench_attn_split.py: dK/dV at L_k = 128 51.0 vs 60.5 us, dQ at L_q = 128 39.8 vs 43.5 us).
+static bool bwd_wide(int L, int BH, int head_dim, int cus) {
+  if (L <= 64) return false;
+  if (head_dim > 96) return false;                       // register budgets above were measured for hd <= 96
+  const long sn = 3L * cus, sw = 2L * cus;
+  const long nn = (long)((L + 63) / 64) * BH, nw = (long)((L + 127) / 128) * BH;
+  const double en = (double)nn / (double)(((nn + sn - 1) / sn) * sn), ew = (double)nw / (double)(((nw + sw - 1) / sw) * sw);
+  return en < 0.75 && ew >= 0.9;
+}
+// Single-pass backward: one block holds all keys of a (batch, head) (16 < L_k <= 128) and produces dQ, dK and dV together
+// (5 GEMMs per tile instead of 7, Q/K/V/dO read once): a2t backward 82 us instead of 114 at cfg 2.
+// Its first build returned a few wrong dS elements per
+// launch with the bit-word mask at two waves per SIMD; traced to the compiler's packed form of the (dP - delta') subtraction
+// (v_pk_add_f32 with the low result reading the high dword of src1: round 3's scripts_dev/forensics reproduce it in 20 of 20
+// runs and isolate the operand select); the file is compiled without SLP vectorisation since (DESIGN.md section 3.2).
+static bool bwd_fused(int Lk, int head_dim) {
+  // (one 256-thread workgroup per (batch, head).  Round 2 first shipped heads 2j, 2j+1 of a sample in ONE 512-thread workgroup:
+  // its block-wide barriers coupled the two problems -- a2t backward 80 us against 66 -- and that instantiation spilled inside
+  // its loops; removed in round 4)
+  return Lk > 16 && Lk <= 128 && head_dim >= 32;
+}
+// Query-resident single pass (attn_bwd_qres_kernel): all queries of a (batch, head) in one block, the keys swept -- for
+// 16 < L_q <= 128 < L_k (t2a at cfg 2; the key-resident form above takes L_k <= 128) and for 16 < L_q <= 128 with L_k <= 16.
+static bool bwd_qres(int Lq, int Lk, int head_dim) {
+  return !bwd_fused(Lk, head_dim) && Lq > 16 && Lq <= 128 && head_dim >= 32;
+}
+
+// The launch plan of a shape: every choice between kernel forms and tile widths is made HERE, once.  attn_fwd_impl and
+// attn_bwd_impl launch exactly this, hriemo_attn_plan and the buffer-size queries report it, and the tests read it.  Grids,
+// block sizes and the column-sum row counts follow from the *_rows fields (rows per block: 128 = 4 waves x 2 sixteen-row
+// sub-tiles, 64 = 4 x 1, 16 = 1 x 1), never from the shape a second time.
+struct AttnPlan {
+  int fwd_rows;        // query rows per forward block: 128 (<4,2>), 64 (<4,1>), 16 (<1,1>)
+  int bwd_form;        // 0 two kernels, 1 key-resident single pass, 2 query-resident single pass
+  int dq_rows;         // rows per dQ block: 128 / 64 / 16; 0 when bwd_form != 0
+  int dkv_rows;        // rows per dK|dV block: 128 / 64 / 16; form 1: 64 (KW 1) or 128 (KW 2); form 2: 0
+  int dq_colsum_rows, kv_colsum_rows;      // rows of the column-sum partials the backward leaves (kernels index them b * tiles + tile)
+};
+static int tiles(int L, int rows) { return (L + rows - 1) / rows; }
+// cus <= 0: the CU count of this device
+static AttnPlan attn_plan(int B, int H, int Lq, int Lk, int head_dim, int cus) {
+  if (cus <= 0) cus = cu_count();
+  AttnPlan p = {};
+  // Sub-tiles per wave.  Measured on cfg 2 (profiles/): the forward is fastest with two 16-row query sub-tiles
+  // per wave (K/V fragment reuse), the backward kernels with one (128 instead of ~220 VGPRs -> twice the
+  // waves per SIMD to cover their long VALU chains, and less padding waste at L=400; bwd_wide has the exception).
+  // The forward takes two unless the key loop is short and the 128-row tiles pad the query side visibly more than
+  // 64-row tiles do (L_q = 400, L_k = 128: 512 vs 448 rows, 44.3 vs 40.5 us)
+  const bool short_keys_padded = Lk <= 128 && ((Lq + 63) / 64) * 64 * 20 < ((Lq + 127) / 128) * 128 * 19;
+  p.fwd_rows = (Lq > 64 && !short_keys_padded) ? 128 : Lq > 16 ? 64 : 16;
+  auto side = [&](int L) { return bwd_wide(L, B * H, head_dim, cus) ? 128 : L > 16 ? 64 : 16; };
+  if (bwd_fused(Lk, head_dim)) {
+    p.bwd_form = 1;
+    p.dkv_rows = Lk <= 64 ? 64 : 128;      // the block's key capacity: one or two 16-key sub-tiles per wave
+  } else if (bwd_qres(Lq, Lk, head_dim)) {
+    p.bwd_form = 2;
+  } else {
+    p.dq_rows = side(Lq);
+    p.dkv_rows = side(Lk);
+  }
+  // the single-pass kernels leave one row per batch on both sides
+  p.dq_colsum_rows = p.bwd_form != 0 ? B : B * tiles(Lq, p.dq_rows);
+  p.kv_colsum_rows = p.bwd_form != 0 ? B : B * tiles(Lk, p.dkv_rows);
+  return p;
+}
+
+static int check_shape(int B, int H, int Lq, int Lk, int hd) {
+  HRIEMO_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0, "attn: empty problem");
   HRIEMO_CHECK(hd == 16 || hd == 32 || hd == 64 || hd == 96 || hd == 128, "attn: head_dim %d not built (16/32/64/96/128)", hd);
+  return 0;
+}
+static int check_common(const AttnArgs& a, int hd) {
+  if (check_shape(a.B, a.H, a.Lq, a.Lk, hd)) return 1;
   HRIEMO_CHECK(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0, "attn: leading dims must be multiples of 8");
   HRIEMO_CHECK(((uintptr_t)a.Q % 16) == 0 && ((uintptr_t)a.K % 16) == 0 && ((uintptr_t)a.V % 16) == 0, "attn: unaligned Q/K/V");
   return 0;
 }
+static int check_packed(const AttnArgs& a) {
+  HRIEMO_CHECK((a.cu_q == nullptr) == (a.cu_k == nullptr), "attn: cu_seqlens_q and cu_seqlens_k must be given together");
+  HRIEMO_CHECK(a.cu_q == nullptr || a.kpm == nullptr, "attn: packed sequences carry their lengths, a key_padding_mask cannot be combined with them");
+  return 0;
+}
 
-#define DISPATCH_HD(hd, CALL)               \
-  switch (hd) {                             \
-    case 16: { CALL(16); } break;           \
-    case 32: { CALL(32); } break;           \
-    case 64: { CALL(64); } break;           \
-    case 96: { CALL(96); } break;           \
-    case 128: { CALL(128); } break;         \
+// The plan for callers and tests (host code, no launch).  cus <= 0: this device (256 CUs assumed without one).
+extern "C" int hriemo_attn_plan(int B, int H, int Lq, int Lk, int head_dim, int cus, int* fwd_rows, int* bwd_form, int* dq_rows,
+                                int* dkv_rows, int* dq_colsum_rows, int* kv_colsum_rows) {
+  HRIEMO_CHECK(fwd_rows != nullptr && bwd_form != nullptr && dq_rows != nullptr && dkv_rows != nullptr && dq_colsum_rows != nullptr &&
+                   kv_colsum_rows != nullptr, "attn_plan: bad arguments");
+  if (check_shape(B, H, Lq, Lk, head_dim)) return 1;
+  const AttnPlan p = attn_plan(B, H, Lq, Lk, head_dim, cus);
+  *fwd_rows = p.fwd_rows; *bwd_form = p.bwd_form; *dq_rows = p.dq_rows; *dkv_rows = p.dkv_rows;
+  *dq_colsum_rows = p.dq_colsum_rows; *kv_colsum_rows = p.kv_colsum_rows;
+  return 0;
+}
+// The older queries, each one field of the plan.  Those without L_q ask with L_q = 1, which no single-pass form over the queries
+// takes: the L_k-only rule.
+// 1 when the backward is the key-resident single kernel
+extern "C" int hriemo_attn_bwd_single_pass(int B, int H, int Lk, int head_dim) { return attn_plan(B, H, 1, Lk, head_dim, 0).bwd_form == 1; }
+// 1 if the backward of this shape is ONE kernel of either form (the forward then writes the dropout keep-mask as bit words)
+extern "C" int hriemo_attn_bwd_single_pass_q(int B, int H, int Lq, int Lk, int head_dim) { return attn_plan(B, H, Lq, Lk, head_dim, 0).bwd_form != 0; }
+// rows of the column-sum partials hriemo_attn_bwd leaves behind: dK|dV side ...
+extern "C" int hriemo_attn_bwd_kv_colsum_rows(int B, int H, int Lq, int Lk, int head_dim) { return attn_plan(B, H, Lq, Lk, head_dim, 0).kv_colsum_rows; }
+extern "C" int hriemo_attn_bwd_colsum_rows(int B, int H, int L, int head_dim) { return attn_plan(B, H, 1, L, head_dim, 0).kv_colsum_rows; }
+// ... and dQ side
+extern "C" int hriemo_attn_bwd_dq_colsum_rows(int B, int H, int Lq, int Lk, int head_dim) { return attn_plan(B, H, Lq, Lk, head_dim, 0).dq_colsum_rows; }
+
+extern "C" long hriemo_attn_mask_bytes(int B, int H, int Lq, int Lk) { return (long)B * H * Lq * ((Lk + 63) / 64) * 8; }
+
+// Run-time values as compile-time constants for a generic lambda: f(Int<HD>) for the head dim, f(Int<NW>, Int<W>) for the rows of a
+// block, f(std::bool_constant) for a flag.  Only the listed values are ever instantiated.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F> static void with_head_dim(int head_dim, F&& f) {
+  switch (head_dim) {
+    case 16: f(Int<16>{}); break;
+    case 32: f(Int<32>{}); break;
+    case 64: f(Int<64>{}); break;
+    case 96: f(Int<96>{}); break;
+    case 128: f(Int<128>{}); break;
   }
+}
+template <class F> static void with_tile(int rows, F&& f) {
+  if (rows == 128) f(Int<4>{}, Int<2>{});
+  else if (rows == 64) f(Int<4>{}, Int<1>{});
+  else f(Int<1>{}, Int<1>{});
+}
+template <class F> static void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 static void fill_drop(AttnArgs& a, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site, int b_offset) {
   DropCfg d = make_drop(p, seed, site);
@@ -1530,13 +1651,17 @@ static void fill_drop(AttnArgs& a, float p, uint64_t seed, const unsigned long l
   a.l2ik = d.thr16 != 0 ? log2f(d.inv_keep) : 0.f;
   a.keepfrac = d.thr16 != 0 ? 1.f / d.inv_keep : 1.f;
 }
-
-extern "C" long hriemo_attn_mask_bytes(int B, int H, int Lq, int Lk) { return (long)B * H * Lq * ((Lk + 63) / 64) * 8; }
-
-static int check_packed(const AttnArgs& a) {
-  HRIEMO_CHECK((a.cu_q == nullptr) == (a.cu_k == nullptr), "attn: cu_seqlens_q and cu_seqlens_k must be given together");
-  HRIEMO_CHECK(a.cu_q == nullptr || a.kpm == nullptr, "attn: packed sequences carry their lengths, a key_padding_mask cannot be combined with them");
-  return 0;
+// what every attention launch is given: operands, shape, softmax scale, dropout
+static AttnArgs attn_args(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, const unsigned char* key_padding_mask,
+                          const float* lse, int B, int H, int Lq, int Lk, int head_dim, float p_drop, unsigned long long seed,
+                          const unsigned long long* seed_dev, unsigned site, int b_offset) {
+  AttnArgs a = {};
+  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.V = (const bf16_t*)V;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.kpm = key_padding_mask; a.lse = (float*)lse; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
+  a.scale = 1.0f / sqrtf((float)head_dim);
+  fill_drop(a, p_drop, seed, seed_dev, site, b_offset);
+  return a;
 }
 
 static int attn_fwd_impl(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O,
@@ -1544,42 +1669,26 @@ static int attn_fwd_impl(const void* Q, long ldq, const void* K, long ldk, const
                          int Lk, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
                          unsigned site, int b_offset, void* drop_mask_bits, const int* cu_q, const int* cu_k, hipStream_t st,
                          void* Oq = nullptr, long ldoq = 0, void* So = nullptr, long ldso = 0) {
-  AttnArgs a = {};
+  AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, key_padding_mask, lse, B, H, Lq, Lk, head_dim, p_drop, seed, seed_dev, site, b_offset);
   a.cu_q = cu_q; a.cu_k = cu_k;
-  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.V = (const bf16_t*)V;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.O = (bf16_t*)O; a.ldo = ldo;
   a.Oq = (uint8_t*)Oq; a.ldoq = ldoq; a.So = (uint8_t*)So; a.ldso = ldso;
   HRIEMO_CHECK(Oq == nullptr || (cu_q == nullptr && head_dim % 32 == 0 && So != nullptr && ldoq % 4 == 0 && ((uintptr_t)Oq % 4) == 0 &&
                                  ldso >= (long)B * Lq),
                "attn_fwd: the MX-fp8 copy of O needs padded rows, head_dim %% 32 == 0 and a scale buffer of >= B*Lq columns");
-  a.kpm = key_padding_mask; a.lse = lse; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
-  a.scale = 1.0f / sqrtf((float)head_dim);
-  fill_drop(a, p_drop, seed, seed_dev, site, b_offset);
   a.mbits = (unsigned long long*)drop_mask_bits;
   if (check_common(a, head_dim) || check_packed(a)) return 1;
   HRIEMO_CHECK(ldo % 4 == 0 && ((uintptr_t)O % 8) == 0 && ((uintptr_t)drop_mask_bits % 8) == 0, "attn_fwd: unaligned O / mask bits");
+  const AttnPlan p = attn_plan(B, H, Lq, Lk, head_dim, 0);
   hriemo_prof_begin(HP_ATTN_FWD, st);
-  // two 16-row query sub-tiles per wave (K/V fragment reuse) unless the key loop is short and the 128-row tiles pad the
-  // query side visibly more than 64-row tiles do (L_q = 400, L_k = 128: 512 vs 448 rows, 44.3 vs 40.5 us)
-  const bool short_keys_padded = Lk <= 128 && ((Lq + 63) / 64) * 64 * 20 < ((Lq + 127) / 128) * 128 * 19;
-  const bool wb = a.mbits != nullptr && a.thr16 != 0;
-#define FWD(HD, NW_, QW_, GRID, THREADS)                                                                         \
-  if (wb) hipLaunchKernelGGL((attn_fwd_kernel<HD, NW_, QW_, true>), dim3(GRID), dim3(THREADS), 0, st, a);         \
-  else hipLaunchKernelGGL((attn_fwd_kernel<HD, NW_, QW_, false>), dim3(GRID), dim3(THREADS), 0, st, a)
-  if (Lq > 64 && attn_wide(0) && !short_keys_padded) {
-#define CALL(HD) FWD(HD, 4, 2, ((Lq + 127) / 128) * B * H, 256)
-    DISPATCH_HD(head_dim, CALL)
-#undef CALL
-  } else if (Lq > 16) {
-#define CALL(HD) FWD(HD, 4, 1, ((Lq + 63) / 64) * B * H, 256)
-    DISPATCH_HD(head_dim, CALL)
-#undef CALL
-  } else {
-#define CALL(HD) FWD(HD, 1, 1, B * H, 64)
-    DISPATCH_HD(head_dim, CALL)
-#undef CALL
-  }
-#undef FWD
+  with_head_dim(head_dim, [&](auto hd) {
+    with_tile(p.fwd_rows, [&](auto nw, auto w) {
+      with_bool(a.mbits != nullptr && a.thr16 != 0, [&](auto wb) {
+        hipLaunchKernelGGL((attn_fwd_kernel<decltype(hd)::value, decltype(nw)::value, decltype(w)::value, decltype(wb)::value>),
+                           dim3(tiles(Lq, p.fwd_rows) * B * H), dim3(decltype(nw)::value * 64), 0, st, a);
+      });
+    });
+  });
   HRIEMO_LAUNCH_CHECK("attn_fwd_kernel");
   hriemo_prof_end(HP_ATTN_FWD, st, 4.0 * B * H * (double)Lq * Lk * head_dim);
   return 0;
@@ -1613,84 +1722,6 @@ extern "C" int hriemo_attn_fwd_varlen(const void* Q, long ldq, const void* K, lo
                        site, b_offset, drop_mask_bits, cu_seqlens_q, cu_seqlens_k, st);
 }
 
-// Backward tile width for a row side of length L (queries for dQ, keys for dK/dV).  Narrow blocks (64 rows, ~160
-// VGPRs, 3 per CU) win in general; but their blocks live as long as the whole key / query loop, so a grid that fills
-// the chip 1.33 times (B*H = 512, L = 128: 1024 blocks on 768 slots) runs a second, mostly empty round.  The wide tile
-// (128 rows, 2 blocks per CU) is picked when it fills its slots >= 90 % and the narrow one < 75 %
-// (scripts_dev/bench_attn_split.py: dK/dV at L_k = 128 51.0 vs 60.5 us, dQ at L_q = 128 39.8 vs 43.5 us).
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-static bool bwd_wide(int L, int BH, int head_dim) {
-  if (L <= 64) return false;
-  if (attn_wide(1)) return true;
-  if (head_dim > 96) return false;                       // register budgets above were measured for hd <= 96
-  const long sn = 3L * cu_count(), sw = 2L * cu_count();
-  const long nn = (long)((L + 63) / 64) * BH, nw = (long)((L + 127) / 128) * BH;
-  const double en = (double)nn / (double)(((nn + sn - 1) / sn) * sn), ew = (double)nw / (double)(((nw + sw - 1) / sw) * sw);
-  return en < 0.75 && ew >= 0.9;
-}
-// Single-pass backward: one block holds all keys of a (batch, head) (16 < L_k <= 128) and produces dQ, dK and dV together
-// (5 GEMMs per tile instead of 7, Q/K/V/dO read once): a2t backward 82 us instead of 114 at cfg 2.
-// Its first build returned a few wrong dS elements per
-// launch with the bit-word mask at two waves per SIMD; traced to the compiler's packed form of the (dP - delta') subtraction
-// (v_pk_add_f32 with the low result reading the high dword of src1: round 3's scripts_dev/forensics reproduce it in 20 of 20
-// runs and isolate the operand select); the file is compiled without SLP vectorisation since (DESIGN.md section 3.2).
-static bool bwd_fused(int Lk, int head_dim, int B, int H) {
-  // (one 256-thread workgroup per (batch, head).  Round 2 first shipped heads 2j, 2j+1 of a sample in ONE 512-thread workgroup:
-  // its block-wide barriers coupled the two problems -- a2t backward 80 us against 66 -- and that instantiation spilled inside
-  // its loops; removed in round 4)
-  (void)B; (void)H;
-  return Lk > 16 && Lk <= 128 && head_dim >= 32;
-}
-
-extern "C" int hriemo_attn_bwd_colsum_rows(int B, int H, int L, int head_dim);
-extern "C" int hriemo_attn_bwd_single_pass(int B, int H, int Lk, int head_dim) { return bwd_fused(Lk, head_dim, B, H) ? 1 : 0; }
-
-// Query-resident single pass (attn_bwd_qres_kernel): all queries of a (batch, head) in one block, the keys swept -- for
-// 16 < L_q <= 128 < L_k (t2a at cfg 2; the key-resident form above takes L_k <= 128).
-static bool bwd_qres(int Lq, int Lk, int head_dim, int B, int H) {
-  return !bwd_fused(Lk, head_dim, B, H) && Lq > 16 && Lq <= 128 && head_dim >= 32;
-}
-// 1 if the backward of this shape is ONE kernel of either form (the forward then writes the dropout keep-mask as bit words)
-extern "C" int hriemo_attn_bwd_single_pass_q(int B, int H, int Lq, int Lk, int head_dim) {
-  return (bwd_fused(Lk, head_dim, B, H) || bwd_qres(Lq, Lk, head_dim, B, H)) ? 1 : 0;
-}
-// rows of the dK | dV column-sum partials when both lengths are known (the query-resident kernel leaves one row per batch)
-extern "C" int hriemo_attn_bwd_kv_colsum_rows(int B, int H, int Lq, int Lk, int head_dim) {
-  if (bwd_qres(Lq, Lk, head_dim, B, H)) return B;
-  return hriemo_attn_bwd_colsum_rows(B, H, Lk, head_dim);
-}
-
-// rows of the column-sum partials hriemo_attn_bwd leaves behind: dK|dV side (sequence of length Lk) ...
-extern "C" int hriemo_attn_bwd_colsum_rows(int B, int H, int L, int head_dim) {
-  if (bwd_fused(L, head_dim, B, H)) return B;
-  if (bwd_wide(L, B * H, head_dim)) return B * ((L + 127) / 128);
-  if (L > 16) return B * ((L + 63) / 64);
-  return B;
-}
-// ... and dQ side (depends on both lengths: the fused kernel writes one row per (batch, head))
-extern "C" int hriemo_attn_bwd_dq_colsum_rows(int B, int H, int Lq, int Lk, int head_dim) {
-  if (bwd_fused(Lk, head_dim, B, H) || bwd_qres(Lq, Lk, head_dim, B, H)) return B;
-  if (bwd_wide(Lq, B * H, head_dim)) return B * ((Lq + 127) / 128);
-  if (Lq > 16) return B * ((Lq + 63) / 64);
-  return B;
-}
-
-#define DISPATCH_HD_EVEN(hd, CALL)          \
-  switch (hd) {                             \
-    case 32: { CALL(32); } break;           \
-    case 64: { CALL(64); } break;           \
-    case 96: { CALL(96); } break;           \
-    case 128: { CALL(128); } break;         \
-  }
-
 static int attn_bwd_impl(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                          const void* O, long ldo, const void* dO, long lddo, void* dQ, long lddq, void* dK,
                          long lddk, void* dV, long lddv, const unsigned char* key_padding_mask,
@@ -1698,145 +1729,77 @@ static int attn_bwd_impl(const void* Q, long ldq, const void* K, long ldk, const
                          float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site, int b_offset,
                          float* dq_colsum_partials, float* dkv_colsum_partials, const void* drop_mask_bits, const int* cu_q,
                          const int* cu_k, hipStream_t st) {
-  AttnArgs a = {};
+  AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, key_padding_mask, lse, B, H, Lq, Lk, head_dim, p_drop, seed, seed_dev, site, b_offset);
   a.cu_q = cu_q; a.cu_k = cu_k;
-  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.V = (const bf16_t*)V;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.O = (bf16_t*)O; a.ldo = ldo;
+  a.O = (bf16_t*)O; a.ldo = ldo;
   a.csq = dq_colsum_partials; a.cskv = dkv_colsum_partials;
   a.dO = (const bf16_t*)dO; a.lddo = lddo;
   a.dQ = (bf16_t*)dQ; a.dK = (bf16_t*)dK; a.dV = (bf16_t*)dV; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.kpm = key_padding_mask; a.lse = (float*)lse; a.delta = delta; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
-  a.scale = 1.0f / sqrtf((float)head_dim);
-  fill_drop(a, p_drop, seed, seed_dev, site, b_offset);
+  a.delta = delta;
   a.mbits = (unsigned long long*)drop_mask_bits;
   if (check_common(a, head_dim) || check_packed(a)) return 1;
   HRIEMO_CHECK(ldo % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0, "attn_bwd: bad leading dims");
   HRIEMO_CHECK(((uintptr_t)O % 16) == 0 && ((uintptr_t)dO % 16) == 0 && ((uintptr_t)dQ % 8) == 0 &&
                    ((uintptr_t)dK % 8) == 0 && ((uintptr_t)dV % 8) == 0 && ((uintptr_t)drop_mask_bits % 8) == 0, "attn_bwd: unaligned operand");
-  const bool bits = a.thr16 != 0 && a.mbits != nullptr;
-  if (bwd_fused(Lk, head_dim, B, H)) {
-    hriemo_prof_begin(HP_ATTN_BWD_DKV, st);
+  const AttnPlan p = attn_plan(B, H, Lq, Lk, head_dim, 0);
+  const bool bits = a.thr16 != 0 && a.mbits != nullptr, packed = a.cu_q != nullptr;
+  const double flop = B * H * (double)Lq * Lk * head_dim;
+  if (p.bwd_form == 1) {
     // one 256-thread workgroup per (batch, head); two of them share a CU where two problems fit its LDS
-#define CALLF(HD, KW_, BITS_)                                                                                                    \
-  {                                                                                                                              \
-    if (a.cu_q != nullptr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, KW_, 32, BITS_, true, false, true>), dim3(B * H), dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, KW_, 32, BITS_, true, false>), dim3(B * H), dim3(256), 0, st, a);          \
-  }
-    if (Lk <= 64) {
-      if (bits) {
-#define CALL(HD) CALLF(HD, 1, true)
-        DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-      } else {
-#define CALL(HD) CALLF(HD, 1, false)
-        DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-      }
-    } else {
-      if (bits) {
-#define CALL(HD) CALLF(HD, 2, true)
-        DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-      } else {
-#define CALL(HD) CALLF(HD, 2, false)
-        DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-      }
-    }
-#undef CALLF
+    hriemo_prof_begin(HP_ATTN_BWD_DKV, st);
+    with_head_dim(head_dim, [&](auto hd) {
+      if constexpr (decltype(hd)::value >= 32)      // the single-pass forms are not built for head_dim 16 (bwd_fused, bwd_qres)
+        with_bool(p.dkv_rows == 128, [&](auto two) {
+          with_bool(bits, [&](auto bw) {
+            with_bool(packed, [&](auto pk) {
+              hipLaunchKernelGGL((attn_bwd_dkv_kernel<decltype(hd)::value, 4, decltype(two)::value ? 2 : 1, 32, decltype(bw)::value, true, decltype(pk)::value>),
+                                 dim3(B * H), dim3(256), 0, st, a);
+            });
+          });
+        });
+    });
     HRIEMO_LAUNCH_CHECK("attn_bwd_dkv_kernel (fused dQ)");
-    hriemo_prof_end(HP_ATTN_BWD_DKV, st, 10.0 * B * H * (double)Lq * Lk * head_dim);
+    hriemo_prof_end(HP_ATTN_BWD_DKV, st, 10.0 * flop);
     return 0;
   }
-  if (bwd_qres(Lq, Lk, head_dim, B, H)) {
+  if (p.bwd_form == 2) {
     hriemo_prof_begin(HP_ATTN_BWD_DKV, st);
-    if (bits) {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_qres_kernel<HD, true>), dim3(B * H), dim3(512), 0, st, a)
-      DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_qres_kernel<HD, false>), dim3(B * H), dim3(512), 0, st, a)
-      DISPATCH_HD_EVEN(head_dim, CALL)
-#undef CALL
-    }
+    with_head_dim(head_dim, [&](auto hd) {
+      if constexpr (decltype(hd)::value >= 32)
+        with_bool(bits, [&](auto bw) {
+          hipLaunchKernelGGL((attn_bwd_qres_kernel<decltype(hd)::value, decltype(bw)::value>), dim3(B * H), dim3(512), 0, st, a);
+        });
+    });
     HRIEMO_LAUNCH_CHECK("attn_bwd_qres_kernel");
-    hriemo_prof_end(HP_ATTN_BWD_DKV, st, 10.0 * B * H * (double)Lq * Lk * head_dim);
+    hriemo_prof_end(HP_ATTN_BWD_DKV, st, 10.0 * flop);
     return 0;
   }
   hriemo_prof_begin(HP_ATTN_BWD_DQ, st);
-  if (bwd_wide(Lq, B * H, head_dim)) {
-    if (bits) {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 4, 2, true>), dim3(((Lq + 127) / 128) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 4, 2, false>), dim3(((Lq + 127) / 128) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  } else if (Lq > 16) {
-    if (bits) {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 4, 1, true>), dim3(((Lq + 63) / 64) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 4, 1, false>), dim3(((Lq + 63) / 64) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  } else {
-    if (bits) {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 1, 1, true>), dim3(B * H), dim3(64), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 1, 1, false>), dim3(B * H), dim3(64), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  }
+  with_head_dim(head_dim, [&](auto hd) {
+    with_tile(p.dq_rows, [&](auto nw, auto w) {
+      with_bool(bits, [&](auto bw) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<decltype(hd)::value, decltype(nw)::value, decltype(w)::value, decltype(bw)::value>),
+                           dim3(tiles(Lq, p.dq_rows) * B * H), dim3(decltype(nw)::value * 64), 0, st, a);
+      });
+    });
+  });
   HRIEMO_LAUNCH_CHECK("attn_bwd_dq_kernel");
-  hriemo_prof_end(HP_ATTN_BWD_DQ, st, 6.0 * B * H * (double)Lq * Lk * head_dim);
+  hriemo_prof_end(HP_ATTN_BWD_DQ, st, 6.0 * flop);
   hriemo_prof_begin(HP_ATTN_BWD_DKV, st);
-  if (bwd_wide(Lk, B * H, head_dim)) {
-    if (bits) {
-#define CALL(HD)                                                                                                             \
-  if (a.cu_q != nullptr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, 2, 32, true, false, false, true>), dim3(((Lk + 127) / 128) * B * H), dim3(256), 0, st, a); \
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, 2, 32, true, false>), dim3(((Lk + 127) / 128) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dkv_hash_kernel<HD, 4, 2, 32>), dim3(((Lk + 127) / 128) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  } else if (Lk > 16) {
-    if (bits) {
-#define CALL(HD)                                                                                                             \
-  if (a.cu_q != nullptr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, 1, 32, true, false, false, true>), dim3(((Lk + 63) / 64) * B * H), dim3(256), 0, st, a); \
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 4, 1, 32, true, false>), dim3(((Lk + 63) / 64) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dkv_hash_kernel<HD, 4, 1, 32>), dim3(((Lk + 63) / 64) * B * H), dim3(256), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  } else {
-    if (bits) {
-#define CALL(HD)                                                                                                             \
-  if (a.cu_q != nullptr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 1, 1, 32, true, false, false, true>), dim3(B * H), dim3(64), 0, st, a); \
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 1, 1, 32, true, false>), dim3(B * H), dim3(64), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    } else {
-#define CALL(HD) hipLaunchKernelGGL((attn_bwd_dkv_hash_kernel<HD, 1, 1, 32>), dim3(B * H), dim3(64), 0, st, a)
-      DISPATCH_HD(head_dim, CALL)
-#undef CALL
-    }
-  }
+  with_head_dim(head_dim, [&](auto hd) {
+    with_tile(p.dkv_rows, [&](auto nw, auto kw) {
+      const dim3 grid(tiles(Lk, p.dkv_rows) * B * H), block(decltype(nw)::value * 64);
+      if (bits)       // PACKED is a separate instantiation of this kernel only (see its comment); the hash replay localizes in one body
+        with_bool(packed, [&](auto pk) {
+          hipLaunchKernelGGL((attn_bwd_dkv_kernel<decltype(hd)::value, decltype(nw)::value, decltype(kw)::value, 32, true, false, decltype(pk)::value>),
+                             grid, block, 0, st, a);
+        });
+      else
+        hipLaunchKernelGGL((attn_bwd_dkv_hash_kernel<decltype(hd)::value, decltype(nw)::value, decltype(kw)::value, 32>), grid, block, 0, st, a);
+    });
+  });
   HRIEMO_LAUNCH_CHECK("attn_bwd_dkv_kernel");
-  hriemo_prof_end(HP_ATTN_BWD_DKV, st, 8.0 * B * H * (double)Lq * Lk * head_dim);
+  hriemo_prof_end(HP_ATTN_BWD_DKV, st, 8.0 * flop);
   return 0;
 }
 
@@ -1867,16 +1830,12 @@ extern "C" int hriemo_attn_probs(const void* Q, long ldq, const void* K, long ld
                                  const float* lse, float* probs, int B, int H, int Lq, int Lk, int head_dim,
                                  float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site, int b_offset,
                                hipStream_t st) {
-  AttnArgs a = {};
-  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.V = (const bf16_t*)K;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldk;
-  a.kpm = key_padding_mask; a.lse = (float*)lse; a.probs = probs; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
-  a.scale = 1.0f / sqrtf((float)head_dim);
-  fill_drop(a, p_drop, seed, seed_dev, site, b_offset);
+  AttnArgs a = attn_args(Q, ldq, K, ldk, K, ldk, key_padding_mask, lse, B, H, Lq, Lk, head_dim, p_drop, seed, seed_dev, site, b_offset);
+  a.probs = probs;
   if (check_common(a, head_dim)) return 1;
-#define CALL(HD) hipLaunchKernelGGL((attn_probs_kernel<HD>), dim3((Lk + 63) / 64, (Lq + 7) / 8, B), dim3(64), 0, st, a)
-  DISPATCH_HD(head_dim, CALL)
-#undef CALL
+  with_head_dim(head_dim, [&](auto hd) {
+    hipLaunchKernelGGL((attn_probs_kernel<decltype(hd)::value>), dim3((Lk + 63) / 64, (Lq + 7) / 8, B), dim3(64), 0, st, a);
+  });
   HRIEMO_LAUNCH_CHECK("attn_probs_kernel");
   return 0;
 }

@@ -133,6 +133,14 @@ int hriemo_attn_bwd_single_pass(int B, int H, int Lk, int head_dim);
  * per key tile) -- and the rows of the dK | dV column-sum partials hriemo_attn_bwd then leaves behind. */
 int hriemo_attn_bwd_single_pass_q(int B, int H, int Lq, int Lk, int head_dim);
 int hriemo_attn_bwd_kv_colsum_rows(int B, int H, int Lq, int Lk, int head_dim);
+/* The launch plan of a shape (host code, no launch): what hriemo_attn_fwd / hriemo_attn_bwd launch for it on a device of `cus`
+ * compute units (cus <= 0: this device).  fwd_rows: query rows per forward block (128 / 64 / 16); bwd_form: 0 two kernels, 1
+ * key-resident single pass, 2 query-resident single pass; dq_rows / dkv_rows: rows per dQ and per dK | dV block (128 / 64 / 16;
+ * form 1: dq_rows 0, dkv_rows 64 or 128 = the block's key capacity; form 2: both 0); dq_colsum_rows / kv_colsum_rows: rows of the
+ * two column-sum partial buffers below.  Every query around it is one field of this plan.  Non-zero (hriemo_last_error) for an
+ * empty problem or a head_dim that is not built. */
+int hriemo_attn_plan(int B, int H, int Lq, int Lk, int head_dim, int cus, int* fwd_rows, int* bwd_form, int* dq_rows, int* dkv_rows,
+                     int* dq_colsum_rows, int* kv_colsum_rows);
 /* Packed (varlen) sequences, SURVEY 8(f) rank 4: the reference pads every sample to the batch maximum
  * (scripts/fusion/train_fusion_seq_level_decoder.py:191-232) and computes the PAD rows; here Q / O / dO / dQ hold the valid rows of
  * all samples back to back (sample b = rows cu_seqlens_q[b] .. cu_seqlens_q[b+1]-1) and K / V / dK / dV likewise with
@@ -159,9 +167,10 @@ int hriemo_attn_bwd_varlen(const void* Q, long ldq, const void* K, long ldk, con
                            float* dkv_colsum_partials, const void* drop_mask_bits, hriemo_stream_t stream);
 /* Optional by-product of hriemo_attn_bwd (either pointer may be NULL): per-block column sums of the dQ tiles,
  * [hriemo_attn_bwd_dq_colsum_rows(B, H, Lq, Lk, head_dim), H*head_dim] fp32, and of the dK | dV tiles,
- * [hriemo_attn_bwd_colsum_rows(B, H, Lk, head_dim), 2*H*head_dim] fp32 (values before their bf16 rounding).  Summed over rows
- * (hriemo_colreduce_batch) they are the gradient of the packed in-projection bias (in_proj_bias of nn.MultiheadAttention,
- * cross_modal_block_tacfn.py:24-40) without re-reading dQ/dK/dV. */
+ * [hriemo_attn_bwd_kv_colsum_rows(B, H, Lq, Lk, head_dim), 2*H*head_dim] fp32 (values before their bf16 rounding).  Summed over
+ * rows (hriemo_colreduce_batch) they are the gradient of the packed in-projection bias (in_proj_bias of nn.MultiheadAttention,
+ * cross_modal_block_tacfn.py:24-40) without re-reading dQ/dK/dV.  hriemo_attn_bwd_colsum_rows is the rule without L_q: it
+ * names more rows than are written where the query-resident kernel leaves one row per batch. */
 int hriemo_attn_bwd_colsum_rows(int B, int H, int L, int head_dim);
 int hriemo_attn_bwd_dq_colsum_rows(int B, int H, int Lq, int Lk, int head_dim);
 /* head-averaged attention probabilities [B,Lq,Lk] fp32 (need_weights=True; return_attention path,

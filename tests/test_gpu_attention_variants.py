@@ -2,11 +2,12 @@
 reference of tests/attn_reference.py with limits that come from that reference alone (attn_reference.check), at mask patterns
 that sit on the tile edges, and with every output inside a guarded buffer so that a store outside it is seen.
 
-The variant table names, per row, the form each launch must take.  The backward form is asserted THROUGH THE ABI (the
-dispatch predicates exported for the callers' buffer sizing), so a change of the heuristics that takes a kernel out of the
-table fails here with "update the table" instead of thinning the coverage silently.  The forward rule does not depend on the
-device; the table's forward column is checked against a replica of it.  Rows with B = W use the first batch size for which
+The variant table names, per row, the form each launch must take.  Both forms are asserted THROUGH THE ABI (hriemo_attn_plan:
+the plan the launches themselves follow), so a change of the heuristics that takes a kernel out of the table fails here with
+"update the table" instead of thinning the coverage silently.  Rows with B = W use the first batch size for which
 the ABI reports the 128-row tile on this device (it depends on the CU count); finding none is a failure.  Nothing skips."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -81,34 +82,31 @@ def ops():
     return _ops
 
 
-def forward_form(Lq, Lk):
-    """replica of the forward's tile choice in attn_fwd_impl (no device property enters it)"""
-    short_keys_padded = Lk <= 128 and ((Lq + 63) // 64) * 64 * 20 < ((Lq + 127) // 128) * 128 * 19
-    if Lq > 64 and not short_keys_padded:
-        return "fwd<4,2>"
-    return "fwd<4,1>" if Lq > 16 else "fwd<1,1>"
+FWD_FORM = {128: "fwd<4,2>", 64: "fwd<4,1>", 16: "fwd<1,1>"}       # rows per block -> <waves, 16-row sub-tiles per wave>
+BWD_SIDE = {128: "w128", 64: "n64", 16: "1w"}
 
 
-def _side(rows, B, L):
-    """tile form of one side of the two-kernel backward from the number of column-sum partial rows the ABI reports.  For
-    16 < L <= 64 both tile widths leave B rows; the wide tile is never taken there (bwd_wide: L > 64)."""
-    if L <= 16:
-        return "1w" if rows == B else f"?({rows} rows)"
-    if rows == B * ((L + 63) // 64):
-        return "n64"
-    return "w128" if rows == B * ((L + 127) // 128) else f"?({rows} rows)"
+def plan(L_, B, H, Lq, Lk, hd, cus=0):
+    """hriemo_attn_plan (host code, no launch; cus = 0: this device): (fwd_rows, bwd_form, dq_rows, dkv_rows, dq_colsum_rows,
+    kv_colsum_rows), or None where the library refuses the shape"""
+    out = [ctypes.c_int() for _ in range(6)]
+    if L_.hriemo_attn_plan(B, H, Lq, Lk, hd, cus, *(ctypes.byref(o) for o in out)) != 0:
+        return None
+    return tuple(o.value for o in out)
 
 
-def backward_form(L_, B, H, Lq, Lk, hd):
-    """the form hriemo_attn_bwd takes for this shape on this device, from the exported dispatch predicates"""
-    rq, rk = L_.hriemo_attn_bwd_dq_colsum_rows(B, H, Lq, Lk, hd), L_.hriemo_attn_bwd_kv_colsum_rows(B, H, Lq, Lk, hd)
-    if L_.hriemo_attn_bwd_single_pass(B, H, Lk, hd):
-        assert L_.hriemo_attn_bwd_single_pass_q(B, H, Lq, Lk, hd) and rq == B and rk == B
-        return "fused-KW1" if Lk <= 64 else "fused-KW2"     # the key width follows L_k alone (attn_bwd_impl)
-    if L_.hriemo_attn_bwd_single_pass_q(B, H, Lq, Lk, hd):
-        assert rq == B and rk == B
+def forward_form(L_, B, H, Lq, Lk, hd, cus=0):
+    return FWD_FORM[plan(L_, B, H, Lq, Lk, hd, cus)[0]]
+
+
+def backward_form(L_, B, H, Lq, Lk, hd, cus=0):
+    """the form hriemo_attn_bwd takes for this shape, from the plan it launches"""
+    _, form, dq_rows, dkv_rows, _, _ = plan(L_, B, H, Lq, Lk, hd, cus)
+    if form == 1:
+        return "fused-KW1" if dkv_rows == 64 else "fused-KW2"
+    if form == 2:
         return "qres"
-    return f"two-kernel(dq={_side(rq, B, Lq)},dkv={_side(rk, B, Lk)})"
+    return f"two-kernel(dq={BWD_SIDE[dq_rows]},dkv={BWD_SIDE[dkv_rows]})"
 
 
 def wide_batch(L_, H, Lq, Lk, hd, want):
@@ -169,7 +167,7 @@ def test_attention_variant(ops, B, H, Lq, Lk, hd, pattern, p, fwd, bwd):
     got_form = backward_form(L_, B, H, Lq, Lk, hd)
     assert got_form == bwd, (f"the backward of (B={B}, H={H}, Lq={Lq}, Lk={Lk}, hd={hd}) is now {got_form}, the variant table "
                              f"says {bwd}: update the table so that every kernel form stays covered")
-    assert forward_form(Lq, Lk) == fwd, (forward_form(Lq, Lk), fwd)
+    assert forward_form(L_, B, H, Lq, Lk, hd) == fwd, (forward_form(L_, B, H, Lq, Lk, hd), fwd)
     d = H * hd
     qb, kvb, dob = R.make_inputs(B, H, Lq, Lk, hd, 100 + Lq + Lk)
     kpm = R.key_padding_mask(pattern, B, Lk)
