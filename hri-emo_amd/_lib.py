@@ -111,6 +111,12 @@ _SIGS = {
     "hriemo_ln_pool_bwd_pair": ("pip" + "ppppppppppip" * 2 + "iiip", "i"),
     "hriemo_ln_pool_bwd_workspace_bytes": ("iii", "l"),
     "hriemo_ln_pool_bwd": ("pipipppppppppp" + "iiiipp", "i"),
+    "hriemo_ln_pool_fwd_packed": ("pppiippppppipiiifp", "i"),
+    "hriemo_ln_pool_fwd_packed_pair": ("pppiippppppi" * 2 + "piiifp", "i"),
+    "hriemo_fuse_fwd_packed": ("pppppiiiip", "i"),
+    "hriemo_fuse_bwd_dw_packed": ("pppppiiiip", "i"),
+    "hriemo_ln_pool_bwd_packed": ("ppipippppiipppppp" + "iiiipp", "i"),
+    "hriemo_ln_pool_bwd_packed_pair": ("ppip" + "ppppiippppppip" * 2 + "iiip", "i"),
     "hriemo_prof_enable": ("i", "i"),
     "hriemo_prof_nclass": ("", "i"),
     "hriemo_prof_collect": ("ippp", "i"),

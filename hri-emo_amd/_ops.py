@@ -103,7 +103,7 @@ class StepContext:
     it around capture() / step() (use_context); models used on their own run on the module's default context.
       capturing      set by DataParallelStep.capture(): weight shadows are re-cast inside the graph, buffers are kept, not freed
       capture_origin the stream the capture runs on (every helper-stream fork must start there: fork())
-      seq_override   (Seq audio, Seq text) injected for the bucketed packed graphs (models/cross_modal_block_tacfn.py)
+      seq_override   (Seq audio, Seq text, Seq fused) injected for the bucketed packed graphs (models/cross_modal_block_tacfn.py)
       join_scope     > 0 inside a forward whose outputs ALL depend on both encoder branches (grad_join)
       half_reports   id(parameter) -> SharedProjFn nodes that have written their half of its gradient in this step"""
     __slots__ = ("capturing", "capture_origin", "seq_override", "join_scope", "half_reports")
@@ -1192,15 +1192,31 @@ def varlen():
     return VARLEN
 
 
+# The tail of the model on packed rows: with the encoder packed, the gate reads its packed output and hands the decoder a packed
+# fused memory (PackedBetaGateFn, hriemo_*_packed), so no unpack / pack launch runs behind the encoder.  False: the encoder's output
+# is scattered back to the padded layout in front of the gate (exactly the launches from before the packed tail) -- the A/B handle.
+# Opt-in until the step has been measured against the False arm (scripts_dev/ab_packed_tail.sh).
+PACKED_TAIL = False
+
+
+def packed_tail():
+    """the tail stays packed: bf16 precision and bf16 GEMM operands (the fp32 mode and the MX-fp8 mode unpack behind the encoder)"""
+    return PACKED_TAIL and precision() == "bf16" and gemm_mode() == "bf16"
+
+
 class Seq:
     """packed rows of one modality: cu int32 [B+1] (device), idx int64 [N] packed row -> row of the padded [Breal*L] layout.
     Bucketed form (seq_bucket, one captured graph for every batch): N = the bucket's row count, the rows beyond the last real
-    sequence form ONE extra sequence (B = Breal + 1, cu has B+1 entries) of zeros, so every kernel writes every row."""
-    __slots__ = ("cu", "idx", "B", "L", "Lmax", "N", "Breal")
+    sequence form ONE extra sequence (B = Breal + 1, cu has B+1 entries) of zeros, so every kernel writes every row.
+    surplus: rows behind the last sequence that belong to NO sequence of the plan (the fused memory of a bucket, seq_bucket_fused):
+    the attention kernels never see them, the kernels that write such a buffer write them as zeros.
+    idx None: the rows are the padded rows themselves (the decoder's queries, query_seq)."""
+    __slots__ = ("cu", "idx", "B", "L", "Lmax", "N", "Breal", "surplus")
 
-    def __init__(self, cu, idx, B, L, Lmax, N, Breal=None):
+    def __init__(self, cu, idx, B, L, Lmax, N, Breal=None, surplus=False):
         self.cu, self.idx, self.B, self.L, self.Lmax, self.N = cu, idx, B, L, Lmax, N
         self.Breal = B if Breal is None else Breal
+        self.surplus = bool(surplus)
 
 
 def seq_bucket(cu, B, L, n_rows):
@@ -1210,6 +1226,53 @@ def seq_bucket(cu, B, L, n_rows):
     idx = torch.empty(n_rows, dtype=torch.int64, device=cu.device)      # written by the first pack of the step (hriemo_pack_rows)
     return Seq(cu, idx, B + 1, L, L, n_rows, Breal=B)
 
+
+def seq_bucket_fused(cu_f, B, L, n_rows):
+    """Seq of the fused memory (sample b: min(audio length, text length) rows) over `n_rows` packed rows, lengths in DEVICE memory:
+    cu_f int32 [B+2] = [0, cumulative fused lengths ..., n_rows].  n_rows is the text bucket's row count (sum of the fused lengths
+    <= sum of the text lengths), so the fused plan adds no bucket dimension.  The rows behind cu_f[B] are surplus, not a sequence:
+    the decoder's attention runs the B real sequences only."""
+    return Seq(cu_f, None, B, L, L, n_rows, surplus=True)
+
+
+_QUERY_SEQS = {}
+
+
+def query_seq(B, n, device):
+    """the trivial Seq of the decoder's queries: n rows for every sample, the packed rows are the padded rows (idx None)"""
+    key = (B, n, str(device))
+    s = _QUERY_SEQS.get(key)
+    if s is None:
+        s = _QUERY_SEQS[key] = Seq(torch.arange(B + 1, dtype=torch.int32, device=device) * n, None, B, n, n, B * n)
+    return s
+
+
+_FUSED_PLANS = {}
+
+
+def fused_seq(sa, st):
+    """Seq of the fused memory for the plans of two prefix masks (seq_plan): lf[b] = min(la[b], lt[b]) -- the reference ORs the two
+    masks cut to L_t (models/fusion_with_emotion_decoder.py:62-79), both are prefix masks, and lf >= 1 because seq_plan refuses
+    empty sequences.  One device -> host read per distinct pair of plans."""
+    key = (id(sa), id(st))
+    hit = _FUSED_PLANS.get(key)
+    if hit is not None:
+        return hit[0]
+    if CTX.capturing:
+        raise RuntimeError("varlen: the sequence lengths must be known before the step is captured (run one eager step first)")
+    B = sa.Breal
+    la, lt = sa.cu[1:B + 1] - sa.cu[:B], st.cu[1:B + 1] - st.cu[:B]
+    lf = torch.minimum(la, lt)
+    cu = torch.zeros(B + 1, dtype=torch.int32, device=lf.device)
+    cu[1:] = torch.cumsum(lf, 0)
+    L = min(sa.L, st.L)
+    # Lmax = the padded fused length, not the longest sample: the decoder's attention launches then pick the kernel variant of the
+    # padded call, whatever the batch's lengths (its grid is N_e query rows per sample either way)
+    sf = Seq(cu, None, B, L, L, int(lf.sum()))
+    if len(_FUSED_PLANS) > 64:
+        _FUSED_PLANS.clear()
+    _FUSED_PLANS[key] = (sf, sa, st)          # the plans stay referenced: their ids are the key
+    return sf
 
 
 
@@ -1240,6 +1303,14 @@ def seq_plan(mask, B, L):
         _SEQ_PLANS.clear()
     _SEQ_PLANS[key] = (plan, mask)            # the mask stays referenced: its address is the key
     return plan
+
+
+def seq_plans(mask_a, mask_t, B, La, Lt):
+    """(Seq audio, Seq text, Seq fused) for the two padding masks of a batch, or None when either is not a prefix mask"""
+    sa, st = seq_plan(mask_a, B, La), seq_plan(mask_t, B, Lt)
+    if sa is None or st is None:
+        return None
+    return sa, st, fused_seq(sa, st)
 
 
 class PackFn(torch.autograd.Function):
@@ -1452,6 +1523,7 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
                 raise ValueError("attention maps are exported by the padded path only")
             sq, sk = kpm
             AB, ALq, ALk, cu, RL, rows, kpm = sq.B, sq.Lmax, sk.Lmax, (sq.cu, sk.cu), sq.L, sq.idx, None
+            ctx.kv_surplus = sk.surplus       # key rows of no sequence: the attention backward leaves their dK | dV unwritten
         xq2 = _contig_bf16(xq).view(B * Lq, d)
         xq32 = _c32(xq32)
         x32v = xq32.view(B * Lq, d) if xq32 is not None else None
@@ -1542,7 +1614,7 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
         linear_dw(dg, o, dw_out, acc)
         do = linear_dx(dg, w_out16)
         dq = torch.empty((B * Lq, d), dtype=BF16, device=dev)
-        dkv = torch.empty((B * Lk, 2 * d), dtype=BF16, device=dev)
+        dkv = (torch.zeros if getattr(ctx, "kv_surplus", False) else torch.empty)((B * Lk, 2 * d), dtype=BF16, device=dev)
         db_in = sink.buf(p_b_in)
         folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, AB, H, ALq, ALk, hd, kpm, p, seed,
                           site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=cu)
@@ -1888,17 +1960,29 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
 
 
 class BetaGateFn(_GradModeAware, torch.autograd.Function):
-    """(h_fusion, beta) = BetaGate(h_a, h_t, masks)  -- models/beta_gate_tacfn.py:68-118"""
+    """(h_fusion, beta) = BetaGate(h_a, h_t, masks)  -- models/beta_gate_tacfn.py:68-118
+    plan = (Seq audio, Seq text, Seq fused): the packed form.  h_a / h_t (and twins) are the encoder's packed rows [1, N, d], h_fusion
+    comes back as the packed fused memory [1, N_f, d] (sample b: min(la, lt) rows, surplus rows zero) and backward returns the
+    packed dX of both modalities -- the hriemo_*_packed kernels in place of the padded ones, everything else (gate MLP, GradSink,
+    deferred reduces, pair / two-stream variants) is the same code."""
 
     @staticmethod
-    def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t):
+    def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan=None):
         if precision() == "fp32":            # -> (h_fusion as the fp32 tensor itself, beta)
+            if plan is not None:
+                raise RuntimeError("BetaGate: the packed tail is built for the bf16 precision mode")
             return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t)
         _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
         _require_gpu(h_a)
         h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
-        B, La, d = h_a.shape
-        Lt = h_t.shape[1]
+        if plan is not None:
+            sa, sq_t, sf = plan
+            B, La, Lt, d = sa.Breal, sa.L, sq_t.L, h_a.shape[-1]
+            if h_a.shape[1] != sa.N or h_t.shape[1] != sq_t.N:
+                raise ValueError(f"BetaGate: packed rows {h_a.shape[1]} / {h_t.shape[1]} do not match the plan ({sa.N} / {sq_t.N})")
+        else:
+            B, La, d = h_a.shape
+            Lt = h_t.shape[1]
         L = La if La == Lt else Lt                      # :98-104 (align to the text length)
         if La < L:
             raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
@@ -1907,35 +1991,49 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         L_ = _lib.lib()
         nca, nct = L_.hriemo_pool_chunks(La), L_.hriemo_pool_chunks(Lt)
-        An = torch.empty((B, L, d), dtype=BF16, device=dev)
-        Tn = torch.empty((B, L, d), dtype=BF16, device=dev)
-        mean_a, rstd_a = torch.empty(B * La, **f32), torch.empty(B * La, **f32)
-        mean_t, rstd_t = torch.empty(B * Lt, **f32), torch.empty(B * Lt, **f32)
+        # rows of the two modalities and of the fused buffers (An, Tn, H)
+        Ra, Rt, fshape = (sa.N, sq_t.N, (1, sf.N, d)) if plan is not None else (B * La, B * Lt, (B, L, d))
+        An = torch.empty(fshape, dtype=BF16, device=dev)
+        Tn = torch.empty(fshape, dtype=BF16, device=dev)
+        mean_a, rstd_a = torch.empty(Ra, **f32), torch.empty(Ra, **f32)
+        mean_t, rstd_t = torch.empty(Rt, **f32), torch.empty(Rt, **f32)
         pa, pt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
         st = _stream()
+
+        def ln_pool(x, x32, kpm, seq, gamma, beta_, Yn, mean, rstd, part, Lx):
+            if plan is not None:
+                _lib.call("hriemo_ln_pool_fwd_packed", _p(x), _p(x32), _p(seq.cu), seq.B, seq.N, _p(gamma), _p(beta_), _p(Yn), _p(mean),
+                          _p(rstd), _p(part), Lx, _p(sf.cu), sf.N, B, d, _EPS, _stream())
+            else:
+                _lib.call("hriemo_ln_pool_fwd", _p(x), _p(x32), _p(kpm), _p(gamma), _p(beta_), _p(Yn), _p(mean), _p(rstd), _p(part),
+                          B, Lx, L, d, _EPS, _stream())
+
+        seq_a, seq_t = (sa, sq_t) if plan is not None else (None, None)
         # the two modalities' LayerNorm + pooling are independent: the (small) text one runs on the side stream beside the audio one
         main = torch.cuda.current_stream(dev)
         side = side_stream(dev) if GATE_TWO_STREAMS else None
         if GATE_PAIR and L_.hriemo_ln_pool_pair_supported(d):
             # both modalities from one launch: no fork / join around the step (two graph edges and 10-27 us of idle device each)
-            _lib.call("hriemo_ln_pool_fwd_pair", _p(xa), _p(h_a32), _p(kpm_a), _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa), La,
-                      _p(xt), _p(h_t32), _p(kpm_t), _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt), Lt, B, L, d, _EPS, st)
+            if plan is not None:
+                _lib.call("hriemo_ln_pool_fwd_packed_pair",
+                          _p(xa), _p(h_a32), _p(sa.cu), sa.B, sa.N, _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa), La,
+                          _p(xt), _p(h_t32), _p(sq_t.cu), sq_t.B, sq_t.N, _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt), Lt,
+                          _p(sf.cu), sf.N, B, d, _EPS, st)
+            else:
+                _lib.call("hriemo_ln_pool_fwd_pair", _p(xa), _p(h_a32), _p(kpm_a), _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa), La,
+                          _p(xt), _p(h_t32), _p(kpm_t), _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt), Lt, B, L, d, _EPS, st)
         elif side is not None and side != main:
             fork(side, main)
             with torch.cuda.stream(side):
-                _lib.call("hriemo_ln_pool_fwd", _p(xt), _p(h_t32), _p(kpm_t), _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt),
-                          B, Lt, L, d, _EPS, _stream())
-            _lib.call("hriemo_ln_pool_fwd", _p(xa), _p(h_a32), _p(kpm_a), _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa),
-                      B, La, L, d, _EPS, st)
+                ln_pool(xt, h_t32, kpm_t, seq_t, gt, bt, Tn, mean_t, rstd_t, pt, Lt)
+            ln_pool(xa, h_a32, kpm_a, seq_a, ga, ba, An, mean_a, rstd_a, pa, La)
             main.wait_stream(side)
             if not CTX.capturing:
                 for t_ in (xt, h_t32, kpm_t, Tn, mean_t, rstd_t, pt):
                     share(t_, side)
         else:
-            _lib.call("hriemo_ln_pool_fwd", _p(xa), _p(h_a32), _p(kpm_a), _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa),
-                      B, La, L, d, _EPS, st)
-            _lib.call("hriemo_ln_pool_fwd", _p(xt), _p(h_t32), _p(kpm_t), _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt),
-                      B, Lt, L, d, _EPS, st)
+            ln_pool(xa, h_a32, kpm_a, seq_a, ga, ba, An, mean_a, rstd_a, pa, La)
+            ln_pool(xt, h_t32, kpm_t, seq_t, gt, bt, Tn, mean_t, rstd_t, pt, Lt)
         gin = torch.empty((B, 4 * d), dtype=BF16, device=dev)
         a_pool, t_pool = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
         cnt = torch.empty((B, 2), **f32)
@@ -1947,18 +2045,22 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         w = torch.empty((B, d), **f32)
         beta = torch.empty((B, 1), **f32)
         _lib.call("hriemo_sigmoid_beta", _p(pre), _p(w), _p(beta), B, d, st)
-        H = torch.empty((B, L, d), dtype=BF16, device=dev)
-        _lib.call("hriemo_fuse_fwd", _p(w), _p(An), _p(Tn), _p(H), B, L, d, st)
+        H = torch.empty(fshape, dtype=BF16, device=dev)
+        if plan is not None:
+            _lib.call("hriemo_fuse_fwd_packed", _p(w), _p(An), _p(Tn), _p(H), _p(sf.cu), sf.N, B, L, d, st)
+        else:
+            _lib.call("hriemo_fuse_fwd", _p(w), _p(An), _p(Tn), _p(H), B, L, d, st)
         ctx.save_for_backward(xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16,
                               w2_16, ga, gt, kpm_a, kpm_t, h_a32, h_t32)
         ctx.cfg = (B, La, Lt, L, d)
+        ctx.plan = plan
         ctx.params = (ga, ba, gt, bt, w1, b1, w2, b2)
         return H, beta
 
     @staticmethod
     def backward(ctx, dH, dbeta):
         if getattr(ctx, "fp32", False):
-            return _fp32().beta_gate_bwd(ctx, dH, dbeta)
+            return _fp32().beta_gate_bwd(ctx, dH, dbeta) + (None,)          # (the plan slot)
         (xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt, kpm_a,
          kpm_t, h_a32, h_t32) = ctx.saved_tensors
         B, La, Lt, L, d = ctx.cfg
@@ -1971,10 +2073,16 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         # launches on the serial chain between the decoder's and the encoder's backward
         sink = GradSink(ctx.params)
         acc = sink.fused
-        dH2 = _contig_bf16(dH) if dH is not None else torch.zeros((B, L, d), dtype=BF16, device=dev)
+        plan = ctx.plan
+        if plan is not None:
+            sa, sq_t, sf = plan
+        dH2 = _contig_bf16(dH) if dH is not None else torch.zeros(An.shape, dtype=BF16, device=dev)
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
         part = torch.empty((B, L_.hriemo_pool_chunks(L), d), **f32)
-        _lib.call("hriemo_fuse_bwd_dw", _p(dH2), _p(An), _p(Tn), _p(part), B, L, d, st)
+        if plan is not None:
+            _lib.call("hriemo_fuse_bwd_dw_packed", _p(dH2), _p(An), _p(Tn), _p(part), _p(sf.cu), sf.N, B, L, d, st)
+        else:
+            _lib.call("hriemo_fuse_bwd_dw", _p(dH2), _p(An), _p(Tn), _p(part), B, L, d, st)
         dpre = torch.empty((B, d), dtype=BF16, device=dev)
         _lib.call("hriemo_gate_dpre", _p(part), L, _p(dbeta2), _p(w), _p(dpre), B, d, st)
         Hd = hid.shape[1]
@@ -1990,8 +2098,8 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         dgin = linear_dx(dhid, w1_16)
         da, dt = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
         _lib.call("hriemo_gate_input_bwd", _p(dgin), _p(a_pool), _p(t_pool), _p(cnt), _p(da), _p(dt), B, d, st)
-        dxa = torch.empty((B, La, d), dtype=BF16, device=dev)
-        dxt = torch.empty((B, Lt, d), dtype=BF16, device=dev)
+        dxa = torch.empty((1, sa.N, d) if plan is not None else (B, La, d), dtype=BF16, device=dev)
+        dxt = torch.empty((1, sq_t.N, d) if plan is not None else (B, Lt, d), dtype=BF16, device=dev)
         dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
         # LayerNorm-affine gradients: finished by the launch-boundary reduce when they accumulate into .grad inside backward (the
         # kernel's partial sums then live in a buffer of their own instead of the shared workspace), else by the call's own reduce
@@ -1999,15 +2107,17 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         nba, nbt = L_.hriemo_ln_pool_bwd_workspace_bytes(B, La, d), L_.hriemo_ln_pool_bwd_workspace_bytes(B, Lt, d)
 
         def ln_pool_bwd(is_a, dpool, kpm, x, x32, gamma, mean, rstd, dx, dgam, dbet, Lx, nbytes):
-            if defer:
-                wsx = torch.empty(nbytes // 4 + 16, **f32)
-                _lib.call("hriemo_ln_pool_bwd", _p(dH2), L, _p(w), is_a, _p(dpool), _p(kpm), _p(x), _p(x32), _p(gamma), _p(mean),
-                          _p(rstd), _p(dx), None, None, 1, B, Lx, d, _p(wsx), _stream())
-                _deferred.add(wsx, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lx), d, 2, [dgam, dbet], True)
+            wsx = torch.empty(nbytes // 4 + 16, **f32) if defer else workspace(nbytes, dev, slot=1)
+            outs_ = (None, None, 1) if defer else (_p(dgam), _p(dbet), int(acc))
+            if plan is not None:
+                seq = sa if is_a else sq_t
+                _lib.call("hriemo_ln_pool_bwd_packed", _p(dH2), _p(sf.cu), sf.N, _p(w), is_a, _p(dpool), _p(x), _p(x32), _p(seq.cu), seq.B,
+                          seq.N, _p(gamma), _p(mean), _p(rstd), _p(dx), *outs_, B, Lx, d, _p(wsx), _stream())
             else:
-                wsx = workspace(nbytes, dev, slot=1)
                 _lib.call("hriemo_ln_pool_bwd", _p(dH2), L, _p(w), is_a, _p(dpool), _p(kpm), _p(x), _p(x32), _p(gamma), _p(mean),
-                          _p(rstd), _p(dx), _p(dgam), _p(dbet), int(acc), B, Lx, d, _p(wsx), _stream())
+                          _p(rstd), _p(dx), *outs_, B, Lx, d, _p(wsx), _stream())
+            if defer:
+                _deferred.add(wsx, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lx), d, 2, [dgam, dbet], True)
 
         main = torch.cuda.current_stream(dev)
         side = side_stream(dev) if GATE_TWO_STREAMS else None
@@ -2020,10 +2130,17 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
                 wsa = workspace(nba + nbt + 256, dev, slot=1)
                 wst = wsa[(nba // 4 + 63) // 64 * 64:]
                 outs = (dga, dba, dgt, dbt)
-            _lib.call("hriemo_ln_pool_bwd_pair", _p(dH2), L, _p(w),
-                      _p(da), _p(kpm_a), _p(xa), _p(h_a32), _p(ga), _p(mean_a), _p(rstd_a), _p(dxa), _p(outs[0]), _p(outs[1]), La, _p(wsa),
-                      _p(dt), _p(kpm_t), _p(xt), _p(h_t32), _p(gt), _p(mean_t), _p(rstd_t), _p(dxt), _p(outs[2]), _p(outs[3]), Lt, _p(wst),
-                      int(acc), B, d, _stream())
+            if plan is not None:
+                _lib.call("hriemo_ln_pool_bwd_packed_pair", _p(dH2), _p(sf.cu), sf.N, _p(w),
+                          _p(da), _p(xa), _p(h_a32), _p(sa.cu), sa.B, sa.N, _p(ga), _p(mean_a), _p(rstd_a), _p(dxa), _p(outs[0]), _p(outs[1]),
+                          La, _p(wsa),
+                          _p(dt), _p(xt), _p(h_t32), _p(sq_t.cu), sq_t.B, sq_t.N, _p(gt), _p(mean_t), _p(rstd_t), _p(dxt), _p(outs[2]),
+                          _p(outs[3]), Lt, _p(wst), int(acc), B, d, _stream())
+            else:
+                _lib.call("hriemo_ln_pool_bwd_pair", _p(dH2), L, _p(w),
+                          _p(da), _p(kpm_a), _p(xa), _p(h_a32), _p(ga), _p(mean_a), _p(rstd_a), _p(dxa), _p(outs[0]), _p(outs[1]), La, _p(wsa),
+                          _p(dt), _p(kpm_t), _p(xt), _p(h_t32), _p(gt), _p(mean_t), _p(rstd_t), _p(dxt), _p(outs[2]), _p(outs[3]), Lt, _p(wst),
+                          int(acc), B, d, _stream())
             if defer:
                 _deferred.add(wsa, 2 * d, B * nca_, d, 2, [dga, dba], True)
                 _deferred.add(wst, 2 * d, B * nct_, d, 2, [dgt, dbt], True)
@@ -2042,7 +2159,7 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
             ln_pool_bwd(0, dt, kpm_t, xt, h_t32, gt, mean_t, rstd_t, dxt, dgt, dbt, Lt, nbt)
         sink.done()
         r = sink.ret
-        return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None
+        return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None, None
 
 
 class LegacyBetaGateFn(torch.autograd.Function):

@@ -668,16 +668,54 @@ __global__ __launch_bounds__(ROWDOT_GROUPS * 32) void rowdot_bwd_kernel(const fl
 }
 
 // ------------------------------------------------------------------ beta gate
+// Packed (varlen) tail: the rows of one sample as a block sees them.  Sequence b of a packed [n_rows, d] buffer = rows cu[b] ..
+// cu[b+1]-1: two scalar loads per block, never a search per row.  The lengths are device data, so they are clamped to the buffer
+// (and to the padded length `cap` that sizes the grid and the partial-sum layouts): a stale cu cannot send a block out of bounds.
+struct PackedSpan { int c0, len; };
+__device__ __forceinline__ PackedSpan packed_span(const int* __restrict__ cu, int b, int cap, int n_rows) {
+  const int c0 = cu[b], c1 = cu[b + 1];
+  PackedSpan s;
+  s.c0 = min(max(c0, 0), n_rows);
+  s.len = max(min(min(c1, n_rows) - s.c0, cap), 0);
+  return s;
+}
+// the packed arguments of the gate kernels below (PK = true): cu [nseq+1] of the modality's packed X (nseq = B, or B + 1 when the
+// rows behind the last sample form the bucket's surplus sequence), cu_f [B+1] of the packed fused layout with n_f rows
+struct PackedArgs { const int* cu; int nseq, n_rows; const int* cu_f; int n_f, B; };
+__device__ __forceinline__ void zero_rows16(bf16_t* __restrict__ P, long r0, long r1, int stride, int first, int d, int lane) {
+  for (long r = r0 + first; r < r1; r += stride)
+    for (int o = lane * 8; o < d; o += 64 * 8) *(bf16x8*)(P + r * d + o) = bf16x8{};
+}
+
 // LayerNorm every row of X[b, :, :]; write the first Lkeep rows; pooled partial sums over valid rows.
-template <int NCH, bool PF>
+// PK: X / mean / rstd are packed rows (sample b = rows cu[b] + l, all valid), Yn is the packed fused layout (row cu_f[b] + l for
+// l < cu_f[b+1] - cu_f[b]); the block walks the positions l the padded launch walks, so the partial sums are its sums bit for bit;
+// a chunk behind the sample's end writes zero partials; grid y = nseq + 1: slice nseq zeroes the surplus rows cu_f[B] .. n_f-1 of Yn.
+template <int NCH, bool PF, bool PK = false>
 __device__ __forceinline__ void ln_pool_fwd_body(const bf16_t* __restrict__ X, const float* __restrict__ X32, const uint8_t* __restrict__ mask,
                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                                  bf16_t* __restrict__ Yn, float* __restrict__ mean_o, float* __restrict__ rstd_o,
-                                                 float* __restrict__ partials, int L, int Lkeep, int d, float eps, int chunk, int nchunks) {
+                                                 float* __restrict__ partials, int L, int Lkeep, int d, float eps, int chunk, int nchunks,
+                                                 const PackedArgs pk = PackedArgs{}) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = (float*)smem_raw;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, nchunk = d >> 3;
+  long xbase = (long)b * L, ybase = (long)b * Lkeep;
+  if (PK) {
+    if (b == pk.nseq) {
+      zero_rows16(Yn, min(max(pk.cu_f[pk.B], 0), pk.n_f), pk.n_f, nchunks * 4, chunk * 4 + wave, d, lane);
+      return;
+    }
+    const PackedSpan sx = packed_span(pk.cu, b, L, pk.n_rows);
+    xbase = sx.c0; L = sx.len;
+    if (b >= pk.B) {      // the bucket's surplus sequence (all-zero rows, no sample): finite statistics, nothing pooled
+      for (int l = chunk * 32 + (int)threadIdx.x; l < min(L, chunk * 32 + 32); l += 256) { mean_o[xbase + l] = 0.f; rstd_o[xbase + l] = 0.f; }
+      return;
+    }
+    const PackedSpan sf = packed_span(pk.cu_f, b, L, pk.n_f);
+    ybase = sf.c0; Lkeep = sf.len;
+  }
   const float invd = 1.f / (float)d;
   float acc[NCH][8];
 #pragma unroll
@@ -695,12 +733,12 @@ __device__ __forceinline__ void ln_pool_fwd_body(const bf16_t* __restrict__ X, c
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
-      if (ch < nchunk) load_resid(X, X32, ((long)b * L + l) * d + ch * 8, dst[c]);
+      if (ch < nchunk) load_resid(X, X32, (xbase + l) * d + ch * 8, dst[c]);
     }
   };
   if (PF && chunk * 32 + wave < lend) load_row(chunk * 32 + wave, nx);
   for (int l = chunk * 32 + wave; l < lend; l += 4) {
-    const long row = (long)b * L + l;
+    const long row = xbase + l;
     float s[NCH][8];
     float sum = 0.f;
     if (!PF) load_row(l, nx);
@@ -722,7 +760,7 @@ __device__ __forceinline__ void ln_pool_fwd_body(const bf16_t* __restrict__ X, c
         for (int j = 0; j < 8; ++j) { const float t = s[c][j] - mu; sq += t * t; }
       }
     const float rstd = rsqrtf(wave_sum(sq) * invd + eps);
-    const bool valid = mask == nullptr || mask[(long)b * L + l] == 0;
+    const bool valid = PK || mask == nullptr || mask[row] == 0;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
@@ -733,7 +771,7 @@ __device__ __forceinline__ void ln_pool_fwd_body(const bf16_t* __restrict__ X, c
           o[j] = (s[c][j] - mu) * rstd * (HOIST ? gm8[HOIST ? c : 0][j] : gamma[ch * 8 + j]) + (HOIST ? bt8[HOIST ? c : 0][j] : beta[ch * 8 + j]);
           if (valid) acc[c][j] += o[j];
         }
-        if (l < Lkeep) *(bf16x8*)(Yn + ((long)b * Lkeep + l) * d + ch * 8) = f32_to_bf8(o);
+        if (l < Lkeep) *(bf16x8*)(Yn + (ybase + l) * d + ch * 8) = f32_to_bf8(o);
       }
     }
     if (lane == 0) { mean_o[row] = mu; rstd_o[row] = rstd; }
@@ -761,6 +799,25 @@ __global__ __launch_bounds__(256, 4) void ln_pool_fwd_pair_kernel(const PoolFwdP
   ln_pool_fwd_body<NCH, PF>(PAIR_PICK(X), PAIR_PICK(X32), PAIR_PICK(mask), PAIR_PICK(gamma), PAIR_PICK(beta), PAIR_PICK(Yn), PAIR_PICK(mean),
                             PAIR_PICK(rstd), PAIR_PICK(partials), PAIR_PICK(L), PAIR_PICK(Lkeep), d, eps,
                             (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc));
+}
+// the same two kernels on packed rows (PackedArgs): no unpack between the encoder's last packed layer and the gate
+template <int NCH, bool PF>
+__global__ __launch_bounds__(256) void ln_pool_fwd_packed_kernel(const bf16_t* __restrict__ X, const float* __restrict__ X32,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 bf16_t* __restrict__ Yn, float* __restrict__ mean_o, float* __restrict__ rstd_o,
+                                                                 float* __restrict__ partials, int L, int d, float eps, const PackedArgs pk) {
+  ln_pool_fwd_body<NCH, PF, true>(X, X32, nullptr, gamma, beta, Yn, mean_o, rstd_o, partials, L, 0, d, eps, blockIdx.x, gridDim.x, pk);
+}
+struct PoolFwdSidePk { const bf16_t* X; const float* X32; const int* cu; const float* gamma; const float* beta; bf16_t* Yn; float* mean; float* rstd; float* partials; int L, nc, nseq, n_rows; };
+struct PoolFwdPairPk { PoolFwdSidePk s[2]; };
+template <int NCH, bool PF>
+__global__ __launch_bounds__(256, 4) void ln_pool_fwd_packed_pair_kernel(const PoolFwdPairPk p, const int* __restrict__ cu_f, int n_f, int B, int d, float eps) {
+  const bool second = (int)blockIdx.x >= p.s[0].nc;
+  if ((int)blockIdx.y > PAIR_PICK(nseq)) return;      // grid y is sized by the side with the surplus sequence
+  const PackedArgs pk{PAIR_PICK(cu), PAIR_PICK(nseq), PAIR_PICK(n_rows), cu_f, n_f, B};
+  ln_pool_fwd_body<NCH, PF, true>(PAIR_PICK(X), PAIR_PICK(X32), nullptr, PAIR_PICK(gamma), PAIR_PICK(beta), PAIR_PICK(Yn), PAIR_PICK(mean),
+                                  PAIR_PICK(rstd), PAIR_PICK(partials), PAIR_PICK(L), 0, d, eps,
+                                  (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc), pk);
 }
 
 // pooled means + gate input [a, t, |a-t|, a*t]  (beta_gate_tacfn.py:83-89)
@@ -841,21 +898,60 @@ __global__ void fuse_fwd_kernel(const float* __restrict__ w, const bf16_t* __res
   }
 }
 
-// dw partials: sum_l dH[b,l,:] * (A - T)[b,l,:]
+// the same on the packed fused layout [n_f, d] (A, T, H alike): block (32-row chunk, sample b) walks rows cu_f[b] + l, the gate
+// weights of its sample in registers; grid y = B + 1: slice B zeroes the surplus rows cu_f[B] .. n_f-1 (the decoder's K | V
+// weight-gradient GEMM multiplies every row of H)
 template <int NCH>
+__global__ __launch_bounds__(256) void fuse_fwd_packed_kernel(const float* __restrict__ w, const bf16_t* __restrict__ A, const bf16_t* __restrict__ T,
+                                                              bf16_t* __restrict__ H, const int* __restrict__ cu_f, int n_f, int B, int L, int d) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, chunk = blockIdx.x, nchunk = d >> 3;
+  if (b == B) {
+    zero_rows16(H, min(max(cu_f[B], 0), n_f), n_f, gridDim.x * 4, chunk * 4 + wave, d, lane);
+    return;
+  }
+  const PackedSpan sf = packed_span(cu_f, b, L, n_f);
+  float wv[NCH][8];
+  load_cols<NCH>(w + (long)b * d, nchunk, lane, wv);
+  for (int l = chunk * 32 + wave; l < min(sf.len, chunk * 32 + 32); l += 4) {
+    const long row = (long)sf.c0 + l;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) {
+        float a[8], t[8], o[8];
+        bf8_to_f32(*(const bf16x8*)(A + row * d + ch * 8), a);
+        bf8_to_f32(*(const bf16x8*)(T + row * d + ch * 8), t);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = wv[c][j] * a[j] + (1.f - wv[c][j]) * t[j];
+        *(bf16x8*)(H + row * d + ch * 8) = f32_to_bf8(o);
+      }
+    }
+  }
+}
+
+// dw partials: sum_l dH[b,l,:] * (A - T)[b,l,:]   (PK: the three operands in the packed fused layout, rows cu_f[b] + l; the partial
+// sums keep the padded [B, chunks(L), d] layout, a chunk behind the sample's end writes zeros)
+template <int NCH, bool PK = false>
 __global__ __launch_bounds__(256) void fuse_bwd_dw_kernel(const bf16_t* __restrict__ dH, const bf16_t* __restrict__ A, const bf16_t* __restrict__ T,
-                                                          float* __restrict__ partials, int L, int d) {
+                                                          float* __restrict__ partials, int L, int d, const int* __restrict__ cu_f = nullptr,
+                                                          int n_f = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = (float*)smem_raw;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = d >> 3;
+  long base = (long)b * L;
+  if (PK) {
+    const PackedSpan sf = packed_span(cu_f, b, L, n_f);
+    base = sf.c0; L = sf.len;
+  }
   float acc[NCH][8];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[c][j] = 0.f;
   for (int l = chunk * 32 + wave; l < min(L, chunk * 32 + 32); l += 4) {
-    const long row = (long)b * L + l;
+    const long row = base + l;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
@@ -914,16 +1010,31 @@ constexpr int POOL_BWD_ROWS = 16;
 
 // backward of LayerNorm+pool+fuse-branch for one modality:
 //   dYn[l] = (l < Lf ? coef * dH[b,l] : 0) + (valid_l ? dpool[b] : 0),  coef = is_a ? w : 1-w ;  dX = LN'(dYn)
-template <int NCH>
+// PK: X / mean / rstd / dX are the modality's packed rows (cu[b] + l, all valid), dH the packed fused layout (row cu_f[b] + l for
+// l < cu_f[b+1] - cu_f[b]); every packed row gets its dX (the surplus sequence zeros); the dgamma | dbeta partials stay per
+// (sample, POOL_BWD_ROWS chunk of the padded length), zeros behind the sample's end.
+template <int NCH, bool PK = false>
 __device__ __forceinline__ void ln_pool_bwd_body(const bf16_t* __restrict__ dH, int Lf, const float* __restrict__ w, int is_a,
                                                  const float* __restrict__ dpool, const uint8_t* __restrict__ mask,
                                                  const bf16_t* __restrict__ X, const float* __restrict__ X32, const float* __restrict__ gamma,
                                                  const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
-                                                 bf16_t* __restrict__ dX, float* __restrict__ partials, int L, int d, int chunk, int nchunks) {
+                                                 bf16_t* __restrict__ dX, float* __restrict__ partials, int L, int d, int chunk, int nchunks,
+                                                 const PackedArgs pk = PackedArgs{}) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = (float*)smem_raw;   // [2][d] column-sum scratch (+ [3][d] constants for d <= 1024)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, nchunk = d >> 3;
+  long xbase = (long)b * L, hbase = (long)b * Lf;
+  if (PK) {
+    const PackedSpan sx = packed_span(pk.cu, b, L, pk.n_rows);
+    xbase = sx.c0; L = sx.len;
+    if (b >= pk.B) {      // the bucket's surplus sequence: no sample, no gradient
+      zero_rows16(dX, xbase + chunk * POOL_BWD_ROWS, xbase + min(L, chunk * POOL_BWD_ROWS + POOL_BWD_ROWS), 4, wave, d, lane);
+      return;
+    }
+    const PackedSpan sf = packed_span(pk.cu_f, b, L, pk.n_f);
+    hbase = sf.c0; Lf = sf.len;
+  }
   const float invd = 1.f / (float)d;
   float ag[NCH][8], ab[NCH][8];
 #pragma unroll
@@ -979,8 +1090,8 @@ __device__ __forceinline__ void ln_pool_bwd_body(const bf16_t* __restrict__ dH, 
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
       if (ch < nchunk) {
-        load_resid(X, X32, ((long)b * L + l) * d + ch * 8, nxx[c]);
-        if (has_dh && l < Lf) nxh[c] = *(const bf16x8*)(dH + ((long)b * Lf + l) * d + ch * 8);
+        load_resid(X, X32, (xbase + l) * d + ch * 8, nxx[c]);
+        if (has_dh && l < Lf) nxh[c] = *(const bf16x8*)(dH + (hbase + l) * d + ch * 8);
       }
     }
   };
@@ -995,9 +1106,9 @@ __device__ __forceinline__ void ln_pool_bwd_body(const bf16_t* __restrict__ dH, 
   }
   if (PF && lbeg < lend) load_row(lbeg);
   for (int l = lbeg; l < lend; l += 4) {
-    const long row = (long)b * L + l;
+    const long row = xbase + l;
     const float mu = mean_i[row], rstd = rstd_i[row];
-    const bool valid = mask == nullptr || mask[row] == 0;
+    const bool valid = PK || mask == nullptr || mask[row] == 0;
     const bool grad_row = has_dh && l < Lf;
     float xh[NCH][8], dyg[NCH][8];
     float c1 = 0.f, c2 = 0.f;
@@ -1025,7 +1136,7 @@ __device__ __forceinline__ void ln_pool_bwd_body(const bf16_t* __restrict__ dH, 
           bf8_to_f32(nxh[c], gh);
         } else {
           load_resid(X, X32, row * d + ch * 8, xf);
-          if (grad_row) bf8_to_f32(*(const bf16x8*)(dH + ((long)b * Lf + l) * d + ch * 8), gh);
+          if (grad_row) bf8_to_f32(*(const bf16x8*)(dH + (hbase + l) * d + ch * 8), gh);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -1080,6 +1191,25 @@ __global__ __launch_bounds__(256) void ln_pool_bwd_pair_kernel(const bf16_t* __r
   const bool second = (int)blockIdx.x >= p.s[0].nc;
   ln_pool_bwd_body<NCH>(dH, Lf, w, second ? 0 : 1, PAIR_PICK(dpool), PAIR_PICK(mask), PAIR_PICK(X), PAIR_PICK(X32), PAIR_PICK(gamma), PAIR_PICK(mean),
                         PAIR_PICK(rstd), PAIR_PICK(dX), PAIR_PICK(partials), PAIR_PICK(L), d, (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc));
+}
+// the same two kernels on packed rows (PackedArgs): dX goes straight to the encoder's last packed layer, no pack launch
+template <int NCH>
+__global__ __launch_bounds__(256) void ln_pool_bwd_packed_kernel(const bf16_t* __restrict__ dH, const float* __restrict__ w, int is_a,
+                                                                 const float* __restrict__ dpool, const bf16_t* __restrict__ X, const float* __restrict__ X32,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
+                                                                 bf16_t* __restrict__ dX, float* __restrict__ partials, int L, int d, const PackedArgs pk) {
+  ln_pool_bwd_body<NCH, true>(dH, 0, w, is_a, dpool, nullptr, X, X32, gamma, mean_i, rstd_i, dX, partials, L, d, blockIdx.x, gridDim.x, pk);
+}
+struct PoolBwdSidePk { const float* dpool; const int* cu; const bf16_t* X; const float* X32; const float* gamma; const float* mean; const float* rstd; bf16_t* dX; float* partials; int L, nc, nseq, n_rows; };
+struct PoolBwdPairPk { PoolBwdSidePk s[2]; };
+template <int NCH>
+__global__ __launch_bounds__(256) void ln_pool_bwd_packed_pair_kernel(const bf16_t* __restrict__ dH, const float* __restrict__ w, const PoolBwdPairPk p,
+                                                                      const int* __restrict__ cu_f, int n_f, int B, int d) {
+  const bool second = (int)blockIdx.x >= p.s[0].nc;
+  if ((int)blockIdx.y >= PAIR_PICK(nseq)) return;      // grid y is sized by the side with the surplus sequence
+  const PackedArgs pk{PAIR_PICK(cu), PAIR_PICK(nseq), PAIR_PICK(n_rows), cu_f, n_f, B};
+  ln_pool_bwd_body<NCH, true>(dH, 0, w, second ? 0 : 1, PAIR_PICK(dpool), nullptr, PAIR_PICK(X), PAIR_PICK(X32), PAIR_PICK(gamma), PAIR_PICK(mean),
+                              PAIR_PICK(rstd), PAIR_PICK(dX), PAIR_PICK(partials), PAIR_PICK(L), d, (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc), pk);
 }
 
 // ================================================================== host entry points
@@ -1825,6 +1955,137 @@ extern "C" int hriemo_ln_pool_bwd_pair(const void* dH, int Lf, const float* w,
   else hipLaunchKernelGGL((ln_pool_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, Lf, w, p, d);
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * B * (La + Lt) + 2.0 * B * Lf) * d * 2);
+  if (dgamma_a == nullptr) return 0;
+  for (int side = 0; side < 2; ++side) {
+    float* ws = side ? workspace_t : workspace_a;
+    float* scratch = ws + (long)B * p.s[side].nc * 2 * d;
+    ReduceOut ro; ro.o[0] = side ? dgamma_t : dgamma_a; ro.o[1] = side ? dbeta_t : dbeta_a; ro.o[2] = nullptr;
+    launch_colreduce(ws, (long)2 * d, B * p.s[side].nc, ro, d, 2, accumulate, scratch, st);
+    HRIEMO_LAUNCH_CHECK("colreduce_kernel");
+  }
+  return 0;
+}
+
+// ---- the gate on packed (varlen) rows: the encoder's packed output goes straight into the gate and the gate's h_fusion stays
+// packed for the decoder (no hriemo_unpack_rows / hriemo_pack_rows between them).  See include/hriemo.h for the layouts.
+static int check_packed(const char* who, const int* cu, int nseq, int n_rows, const int* cu_f, int n_f, int B, int L, int d) {
+  HRIEMO_CHECK(B > 0 && L > 0 && d > 0 && d % 8 == 0, "%s: bad shape (B=%d L=%d d=%d)", who, B, L, d);
+  HRIEMO_CHECK(cu_f != nullptr && n_f > 0, "%s: the fused plan is missing (n_f=%d)", who, n_f);
+  HRIEMO_CHECK(cu == nullptr || ((nseq == B || nseq == B + 1) && n_rows > 0), "%s: nseq=%d must be B or B + 1 (B=%d), n_rows=%d positive", who, nseq, B, n_rows);
+  HRIEMO_CHECK((long)n_rows * d < (1L << 31) && (long)n_f * d < (1L << 31), "%s: more than 2^31 elements", who);
+  return 0;
+}
+
+extern "C" int hriemo_ln_pool_fwd_packed(const void* X, const float* X32, const int* cu_seqlens, int nseq, int n_rows, const float* gamma,
+                                         const float* beta, void* Yn, float* mean, float* rstd, float* partials, int L,
+                                         const int* cu_fused, int n_fused, int B, int d, float eps, hipStream_t st) {
+  if (check_packed("ln_pool_fwd_packed", cu_seqlens, nseq, n_rows, cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(cu_seqlens != nullptr && X != nullptr && Yn != nullptr, "ln_pool_fwd_packed: NULL operand");
+  const int nc = (L + 31) / 32;
+  const PackedArgs pk{cu_seqlens, nseq, n_rows, cu_fused, n_fused, B};
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N)                                                                                                                  \
+  if ((N) <= 2)                                                                                                                  \
+    hipLaunchKernelGGL((ln_pool_fwd_packed_kernel<N, ((N) <= 2)>), dim3(nc, nseq + 1), dim3(256), d * 4, st, (const bf16_t*)X, X32, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, d, eps, pk); \
+  else                                                                                                                           \
+    hipLaunchKernelGGL((ln_pool_fwd_packed_kernel<N, false>), dim3(nc, nseq + 1), dim3(256), d * 4, st, (const bf16_t*)X, X32, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, d, eps, pk)
+  DISPATCH_NCH(d, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("ln_pool_fwd_packed_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, ((double)n_rows + (double)n_fused) * d * 2);
+  return 0;
+}
+
+extern "C" int hriemo_ln_pool_fwd_packed_pair(const void* Xa, const float* Xa32, const int* cu_a, int nseq_a, int n_rows_a, const float* gamma_a,
+                                              const float* beta_a, void* Yna, float* mean_a, float* rstd_a, float* partials_a, int La,
+                                              const void* Xt, const float* Xt32, const int* cu_t, int nseq_t, int n_rows_t, const float* gamma_t,
+                                              const float* beta_t, void* Ynt, float* mean_t, float* rstd_t, float* partials_t, int Lt,
+                                              const int* cu_fused, int n_fused, int B, int d, float eps, hipStream_t st) {
+  if (check_packed("ln_pool_fwd_packed_pair", cu_a, nseq_a, n_rows_a, cu_fused, n_fused, B, La, d) ||
+      check_packed("ln_pool_fwd_packed_pair", cu_t, nseq_t, n_rows_t, cu_fused, n_fused, B, Lt, d)) return 1;
+  HRIEMO_CHECK(cu_a != nullptr && cu_t != nullptr && Xa != nullptr && Xt != nullptr && Yna != nullptr && Ynt != nullptr, "ln_pool_fwd_packed_pair: NULL operand");
+  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_fwd_packed_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_fwd_packed calls)", d);
+  PoolFwdPairPk p;
+  p.s[0] = PoolFwdSidePk{(const bf16_t*)Xa, Xa32, cu_a, gamma_a, beta_a, (bf16_t*)Yna, mean_a, rstd_a, partials_a, La, (La + 31) / 32, nseq_a, n_rows_a};
+  p.s[1] = PoolFwdSidePk{(const bf16_t*)Xt, Xt32, cu_t, gamma_t, beta_t, (bf16_t*)Ynt, mean_t, rstd_t, partials_t, Lt, (Lt + 31) / 32, nseq_t, n_rows_t};
+  const int nc = p.s[0].nc + p.s[1].nc, ny = (nseq_a > nseq_t ? nseq_a : nseq_t) + 1;
+  hriemo_prof_begin(HP_ROWOPS, st);
+  if (d <= 512) hipLaunchKernelGGL((ln_pool_fwd_packed_pair_kernel<1, true>), dim3(nc, ny), dim3(256), d * 4, st, p, cu_fused, n_fused, B, d, eps);
+  else hipLaunchKernelGGL((ln_pool_fwd_packed_pair_kernel<2, true>), dim3(nc, ny), dim3(256), d * 4, st, p, cu_fused, n_fused, B, d, eps);
+  HRIEMO_LAUNCH_CHECK("ln_pool_fwd_packed_pair_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, ((double)n_rows_a + n_rows_t + 2.0 * n_fused) * d * 2);
+  return 0;
+}
+
+extern "C" int hriemo_fuse_fwd_packed(const float* w, const void* A, const void* T, void* H, const int* cu_fused, int n_fused, int B,
+                                      int L, int d, hipStream_t st) {
+  if (check_packed("fuse_fwd_packed", nullptr, 0, 0, cu_fused, n_fused, B, L, d)) return 1;
+  const int nc = (L + 31) / 32;
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N) hipLaunchKernelGGL((fuse_fwd_packed_kernel<N>), dim3(nc, B + 1), dim3(256), 0, st, w, (const bf16_t*)A, (const bf16_t*)T, (bf16_t*)H, cu_fused, n_fused, B, L, d)
+  DISPATCH_NCH(d, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("fuse_fwd_packed_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, 3.0 * n_fused * d * 2);
+  return 0;
+}
+
+extern "C" int hriemo_fuse_bwd_dw_packed(const void* dH, const void* A, const void* T, float* partials, const int* cu_fused, int n_fused,
+                                         int B, int L, int d, hipStream_t st) {
+  if (check_packed("fuse_bwd_dw_packed", nullptr, 0, 0, cu_fused, n_fused, B, L, d)) return 1;
+  const int nc = (L + 31) / 32;
+#define CALL(N) hipLaunchKernelGGL((fuse_bwd_dw_kernel<N, true>), dim3(nc, B), dim3(256), d * 4, st, (const bf16_t*)dH, (const bf16_t*)A, (const bf16_t*)T, partials, L, d, cu_fused, n_fused)
+  DISPATCH_NCH(d, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("fuse_bwd_dw_kernel (packed)");
+  return 0;
+}
+
+extern "C" int hriemo_ln_pool_bwd_packed(const void* dH, const int* cu_fused, int n_fused, const float* w, int is_a, const float* dpool,
+                                         const void* X, const float* X32, const int* cu_seqlens, int nseq, int n_rows, const float* gamma,
+                                         const float* mean, const float* rstd, void* dX, float* dgamma, float* dbeta, int accumulate, int B,
+                                         int L, int d, float* workspace, hipStream_t st) {
+  if (check_packed("ln_pool_bwd_packed", cu_seqlens, nseq, n_rows, cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(cu_seqlens != nullptr && workspace != nullptr && dX != nullptr && (dgamma == nullptr) == (dbeta == nullptr), "ln_pool_bwd_packed: bad arguments");
+  const int nc = hriemo_ln_pool_bwd_chunks(L);
+  const PackedArgs pk{cu_seqlens, nseq, n_rows, cu_fused, n_fused, B};
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N) hipLaunchKernelGGL((ln_pool_bwd_packed_kernel<N>), dim3(nc, nseq), dim3(256), ((N) <= 2 ? 5 : 2) * d * 4, st, (const bf16_t*)dH, w, is_a, dpool, (const bf16_t*)X, X32, gamma, mean, rstd, (bf16_t*)dX, workspace, L, d, pk)
+  DISPATCH_NCH(d, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("ln_pool_bwd_packed_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (2.0 * n_rows + (double)n_fused) * d * 2);
+  if (dgamma == nullptr) return 0;          // partial sums stay in `workspace` ([B * hriemo_ln_pool_bwd_chunks(L)][2d]) for the launch-boundary reduce
+  float* scratch = workspace + (long)B * nc * 2 * d;
+  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
+  launch_colreduce(workspace, (long)2 * d, B * nc, ro, d, 2, accumulate, scratch, st);
+  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_ln_pool_bwd_packed_pair(const void* dH, const int* cu_fused, int n_fused, const float* w,
+                                              const float* dpool_a, const void* Xa, const float* Xa32, const int* cu_a, int nseq_a, int n_rows_a,
+                                              const float* gamma_a, const float* mean_a, const float* rstd_a, void* dXa, float* dgamma_a, float* dbeta_a,
+                                              int La, float* workspace_a,
+                                              const float* dpool_t, const void* Xt, const float* Xt32, const int* cu_t, int nseq_t, int n_rows_t,
+                                              const float* gamma_t, const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t, float* dbeta_t,
+                                              int Lt, float* workspace_t, int accumulate, int B, int d, hipStream_t st) {
+  if (check_packed("ln_pool_bwd_packed_pair", cu_a, nseq_a, n_rows_a, cu_fused, n_fused, B, La, d) ||
+      check_packed("ln_pool_bwd_packed_pair", cu_t, nseq_t, n_rows_t, cu_fused, n_fused, B, Lt, d)) return 1;
+  HRIEMO_CHECK(cu_a != nullptr && cu_t != nullptr && workspace_a != nullptr && workspace_t != nullptr && workspace_a != workspace_t && dXa != nullptr && dXt != nullptr,
+               "ln_pool_bwd_packed_pair: bad arguments");
+  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_bwd_packed_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_bwd_packed calls)", d);
+  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
+               "ln_pool_bwd_packed_pair: the four LayerNorm gradients come together or not at all");
+  PoolBwdPairPk p;
+  p.s[0] = PoolBwdSidePk{dpool_a, cu_a, (const bf16_t*)Xa, Xa32, gamma_a, mean_a, rstd_a, (bf16_t*)dXa, workspace_a, La, hriemo_ln_pool_bwd_chunks(La), nseq_a, n_rows_a};
+  p.s[1] = PoolBwdSidePk{dpool_t, cu_t, (const bf16_t*)Xt, Xt32, gamma_t, mean_t, rstd_t, (bf16_t*)dXt, workspace_t, Lt, hriemo_ln_pool_bwd_chunks(Lt), nseq_t, n_rows_t};
+  const int nc = p.s[0].nc + p.s[1].nc, ny = nseq_a > nseq_t ? nseq_a : nseq_t;
+  hriemo_prof_begin(HP_ROWOPS, st);
+  if (d <= 512) hipLaunchKernelGGL((ln_pool_bwd_packed_pair_kernel<1>), dim3(nc, ny), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, w, p, cu_fused, n_fused, B, d);
+  else hipLaunchKernelGGL((ln_pool_bwd_packed_pair_kernel<2>), dim3(nc, ny), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, w, p, cu_fused, n_fused, B, d);
+  HRIEMO_LAUNCH_CHECK("ln_pool_bwd_packed_pair_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (2.0 * (n_rows_a + n_rows_t) + 2.0 * n_fused) * d * 2);
   if (dgamma_a == nullptr) return 0;
   for (int side = 0; side < 2; ++side) {
     float* ws = side ? workspace_t : workspace_a;

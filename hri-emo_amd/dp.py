@@ -343,7 +343,8 @@ class DataParallelStep:
 
         Packed (varlen) mode (``hri_emo_amd.set_varlen(True)`` and both padding masks given): the sequence lengths are DEVICE
         data of the captured step (cu_seqlens buffers refreshed before every replay), only the packed row counts are baked in,
-        rounded up to a bucket (1/64 of the padded rows; the surplus rows form one extra all-zero sequence).  ``step()`` then
+        rounded up to a bucket (1/64 of the padded rows; the surplus rows form one extra all-zero sequence).  The fused memory of
+        the packed tail (min of the two lengths per utterance) has a third cu_seqlens buffer and the text bucket's row count.  ``step()`` then
         serves EVERY batch of these shapes: a batch whose row counts fall into a bucket not seen yet captures that bucket's
         graph on the spot (same static inputs, one memory pool).  ``lengths`` = (audio lengths, text lengths) as host lists /
         CPU tensors spares the device -> host read of the masks' row sums (one sync per step otherwise).
@@ -383,7 +384,8 @@ class DataParallelStep:
             dev = self._static[0].device
             B, La, Lt = h_a.shape[0], h_a.shape[1], h_t.shape[1]
             self._pb = {"graphs": collections.OrderedDict(), "B": B, "La": La, "Lt": Lt,
-                        "cu_a": torch.zeros(B + 2, dtype=torch.int32, device=dev), "cu_t": torch.zeros(B + 2, dtype=torch.int32, device=dev)}
+                        "cu_a": torch.zeros(B + 2, dtype=torch.int32, device=dev), "cu_t": torch.zeros(B + 2, dtype=torch.int32, device=dev),
+                        "cu_f": torch.zeros(B + 2, dtype=torch.int32, device=dev)}
             key = self._packed_key(m_a, m_t, lengths)
             rec = self._packed_graph(key)
             self._graph, self._static_loss, self._keep = rec["graph"], rec["loss"], []
@@ -417,6 +419,7 @@ class DataParallelStep:
             if len(la) != B or len(lt) != B or min(la) < 1 or min(lt) < 1 or max(la) > La or max(lt) > Lt:
                 raise ValueError("DataParallelStep (packed mode): lengths must hold one value in [1, L] per utterance and modality")
         out = []
+        lf = [min(x, y) for x, y in zip(la, lt)]      # the fused memory of a sample: the reference ORs the two prefix masks
         for lens, L, buf in ((la, La, pb["cu_a"]), (lt, Lt, pb["cu_t"])):
             g = max(8, (B * L) // _VARLEN_BUCKETS // 8 * 8)
             g = min(g, L)                         # the surplus rows are ONE sequence of at most L rows
@@ -428,6 +431,13 @@ class DataParallelStep:
             cu.append(rows)
             buf.copy_(torch.tensor(cu, dtype=torch.int32))
             out.append(rows)
+        # the fused plan rides in the text bucket (sum lf <= sum lt < its row count): no bucket dimension, no graph of its own
+        if pb.get("cu_f") is not None:
+            cu = [0]
+            for x in lf:
+                cu.append(cu[-1] + x)
+            cu.append(out[1])
+            pb["cu_f"].copy_(torch.tensor(cu, dtype=torch.int32))
         return tuple(out)
 
     def _packed_graph(self, key):
@@ -442,7 +452,8 @@ class DataParallelStep:
                 old.clear()
                 _ops.GRAPHS_ALIVE = max(1, _ops.GRAPHS_ALIVE - 1)
                 log.info("packed step: released the graph of bucket %s (cap %d)", old_key, _VARLEN_MAX_GRAPHS)
-            seqs = (_ops.seq_bucket(pb["cu_a"], pb["B"], pb["La"], key[0]), _ops.seq_bucket(pb["cu_t"], pb["B"], pb["Lt"], key[1]))
+            seqs = (_ops.seq_bucket(pb["cu_a"], pb["B"], pb["La"], key[0]), _ops.seq_bucket(pb["cu_t"], pb["B"], pb["Lt"], key[1]),
+                    _ops.seq_bucket_fused(pb["cu_f"], pb["B"], min(pb["La"], pb["Lt"]), key[1]))
             # a bucket met inside step() runs two eager warm-up passes + the capture pass; each draws dropout seeds from torch's
             # CPU generator.  Ranks meet new buckets at different steps, so the generator is put back: its stream stays the one
             # the caller (and every other rank) sees, as _ops.next_seed documents.
@@ -550,12 +561,13 @@ class DataParallelStep:
                 seen = (m_a.data_ptr(), m_a._version, m_t.data_ptr(), m_t._version)
                 if lengths is None and self._mask_seen.get("key") == seen:
                     key = self._mask_seen["val"]          # the same mask tensors as last step: no second device -> host read
-                    self._pb["cu_a"].copy_(self._mask_seen["cu"][0]); self._pb["cu_t"].copy_(self._mask_seen["cu"][1])
+                    for name, saved in zip(("cu_a", "cu_t", "cu_f"), self._mask_seen["cu"]):
+                        self._pb[name].copy_(saved)
                 else:
                     key = self._packed_key(m_a, m_t, lengths)
                     # the entry HOLDS the masks: while it is the cache entry their addresses cannot be handed to the next batch's
                     # masks (same address + version 0 would otherwise pass for "the same tensors" with other lengths inside)
-                    self._mask_seen = {"key": seen, "val": key, "cu": (self._pb["cu_a"].clone(), self._pb["cu_t"].clone()),
+                    self._mask_seen = {"key": seen, "val": key, "cu": (self._pb["cu_a"].clone(), self._pb["cu_t"].clone(), self._pb["cu_f"].clone()),
                                        "masks": (m_a, m_t)}
                 for s, t in zip(self._static, (h_a, h_t, m_a, m_t, y)):
                     if s is not None and t is not None and s.data_ptr() != t.data_ptr():

@@ -215,7 +215,11 @@ class CrossModalTransformer(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([CrossModalBlock(d_model, n_heads, dropout) for _ in range(num_layers)])
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need):
+    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=None):
+        """tail: a list the caller hands in to take the packed tail (_ops.PACKED_TAIL).  When the encoder ran packed, its outputs
+        then STAY packed ([1, N, d] pairs) and the plan (Seq audio, Seq text, Seq fused) is appended to the list -- the gate and
+        the decoder read the packed rows, nothing is scattered back.  Without it (forward() below, whose public output is
+        padded) the outputs are unpacked as before."""
         all_layers_attn = []
         plan = None
         _ops.FLUSH_SITES.add(self.layers[0]._site[1])        # layer-0 text self-attention: the last text-branch backward (_ops._DeferredWgrad)
@@ -223,19 +227,21 @@ class CrossModalTransformer(nn.Module):
             # the encoder on the valid rows only (prefix masks, as the collate builds them); anything else
             # takes the padded path.  dp.DataParallelStep injects bucketed plans whose lengths are device data (_ops.CTX.seq_override).
             if _ops.CTX.seq_override is not None:
-                sa, st = _ops.CTX.seq_override
+                plan3 = tuple(_ops.CTX.seq_override)
             else:
-                sa = _ops.seq_plan(mask_a, a.shape[0], a.shape[1])
-                st = _ops.seq_plan(mask_t, t.shape[0], t.shape[1])
-            if sa is not None and st is not None:
-                plan = (sa, st)
+                plan3 = _ops.seq_plans(mask_a, mask_t, a.shape[0], a.shape[1], t.shape[1])
+            if plan3 is not None:
+                sa, st = plan = plan3[:2]
                 (a, a32), (t, t32) = _ops.pack_pair(a, a32, sa), _ops.pack_pair(t, t32, st)
         for i, layer in enumerate(self.layers):
             a, a32, t, t32, maps = layer._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, plan)
             if need:
                 all_layers_attn.append(maps)
         if plan is not None:
-            (a, a32), (t, t32) = _ops.unpack_pair(a, a32, plan[0]), _ops.unpack_pair(t, t32, plan[1])
+            if tail is not None and len(plan3) == 3 and _ops.packed_tail():
+                tail.append(plan3)
+            else:
+                (a, a32), (t, t32) = _ops.unpack_pair(a, a32, plan[0]), _ops.unpack_pair(t, t32, plan[1])
         return a, a32, t, t32, all_layers_attn
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):

@@ -51,17 +51,30 @@ class ExplainableDecoderLayer(nn.Module):
         return tgt, tgt32, seed
 
     def _fwd_pair(self, tgt, tgt32, memory, memory_key_padding_mask, need, kv_pre=None, kv_ready=None):
-        B, L, _ = memory.shape
-        kpm = _ops.mask_u8(memory_key_padding_mask, B, L)
+        """memory_key_padding_mask may be the fused _ops.Seq: memory is then the packed fused memory [1, N_f, d] and the
+        cross-attention runs on cu_seqlens (N_e query rows per sample, the fused lengths as keys)."""
+        packed = isinstance(memory_key_padding_mask, _ops.Seq)
+        Bq, Nq, dq = tgt.shape
+        if packed:
+            kpm = (_ops.query_seq(Bq, Nq, tgt.device), memory_key_padding_mask)
+        else:
+            B, L, _ = memory.shape
+            kpm = _ops.mask_u8(memory_key_padding_mask, B, L)
         p = self.p if self.training else 0.0
         ca, s = self.cross_attn, self._site
         tgt, tgt32, seed = self._self_block(tgt, tgt32)
         if kv_ready is not None:          # K | V of the memory were projected on the side stream (EmotionDecoder._fwd)
             torch.cuda.current_stream(memory.device).wait_event(kv_ready)
+        if packed:
+            # the queries are not ragged: their packed rows ARE the padded rows ([1, B*N_e, d]), so the dropout row keys of this
+            # sub-layer's LayerNorm stay those of the padded path
+            tgt, tgt32 = tgt.view(1, Bq * Nq, dq), (tgt32.view(1, Bq * Nq, dq) if tgt32 is not None else None)
         tgt, tgt32, w = _ops.CrossAttnLN.apply(tgt, tgt32, memory, ca.in_proj_weight, ca.in_proj_bias,
                                                ca.out_proj.weight, ca.out_proj.bias, self.norm2.weight,
                                                self.norm2.bias, self._sh, self.nhead, kpm, p, seed, s[1],
                                                self.batch_offset, need, kv_pre)                               # :48-55
+        if packed:
+            tgt, tgt32 = tgt.view(Bq, Nq, dq), (tgt32.view(Bq, Nq, dq) if tgt32 is not None else None)
         tgt, tgt32 = _ops.FFNLN.apply(tgt, tgt32, self.linear1.weight, self.linear1.bias, self.linear2.weight,
                                       self.linear2.bias, self.norm3.weight, self.norm3.bias, self._sh, p, p, seed,
                                       s[2], self.batch_offset)                                                # :58-59
@@ -99,7 +112,10 @@ class EmotionDecoder(nn.Module):
         return out, out32
 
     def _fwd(self, memory16, memory_key_padding_mask, need, out_dtype):
-        B = memory16.size(0)
+        """memory_key_padding_mask: the [B, L_f] mask of a padded memory [B, L_f, d], or the fused _ops.Seq of a packed memory
+        [1, N_f, d] (the K | V projections then run over the N_f packed rows)"""
+        packed = isinstance(memory_key_padding_mask, _ops.Seq)
+        B = memory_key_padding_mask.Breal if packed else memory16.size(0)
         out, out32 = self._queries(B)
         all_layers_attn = []
         if _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):

@@ -358,6 +358,48 @@ int hriemo_ln_pool_bwd(const void* dH, int Lf, const float* w, int is_a, const f
 /* (dgamma / dbeta: overwritten, or added to when accumulate != 0; both NULL: the per-block partial sums stay in `workspace`, rows
  * [B * ceil(L/32)] of [dgamma | dbeta] (2d floats each), for hriemo_colreduce_batch at the end of backward) */
 
+/* ---- the gate on packed (varlen) rows: the encoder's packed output feeds the gate and the gate's h_fusion stays packed for the
+ * decoder, so no hriemo_unpack_rows / hriemo_pack_rows runs between the encoder and the loss.
+ *  - A modality's X / X32 / mean / rstd / dX are packed [n_rows, d] buffers with cu_seqlens (int32 [nseq + 1], device memory):
+ *    sample b = rows cu[b] .. cu[b+1]-1, every row valid.  nseq = B, or B + 1 when the rows behind the last sample form the
+ *    bucket's surplus sequence (hriemo_pack_rows' zero rows): those rows get mean = rstd = 0 and dX = 0, and pool nothing.
+ *  - Yn / H / dH live in the packed FUSED layout [n_fused, d] with cu_fused (int32 [B + 1]): sample b has
+ *    lf[b] = min(audio length, text length) rows (the reference ORs the two prefix masks cut to L_t,
+ *    models/fusion_with_emotion_decoder.py:62-79).  Rows cu_fused[B] .. n_fused-1 are surplus: every kernel here that writes a
+ *    fused buffer writes them as zeros (the decoder's K | V weight-gradient GEMM multiplies every row).
+ *  - L is the padded length of that side (it sizes the grid and the partial-sum layouts; lengths are clamped to it and to the
+ *    buffers).  The pooled partials stay [B, hriemo_pool_chunks(L), d], the dw partials [B, hriemo_pool_chunks(L), d] and the
+ *    dgamma | dbeta partials [B * hriemo_ln_pool_bwd_chunks(L)][2d], chunks behind a sample's end hold zeros: hriemo_gate_input,
+ *    hriemo_gate_dpre, hriemo_colreduce_batch and the gate MLP run unchanged, and a block adds the rows the padded kernel adds in
+ *    the same order -- pooled sums, Yn, H, dw partials and dX equal the padded launch's bit for bit on the valid rows.
+ *  - hriemo_ln_pool_bwd_packed: dH may be NULL (no gradient through h_fusion); rows l >= lf[b] of a sample get the pooled
+ *    gradient only.  workspace as hriemo_ln_pool_bwd (hriemo_ln_pool_bwd_workspace_bytes(B, L, d)).
+ *  - *_pair: both modalities from one launch (d <= 1024), the blocks -- and the results -- of the single calls. */
+int hriemo_ln_pool_fwd_packed(const void* X, const float* X32, const int* cu_seqlens, int nseq, int n_rows, const float* gamma,
+                              const float* beta, void* Yn, float* mean, float* rstd, float* partials, int L,
+                              const int* cu_fused, int n_fused, int B, int d, float eps, hriemo_stream_t stream);
+int hriemo_ln_pool_fwd_packed_pair(const void* Xa, const float* Xa32, const int* cu_a, int nseq_a, int n_rows_a, const float* gamma_a,
+                                   const float* beta_a, void* Yna, float* mean_a, float* rstd_a, float* partials_a, int La,
+                                   const void* Xt, const float* Xt32, const int* cu_t, int nseq_t, int n_rows_t, const float* gamma_t,
+                                   const float* beta_t, void* Ynt, float* mean_t, float* rstd_t, float* partials_t, int Lt,
+                                   const int* cu_fused, int n_fused, int B, int d, float eps, hriemo_stream_t stream);
+/* H = w * A + (1 - w) * T on the packed fused rows (the sample of a row comes from cu_fused); dw partials of the same rows */
+int hriemo_fuse_fwd_packed(const float* w, const void* A, const void* T, void* H, const int* cu_fused, int n_fused, int B, int L, int d,
+                           hriemo_stream_t stream);
+int hriemo_fuse_bwd_dw_packed(const void* dH, const void* A, const void* T, float* partials, const int* cu_fused, int n_fused, int B,
+                              int L, int d, hriemo_stream_t stream);
+int hriemo_ln_pool_bwd_packed(const void* dH, const int* cu_fused, int n_fused, const float* w, int is_a, const float* dpool,
+                              const void* X, const float* X32, const int* cu_seqlens, int nseq, int n_rows, const float* gamma,
+                              const float* mean, const float* rstd, void* dX, float* dgamma, float* dbeta, int accumulate, int B, int L,
+                              int d, float* workspace, hriemo_stream_t stream);
+int hriemo_ln_pool_bwd_packed_pair(const void* dH, const int* cu_fused, int n_fused, const float* w,
+                                   const float* dpool_a, const void* Xa, const float* Xa32, const int* cu_a, int nseq_a, int n_rows_a,
+                                   const float* gamma_a, const float* mean_a, const float* rstd_a, void* dXa, float* dgamma_a,
+                                   float* dbeta_a, int La, float* workspace_a,
+                                   const float* dpool_t, const void* Xt, const float* Xt32, const int* cu_t, int nseq_t, int n_rows_t,
+                                   const float* gamma_t, const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t,
+                                   float* dbeta_t, int Lt, float* workspace_t, int accumulate, int B, int d, hriemo_stream_t stream);
+
 /* ---- fp32-tolerance mode, forward (csrc/fp32mode.hip; host side hri-emo_amd/_fp32.py, HRIEMO_PRECISION=fp32).
  * The reference's modules are fp32 nn.Modules throughout (models/cross_modal_block_tacfn.py:70-125, beta_gate_tacfn.py:68-118,
  * emotion_decoder.py:30-64,116-162); this mode reproduces them to 1e-3 (no dropout; the backward follows below):

@@ -1,0 +1,23 @@
+#!/bin/bash
+# GPU box: the packed tail as a step.  First the interleaved A/B of scripts_dev/ab_packed_tail.py (profiler off), then each arm alone
+# under rocprofv3 --kernel-trace --stats for the per-kernel totals; everything into $OUT (default bench_out/ab)
+set -o pipefail
+export TMPDIR=/tmp
+export OUT=${OUT:-bench_out/ab}
+mkdir -p $OUT
+timeout -k 10 400 python3 scripts_dev/ab_packed_tail.py 7 30 2>&1 | tee $OUT/ab.log | tail -15 || exit 3
+for m in off on; do
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$m -- python3 scripts_dev/ab_packed_tail.py profile $m 20 > $OUT/$m.log 2>&1 || exit 4
+  python3 - $m <<'PY' || exit 5
+import csv, glob, os, sqlite3, sys
+m = sys.argv[1]
+d = sqlite3.connect(glob.glob(os.environ["OUT"] + f"/{m}/**/*.db", recursive=True)[0])
+with open(os.environ["OUT"] + f"/{m}_kernel_stats.csv", "w", newline="") as f:
+    w = csv.writer(f)
+    w.writerow(["Name", "Calls", "TotalDurationUs", "AverageUs", "Percentage"])
+    for n, c, t, a, p in d.execute("select name,total_calls,total_duration,average,percentage from top_kernels"):
+        w.writerow([n, c, round(t, 1), round(a, 2), round(p, 3)])
+PY
+  rm -rf $OUT/$m
+  tail -2 $OUT/$m.log
+done

@@ -1,0 +1,91 @@
+"""Host side of the packed tail (no GPU): the fused sequence plan -- sample b of the fused memory has min(la[b], lt[b]) rows,
+because the reference ORs the two prefix masks cut to the text length (models/fusion_with_emotion_decoder.py:62-79)."""
+import types
+
+import torch
+
+LENS_A = [70, 33, 32, 1, 17]
+LENS_T = [40, 1, 32, 31, 16]
+LENS_F = [40, 1, 32, 1, 16]
+B, LA, LT = 5, 70, 40
+
+
+def _masks():
+    return (torch.arange(LA)[None] >= torch.tensor(LENS_A)[:, None]), (torch.arange(LT)[None] >= torch.tensor(LENS_T)[:, None])
+
+
+def _cum(lens):
+    out = [0]
+    for x in lens:
+        out.append(out[-1] + x)
+    return out
+
+
+def test_fused_plan_comes_from_the_masks():
+    from hri_emo_amd import _ops
+    m_a, m_t = _masks()
+    plans = _ops.seq_plans(m_a, m_t, B, LA, LT)
+    assert plans is not None and len(plans) == 3
+    sa, st, sf = plans
+    assert sa.cu.tolist() == _cum(LENS_A) and st.cu.tolist() == _cum(LENS_T)
+    assert sf.cu.tolist() == _cum(LENS_F) and sf.cu.dtype == torch.int32
+    assert (sf.B, sf.Breal, sf.L, sf.Lmax, sf.N, sf.surplus, sf.idx) == (B, B, LT, 40, sum(LENS_F), False, None)
+    # what the reference's fused mask leaves valid
+    fused = m_a[:, :LT] | m_t
+    assert (~fused).sum(1).tolist() == LENS_F
+    assert _ops.seq_plans(m_a, m_t, B, LA, LT)[2] is sf          # cached: no second read of the lengths
+
+
+def test_masks_that_are_not_prefixes_give_no_plan():
+    from hri_emo_amd import _ops
+    m_a, m_t = _masks()
+    hole = m_t.clone(); hole[0, 3] = True
+    assert _ops.seq_plans(m_a, hole, B, LA, LT) is None
+    empty = m_a.clone(); empty[2, :] = True
+    assert _ops.seq_plans(empty, m_t, B, LA, LT) is None
+    assert _ops.seq_plans(None, m_t, B, LA, LT) is None
+
+
+def test_bucket_fused_plan_rides_in_the_text_bucket():
+    from hri_emo_amd import _ops, dp
+    pb = {"B": B, "La": LA, "Lt": LT, "cu_a": torch.zeros(B + 2, dtype=torch.int32), "cu_t": torch.zeros(B + 2, dtype=torch.int32),
+          "cu_f": torch.zeros(B + 2, dtype=torch.int32)}
+    stub = types.SimpleNamespace(_pb=pb)
+    m_a, m_t = _masks()
+    for lengths in (None, (LENS_A, LENS_T)):
+        pb["cu_f"].zero_()
+        ra, rt = dp.DataParallelStep._packed_key(stub, m_a, m_t, lengths)
+        cu_f = pb["cu_f"].tolist()
+        assert cu_f[:B + 1] == _cum(LENS_F)
+        assert cu_f[B + 1] == rt == pb["cu_t"].tolist()[B + 1] and cu_f[B] < rt          # ends at the text bucket's row count
+    sf = _ops.seq_bucket_fused(pb["cu_f"], B, LT, rt)
+    # the surplus rows form no sequence on the attention side: B sequences, not B + 1, and the plan says that rows are left over
+    assert (sf.B, sf.Breal, sf.N, sf.L, sf.Lmax, sf.surplus) == (B, B, rt, LT, LT, True)
+    st = _ops.seq_bucket(pb["cu_t"], B, LT, rt)
+    assert st.B == B + 1 and st.N == sf.N
+
+
+def test_decoder_query_plan_is_trivial():
+    from hri_emo_amd import _ops
+    sq = _ops.query_seq(B, 6, torch.device("cpu"))
+    assert sq.cu.tolist() == [6 * b for b in range(B + 1)] and sq.idx is None and (sq.B, sq.L, sq.Lmax, sq.N) == (B, 6, 6, 6 * B)
+    assert _ops.query_seq(B, 6, torch.device("cpu")) is sq
+
+
+def test_the_tail_unpacks_outside_the_bf16_path():
+    from hri_emo_amd import _ops
+    prec, mode, tail = _ops.precision(), _ops.gemm_mode(), _ops.PACKED_TAIL
+    try:
+        _ops.PACKED_TAIL = False
+        assert not _ops.packed_tail()
+        _ops.PACKED_TAIL = True
+        assert _ops.packed_tail()
+        _ops.set_precision("fp32")
+        assert not _ops.packed_tail()
+        _ops.set_precision("bf16")
+        _ops.set_gemm_mode("mx_fp8")
+        assert not _ops.packed_tail()
+    finally:
+        _ops.set_precision(prec)
+        _ops.set_gemm_mode(mode)
+        _ops.PACKED_TAIL = tail
