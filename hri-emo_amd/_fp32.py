@@ -355,6 +355,7 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
     Lk = xkv.shape[1]
     hd = _ops._heads(d, H)
     rec = recording(ctx)
+    kv_surplus = isinstance(kpm, tuple) and kpm[1].surplus          # key rows of no sequence (the fused bucket plan)
     kpm, AB, ALq, ALk, cu, RL, rows = _packing(kpm, B, Lq, Lk, need_w)
     d_attn, d_res = _drops(p, seed, site, b_off, RL)
     xqf = _twin(xq, xq32).view(B * Lq, d)
@@ -372,6 +373,7 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
         ctx.save_for_backward(xqf, xkvf, q, kv, o, lse, g, kpm)
         ctx.f32_cfg = (B, Lq, Lk, d, H, hd)
         ctx.f32_packed = (AB, ALq, ALk, cu, rows)
+        ctx.f32_kv_surplus = kv_surplus
         ctx.f32_drop = (d_attn, d_res)
         ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype, ctx.f32_kv_dtype = xq32 is not None, xq.dtype, xkv.dtype
@@ -391,7 +393,9 @@ def cross_attn_ln_bwd(ctx, dy, dy32):
     dw_out = linear_dw(dg, o)
     do = linear_dx(dg, sh, w_out)
     dq = _new((B * Lq, d), xqf)
-    dkv = _new((B * Lk, 2 * d), xqf)
+    # packed memory with surplus rows (the fused bucket plan): the varlen backward writes the rows of the B real sequences only,
+    # the K | V weight-gradient GEMM and colsum read every row
+    dkv = (torch.zeros if ctx.f32_kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=F32, device=xqf.device)
     attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], AB, H, ALq, ALk, hd, kpm, drop=d_attn, cu=cu)
     dw_in = _new((3 * d, d), xqf)
     dw_in[:d].copy_(linear_dw(dq, xqf))
@@ -462,26 +466,42 @@ def ffn_ln_bwd(ctx, dy, dy32):
     return (gx[0], gx[1], dw1, db1, dw2, db2, dgamma, dbeta) + (None,) * 7
 
 
-def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t):
+def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan=None):
     """models/beta_gate_tacfn.py:68-118 in fp32 -> (h_fusion fp32 [B,L,d], beta [B,1]).  h_fusion is handed on as the fp32 tensor
-    itself (the decoder reads it as its memory and autograd sees it); ctx None: plain forward, nothing saved"""
+    itself (the decoder reads it as its memory and autograd sees it); ctx None: plain forward, nothing saved.
+    plan = (Seq audio, Seq text, Seq fused): h_a / h_t (and twins) are the encoder's packed rows [1, N, d], h_fusion comes back as
+    the packed fused memory [1, N_f, d] (surplus rows zero).  The two LayerNorms are row-wise and run on the packed rows as they
+    are; pool, fuse and their backward read cu_seqlens (hriemo_*_f32_packed)."""
     _ops._require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
     _ops._require_gpu(h_a)
-    B, La, d = h_a.shape
-    Lt = h_t.shape[1]
+    d = h_a.shape[-1]
+    if plan is not None:
+        sa, sq_t, sf = plan
+        B, La, Lt = sa.Breal, sa.L, sq_t.L
+        if h_a.shape[1] != sa.N or h_t.shape[1] != sq_t.N:
+            raise ValueError(f"BetaGate: packed rows {h_a.shape[1]} / {h_t.shape[1]} do not match the plan ({sa.N} / {sq_t.N})")
+        Ra, Rt = sa.N, sq_t.N
+    else:
+        B, La, _ = h_a.shape
+        Lt = h_t.shape[1]
+        Ra, Rt = B * La, B * Lt
     L = La if La == Lt else Lt
     if La < L:
         raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
     dev = h_a.device
     st = _ops._stream()
-    a32 = _twin(h_a, h_a32).view(B * La, d)
-    t32 = _twin(h_t, h_t32).view(B * Lt, d)
+    a32 = _twin(h_a, h_a32).view(Ra, d)
+    t32 = _twin(h_t, h_t32).view(Rt, d)
     _, An = add_ln(a32, None, ga, ba, want16=False)
     _, Tn = add_ln(t32, None, gt, bt, want16=False)
     a_pool = torch.empty((B, d), dtype=F32, device=dev)
     t_pool = torch.empty((B, d), dtype=F32, device=dev)
-    _lib.call("hriemo_masked_mean_f32", _ops._p(An), _ops._p(kpm_a), _ops._p(a_pool), B, La, d, st)
-    _lib.call("hriemo_masked_mean_f32", _ops._p(Tn), _ops._p(kpm_t), _ops._p(t_pool), B, Lt, d, st)
+    if plan is not None:
+        _lib.call("hriemo_masked_mean_f32_packed", _ops._p(An), _ops._p(sa.cu), sa.N, _ops._p(a_pool), B, La, d, st)
+        _lib.call("hriemo_masked_mean_f32_packed", _ops._p(Tn), _ops._p(sq_t.cu), sq_t.N, _ops._p(t_pool), B, Lt, d, st)
+    else:
+        _lib.call("hriemo_masked_mean_f32", _ops._p(An), _ops._p(kpm_a), _ops._p(a_pool), B, La, d, st)
+        _lib.call("hriemo_masked_mean_f32", _ops._p(Tn), _ops._p(kpm_t), _ops._p(t_pool), B, Lt, d, st)
     gin = torch.empty((B, 4 * d), dtype=F32, device=dev)
     _lib.call("hriemo_gate_input_f32", _ops._p(a_pool), _ops._p(t_pool), _ops._p(gin), B, d, st)
     hid = linear(gin, sh, w1, b1)
@@ -489,14 +509,20 @@ def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, k
     w = torch.empty((B, d), dtype=F32, device=dev)
     beta = torch.empty((B, 1), dtype=F32, device=dev)
     _lib.call("hriemo_sigmoid_beta_f32", _ops._p(pre), _ops._p(w), _ops._p(beta), B, d, st)
-    H32 = torch.empty((B, L, d), dtype=F32, device=dev)
-    _lib.call("hriemo_fuse_f32", _ops._p(w), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(H32), None, B, L, d, st)
+    if plan is not None:
+        H32 = torch.empty((1, sf.N, d), dtype=F32, device=dev)
+        _lib.call("hriemo_fuse_f32_packed", _ops._p(w), _ops._p(An), _ops._p(sa.cu), sa.N, La, _ops._p(Tn), _ops._p(sq_t.cu), sq_t.N, Lt,
+                  _ops._p(H32), None, _ops._p(sf.cu), sf.N, B, L, d, st)
+    else:
+        H32 = torch.empty((B, L, d), dtype=F32, device=dev)
+        _lib.call("hriemo_fuse_f32", _ops._p(w), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(H32), None, B, L, d, st)
     if ctx is not None:
         ctx.fp32 = True
         if recording(ctx):
             ctx.set_materialize_grads(False)
             ctx.save_for_backward(a32, t32, An, Tn, a_pool, t_pool, gin, hid, w, kpm_a, kpm_t)
             ctx.f32_cfg = (B, La, Lt, L, d)
+            ctx.f32_plan = plan
             ctx.f32_params = (ga, ba, gt, bt, w1, b1, w2, b2, sh)
             ctx.f32_twins = (h_a32 is not None, h_t32 is not None, h_a.dtype, h_t.dtype)
     return H32, beta
@@ -505,13 +531,20 @@ def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, k
 def beta_gate_bwd(ctx, dH, dbeta):
     a32, t32, An, Tn, a_pool, t_pool, gin, hid, w, kpm_a, kpm_t = ctx.saved_tensors
     B, La, Lt, L, d = ctx.f32_cfg
+    plan = ctx.f32_plan
     ga, ba, gt, bt, w1, b1, w2, b2, sh = ctx.f32_params
     dev = a32.device
     st = _ops._stream()
-    dH = _c(dH.float()) if dH is not None else torch.zeros((B, L, d), dtype=F32, device=dev)
+    if plan is not None:
+        sa, sq_t, sf = plan
+    dH = _c(dH.float()) if dH is not None else torch.zeros((1, sf.N, d) if plan is not None else (B, L, d), dtype=F32, device=dev)
     db = _c(dbeta.float()).view(B) if dbeta is not None else None
     dpre = torch.empty((B, d), dtype=F32, device=dev)
-    _lib.call("hriemo_gate_dpre_f32", _ops._p(dH), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(w), _ops._p(db), _ops._p(dpre), B, L, d, st)
+    if plan is not None:
+        _lib.call("hriemo_gate_dpre_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(An), _ops._p(sa.cu), sa.N, La, _ops._p(Tn),
+                  _ops._p(sq_t.cu), sq_t.N, Lt, _ops._p(w), _ops._p(db), _ops._p(dpre), B, L, d, st)
+    else:
+        _lib.call("hriemo_gate_dpre_f32", _ops._p(dH), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(w), _ops._p(db), _ops._p(dpre), B, L, d, st)
     # MLP: pre = relu(hid) . W2^T + b2, hid = gin . W1^T + b1
     dw2 = linear_dw(dpre, hid, relu_x=True)
     db2 = colsum(dpre)
@@ -524,10 +557,15 @@ def beta_gate_bwd(ctx, dH, dbeta):
     _lib.call("hriemo_gate_input_bwd_f32", _ops._p(dgin), _ops._p(a_pool), _ops._p(t_pool), _ops._p(da), _ops._p(dt), B, d, st)
     outs = []
     for is_a, dpool, kpm, x32, gamma, Lx in ((1, da, kpm_a, a32, ga, La), (0, dt, kpm_t, t32, gt, Lt)):
-        dY = torch.empty((B * Lx, d), dtype=F32, device=dev)
-        _lib.call("hriemo_gate_dy_f32", _ops._p(dH), _ops._p(w), is_a, _ops._p(dpool), _ops._p(kpm), _ops._p(dY), B, L, Lx, d, st)
+        dY = torch.empty((x32.shape[0], d), dtype=F32, device=dev)
+        if plan is not None:
+            seq = sa if is_a else sq_t
+            _lib.call("hriemo_gate_dy_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(w), is_a, _ops._p(dpool), _ops._p(seq.cu), seq.N,
+                      _ops._p(dY), B, L, Lx, d, st)
+        else:
+            _lib.call("hriemo_gate_dy_f32", _ops._p(dH), _ops._p(w), is_a, _ops._p(dpool), _ops._p(kpm), _ops._p(dY), B, L, Lx, d, st)
         dx, _, dgam, dbet, _ = add_ln_bwd(dY, x32, None, gamma, want_dbias=False)
-        outs.append((dx.view(B, Lx, d), dgam, dbet))
+        outs.append((dx.view((1, x32.shape[0], d) if plan is not None else (B, Lx, d)), dgam, dbet))
     (dxa, dga, dba), (dxt, dgt, dbt) = outs
     twin_a, twin_t, dt_a, dt_t = ctx.f32_twins
     ga16 = None if twin_a else (dxa.to(dt_a) if ctx.needs_input_grad[0] else None)

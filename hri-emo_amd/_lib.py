@@ -60,6 +60,10 @@ _SIGS = {
     "hriemo_attn_bwd_f32_varlen": ("plplplplplpppplplplpiiiiifQpIip", "i"),
     "hriemo_add_ln_f32_rows": ("ppppppiiffQpIlpp", "i"),
     "hriemo_add_ln_bwd_f32_rows": ("pppppppppiiiffQpIlppp", "i"),
+    "hriemo_masked_mean_f32_packed": ("ppipiiip", "i"),
+    "hriemo_fuse_f32_packed": ("pppiippiipppiiiip", "i"),
+    "hriemo_gate_dpre_f32_packed": ("ppippiippiipppiiip", "i"),
+    "hriemo_gate_dy_f32_packed": ("ppipippipiiiip", "i"),
     "hriemo_attn_probs": ("plplpppiiiiifQpIip", "i"),
     "hriemo_add_ln_fwd": ("pppppppppiiffQpIlp", "i"),
     "hriemo_add_ln_fwd_mx8": ("pppppppppiiffQpIlpplp", "i"),

@@ -1197,11 +1197,18 @@ def varlen():
 # is scattered back to the padded layout in front of the gate (exactly the launches from before the packed tail) -- the A/B handle.
 # Opt-in until the step has been measured against the False arm (scripts_dev/ab_packed_tail.sh).
 PACKED_TAIL = False
+# The same for the fp32 precision mode (_fp32.beta_gate with a plan, hriemo_*_f32_packed): a switch of its own, because PACKED_TAIL
+# alone must keep meaning "the bf16 tail" (with only PACKED_TAIL set, the fp32 mode issues exactly its previous launches) and
+# because each arm becomes the default only after its own measurement (scripts_dev/ab_packed_tail.sh fp32).
+PACKED_TAIL_FP32 = False
 
 
 def packed_tail():
-    """the tail stays packed: bf16 precision and bf16 GEMM operands (the fp32 mode and the MX-fp8 mode unpack behind the encoder)"""
-    return PACKED_TAIL and precision() == "bf16" and gemm_mode() == "bf16"
+    """the tail stays packed: bf16 GEMM operands (the MX-fp8 mode unpacks behind the encoder) and the switch of the precision
+    mode -- PACKED_TAIL for bf16, PACKED_TAIL_FP32 for fp32"""
+    if gemm_mode() != "bf16":
+        return False
+    return bool(PACKED_TAIL_FP32) if precision() == "fp32" else bool(PACKED_TAIL and precision() == "bf16")
 
 
 class Seq:
@@ -1969,9 +1976,7 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
     @staticmethod
     def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan=None):
         if precision() == "fp32":            # -> (h_fusion as the fp32 tensor itself, beta)
-            if plan is not None:
-                raise RuntimeError("BetaGate: the packed tail is built for the bf16 precision mode")
-            return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t)
+            return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan)
         _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
         _require_gpu(h_a)
         h_a32, h_t32 = _c32(h_a32), _c32(h_t32)

@@ -44,6 +44,19 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- packed (varlen) rows
+// The rows of one sample as a block sees them.  Sequence b of a packed [n_rows, d] buffer = rows cu[b] .. cu[b+1]-1: two scalar
+// loads per block, never a search per row.  The lengths are device data, so they are clamped to the buffer (and to the padded
+// length `cap` that sizes the grid and the partial-sum layouts): a stale cu cannot send a block out of bounds.
+struct PackedSpan { int c0, len; };
+__device__ __forceinline__ PackedSpan packed_span(const int* __restrict__ cu, int b, int cap, int n_rows) {
+  const int c0 = cu[b], c1 = cu[b + 1];
+  PackedSpan s;
+  s.c0 = min(max(c0, 0), n_rows);
+  s.len = max(min(min(c1, n_rows) - s.c0, cap), 0);
+  return s;
+}
+
 // ---------------------------------------------------------------- dropout RNG
 // Counter hash (murmur3 finaliser) -- one 16-bit uniform per element, replayable in the
 // backward from (key, a, b) alone so no mask is ever stored.  key = site_key(seed, site, c).

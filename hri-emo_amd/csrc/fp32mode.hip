@@ -209,15 +209,31 @@ extern "C" int hriemo_add_ln_f32_rows(const float* G, const float* X, const floa
 }
 
 // ------------------------------------------------------------------------------------------- gate pieces (beta_gate_tacfn.py)
+// The gate on packed (varlen) rows: the kernels below that index by sequence position have a packed arm (PK = true) of the SAME
+// body, so the arithmetic and its order cannot drift.  Sample b of a packed [n_rows, d] buffer = rows cu[b] .. cu[b+1]-1
+// (packed_span, common.h: the lengths are device data and are clamped to the buffer and to the padded length that sizes the
+// grid).  Three layouts meet in the gate: the audio rows (cu_a), the text rows (cu_t) and the fused rows (cu_f, min(la, lt) per
+// sample); rows behind the last sample of a buffer (the surplus / filler rows of a bucket plan) are written as zeros.
+struct PackedRows { const int* cu; int n_rows; };
+// the packed arguments ride behind the padded ones as a parameter pack: the padded instantiation <false> has none, its
+// signature and its code are those of the kernel before the packed arm existed
+template <class T> __device__ __forceinline__ const T& pk_arg(const T& t) { return t; }
 // masked mean over the sequence (:6-24): pooled[b][c] = sum_{valid l} X[b][l][c] / max(#valid, 1); fixed summation order
+// PK (one PackedRows): every row of the sample is valid, summed in position order (the padded kernel's order over a prefix mask)
+template <bool PK, class... PKA>
 __global__ __launch_bounds__(256) void masked_mean_f32_kernel(const float* __restrict__ X, const uint8_t* __restrict__ mask, float* __restrict__ pooled,
-                                                              int L, int d) {
+                                                              int L, int d, const PKA... pk) {
   const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
   if (c >= d) return;
+  long base = 0;          // PK: the sample's first packed row
+  if constexpr (PK) {
+    const PackedSpan sx = packed_span(pk_arg(pk...).cu, b, L, pk_arg(pk...).n_rows);
+    base = sx.c0; L = sx.len;
+  }
   float s = 0.f, n = 0.f;
   for (int l = 0; l < L; ++l) {
-    const bool valid = mask == nullptr || mask[(long)b * L + l] == 0;
-    if (valid) { s += X[((long)b * L + l) * d + c]; n += 1.f; }
+    const bool valid = PK || mask == nullptr || mask[(long)b * L + l] == 0;
+    if (valid) { s += X[(PK ? base + l : (long)b * L + l) * d + c]; n += 1.f; }
   }
   pooled[(long)b * d + c] = s / fmaxf(n, 1.f);
 }
@@ -245,6 +261,11 @@ __global__ __launch_bounds__(256) void sigmoid_beta_f32_kernel(const float* __re
   if (tid == 0) beta[b] = (red[0] + red[1] + red[2] + red[3]) / (float)d;
 }
 // h[b][l] = w[b] * A[b][l] + (1 - w[b]) * T[b][l] over the first L positions (:98-116); A, T have their own sequence lengths
+// four columns of one row: the arithmetic of the padded and of the packed kernel, as one text.  The fused multiply-add is
+// spelled out (it is the contraction the compiler chose for the padded kernel): left to the compiler, the packed kernel got a
+// multiply and an add for two of the four columns, a last-bit difference between the two layouts
+#define FUSE_F32_QUAD(wv, a, t, o, o16) \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j) { o[j] = __builtin_fmaf(t[j], 1.f - wv[j], wv[j] * a[j]); o16[j] = (bf16_t)o[j]; }
 __global__ __launch_bounds__(256) void fuse_f32_kernel(const float* __restrict__ w, const float* __restrict__ A, int La, const float* __restrict__ T,
                                                        int Lt, float* __restrict__ H32, bf16_t* __restrict__ H16, int B, int L, int d) {
   const int nq = d >> 2;
@@ -258,17 +279,66 @@ __global__ __launch_bounds__(256) void fuse_f32_kernel(const float* __restrict__
     const f32x4 wv = *(const f32x4*)(w + b * d + q * 4);
     f32x4 o;
     bf16x4 o16;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o[j] = wv[j] * a[j] + (1.f - wv[j]) * t[j]; o16[j] = (bf16_t)o[j]; }
+    FUSE_F32_QUAD(wv, a, t, o, o16)
     *(f32x4*)(H32 + v * 4) = o;
     if (H16 != nullptr) *(bf16x4*)(H16 + v * 4) = o16;
+  }
+}
+// the same on packed rows: H[cu_f[b] + j] = w[b] * A[cu_a[b] + j] + (1 - w[b]) * T[cu_t[b] + j] for j < cu_f[b+1] - cu_f[b].
+// Block (x, b) walks the positions x * FUSE_PK_ROWS .. of sample b; grid y = B + 1: slice B zeroes the surplus rows cu_f[B] ..
+// n_f-1 (the decoder's K | V projections and their weight gradients read every row).  A fused row whose audio or text row would
+// lie outside its sample (a stale cu) is written as zeros, never read out of bounds.
+#define FUSE_PK_ROWS 8
+__global__ __launch_bounds__(256) void fuse_f32_packed_kernel(const float* __restrict__ w, const float* __restrict__ A, const PackedRows pa, int La,
+                                                              const float* __restrict__ T, const PackedRows pt, int Lt, float* __restrict__ H32,
+                                                              bf16_t* __restrict__ H16, const PackedRows pf, int B, int L, int d) {
+  const int nq = d >> 2, b = blockIdx.y;
+  if (b == B) {
+    const long r0 = min(max(pf.cu[B], 0), pf.n_rows);
+    for (long r = r0 + blockIdx.x; r < pf.n_rows; r += gridDim.x)
+      for (int q = threadIdx.x; q < nq; q += 256) {
+        *(f32x4*)(H32 + r * d + q * 4) = f32x4{};
+        if (H16 != nullptr) *(bf16x4*)(H16 + r * d + q * 4) = bf16x4{};
+      }
+    return;
+  }
+  const PackedSpan sf = packed_span(pf.cu, b, L, pf.n_rows);
+  const PackedSpan sa = packed_span(pa.cu, b, La, pa.n_rows), st = packed_span(pt.cu, b, Lt, pt.n_rows);
+  const int j0 = blockIdx.x * FUSE_PK_ROWS, j1 = min(j0 + FUSE_PK_ROWS, sf.len), have = min(sa.len, st.len);
+  for (int v = threadIdx.x; v < (j1 - j0) * nq; v += 256) {
+    const int j = j0 + v / nq, q = v % nq;
+    const long h = ((long)sf.c0 + j) * d + q * 4;
+    f32x4 o{};
+    bf16x4 o16{};
+    if (j < have) {
+      const f32x4 a = *(const f32x4*)(A + ((long)sa.c0 + j) * d + q * 4), t = *(const f32x4*)(T + ((long)st.c0 + j) * d + q * 4);
+      const f32x4 wv = *(const f32x4*)(w + (long)b * d + q * 4);
+      FUSE_F32_QUAD(wv, a, t, o, o16)
+    }
+    *(f32x4*)(H32 + h) = o;
+    if (H16 != nullptr) *(bf16x4*)(H16 + h) = o16;
   }
 }
 
 extern "C" int hriemo_masked_mean_f32(const float* X, const unsigned char* mask, float* pooled, int B, int L, int d, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && L > 0 && d > 0, "masked_mean_f32: empty input");
-  hipLaunchKernelGGL(masked_mean_f32_kernel, dim3((d + 255) / 256, B), dim3(256), 0, st, X, mask, pooled, L, d);
+  hipLaunchKernelGGL((masked_mean_f32_kernel<false>), dim3((d + 255) / 256, B), dim3(256), 0, st, X, mask, pooled, L, d);
   HRIEMO_LAUNCH_CHECK("masked_mean_f32_kernel");
+  return 0;
+}
+static int check_packed_f32(const char* who, const int* cu, int n_rows, int B, int L, int d) {
+  HRIEMO_CHECK(B > 0 && L > 0 && d > 0 && d % 4 == 0, "%s: bad shape (B=%d L=%d d=%d)", who, B, L, d);
+  HRIEMO_CHECK(cu != nullptr && n_rows > 0, "%s: a sequence plan is missing (n_rows=%d)", who, n_rows);
+  HRIEMO_CHECK((long)n_rows * d < (1L << 31), "%s: more than 2^31 elements", who);
+  return 0;
+}
+extern "C" int hriemo_masked_mean_f32_packed(const float* X, const int* cu_seqlens, int n_rows, float* pooled, int B, int L, int d,
+                                             hipStream_t st) {
+  if (check_packed_f32("masked_mean_f32_packed", cu_seqlens, n_rows, B, L, d)) return 1;
+  HRIEMO_CHECK(X != nullptr && pooled != nullptr, "masked_mean_f32_packed: NULL operand");
+  hipLaunchKernelGGL((masked_mean_f32_kernel<true, PackedRows>), dim3((d + 255) / 256, B), dim3(256), 0, st, X, (const uint8_t*)nullptr, pooled, L, d,
+                     PackedRows{cu_seqlens, n_rows});
+  HRIEMO_LAUNCH_CHECK("masked_mean_f32_kernel<packed>");
   return 0;
 }
 extern "C" int hriemo_gate_input_f32(const float* a_pool, const float* t_pool, float* gate_in, int B, int d, hipStream_t st) {
@@ -291,6 +361,17 @@ extern "C" int hriemo_fuse_f32(const float* w, const float* A, int La, const flo
   if (grid > 8192) grid = 8192;
   hipLaunchKernelGGL(fuse_f32_kernel, dim3(grid), dim3(256), 0, st, w, A, La, T, Lt, H32, (bf16_t*)H16, B, L, d);
   HRIEMO_LAUNCH_CHECK("fuse_f32_kernel");
+  return 0;
+}
+extern "C" int hriemo_fuse_f32_packed(const float* w, const float* A, const int* cu_a, int n_a, int La, const float* T, const int* cu_t, int n_t,
+                                      int Lt, float* H32, void* H16, const int* cu_fused, int n_fused, int B, int L, int d, hipStream_t st) {
+  if (check_packed_f32("fuse_f32_packed", cu_a, n_a, B, La, d) || check_packed_f32("fuse_f32_packed", cu_t, n_t, B, Lt, d) ||
+      check_packed_f32("fuse_f32_packed", cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(L <= La && L <= Lt && w != nullptr && A != nullptr && T != nullptr && H32 != nullptr,
+               "fuse_f32_packed: bad arguments (L=%d La=%d Lt=%d)", L, La, Lt);
+  hipLaunchKernelGGL(fuse_f32_packed_kernel, dim3((L + FUSE_PK_ROWS - 1) / FUSE_PK_ROWS, B + 1), dim3(256), 0, st, w, A, PackedRows{cu_a, n_a}, La,
+                     T, PackedRows{cu_t, n_t}, Lt, H32, (bf16_t*)H16, PackedRows{cu_fused, n_fused}, B, L, d);
+  HRIEMO_LAUNCH_CHECK("fuse_f32_packed_kernel");
   return 0;
 }
 
@@ -949,18 +1030,32 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __re
 // ------------------------------------------------------------------------------------------- gate backward pieces (fp32)
 // h = w * A[:, :L] + (1 - w) * T[:, :L], beta = mean_d(w), w = sigmoid(pre)  (beta_gate_tacfn.py:92-116):
 //   dpre[b][c] = (sum_{l < L} dH[b][l][c] * (A - T)[b][l][c] + dbeta[b] / d) * w (1 - w)
+// PK: dH on the fused rows (cu_f), A / T on their modality's rows (cu_a / cu_t); the sum runs over j < lf[b] with the same two
+// accumulators (even positions into s0, odd into s1, the tail into s0): the padded launch adds the exact zeros of the masked
+// positions on top and nothing else
+struct GatePacked { PackedRows f, a, t; };
+#define GATE_ROW(base, stride, pos) (PK ? (base) + (pos) : (long)b * (stride) + (pos))
+template <bool PK, class... PKA>
 __global__ __launch_bounds__(256) void gate_dpre_f32_kernel(const float* __restrict__ dH, const float* __restrict__ A, int La,
                                                             const float* __restrict__ T, int Lt, const float* __restrict__ w,
-                                                            const float* __restrict__ dbeta, float* __restrict__ dpre, int L, int d) {
+                                                            const float* __restrict__ dbeta, float* __restrict__ dpre, int L, int d, const PKA... pk) {
   const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
   if (c >= d) return;
+  long hb = 0, ab = 0, tb = 0;          // PK: the sample's first row in the three packed layouts
+  if constexpr (PK) {
+    const GatePacked& g = pk_arg(pk...);
+    const PackedSpan sf = packed_span(g.f.cu, b, L, g.f.n_rows);
+    const PackedSpan sa = packed_span(g.a.cu, b, La, g.a.n_rows), st = packed_span(g.t.cu, b, Lt, g.t.n_rows);
+    hb = sf.c0; ab = sa.c0; tb = st.c0;
+    L = min(sf.len, min(sa.len, st.len));
+  }
   float s0 = 0.f, s1 = 0.f;
   int l = 0;
   for (; l + 2 <= L; l += 2) {
-    s0 += dH[((long)b * L + l) * d + c] * (A[((long)b * La + l) * d + c] - T[((long)b * Lt + l) * d + c]);
-    s1 += dH[((long)b * L + l + 1) * d + c] * (A[((long)b * La + l + 1) * d + c] - T[((long)b * Lt + l + 1) * d + c]);
+    s0 += dH[GATE_ROW(hb, L, l) * d + c] * (A[GATE_ROW(ab, La, l) * d + c] - T[GATE_ROW(tb, Lt, l) * d + c]);
+    s1 += dH[(GATE_ROW(hb, L, l) + 1) * d + c] * (A[(GATE_ROW(ab, La, l) + 1) * d + c] - T[(GATE_ROW(tb, Lt, l) + 1) * d + c]);
   }
-  for (; l < L; ++l) s0 += dH[((long)b * L + l) * d + c] * (A[((long)b * La + l) * d + c] - T[((long)b * Lt + l) * d + c]);
+  for (; l < L; ++l) s0 += dH[GATE_ROW(hb, L, l) * d + c] * (A[GATE_ROW(ab, La, l) * d + c] - T[GATE_ROW(tb, Lt, l) * d + c]);
   const float wv = w[(long)b * d + c];
   const float dw = (s0 + s1) + (dbeta != nullptr ? dbeta[b] / (float)d : 0.f);
   dpre[(long)b * d + c] = dw * wv * (1.f - wv);
@@ -978,27 +1073,49 @@ __global__ __launch_bounds__(256) void gate_in_bwd_f32_kernel(const float* __res
 }
 // gradient that reaches the gate's LayerNorm output of one modality, row (b, l) of Lx:
 //   dY = (l < L ? wsel * dH[b][l] : 0) + (valid(b, l) ? dpool[b] / max(#valid(b), 1) : 0),  wsel = w (audio) or 1 - w (text)
+// PK: grid (Lx, B + 1); block (l, b) writes row cu_x[b] + l of the modality's packed dY (every row of a sample is valid, so the
+// count is its length), dH is read on the fused rows cu_f[b] + l for l < lf[b]; slice B zeroes the rows behind cu_x[B] (the
+// all-zero filler sequence of a bucket plan: the LayerNorm backward sums every row into dgamma / dbeta)
+struct GateDyPacked { PackedRows f, x; int B; };
+template <bool PK, class... PKA>
 __global__ __launch_bounds__(256) void gate_dy_f32_kernel(const float* __restrict__ dH, const float* __restrict__ w, int is_a,
                                                           const float* __restrict__ dpool, const uint8_t* __restrict__ mask,
-                                                          float* __restrict__ dY, int L, int Lx, int d) {
-  __shared__ float cnt_s;
+                                                          float* __restrict__ dY, int L, int Lx, int d, const PKA... pk) {
   const int b = blockIdx.y, l = blockIdx.x, tid = threadIdx.x;
-  if (tid < 64) {
-    float n = 0.f;
-    for (int k = tid; k < Lx; k += 64) n += (mask == nullptr || mask[(long)b * Lx + k] == 0) ? 1.f : 0.f;
-    n = wave_sum(n);
-    if (tid == 0) cnt_s = fmaxf(n, 1.f);
+  long xb = 0, hb = 0;          // PK: the sample's first row in the modality's and in the fused packed layout
+  float inv;
+  if constexpr (PK) {
+    const GateDyPacked& g = pk_arg(pk...);
+    if (b == g.B) {
+      for (long r = (long)min(max(g.x.cu[g.B], 0), g.x.n_rows) + l; r < g.x.n_rows; r += gridDim.x)
+        for (int c = tid; c < d; c += 256) dY[r * d + c] = 0.f;
+      return;
+    }
+    const PackedSpan sx = packed_span(g.x.cu, b, Lx, g.x.n_rows);
+    if (l >= sx.len) return;
+    const PackedSpan sf = packed_span(g.f.cu, b, L, g.f.n_rows);
+    xb = sx.c0; hb = sf.c0; L = sf.len;
+    inv = 1.f / fmaxf((float)sx.len, 1.f);
+  } else {
+    __shared__ float cnt_s;
+    if (tid < 64) {
+      float n = 0.f;
+      for (int k = tid; k < Lx; k += 64) n += (mask == nullptr || mask[(long)b * Lx + k] == 0) ? 1.f : 0.f;
+      n = wave_sum(n);
+      if (tid == 0) cnt_s = fmaxf(n, 1.f);
+    }
+    __syncthreads();
+    const bool valid = mask == nullptr || mask[(long)b * Lx + l] == 0;
+    inv = valid ? 1.f / cnt_s : 0.f;
   }
-  __syncthreads();
-  const bool valid = mask == nullptr || mask[(long)b * Lx + l] == 0;
-  const float inv = valid ? 1.f / cnt_s : 0.f;
   for (int c = tid; c < d; c += 256) {
     const float wv = w[(long)b * d + c];
     float v = dpool[(long)b * d + c] * inv;
-    if (l < L) v += (is_a ? wv : 1.f - wv) * dH[((long)b * L + l) * d + c];
-    dY[((long)b * Lx + l) * d + c] = v;
+    if (l < L) v += (is_a ? wv : 1.f - wv) * dH[GATE_ROW(hb, L, l) * d + c];
+    dY[GATE_ROW(xb, Lx, l) * d + c] = v;
   }
 }
+#undef GATE_ROW
 // logits[m] = z[m] . w + b (emotion_decoder.py:155): dz = dl w, dw = sum_m dl[m] z[m], db = sum_m dl[m]; fixed summation order
 __global__ __launch_bounds__(256) void rowdot_bwd_f32_kernel(const float* __restrict__ dl, const float* __restrict__ Z, const float* __restrict__ w,
                                                              float* __restrict__ dZ, float* __restrict__ dw, float* __restrict__ db, int M, int d,
@@ -1024,8 +1141,20 @@ __global__ __launch_bounds__(256) void rowdot_bwd_f32_kernel(const float* __rest
 extern "C" int hriemo_gate_dpre_f32(const float* dH, const float* A, int La, const float* T, int Lt, const float* w, const float* dbeta,
                                     float* dpre, int B, int L, int d, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && L > 0 && d > 0 && L <= La && L <= Lt, "gate_dpre_f32: bad shape");
-  hipLaunchKernelGGL(gate_dpre_f32_kernel, dim3((d + 255) / 256, B), dim3(256), 0, st, dH, A, La, T, Lt, w, dbeta, dpre, L, d);
+  hipLaunchKernelGGL((gate_dpre_f32_kernel<false>), dim3((d + 255) / 256, B), dim3(256), 0, st, dH, A, La, T, Lt, w, dbeta, dpre, L, d);
   HRIEMO_LAUNCH_CHECK("gate_dpre_f32_kernel");
+  return 0;
+}
+extern "C" int hriemo_gate_dpre_f32_packed(const float* dH, const int* cu_fused, int n_fused, const float* A, const int* cu_a, int n_a, int La,
+                                           const float* T, const int* cu_t, int n_t, int Lt, const float* w, const float* dbeta, float* dpre,
+                                           int B, int L, int d, hipStream_t st) {
+  if (check_packed_f32("gate_dpre_f32_packed", cu_a, n_a, B, La, d) || check_packed_f32("gate_dpre_f32_packed", cu_t, n_t, B, Lt, d) ||
+      check_packed_f32("gate_dpre_f32_packed", cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(L <= La && L <= Lt && dH != nullptr && A != nullptr && T != nullptr && w != nullptr && dpre != nullptr,
+               "gate_dpre_f32_packed: bad arguments (L=%d La=%d Lt=%d)", L, La, Lt);
+  hipLaunchKernelGGL((gate_dpre_f32_kernel<true, GatePacked>), dim3((d + 255) / 256, B), dim3(256), 0, st, dH, A, La, T, Lt, w, dbeta, dpre, L, d,
+                     GatePacked{PackedRows{cu_fused, n_fused}, PackedRows{cu_a, n_a}, PackedRows{cu_t, n_t}});
+  HRIEMO_LAUNCH_CHECK("gate_dpre_f32_kernel<packed>");
   return 0;
 }
 extern "C" int hriemo_gate_input_bwd_f32(const float* dgin, const float* a_pool, const float* t_pool, float* da, float* dt, int B, int d,
@@ -1038,8 +1167,17 @@ extern "C" int hriemo_gate_input_bwd_f32(const float* dgin, const float* a_pool,
 extern "C" int hriemo_gate_dy_f32(const float* dH, const float* w, int is_a, const float* dpool, const unsigned char* mask, float* dY, int B,
                                   int L, int Lx, int d, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && L > 0 && Lx >= L && d > 0, "gate_dy_f32: bad shape");
-  hipLaunchKernelGGL(gate_dy_f32_kernel, dim3(Lx, B), dim3(256), 0, st, dH, w, is_a, dpool, mask, dY, L, Lx, d);
+  hipLaunchKernelGGL((gate_dy_f32_kernel<false>), dim3(Lx, B), dim3(256), 0, st, dH, w, is_a, dpool, mask, dY, L, Lx, d);
   HRIEMO_LAUNCH_CHECK("gate_dy_f32_kernel");
+  return 0;
+}
+extern "C" int hriemo_gate_dy_f32_packed(const float* dH, const int* cu_fused, int n_fused, const float* w, int is_a, const float* dpool,
+                                         const int* cu_x, int n_x, float* dY, int B, int L, int Lx, int d, hipStream_t st) {
+  if (check_packed_f32("gate_dy_f32_packed", cu_x, n_x, B, Lx, d) || check_packed_f32("gate_dy_f32_packed", cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(Lx >= L && dH != nullptr && w != nullptr && dpool != nullptr && dY != nullptr, "gate_dy_f32_packed: bad arguments (L=%d Lx=%d)", L, Lx);
+  hipLaunchKernelGGL((gate_dy_f32_kernel<true, GateDyPacked>), dim3(Lx, B + 1), dim3(256), 0, st, dH, w, is_a, dpool, (const uint8_t*)nullptr, dY, L,
+                     Lx, d, GateDyPacked{PackedRows{cu_fused, n_fused}, PackedRows{cu_x, n_x}, B});
+  HRIEMO_LAUNCH_CHECK("gate_dy_f32_kernel<packed>");
   return 0;
 }
 extern "C" int hriemo_rowdot_bwd_f32(const float* dl, const float* Z, const float* w, float* dZ, float* dw, float* db, int accumulate, int M,

@@ -668,17 +668,7 @@ __global__ __launch_bounds__(ROWDOT_GROUPS * 32) void rowdot_bwd_kernel(const fl
 }
 
 // ------------------------------------------------------------------ beta gate
-// Packed (varlen) tail: the rows of one sample as a block sees them.  Sequence b of a packed [n_rows, d] buffer = rows cu[b] ..
-// cu[b+1]-1: two scalar loads per block, never a search per row.  The lengths are device data, so they are clamped to the buffer
-// (and to the padded length `cap` that sizes the grid and the partial-sum layouts): a stale cu cannot send a block out of bounds.
-struct PackedSpan { int c0, len; };
-__device__ __forceinline__ PackedSpan packed_span(const int* __restrict__ cu, int b, int cap, int n_rows) {
-  const int c0 = cu[b], c1 = cu[b + 1];
-  PackedSpan s;
-  s.c0 = min(max(c0, 0), n_rows);
-  s.len = max(min(min(c1, n_rows) - s.c0, cap), 0);
-  return s;
-}
+// Packed (varlen) tail: the rows of one sample as a block sees them are a PackedSpan (packed_span, common.h).
 // the packed arguments of the gate kernels below (PK = true): cu [nseq+1] of the modality's packed X (nseq = B, or B + 1 when the
 // rows behind the last sample form the bucket's surplus sequence), cu_f [B+1] of the packed fused layout with n_f rows
 struct PackedArgs { const int* cu; int nseq, n_rows; const int* cu_f; int n_f, B; };

@@ -512,6 +512,30 @@ int hriemo_add_ln_bwd_f32_rows(const float* dY, const float* G, const float* X, 
                                const unsigned long long* seed_dev, unsigned site, long row_offset, float* workspace,
                                const long long* row_index, hriemo_stream_t stream);
 
+/* ---- fp32-tolerance mode, the gate on packed (varlen) rows: the packed arm of the four gate kernels that index by sequence
+ * position (same kernel bodies, so the arithmetic and its order are the padded launch's).  Three layouts meet: the audio rows
+ * (cu_a [B+1], n_a rows), the text rows (cu_t, n_t) and the fused rows (cu_fused, n_fused; sample b owns min(la, lt) rows); sample
+ * b of a layout = rows cu[b] .. cu[b+1]-1.  The cu arrays are int32 DEVICE memory: grids depend on (B, L, d) only, the lengths are
+ * read by the blocks and clamped to the buffers and to the padded lengths La / Lt / L (a stale cu cannot send a block out of
+ * bounds), so one captured graph serves every batch of a bucket.  Rows of a buffer behind its last sample (the surplus rows of a
+ * fused bucket plan, the all-zero filler sequence of a modality's) are written as ZEROS.  The LayerNorms of the gate are
+ * row-wise: hriemo_add_ln_f32 / hriemo_add_ln_bwd_f32 run on the packed rows as they are.
+ *  - hriemo_masked_mean_f32_packed: pooled[b] = sum of the sample's rows of X [n_rows, d] / max(len, 1), in position order.
+ *  - hriemo_fuse_f32_packed: H[cu_fused[b] + j] = w[b] A[cu_a[b] + j] + (1 - w[b]) T[cu_t[b] + j] for j < cu_fused[b+1] -
+ *    cu_fused[b]; rows cu_fused[B] .. n_fused-1 of H32 and (when given) H16 are zeros.
+ *  - hriemo_gate_dpre_f32_packed: hriemo_gate_dpre_f32 with the sum over j < lf[b] (dH on the fused rows, A / T on their own).
+ *  - hriemo_gate_dy_f32_packed: dY[cu_x[b] + i] = dpool[b] / max(len_x[b], 1) + (i < lf[b] ? wsel dH[cu_fused[b] + i] : 0) on
+ *    the modality's n_x packed rows; rows cu_x[B] .. n_x-1 are zeros. */
+int hriemo_masked_mean_f32_packed(const float* X, const int* cu_seqlens, int n_rows, float* pooled, int B, int L, int d,
+                                  hriemo_stream_t stream);
+int hriemo_fuse_f32_packed(const float* w, const float* A, const int* cu_a, int n_a, int La, const float* T, const int* cu_t, int n_t, int Lt,
+                           float* H32, void* H16, const int* cu_fused, int n_fused, int B, int L, int d, hriemo_stream_t stream);
+int hriemo_gate_dpre_f32_packed(const float* dH, const int* cu_fused, int n_fused, const float* A, const int* cu_a, int n_a, int La,
+                                const float* T, const int* cu_t, int n_t, int Lt, const float* w, const float* dbeta, float* dpre, int B,
+                                int L, int d, hriemo_stream_t stream);
+int hriemo_gate_dy_f32_packed(const float* dH, const int* cu_fused, int n_fused, const float* w, int is_a, const float* dpool,
+                              const int* cu_x, int n_x, float* dY, int B, int L, int Lx, int d, hriemo_stream_t stream);
+
 /* ---- per-kernel-class HIP-event timing on the launch stream (bench.py roofline leg) */
 int hriemo_prof_enable(int on);
 int hriemo_prof_nclass(void);

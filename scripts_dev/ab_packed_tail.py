@@ -2,7 +2,9 @@
 `_ops.PACKED_TAIL` False (the encoder's output unpacked in front of the gate: the launches from before the packed tail) against
 True.  Two models from one seed, one DataParallelStep each (a capture bakes the switch in), replays interleaved round by round
 and timed with device events.  `profile off|on [replays]` runs one arm alone for rocprofv3 --kernel-trace --stats.
-usage: python scripts_dev/ab_packed_tail.py [rounds] [replays per round]  |  profile off|on [replays]"""
+A leading `fp32` runs the same A/B in the fp32 precision mode: the switch is `_ops.PACKED_TAIL_FP32`, the batch and the model are
+those of scripts_dev/bench_fp32_varlen.py (cfg 2 shape, dropout 0.1), and the yardstick is the False arm of the same run.
+usage: python scripts_dev/ab_packed_tail.py [bf16|fp32] [rounds] [replays per round]  |  [bf16|fp32] profile off|on [replays]"""
 import os
 import statistics
 import sys
@@ -16,21 +18,33 @@ from hri_emo_amd import _ops  # noqa: E402
 from hri_emo_amd.dp import DataParallelStep  # noqa: E402
 from hri_emo_amd.train import fusion_step_loss  # noqa: E402
 
+argv = sys.argv[1:]
+PREC = argv.pop(0) if argv and argv[0] in ("bf16", "fp32") else "bf16"
+SWITCH = "PACKED_TAIL_FP32" if PREC == "fp32" else "PACKED_TAIL"
 dev = torch.device("cuda", 0)
 B, T_A, T_T = 64, bench.T_A, bench.T_T
-batch = bench.synth(B, 0, dev)
 g = torch.Generator().manual_seed(4321)
 la = torch.randint(T_A // 2, T_A + 1, (B,), generator=g)
 lt = torch.randint(T_T // 2, T_T + 1, (B,), generator=g)
-rb = (batch[0], batch[1], (torch.arange(T_A)[None] >= la[:, None]).to(dev), (torch.arange(T_T)[None] >= lt[:, None]).to(dev), batch[4])
+if PREC == "fp32":           # the batch of scripts_dev/bench_fp32_varlen.py, draw for draw
+    assert (T_A, T_T) == (400, 128), (T_A, T_T)
+    H.set_precision("fp32")
+    CFG = dict(d_model=768, num_emotions=6, n_heads=8, dropout=0.1)
+    h_a, h_t = torch.randn(B, T_A, 768, generator=g).to(dev), torch.randn(B, T_T, 768, generator=g).to(dev)
+    m_a, m_t = (torch.arange(T_A)[None] >= la[:, None]).to(dev), (torch.arange(T_T)[None] >= lt[:, None]).to(dev)
+    rb = (h_a, h_t, m_a, m_t, (torch.rand(B, 6, generator=g) < 0.3).float().to(dev))
+else:
+    CFG = bench.CFG
+    batch = bench.synth(B, 0, dev)
+    rb = (batch[0], batch[1], (torch.arange(T_A)[None] >= la[:, None]).to(dev), (torch.arange(T_T)[None] >= lt[:, None]).to(dev), batch[4])
 valid = float((la.sum() / T_A + lt.sum() / T_T) / (2 * B))
 H.set_varlen(True)
 
 
 def arm(tail):
-    _ops.PACKED_TAIL = tail
+    setattr(_ops, SWITCH, tail)
     torch.manual_seed(1234)
-    model = H.FusionWithEmotionDecoder(**bench.CFG).to(dev).train()
+    model = H.FusionWithEmotionDecoder(**CFG).to(dev).train()
     dp = DataParallelStep(model, fusion_step_loss, overlap=False)
     dp.set_global_batch(B)
     dp.step(*rb)
@@ -51,24 +65,26 @@ def timed(dp, n):
     return e0.elapsed_time(e1) / n
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "profile":
-    dp = arm(sys.argv[2] == "on")
-    n = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-    print(f"PACKED_TAIL {sys.argv[2]}: {timed(dp, n):.3f} ms/step over {n} replays (under the profiler), valid fraction {valid:.3f}")
+if argv and argv[0] == "profile":
+    dp = arm(argv[1] == "on")
+    n = int(argv[2]) if len(argv) > 2 else 20
+    print(f"{SWITCH} {argv[1]}: {timed(dp, n):.3f} ms/step over {n} replays (under the profiler), valid fraction {valid:.3f}")
     sys.exit(0)
 
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+rounds = int(argv[0]) if argv else 7
+n = int(argv[1]) if len(argv) > 1 else 30
 off, on = arm(False), arm(True)
 loss_off, loss_on = float(off.step(*rb)), float(on.step(*rb))
 rel = float((on.buckets.flat - off.buckets.flat).norm() / off.buckets.flat.norm())
-print(f"cfg 2 ragged step, B={B}, valid fraction {valid:.3f}; loss off {loss_off:.6f} on {loss_on:.6f}, flat gradients relative L2 {rel:.2e}")
+print(f"{PREC} cfg 2 ragged step, B={B}, valid fraction {valid:.3f}; loss off {loss_off:.6f} on {loss_on:.6f}, flat gradients relative L2 {rel:.2e}"
+      + (" (dropout on: each capture draws its own seed, so the two arms differ by their masks; equality is the tests' business)"
+         if CFG.get("dropout", 0.0) > 0 else ""))
 t_off, t_on = [], []
 for r in range(rounds):
     t_off.append(timed(off, n))
     t_on.append(timed(on, n))
-    print(f"round {r}: PACKED_TAIL off {t_off[-1]:.3f} ms/step, on {t_on[-1]:.3f} ms/step")
+    print(f"round {r}: {SWITCH} off {t_off[-1]:.3f} ms/step, on {t_on[-1]:.3f} ms/step")
 m_off, m_on = statistics.median(t_off), statistics.median(t_on)
 print(f"median of {rounds} rounds x {n} replays: off {m_off:.3f} ms (min {min(t_off):.3f}, max {max(t_off):.3f}), "
       f"on {m_on:.3f} ms (min {min(t_on):.3f}, max {max(t_on):.3f}); on / off = {m_on / m_off:.4f}, "
-      f"difference {m_off - m_on:+.3f} ms")
+      f"difference {m_off - m_on:+.3f} ms; round-to-round spread off {max(t_off) - min(t_off):.3f} ms, on {max(t_on) - min(t_on):.3f} ms")

@@ -1,13 +1,17 @@
 #!/bin/bash
 # GPU box: the packed tail as a step.  First the interleaved A/B of scripts_dev/ab_packed_tail.py (profiler off), then each arm alone
 # under rocprofv3 --kernel-trace --stats for the per-kernel totals; everything into $OUT (default bench_out/ab)
+# usage: scripts_dev/ab_packed_tail.sh [bf16|fp32]   (fp32: _ops.PACKED_TAIL_FP32 on the fp32 step, fewer replays of a ~34 ms step)
 set -o pipefail
+PREC=${1:-bf16}
+ROUNDS=7; REPLAYS=30; PROF=20
+if [ "$PREC" = fp32 ]; then REPLAYS=10; PROF=5; fi
 export TMPDIR=/tmp
 export OUT=${OUT:-bench_out/ab}
 mkdir -p $OUT
-timeout -k 10 400 python3 scripts_dev/ab_packed_tail.py 7 30 2>&1 | tee $OUT/ab.log | tail -15 || exit 3
+timeout -k 10 400 python3 scripts_dev/ab_packed_tail.py $PREC $ROUNDS $REPLAYS 2>&1 | tee $OUT/ab.log | tail -15 || exit 3
 for m in off on; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$m -- python3 scripts_dev/ab_packed_tail.py profile $m 20 > $OUT/$m.log 2>&1 || exit 4
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$m -- python3 scripts_dev/ab_packed_tail.py $PREC profile $m $PROF > $OUT/$m.log 2>&1 || exit 4
   python3 - $m <<'PY' || exit 5
 import csv, glob, os, sqlite3, sys
 m = sys.argv[1]
