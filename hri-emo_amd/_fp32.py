@@ -14,8 +14,8 @@ the fp32 kernels drop where the bf16 ones do -- attention weights, sub-layer out
 hidden layer -- from the same counter hash with the same (seed, site, offset) keys, so a model draws the same masks in either
 precision; the backward replays them, nothing is stored.
 
-Packed (varlen) sequences: the sub-layers take the Seq of _ops.pack_pair in the kpm slot, as the bf16 Functions do -- attention on
-cu_seqlens (hriemo_attn_*_f32_varlen), LayerNorm on the gathered rows with the dropout keyed by the padded row (*_f32_rows), every
+Packed (varlen) sequences: the sub-layers take the layouts (_ops.Seq) of their inputs, as the bf16 Functions do, and read them through
+_ops.attn_rows -- attention on cu_seqlens (hriemo_attn_*_f32_varlen), LayerNorm on the gathered rows with the dropout keyed by the padded row (*_f32_rows), every
 Linear on the N packed rows (the bucket's surplus rows carry zero gradients, so the weight-gradient GEMMs need no PAD mask).
 
 Reference arithmetic: models/cross_modal_block_tacfn.py:70-125, models/beta_gate_tacfn.py:68-118, models/emotion_decoder.py:30-64,
@@ -283,42 +283,27 @@ def _drops(p, seed, site, b_off, rows_per_sample):
     return (p, seed, site, b_off), (p, seed, site + 1, b_off * rows_per_sample)
 
 
-def _packing(kpm, B, Lq, Lk, need_w):
-    """the kpm slot -> (kpm | None, attention batch, Lq, Lk, cu | None, rows per padded sample, LayerNorm row index | None).
-    Packed sequences (x is [1, N_valid, d]) carry a Seq there (self-attention) or (Seq of the queries, Seq of the keys)
-    (cross-attention), as in _ops.SelfAttnLN / CrossAttnLN: the attention sees Seq.B samples of up to Seq.Lmax rows, the
-    LayerNorm dropout is keyed by the rows of the padded layout"""
-    if isinstance(kpm, _ops.Seq):
-        kpm = (kpm, kpm)
-    if not isinstance(kpm, tuple):
-        return kpm, B, Lq, Lk, None, Lq, None
-    if need_w:
-        raise ValueError("attention maps are exported by the padded path only")
-    sq, sk = kpm
-    return None, sq.B, sq.Lmax, sk.Lmax, (sq.cu, sk.cu), sq.L, sq.idx
-
-
-def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, need_w, p=0.0, seed=0, site=0, b_off=0):
+def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq, need_w, p=0.0, seed=0, site=0, b_off=0):
     _ops._require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
     _ops._require_gpu(x)
     B, L, d = x.shape
     hd = _ops._heads(d, H)
     rec = recording(ctx)
-    kpm, AB, AL, _, cu, RL, rows = _packing(kpm, B, L, L, need_w)
-    d_attn, d_res = _drops(p, seed, site, b_off, RL)
+    ar = _ops.attn_rows(seq, seq, need_w)
+    d_attn, d_res = _drops(p, seed, site, b_off, ar.stride)
     xf = _twin(x, x32).view(B * L, d)
     qkv = linear(xf, sh, w_in, b_in)
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    o, lse = attn(q, k, v, AB, H, AL, AL, hd, kpm, want_lse=need_w or rec, drop=d_attn, cu=cu)
+    o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
     g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=rows)
-    pr = probs(q, k, B, H, L, L, hd, kpm, lse, drop=d_attn) if need_w else None
+    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=ar.rows)
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xf, qkv, o, lse, g, kpm)
+        ctx.save_for_backward(xf, qkv, o, lse, g)
         ctx.f32_cfg = (B, L, d, H, hd)
-        ctx.f32_packed = (AB, AL, AL, cu, rows)
+        ctx.rows = ar
         ctx.f32_drop = (d_attn, d_res)
         ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
@@ -328,19 +313,19 @@ def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm,
 
 
 def self_attn_ln_bwd(ctx, dy, dy32):
-    xf, qkv, o, lse, g, kpm = ctx.saved_tensors
+    xf, qkv, o, lse, g = ctx.saved_tensors
     B, L, d, H, hd = ctx.f32_cfg
-    AB, ALq, ALk, cu, rows = ctx.f32_packed
+    ar = ctx.rows
     w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
     M = B * L
     d_attn, d_res = ctx.f32_drop
     dyt = _total(dy, dy32, (M, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=rows)
+    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=ar.rows)
     dw_out = linear_dw(dg, o)
     do = linear_dx(dg, sh, w_out)
     dqkv = _new((M, 3 * d), xf)
-    attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], AB, H, ALq, ALk, hd,
-             kpm, drop=d_attn, cu=cu)
+    attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], ar.B, H, ar.Lq, ar.Lk, hd,
+             ar.kpm, drop=d_attn, cu=ar.cu)
     dw_in = linear_dw(dqkv, xf)
     db_in = colsum(dqkv)
     dx = linear_dx(dqkv, sh, w_in, into=ds)            # + the residual path's gradient
@@ -348,32 +333,30 @@ def self_attn_ln_bwd(ctx, dy, dy32):
     return (gx[0], gx[1], dw_in, db_in, dw_out, db_out, dgamma, dbeta) + (None,) * 8
 
 
-def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, need_w, p=0.0, seed=0, site=0, b_off=0):
+def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq_q, seq_k, need_w, p=0.0, seed=0, site=0, b_off=0):
     _ops._require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
     _ops._require_gpu(xq)
     B, Lq, d = xq.shape
     Lk = xkv.shape[1]
     hd = _ops._heads(d, H)
     rec = recording(ctx)
-    kv_surplus = isinstance(kpm, tuple) and kpm[1].surplus          # key rows of no sequence (the fused bucket plan)
-    kpm, AB, ALq, ALk, cu, RL, rows = _packing(kpm, B, Lq, Lk, need_w)
-    d_attn, d_res = _drops(p, seed, site, b_off, RL)
+    ar = _ops.attn_rows(seq_q, seq_k, need_w)
+    d_attn, d_res = _drops(p, seed, site, b_off, ar.stride)
     xqf = _twin(xq, xq32).view(B * Lq, d)
     xkvf = _c(f32_of(xkv)).view(B * Lk, d)
     q = linear(xqf, sh, w_in, b_in, rows=(0, d))
     kv = linear(xkvf, sh, w_in, b_in, rows=(d, 3 * d))
     k, v = kv[:, :d], kv[:, d:]
-    o, lse = attn(q, k, v, AB, H, ALq, ALk, hd, kpm, want_lse=need_w or rec, drop=d_attn, cu=cu)
+    o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
     g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res, rows=rows)
-    pr = probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=d_attn) if need_w else None
+    y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res, rows=ar.rows)
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xqf, xkvf, q, kv, o, lse, g, kpm)
+        ctx.save_for_backward(xqf, xkvf, q, kv, o, lse, g)
         ctx.f32_cfg = (B, Lq, Lk, d, H, hd)
-        ctx.f32_packed = (AB, ALq, ALk, cu, rows)
-        ctx.f32_kv_surplus = kv_surplus
+        ctx.rows = ar
         ctx.f32_drop = (d_attn, d_res)
         ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype, ctx.f32_kv_dtype = xq32 is not None, xq.dtype, xkv.dtype
@@ -383,20 +366,20 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
 
 
 def cross_attn_ln_bwd(ctx, dy, dy32):
-    xqf, xkvf, q, kv, o, lse, g, kpm = ctx.saved_tensors
+    xqf, xkvf, q, kv, o, lse, g = ctx.saved_tensors
     B, Lq, Lk, d, H, hd = ctx.f32_cfg
-    AB, ALq, ALk, cu, rows = ctx.f32_packed
+    ar = ctx.rows
     w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
     d_attn, d_res = ctx.f32_drop
     dyt = _total(dy, dy32, (B * Lq, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xqf, gamma, drop=d_res, rows=rows)
+    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xqf, gamma, drop=d_res, rows=ar.rows)
     dw_out = linear_dw(dg, o)
     do = linear_dx(dg, sh, w_out)
     dq = _new((B * Lq, d), xqf)
     # packed memory with surplus rows (the fused bucket plan): the varlen backward writes the rows of the B real sequences only,
     # the K | V weight-gradient GEMM and colsum read every row
-    dkv = (torch.zeros if ctx.f32_kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=F32, device=xqf.device)
-    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], AB, H, ALq, ALk, hd, kpm, drop=d_attn, cu=cu)
+    dkv = (torch.zeros if ar.kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=F32, device=xqf.device)
+    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, drop=d_attn, cu=ar.cu)
     dw_in = _new((3 * d, d), xqf)
     dw_in[:d].copy_(linear_dw(dq, xqf))
     dw_in[d:].copy_(linear_dw(dkv, xkvf))
@@ -406,21 +389,16 @@ def cross_attn_ln_bwd(ctx, dy, dy32):
     dxkv = None
     if ctx.needs_input_grad[2]:
         dxkv = linear_dx(dkv, sh, w_in, rows=(d, 3 * d)).view(B, Lk, d).to(ctx.f32_kv_dtype)
-    return (gx[0], gx[1], dxkv, dw_in, db_in, dw_out, db_out, dgamma, dbeta) + (None,) * 12
+    return (gx[0], gx[1], dxkv, dw_in, db_in, dw_out, db_out, dgamma, dbeta) + (None,) * 13
 
 
-def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p=0.0, p_mid=0.0, seed=0, site=0, b_off=0, seq=None):
-    """seq: the Seq of packed rows (x is [1, N_valid, d]): the LayerNorm dropout is keyed by the rows of the padded layout"""
+def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq):
+    """seq: the Seq of x's rows; packed (x is [1, N_valid, d]) the LayerNorm dropout is keyed by the rows of the padded layout"""
     _ops._require_fp32_masters(w1, b1, w2, b2, gamma, beta)
     _ops._require_gpu(x)
     shape = x.shape
     d = shape[-1]
-    L = shape[1] if len(shape) == 3 else 1
-    rows = None
-    if seq is not None:
-        if p_mid > 0:
-            raise ValueError("FFNLN: packed rows with a mid-FFN dropout are not built (the encoder's FFNs have none)")
-        L, rows = seq.L, seq.idx
+    L, rows = seq.L, seq.idx
     d_res = (p, seed, site + 1, b_off * L) if p > 0 else None
     d_mid = (p_mid, seed, site + 2, b_off * L) if p_mid > 0 else None        # keys of _ops.FFNLN.forward
     xf = _twin(x, x32).view(-1, d)
@@ -435,7 +413,7 @@ def ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p=0.0, p_mid=0.0, seed=
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xf, h, g)
         ctx.f32_cfg = tuple(shape)
-        ctx.f32_rows = rows
+        ctx.seq = seq
         ctx.f32_drop = (d_res, d_mid)
         ctx.f32_params = (w1, b1, w2, b2, gamma, beta, sh)
         ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
@@ -449,7 +427,7 @@ def ffn_ln_bwd(ctx, dy, dy32):
     M, d = xf.shape
     d_res, d_mid = ctx.f32_drop
     dyt = _total(dy, dy32, (M, d))
-    ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=ctx.f32_rows)
+    ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=ctx.seq.idx)
     if d_mid is not None:                             # g = drop(relu(h)) . W2^T + b2: the dropped activations are rebuilt, not stored
         dw2 = linear_dw(dg, dropout(h, d_mid, relu=True, log=False))
         da = dropout(linear_dx(dg, sh, w2), d_mid, gate=h, log=False)     # * keep / (1 - p) * relu'(h)
@@ -466,85 +444,89 @@ def ffn_ln_bwd(ctx, dy, dy32):
     return (gx[0], gx[1], dw1, db1, dw2, db2, dgamma, dbeta) + (None,) * 7
 
 
-def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan=None):
-    """models/beta_gate_tacfn.py:68-118 in fp32 -> (h_fusion fp32 [B,L,d], beta [B,1]).  h_fusion is handed on as the fp32 tensor
-    itself (the decoder reads it as its memory and autograd sees it); ctx None: plain forward, nothing saved.
-    plan = (Seq audio, Seq text, Seq fused): h_a / h_t (and twins) are the encoder's packed rows [1, N, d], h_fusion comes back as
-    the packed fused memory [1, N_f, d] (surplus rows zero).  The two LayerNorms are row-wise and run on the packed rows as they
-    are; pool, fuse and their backward read cu_seqlens (hriemo_*_f32_packed)."""
+# The gate's row kernels: each takes the layouts (_ops.Seq) of its buffers and picks the padded or the packed entry point itself
+# (sx / sa / st: a modality's rows, sf: the fused memory's; all padded or all packed)
+def masked_mean(Xn, sx, pool, d):
+    if sx.packed:
+        _lib.call("hriemo_masked_mean_f32_packed", _ops._p(Xn), _ops._p(sx.cu), sx.N, _ops._p(pool), sx.Breal, sx.L, d, _ops._stream())
+    else:
+        _lib.call("hriemo_masked_mean_f32", _ops._p(Xn), _ops._p(sx.kpm), _ops._p(pool), sx.B, sx.L, d, _ops._stream())
+
+
+def fuse(w, An, sa, Tn, st, H32, sf, d):
+    if sf.packed:
+        _lib.call("hriemo_fuse_f32_packed", _ops._p(w), _ops._p(An), _ops._p(sa.cu), sa.N, sa.L, _ops._p(Tn), _ops._p(st.cu), st.N, st.L,
+                  _ops._p(H32), None, _ops._p(sf.cu), sf.N, sf.Breal, sf.L, d, _ops._stream())
+    else:
+        _lib.call("hriemo_fuse_f32", _ops._p(w), _ops._p(An), sa.L, _ops._p(Tn), st.L, _ops._p(H32), None, sf.B, sf.L, d, _ops._stream())
+
+
+def gate_dpre(dH, sf, An, sa, Tn, st, w, db, dpre, d):
+    if sf.packed:
+        _lib.call("hriemo_gate_dpre_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(An), _ops._p(sa.cu), sa.N, sa.L, _ops._p(Tn),
+                  _ops._p(st.cu), st.N, st.L, _ops._p(w), _ops._p(db), _ops._p(dpre), sf.Breal, sf.L, d, _ops._stream())
+    else:
+        _lib.call("hriemo_gate_dpre_f32", _ops._p(dH), _ops._p(An), sa.L, _ops._p(Tn), st.L, _ops._p(w), _ops._p(db), _ops._p(dpre),
+                  sf.B, sf.L, d, _ops._stream())
+
+
+def gate_dy(dH, sf, w, is_a, dpool, sx, dY, d):
+    if sf.packed:
+        _lib.call("hriemo_gate_dy_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(w), is_a, _ops._p(dpool), _ops._p(sx.cu), sx.N,
+                  _ops._p(dY), sf.Breal, sf.L, sx.L, d, _ops._stream())
+    else:
+        _lib.call("hriemo_gate_dy_f32", _ops._p(dH), _ops._p(w), is_a, _ops._p(dpool), _ops._p(sx.kpm), _ops._p(dY), sf.B, sf.L, sx.L, d,
+                  _ops._stream())
+
+
+def beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st, sf):
+    """models/beta_gate_tacfn.py:68-118 in fp32 -> (h_fusion fp32, beta [B,1]); sa / st / sf as _ops.BetaGateFn, which has checked
+    them.  h_fusion is handed on as the fp32 tensor itself (the decoder reads it as its memory and autograd sees it).
+    Packed: h_a / h_t (and twins) are the encoder's packed rows [1, N, d], h_fusion comes back as the packed fused memory
+    [1, N_f, d] (surplus rows zero).  The two LayerNorms are row-wise and run on the rows as they are; pool, fuse and their backward
+    go through the wrappers above."""
     _ops._require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
     _ops._require_gpu(h_a)
-    d = h_a.shape[-1]
-    if plan is not None:
-        sa, sq_t, sf = plan
-        B, La, Lt = sa.Breal, sa.L, sq_t.L
-        if h_a.shape[1] != sa.N or h_t.shape[1] != sq_t.N:
-            raise ValueError(f"BetaGate: packed rows {h_a.shape[1]} / {h_t.shape[1]} do not match the plan ({sa.N} / {sq_t.N})")
-        Ra, Rt = sa.N, sq_t.N
-    else:
-        B, La, _ = h_a.shape
-        Lt = h_t.shape[1]
-        Ra, Rt = B * La, B * Lt
-    L = La if La == Lt else Lt
-    if La < L:
-        raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
+    B, d = sa.Breal, h_a.shape[-1]
     dev = h_a.device
-    st = _ops._stream()
-    a32 = _twin(h_a, h_a32).view(Ra, d)
-    t32 = _twin(h_t, h_t32).view(Rt, d)
+    st_ = _ops._stream()
+    a32 = _twin(h_a, h_a32).view(sa.N, d)
+    t32 = _twin(h_t, h_t32).view(st.N, d)
     _, An = add_ln(a32, None, ga, ba, want16=False)
     _, Tn = add_ln(t32, None, gt, bt, want16=False)
     a_pool = torch.empty((B, d), dtype=F32, device=dev)
     t_pool = torch.empty((B, d), dtype=F32, device=dev)
-    if plan is not None:
-        _lib.call("hriemo_masked_mean_f32_packed", _ops._p(An), _ops._p(sa.cu), sa.N, _ops._p(a_pool), B, La, d, st)
-        _lib.call("hriemo_masked_mean_f32_packed", _ops._p(Tn), _ops._p(sq_t.cu), sq_t.N, _ops._p(t_pool), B, Lt, d, st)
-    else:
-        _lib.call("hriemo_masked_mean_f32", _ops._p(An), _ops._p(kpm_a), _ops._p(a_pool), B, La, d, st)
-        _lib.call("hriemo_masked_mean_f32", _ops._p(Tn), _ops._p(kpm_t), _ops._p(t_pool), B, Lt, d, st)
+    masked_mean(An, sa, a_pool, d)
+    masked_mean(Tn, st, t_pool, d)
     gin = torch.empty((B, 4 * d), dtype=F32, device=dev)
-    _lib.call("hriemo_gate_input_f32", _ops._p(a_pool), _ops._p(t_pool), _ops._p(gin), B, d, st)
+    _lib.call("hriemo_gate_input_f32", _ops._p(a_pool), _ops._p(t_pool), _ops._p(gin), B, d, st_)
     hid = linear(gin, sh, w1, b1)
     pre = linear(hid, sh, w2, b2, relu_in=True)
     w = torch.empty((B, d), dtype=F32, device=dev)
     beta = torch.empty((B, 1), dtype=F32, device=dev)
-    _lib.call("hriemo_sigmoid_beta_f32", _ops._p(pre), _ops._p(w), _ops._p(beta), B, d, st)
-    if plan is not None:
-        H32 = torch.empty((1, sf.N, d), dtype=F32, device=dev)
-        _lib.call("hriemo_fuse_f32_packed", _ops._p(w), _ops._p(An), _ops._p(sa.cu), sa.N, La, _ops._p(Tn), _ops._p(sq_t.cu), sq_t.N, Lt,
-                  _ops._p(H32), None, _ops._p(sf.cu), sf.N, B, L, d, st)
-    else:
-        H32 = torch.empty((B, L, d), dtype=F32, device=dev)
-        _lib.call("hriemo_fuse_f32", _ops._p(w), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(H32), None, B, L, d, st)
-    if ctx is not None:
-        ctx.fp32 = True
-        if recording(ctx):
-            ctx.set_materialize_grads(False)
-            ctx.save_for_backward(a32, t32, An, Tn, a_pool, t_pool, gin, hid, w, kpm_a, kpm_t)
-            ctx.f32_cfg = (B, La, Lt, L, d)
-            ctx.f32_plan = plan
-            ctx.f32_params = (ga, ba, gt, bt, w1, b1, w2, b2, sh)
-            ctx.f32_twins = (h_a32 is not None, h_t32 is not None, h_a.dtype, h_t.dtype)
+    _lib.call("hriemo_sigmoid_beta_f32", _ops._p(pre), _ops._p(w), _ops._p(beta), B, d, st_)
+    H32 = torch.empty(sf.shape(d), dtype=F32, device=dev)
+    fuse(w, An, sa, Tn, st, H32, sf, d)
+    ctx.fp32 = True
+    if recording(ctx):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a32, t32, An, Tn, a_pool, t_pool, gin, hid, w)
+        ctx.seqs = (sa, st, sf)
+        ctx.f32_params = (ga, ba, gt, bt, w1, b1, w2, b2, sh)
+        ctx.f32_twins = (h_a32 is not None, h_t32 is not None, h_a.dtype, h_t.dtype)
     return H32, beta
 
 
 def beta_gate_bwd(ctx, dH, dbeta):
-    a32, t32, An, Tn, a_pool, t_pool, gin, hid, w, kpm_a, kpm_t = ctx.saved_tensors
-    B, La, Lt, L, d = ctx.f32_cfg
-    plan = ctx.f32_plan
+    a32, t32, An, Tn, a_pool, t_pool, gin, hid, w = ctx.saved_tensors
+    sa, st, sf = ctx.seqs
+    B, d = sa.Breal, a32.shape[1]
     ga, ba, gt, bt, w1, b1, w2, b2, sh = ctx.f32_params
     dev = a32.device
-    st = _ops._stream()
-    if plan is not None:
-        sa, sq_t, sf = plan
-    dH = _c(dH.float()) if dH is not None else torch.zeros((1, sf.N, d) if plan is not None else (B, L, d), dtype=F32, device=dev)
+    dH = _c(dH.float()) if dH is not None else torch.zeros(sf.shape(d), dtype=F32, device=dev)
     db = _c(dbeta.float()).view(B) if dbeta is not None else None
     dpre = torch.empty((B, d), dtype=F32, device=dev)
-    if plan is not None:
-        _lib.call("hriemo_gate_dpre_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(An), _ops._p(sa.cu), sa.N, La, _ops._p(Tn),
-                  _ops._p(sq_t.cu), sq_t.N, Lt, _ops._p(w), _ops._p(db), _ops._p(dpre), B, L, d, st)
-    else:
-        _lib.call("hriemo_gate_dpre_f32", _ops._p(dH), _ops._p(An), La, _ops._p(Tn), Lt, _ops._p(w), _ops._p(db), _ops._p(dpre), B, L, d, st)
+    gate_dpre(dH, sf, An, sa, Tn, st, w, db, dpre, d)
     # MLP: pre = relu(hid) . W2^T + b2, hid = gin . W1^T + b1
     dw2 = linear_dw(dpre, hid, relu_x=True)
     db2 = colsum(dpre)
@@ -554,25 +536,20 @@ def beta_gate_bwd(ctx, dH, dbeta):
     dgin = linear_dx(dhid, sh, w1, mask=hid)
     da = torch.empty((B, d), dtype=F32, device=dev)
     dt = torch.empty((B, d), dtype=F32, device=dev)
-    _lib.call("hriemo_gate_input_bwd_f32", _ops._p(dgin), _ops._p(a_pool), _ops._p(t_pool), _ops._p(da), _ops._p(dt), B, d, st)
+    _lib.call("hriemo_gate_input_bwd_f32", _ops._p(dgin), _ops._p(a_pool), _ops._p(t_pool), _ops._p(da), _ops._p(dt), B, d, _ops._stream())
     outs = []
-    for is_a, dpool, kpm, x32, gamma, Lx in ((1, da, kpm_a, a32, ga, La), (0, dt, kpm_t, t32, gt, Lt)):
-        dY = torch.empty((x32.shape[0], d), dtype=F32, device=dev)
-        if plan is not None:
-            seq = sa if is_a else sq_t
-            _lib.call("hriemo_gate_dy_f32_packed", _ops._p(dH), _ops._p(sf.cu), sf.N, _ops._p(w), is_a, _ops._p(dpool), _ops._p(seq.cu), seq.N,
-                      _ops._p(dY), B, L, Lx, d, st)
-        else:
-            _lib.call("hriemo_gate_dy_f32", _ops._p(dH), _ops._p(w), is_a, _ops._p(dpool), _ops._p(kpm), _ops._p(dY), B, L, Lx, d, st)
+    for is_a, dpool, sx, x32, gamma in ((1, da, sa, a32, ga), (0, dt, st, t32, gt)):
+        dY = torch.empty((sx.N, d), dtype=F32, device=dev)
+        gate_dy(dH, sf, w, is_a, dpool, sx, dY, d)
         dx, _, dgam, dbet, _ = add_ln_bwd(dY, x32, None, gamma, want_dbias=False)
-        outs.append((dx.view((1, x32.shape[0], d) if plan is not None else (B, Lx, d)), dgam, dbet))
+        outs.append((dx.view(sx.shape(d)), dgam, dbet))
     (dxa, dga, dba), (dxt, dgt, dbt) = outs
     twin_a, twin_t, dt_a, dt_t = ctx.f32_twins
     ga16 = None if twin_a else (dxa.to(dt_a) if ctx.needs_input_grad[0] else None)
     ga32 = dxa if (twin_a and ctx.needs_input_grad[1]) else None
     gt16 = None if twin_t else (dxt.to(dt_t) if ctx.needs_input_grad[2] else None)
     gt32 = dxt if (twin_t and ctx.needs_input_grad[3]) else None
-    return ga16, ga32, gt16, gt32, dga, dba, dgt, dbt, dw1, db1, dw2, db2, None, None, None
+    return ga16, ga32, gt16, gt32, dga, dba, dgt, dbt, dw1, db1, dw2, db2, None, None, None, None
 
 
 def linear_any_k(ctx, x, w, b, sh):

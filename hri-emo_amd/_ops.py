@@ -11,13 +11,11 @@ torch is used for device memory, streams and autograd bookkeeping only; all arit
 libhriemo.so.  Activations are bf16, statistics/parameter gradients fp32.  No CPU fallback exists.
 """
 import itertools
-import math
 import os as _os
-
 import threading
+from collections import namedtuple
 
 import torch
-import torch.nn.functional as F
 
 from . import _lib
 
@@ -132,8 +130,6 @@ class use_context:
         return False
 
 
-
-
 def fork(child, parent):
     """`child` starts to depend on `parent`: a stream fork.  While a step is being captured, every fork has to start at the
     capture's origin stream: a helper stream forked from an already forked stream (a fork nested inside a fork) makes
@@ -164,15 +160,9 @@ def branch_streams(device):
 
 
 def share(t, stream):
-    """tensor produced on another stream is about to be read on `stream`"""
-    if isinstance(t, torch.Tensor):
+    """tensor (or Seq: its index and mask tensors) produced on another stream is about to be read on `stream`"""
+    if t is not None:
         t.record_stream(stream)
-    elif isinstance(t, tuple):
-        for e in t:
-            share(e, stream)
-    elif t is not None and hasattr(t, "cu"):             # Seq (packed sequences): its index tensors
-        t.cu.record_stream(stream)
-        t.idx.record_stream(stream)
     return t
 
 
@@ -828,7 +818,7 @@ def attn_mask_bits(B, H, Lk, hd, Lq=None):
 
 def attn_fwd(q, k, v, B, H, Lq, Lk, hd, kpm, p, seed, site, b_off, want_bits=False, cu=None):
     """-> (o, lse) or, with want_bits, (o, lse, mask_bits|None): the dropout keep-mask as bit words for the backward.
-    cu = (cu_seqlens_q, cu_seqlens_k) int32 device tensors: q / k / v hold packed rows, Lq / Lk are the longest sequences"""
+    cu = (cu_seqlens_q, cu_seqlens_k) int32 device tensors: q / k / v hold packed rows, Lq / Lk are the longest sequences, kpm is None"""
     o = torch.empty((q.shape[0], H * hd), dtype=BF16, device=q.device)
     lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
     if DROP_LOG is not None and p > 0:
@@ -847,8 +837,6 @@ def attn_fwd(q, k, v, B, H, Lq, Lk, hd, kpm, p, seed, site, b_off, want_bits=Fal
         tag_mx(o, (oq, so))
         return (o, lse, mb) if want_bits else (o, lse)
     if cu is not None:
-        if kpm is not None:
-            raise ValueError("attn_fwd: packed sequences carry their lengths; no key_padding_mask")
         _lib.call("hriemo_attn_fwd_varlen", _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
                   _p(cu[0]), _p(cu[1]), _p(lse), B, H, Lq, Lk, hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _p(mb),
                   _stream())
@@ -939,7 +927,6 @@ def add_ln_fwd(g, x, gamma, beta, p, seed, site, row_off, x32=None, want32=False
 def add_ln_bwd(dy, g, x, gamma, mean, rstd, p, seed, site, row_off, want_dx=True, outs=None, accumulate=False, x32=None, rows=None):
     """outs = (dgamma, dbeta, dbias) destination tensors (fp32 [d]); fresh ones when None.  rows: the row index that keys the
     dropout hash (packed sequences), see add_ln_fwd."""
-    row_index = rows          # (`rows` below counts partial rows)
     M, d = g.shape
     dev = g.device
     dx = torch.empty((M, d), dtype=BF16, device=dev) if want_dx else None
@@ -948,20 +935,79 @@ def add_ln_bwd(dy, g, x, gamma, mean, rstd, p, seed, site, row_off, want_dx=True
         stats = torch.empty((3, d), dtype=torch.float32, device=dev)
         outs = (stats[0], stats[1], stats[2])
     L_ = _lib.lib()
-    if accumulate and DEFER_REDUCE and _in_backward():
-        rows = L_.hriemo_add_ln_bwd_partial_rows(M, d)
-        part = torch.empty(rows * 3 * d, dtype=torch.float32, device=dev)
-        _lib.call("hriemo_add_ln_bwd_rows", _p(dy), _p(g), _p(x), _p(x32), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg), None,
-                  None, None, 0, M, d, float(p), seed, _p(seed_word(dev)), site, row_off, _p(part), _p(row_index), _stream())
-        _deferred.add(part, 3 * d, rows, d, 3 if outs[2] is not None else 2, [o for o in outs if o is not None], True)
+    defer = accumulate and DEFER_REDUCE and _in_backward()
+    if defer:             # the kernel leaves its partial sums in a buffer of their own, finished by the launch-boundary reduce
+        nparts = L_.hriemo_add_ln_bwd_partial_rows(M, d)
+        ws = torch.empty(nparts * 3 * d, dtype=torch.float32, device=dev)
+        dests = (None, None, None, 0)
     else:
         ws = workspace(L_.hriemo_add_ln_bwd_workspace_bytes(M, d), dev, slot=1)
-        _lib.call("hriemo_add_ln_bwd_rows", _p(dy), _p(g), _p(x), _p(x32), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg), _p(outs[0]),
-                  _p(outs[1]), _p(outs[2]), int(accumulate), M, d, float(p), seed, _p(seed_word(dev)), site, row_off,
-                  _p(ws), _p(row_index), _stream())
+        dests = (_p(outs[0]), _p(outs[1]), _p(outs[2]), int(accumulate))
+    _lib.call("hriemo_add_ln_bwd_rows", _p(dy), _p(g), _p(x), _p(x32), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg), *dests, M, d,
+              float(p), seed, _p(seed_word(dev)), site, row_off, _p(ws), _p(rows), _stream())
+    if defer:
+        _deferred.add(ws, 3 * d, nparts, d, 3 if outs[2] is not None else 2, [o for o in outs if o is not None], True)
     if dg is None:
         dg = dx           # no dropout: both branches get the same gradient
     return dx, dg, outs[0], outs[1], outs[2]
+
+
+# The gate's row kernels: each picks the padded or the packed entry point itself from the layouts (Seq) of its buffers -- sx one
+# modality's rows, sf the fused buffers' (An, Tn, H, dH); all padded or all packed.
+def ln_pool_fwd(x, x32, sx, gamma, beta, Yn, mean, rstd, part, sf, d):
+    """Yn = LayerNorm(x) on the rows the fused layout keeps, row statistics, per-chunk partial sums of the masked pooling"""
+    if sf.packed:
+        _lib.call("hriemo_ln_pool_fwd_packed", _p(x), _p(x32), _p(sx.cu), sx.B, sx.N, _p(gamma), _p(beta), _p(Yn), _p(mean), _p(rstd),
+                  _p(part), sx.L, _p(sf.cu), sf.N, sx.Breal, d, _EPS, _stream())
+    else:
+        _lib.call("hriemo_ln_pool_fwd", _p(x), _p(x32), _p(sx.kpm), _p(gamma), _p(beta), _p(Yn), _p(mean), _p(rstd), _p(part),
+                  sx.B, sx.L, sf.L, d, _EPS, _stream())
+
+
+def ln_pool_fwd_pair(a, t, sf, d):
+    """ln_pool_fwd of both modalities from one launch; a / t = (x, x32, sx, gamma, beta, Yn, mean, rstd, part) of each"""
+    if sf.packed:
+        side = lambda x, x32, sx, *rest: (_p(x), _p(x32), _p(sx.cu), sx.B, sx.N, *map(_p, rest), sx.L)          # noqa: E731
+        _lib.call("hriemo_ln_pool_fwd_packed_pair", *side(*a), *side(*t), _p(sf.cu), sf.N, a[2].Breal, d, _EPS, _stream())
+    else:
+        side = lambda x, x32, sx, *rest: (_p(x), _p(x32), _p(sx.kpm), *map(_p, rest), sx.L)          # noqa: E731
+        _lib.call("hriemo_ln_pool_fwd_pair", *side(*a), *side(*t), a[2].B, sf.L, d, _EPS, _stream())
+
+
+def fuse_fwd(w, An, Tn, H, sf, d):
+    """H = w * An + (1 - w) * Tn on the rows of the fused layout (the surplus rows of a packed one: zeros)"""
+    if sf.packed:
+        _lib.call("hriemo_fuse_fwd_packed", _p(w), _p(An), _p(Tn), _p(H), _p(sf.cu), sf.N, sf.Breal, sf.L, d, _stream())
+    else:
+        _lib.call("hriemo_fuse_fwd", _p(w), _p(An), _p(Tn), _p(H), sf.B, sf.L, d, _stream())
+
+
+def fuse_bwd_dw(dH, An, Tn, part, sf, d):
+    """per-chunk partial sums of dL/dw = sum over the fused rows of dH * (An - Tn)"""
+    if sf.packed:
+        _lib.call("hriemo_fuse_bwd_dw_packed", _p(dH), _p(An), _p(Tn), _p(part), _p(sf.cu), sf.N, sf.Breal, sf.L, d, _stream())
+    else:
+        _lib.call("hriemo_fuse_bwd_dw", _p(dH), _p(An), _p(Tn), _p(part), sf.B, sf.L, d, _stream())
+
+
+def ln_pool_bwd(dH, sf, w, is_a, dpool, x, x32, sx, gamma, mean, rstd, dx, dgamma, dbeta, accumulate, ws, d):
+    """backward of ln_pool_fwd and the fusion for one modality; dgamma / dbeta None: the partial sums stay in ws (deferred reduce)"""
+    if sf.packed:
+        _lib.call("hriemo_ln_pool_bwd_packed", _p(dH), _p(sf.cu), sf.N, _p(w), is_a, _p(dpool), _p(x), _p(x32), _p(sx.cu), sx.B, sx.N,
+                  _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), accumulate, sx.Breal, sx.L, d, _p(ws), _stream())
+    else:
+        _lib.call("hriemo_ln_pool_bwd", _p(dH), sf.L, _p(w), is_a, _p(dpool), _p(sx.kpm), _p(x), _p(x32), _p(gamma), _p(mean),
+                  _p(rstd), _p(dx), _p(dgamma), _p(dbeta), accumulate, sx.B, sx.L, d, _p(ws), _stream())
+
+
+def ln_pool_bwd_pair(dH, sf, w, a, t, accumulate, d):
+    """ln_pool_bwd of both modalities from one launch; a / t = (ws, dpool, x, x32, sx, gamma, mean, rstd, dx, dgamma, dbeta)"""
+    if sf.packed:
+        side = lambda ws, dpool, x, x32, sx, *rest: (_p(dpool), _p(x), _p(x32), _p(sx.cu), sx.B, sx.N, *map(_p, rest), sx.L, _p(ws))  # noqa: E731
+        _lib.call("hriemo_ln_pool_bwd_packed_pair", _p(dH), _p(sf.cu), sf.N, _p(w), *side(*a), *side(*t), accumulate, a[4].Breal, d, _stream())
+    else:
+        side = lambda ws, dpool, x, x32, sx, *rest: (_p(dpool), _p(sx.kpm), _p(x), _p(x32), *map(_p, rest), sx.L, _p(ws))  # noqa: E731
+        _lib.call("hriemo_ln_pool_bwd_pair", _p(dH), sf.L, _p(w), *side(*a), *side(*t), accumulate, a[4].B, d, _stream())
 
 
 TWIN = _os.environ.get("HRIEMO_FP32_TWIN", "1") != "0"      # carry the fp32 twin of the residual stream (LayerNorm outputs)
@@ -1193,7 +1239,7 @@ def varlen():
 
 
 # The tail of the model on packed rows: with the encoder packed, the gate reads its packed output and hands the decoder a packed
-# fused memory (PackedBetaGateFn, hriemo_*_packed), so no unpack / pack launch runs behind the encoder.  False: the encoder's output
+# fused memory (BetaGateFn on packed layouts, hriemo_*_packed), so no unpack / pack launch runs behind the encoder.  False: the encoder's output
 # is scattered back to the padded layout in front of the gate (exactly the launches from before the packed tail) -- the A/B handle.
 # Opt-in until the step has been measured against the False arm (scripts_dev/ab_packed_tail.sh).
 PACKED_TAIL = False
@@ -1212,18 +1258,66 @@ def packed_tail():
 
 
 class Seq:
-    """packed rows of one modality: cu int32 [B+1] (device), idx int64 [N] packed row -> row of the padded [Breal*L] layout.
+    """How the rows of one activation buffer are laid out -- the ONE value every Function and kernel wrapper takes for it.
+    Padded (Seq.padded): the buffer is [B, L, d], cu and idx are None, N = B * L, kpm is the uint8 key-padding mask [B, L] or None.
+    Packed: the buffer is [1, N, d]; cu int32 [B+1] (device), idx int64 [N] packed row -> row of the padded [Breal*L] layout, kpm
+    None (the lengths are in cu; only the copies the gate gets carry the masks, with_kpm).
     Bucketed form (seq_bucket, one captured graph for every batch): N = the bucket's row count, the rows beyond the last real
     sequence form ONE extra sequence (B = Breal + 1, cu has B+1 entries) of zeros, so every kernel writes every row.
     surplus: rows behind the last sequence that belong to NO sequence of the plan (the fused memory of a bucket, seq_bucket_fused):
     the attention kernels never see them, the kernels that write such a buffer write them as zeros.
     idx None: the rows are the padded rows themselves (the decoder's queries, query_seq)."""
-    __slots__ = ("cu", "idx", "B", "L", "Lmax", "N", "Breal", "surplus")
+    __slots__ = ("cu", "idx", "B", "L", "Lmax", "N", "Breal", "surplus", "kpm")
 
-    def __init__(self, cu, idx, B, L, Lmax, N, Breal=None, surplus=False):
+    def __init__(self, cu, idx, B, L, Lmax, N, Breal=None, surplus=False, kpm=None):
         self.cu, self.idx, self.B, self.L, self.Lmax, self.N = cu, idx, B, L, Lmax, N
         self.Breal = B if Breal is None else Breal
         self.surplus = bool(surplus)
+        self.kpm = kpm
+
+    @classmethod
+    def padded(cls, B, L, mask=None):
+        """the padded layout [B, L] with its key-padding mask (bool or uint8 [B, L], True = PAD; a bool mask is viewed, not copied)"""
+        return cls(None, None, B, L, L, B * L, kpm=mask_u8(mask, B, L))
+
+    @property
+    def packed(self):
+        return self.cu is not None
+
+    def shape(self, d):          # of a buffer of these rows
+        return (1, self.N, d) if self.packed else (self.Breal, self.L, d)
+
+    def holds(self, x):          # x [., ., d] is a buffer of these rows, or the kernels would be handed row counts that are not x's
+        if x.shape[0] * x.shape[1] != self.N:
+            raise ValueError(f"activation of shape {tuple(x.shape)} does not have the {self.N} rows of its layout")
+
+    def with_kpm(self, mask):
+        """this layout with the padded [Breal, L] mask riding along: the gate reads its valid counts from the masks in either form"""
+        return Seq(self.cu, self.idx, self.B, self.L, self.Lmax, self.N, self.Breal, self.surplus, mask_u8(mask, self.Breal, self.L))
+
+    def record_stream(self, stream):
+        for t in (self.cu, self.idx, self.kpm):
+            if t is not None:
+                t.record_stream(stream)
+
+
+# What two layouts mean to an attention sub-layer (attn_rows): B sequences of up to Lq / Lk rows with the keys' uint8 mask kpm (padded)
+# or cu = (cu_seqlens_q, cu_seqlens_k) (packed); the LayerNorm dropout is keyed by `stride` rows per padded sample and by `rows`, the
+# padded row of every packed query row (None: the rows are the padded ones); kv_surplus: key rows of no sequence, whose dK | dV the
+# attention backward leaves unwritten.
+AttnRows = namedtuple("AttnRows", "B Lq Lk kpm cu stride rows kv_surplus")
+
+
+def attn_rows(seq_q, seq_k, need_w):
+    """AttnRows of a sub-layer whose queries are laid out as seq_q and whose keys as seq_k (the same Seq for a self-attention).
+    Packed: the attention sees Seq.B sequences of up to Seq.Lmax rows, the LayerNorm dropout stays keyed by the padded rows."""
+    if not (seq_q.packed or seq_k.packed):
+        return AttnRows(seq_q.B, seq_q.L, seq_k.L, seq_k.kpm, None, seq_q.L, None, False)
+    if need_w:
+        raise ValueError("attention maps are exported by the padded path only")
+    if not (seq_q.packed and seq_k.packed) or seq_q.kpm is not None or seq_k.kpm is not None:
+        raise ValueError("attn_fwd: packed sequences carry their lengths; no key_padding_mask")
+    return AttnRows(seq_q.B, seq_q.Lmax, seq_k.Lmax, None, (seq_q.cu, seq_k.cu), seq_q.L, seq_q.idx, seq_k.surplus)
 
 
 def seq_bucket(cu, B, L, n_rows):
@@ -1282,7 +1376,6 @@ def fused_seq(sa, st):
     return sf
 
 
-
 _SEQ_PLANS = {}
 
 
@@ -1320,6 +1413,17 @@ def seq_plans(mask_a, mask_t, B, La, Lt):
     return sa, st, fused_seq(sa, st)
 
 
+def _pack_pair(x16, x32, seq, d, idx):
+    """padded [Breal, L, d] pair (either member may be None) -> packed [1, N, d] pair: ONE gather launch, bucket padding rows written
+    as zeros; idx: the tensor that receives the padded row of every packed row (seq.idx), or None"""
+    dev = (x16 if x16 is not None else x32).device
+    p16 = torch.empty((1, seq.N, d), dtype=BF16, device=dev) if x16 is not None else None
+    p32 = torch.empty((1, seq.N, d), dtype=torch.float32, device=dev) if x32 is not None else None
+    x16c = None if x16 is None else _contig_bf16(x16)
+    _lib.call("hriemo_pack_rows", _p(x16c), _p(_c32(x32)), _p(seq.cu), seq.Breal, seq.L, d, seq.N, _p(p16), _p(p32), _p(idx), _stream())
+    return p16, p32
+
+
 class PackFn(torch.autograd.Function):
     """(x16 [B, L, d], x32 | None) -> packed ([1, N, d], twin | None): ONE gather launch for the pair (hriemo_pack_rows), bucket
     padding rows written as zeros; also fills seq.idx (padded row of every packed row)."""
@@ -1327,14 +1431,11 @@ class PackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x16, x32, seq):
         ctx.set_materialize_grads(False)
-        B, L, d = x16.shape
-        x16c = _contig_bf16(x16)
-        x32c = _c32(x32)
-        p16 = torch.empty((1, seq.N, d), dtype=BF16, device=x16.device)
-        p32 = torch.empty((1, seq.N, d), dtype=torch.float32, device=x16.device) if x32 is not None else None
-        _lib.call("hriemo_pack_rows", _p(x16c), _p(x32c), _p(seq.cu), seq.Breal, L, d, seq.N, _p(p16), _p(p32), _p(seq.idx), _stream())
+        d = x16.shape[2]
+        if tuple(x16.shape[:2]) != (seq.Breal, seq.L):
+            raise ValueError(f"pack: activation of shape {tuple(x16.shape)} is not the padded [{seq.Breal}, {seq.L}] layout of its plan")
         ctx.seq, ctx.d, ctx.has32 = seq, d, x32 is not None
-        return p16, p32
+        return _pack_pair(x16, x32, seq, d, seq.idx)
 
     @staticmethod
     def backward(ctx, d16, d32):
@@ -1368,13 +1469,7 @@ class UnpackFn(torch.autograd.Function):
     def backward(ctx, d16, d32):
         if d16 is None and d32 is None:
             return None, None, None
-        seq, d = ctx.seq, ctx.d
-        dev = (d16 if d16 is not None else d32).device
-        g16 = torch.empty((1, seq.N, d), dtype=BF16, device=dev) if d16 is not None else None
-        g32 = torch.empty((1, seq.N, d), dtype=torch.float32, device=dev) if d32 is not None else None
-        d16c = None if d16 is None else _contig_bf16(d16)
-        _lib.call("hriemo_pack_rows", _p(d16c), _p(_c32(d32)), _p(seq.cu), seq.Breal, seq.L, d, seq.N, _p(g16), _p(g32), None, _stream())
-        return g16, g32, None
+        return _pack_pair(d16, d32, ctx.seq, ctx.d, None) + (None,)
 
 
 def pack_rows(x, seq):
@@ -1396,8 +1491,7 @@ def unpack_rows(x, seq):
 
 def pack_pair(x16, x32, seq):
     """[B, L, d] pair -> packed [1, N, d] pair (valid rows only)"""
-    p16, p32 = PackFn.apply(x16, x32, seq)
-    return p16, p32
+    return PackFn.apply(x16, x32, seq)
 
 
 def unpack_pair(p16, p32, seq):
@@ -1426,72 +1520,75 @@ def recording(ctx):
     return bool(getattr(_apply_tls, "grad_mode", True)) and any(ctx.needs_input_grad)
 
 
+def _proj_ln(a, sh, w, w16, b, x2, x32v, gamma, beta, p, seed, site, row_off, rows):
+    """the tail of every sub-layer: g = a . W^T + b, y = LN(x + drop(g)) -> (g, y, y32, mean, rstd, MX-fp8 copy of y | None)"""
+    M, d = x2.shape
+    if fuse_ln(M, d):
+        return proj_add_ln_fwd(a, w16, b, x2, x32v, gamma, beta, p, seed, site, row_off, TWIN, rows) + (None,)
+    g = proj_fwd(Operand(a, mx_of(a)), sh, w, w16, b)
+    y, y32, mean, rstd, *mx = add_ln_fwd(g, x2, gamma, beta, p, seed, site, row_off, x32=x32v, want32=TWIN, want_mx=want_mx_copy(M, d),
+                                         rows=rows)
+    return g, y, y32, mean, rstd, (mx[0] if mx else None)
+
+
 class SelfAttnLN(_GradModeAware, torch.autograd.Function):
     """y = LN(x + drop(out_proj(MHA_core(in_proj(x))))) ; returns (y, probs|None)"""
 
     @staticmethod
-    def forward(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, p, seed, site, b_off, need_w):
+    def forward(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq, p, seed, site, b_off, need_w):
+        """seq: the Seq of x's rows ([B, L, d] padded with its mask, or [1, N_valid, d] packed)"""
+        seq.holds(x)
         if precision() == "fp32":
-            return _fp32().self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, need_w, p, seed, site, b_off)
+            return _fp32().self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq, need_w, p, seed, site, b_off)
         _require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
         ctx.set_materialize_grads(False)      # an unused twin output must arrive as None, not as zeros
         _require_gpu(x)
         B, L, d = x.shape
         hd = _heads(d, H)
         M = B * L
-        # packed sequences (x is [1, N_valid, d], the kpm slot carries the Seq): the attention sees AB samples of up to AL rows
-        AB, AL, cu, RL, rows = B, L, None, L, None          # RL / rows: row stride and row index that key the LayerNorm dropout
-        if isinstance(kpm, Seq):
-            if need_w:
-                raise ValueError("attention maps are exported by the padded path only")
-            AB, AL, cu, RL, rows, kpm = kpm.B, kpm.Lmax, (kpm.cu, kpm.cu), kpm.L, kpm.idx, None
+        ar = attn_rows(seq, seq, need_w)
         x2 = _contig_bf16(x).view(M, d)
         x32 = _c32(x32)
         x32v = x32.view(M, d) if x32 is not None else None
         w_in16, w_out16 = sh.get(w_in), sh.get(w_out)
         qkv = proj_fwd(Operand(x2, mx_of(x)), sh, w_in, w_in16, b_in)
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-        o, lse, mbits = attn_fwd(q, k, v, AB, H, AL, AL, hd, kpm, p, seed, site, b_off, want_bits=True, cu=cu) if attn_mask_bits(AB, H, AL, hd, AL) else \
-            attn_fwd(q, k, v, AB, H, AL, AL, hd, kpm, p, seed, site, b_off, cu=cu) + (None,)
-        if fuse_ln(M, d):
-            g, y, y32, mean, rstd = proj_add_ln_fwd(o, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * RL, TWIN, rows)
-            mx = []
-        else:
-            g = proj_fwd(Operand(o, mx_of(o)), sh, w_out, w_out16, b_out)
-            y, y32, mean, rstd, *mx = add_ln_fwd(g, x2, gamma, beta, p, seed, site + 1, b_off * RL, x32=x32v, want32=TWIN,
-                                                 want_mx=want_mx_copy(M, d), rows=rows)
-        probs = attn_probs(q, k, B, H, L, L, hd, kpm, lse, p, seed, site, b_off) if need_w else None
-        ctx.save_for_backward(x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, kpm, mbits)
+        o, lse, mbits = attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, want_bits=True, cu=ar.cu) if attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq) else \
+            attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
+        g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
+                                             ar.rows)
+        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off) if need_w else None
+        ctx.save_for_backward(x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
         ctx.cfg = (B, L, d, H, hd, p, seed, site, b_off)
-        ctx.packed = (AB, AL, cu, RL, rows)
+        ctx.rows = ar
         ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
         ctx.mark_non_differentiable(*( [probs] if probs is not None else []))
-        return tag_mx(y.view(B, L, d), mx[0] if mx else None), (y32.view(B, L, d) if y32 is not None else None), probs
+        return tag_mx(y.view(B, L, d), mx), (y32.view(B, L, d) if y32 is not None else None), probs
 
     @staticmethod
     def backward(ctx, dy, dy32, _dprobs):
         if getattr(ctx, "fp32", False):
             return _fp32().self_attn_ln_bwd(ctx, dy, dy32)
-        x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, kpm, mbits = ctx.saved_tensors
+        x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
         B, L, d, H, hd, p, seed, site, b_off = ctx.cfg
-        AB, AL, cu, RL, rows = ctx.packed
+        ar = ctx.rows
         M = B * L
         dev = x2.device
         dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(M, d)
         p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
         sink = GradSink(ctx.params)
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * RL,
+        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
                                                    outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=rows)
+                                                   accumulate=acc, x32=x32v, rows=ar.rows)
         dw_out = sink.buf(p_w_out)
         linear_dw(dg, o, dw_out, acc)
         do = linear_dx(dg, w_out16)
         dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
         db_in = sink.buf(p_b_in)
         folded = attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:],
-                          lse, AB, H, AL, AL, hd, kpm, p, seed, site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits,
-                          cu=cu)
+                          lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits,
+                          cu=ar.cu)
         dw_in = sink.buf(p_w_in)
         linear_dw(dqkv, x2, dw_in, acc)
         if not folded:
@@ -1508,29 +1605,26 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
     """y = LN(xq + drop(out_proj(MHA_core(Wq xq, Wkv xkv)))) ; returns (y, probs|None)"""
 
     @staticmethod
-    def forward(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, p, seed, site, b_off, need_w, kv_pre=None,
-                join_q=None, q_pre=None, slots=None):
-        """kv_pre: the K | V projection of xkv computed by KVProjFn ahead of time (the decoder hoists it onto the side stream); its
+    def forward(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq_q, seq_k, p, seed, site, b_off, need_w,
+                kv_pre=None, join_q=None, q_pre=None, slots=None):
+        """seq_q / seq_k: the Seq of xq's and of xkv's rows (both padded, the keys' mask on seq_k, or both packed).
+        kv_pre: the K | V projection of xkv computed by KVProjFn ahead of time (the decoder hoists it onto the side stream); its
         weight-gradient and dX then belong to that Function, this one returns dK | dV for it.
         q_pre: likewise the Q projection of xq (SharedProjFn: one GEMM per shared input); this Function then only returns dQ for it
         and hands the residual-path gradient of xq to join_q.  slots = (SharedGrad of dQ, SharedGrad of dK|dV): where the attention
         backward writes those gradients, so that they arrive at the projection's backward as column slices of ONE buffer."""
+        seq_q.holds(xq)
+        seq_k.holds(xkv)
         if precision() == "fp32":
-            return _fp32().cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, kpm, need_w, p, seed, site, b_off)
+            return _fp32().cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq_q, seq_k, need_w, p, seed,
+                                         site, b_off)
         _require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
         ctx.set_materialize_grads(False)      # an unused twin output must arrive as None, not as zeros
         _require_gpu(xq)
         B, Lq, d = xq.shape
         Lk = xkv.shape[1]
         hd = _heads(d, H)
-        # packed sequences: the kpm slot carries (Seq of the query side, Seq of the key side)
-        AB, ALq, ALk, cu, RL, rows = B, Lq, Lk, None, Lq, None
-        if isinstance(kpm, tuple):
-            if need_w:
-                raise ValueError("attention maps are exported by the padded path only")
-            sq, sk = kpm
-            AB, ALq, ALk, cu, RL, rows, kpm = sq.B, sq.Lmax, sk.Lmax, (sq.cu, sk.cu), sq.L, sq.idx, None
-            ctx.kv_surplus = sk.surplus       # key rows of no sequence: the attention backward leaves their dK | dV unwritten
+        ar = attn_rows(seq_q, seq_k, need_w)
         xq2 = _contig_bf16(xq).view(B * Lq, d)
         xq32 = _c32(xq32)
         x32v = xq32.view(B * Lq, d) if xq32 is not None else None
@@ -1543,50 +1637,45 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
             xkv2 = _contig_bf16(xkv).view(B * Lk, d)
             kv = proj_fwd(Operand(xkv2, mx_of(xkv)), sh, w_in, w_in16, b_in, rows=(d, 3 * d))
         k, v = kv[:, :d], kv[:, d:]
-        o, lse, mbits = attn_fwd(q, k, v, AB, H, ALq, ALk, hd, kpm, p, seed, site, b_off, want_bits=True, cu=cu) if attn_mask_bits(AB, H, ALk, hd, ALq) else \
-            attn_fwd(q, k, v, AB, H, ALq, ALk, hd, kpm, p, seed, site, b_off, cu=cu) + (None,)
-        if fuse_ln(B * Lq, d):
-            g, y, y32, mean, rstd = proj_add_ln_fwd(o, w_out16, b_out, xq2, x32v, gamma, beta, p, seed, site + 1, b_off * RL, TWIN, rows)
-            mx = []
-        else:
-            g = proj_fwd(Operand(o, mx_of(o)), sh, w_out, w_out16, b_out)
-            y, y32, mean, rstd, *mx = add_ln_fwd(g, xq2, gamma, beta, p, seed, site + 1, b_off * RL, x32=x32v, want32=TWIN,
-                                                 want_mx=want_mx_copy(B * Lq, d), rows=rows)
-        probs = attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off) if need_w else None
-        ctx.save_for_backward(xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, kpm, mbits)
+        o, lse, mbits = attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, want_bits=True, cu=ar.cu) if attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq) else \
+            attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
+        g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, xq2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
+                                             ar.rows)
+        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off) if need_w else None
+        ctx.save_for_backward(xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
         ctx.cfg = (B, Lq, Lk, d, H, hd, p, seed, site, b_off)
-        ctx.packed = (AB, ALq, ALk, cu, RL, rows)
+        ctx.rows = ar
         ctx.kv_pre = kv_pre is not None
         ctx.q_pre = q_pre is not None
         ctx.slots = slots
         ctx.join_q = join_q
         ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
         ctx.mark_non_differentiable(*([probs] if probs is not None else []))
-        return tag_mx(y.view(B, Lq, d), mx[0] if mx else None), (y32.view(B, Lq, d) if y32 is not None else None), probs
+        return tag_mx(y.view(B, Lq, d), mx), (y32.view(B, Lq, d) if y32 is not None else None), probs
 
     @staticmethod
     def _backward_shared(ctx, dy, dy32):
         """q_pre and kv_pre: both projections belong to SharedProjFn nodes.  Left here: LayerNorm / out-projection backward, the
         attention core's backward (dQ, dK|dV written into the projections' shared gradient buffers, in-projection bias gradients
         from its column sums), and the residual-path gradient of xq, deposited for the projection's dX GEMM."""
-        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, kpm, mbits = ctx.saved_tensors
+        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
         B, Lq, Lk, d, H, hd, p, seed, site, b_off = ctx.cfg
-        AB, ALq, ALk, cu, RL, rows = ctx.packed
+        ar = ctx.rows
         dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(B * Lq, d)
         p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
         sink = GradSink((p_b_in, p_w_out, p_b_out, p_gamma, p_beta))
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * RL,
+        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
                                                    outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=rows)
+                                                   accumulate=acc, x32=x32v, rows=ar.rows)
         dw_out = sink.buf(p_w_out)
         linear_dw(dg, o, dw_out, acc)
         do = linear_dx(dg, w_out16)
         sq, skv = ctx.slots
         dq, dkv = sq.buf(), skv.buf()
         db_in = sink.buf(p_b_in)
-        folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, AB, H, ALq, ALk, hd, kpm, p, seed,
-                          site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=cu)
+        folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed,
+                          site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=ar.cu)
         if not folded:
             colsum(dq, db_in[:d], acc)
             colsum(dkv, db_in[d:], acc)
@@ -1598,7 +1687,7 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
         sink.done()
         r = sink.ret
         return (dxq.view(B, Lq, d) if dxq is not None else None, None, None, None, r(db_in), r(dw_out), r(db_out), r(dgamma),
-                r(dbeta)) + (None,) * 8 + (dkv, None, dq, None)
+                r(dbeta)) + (None,) * 9 + (dkv, None, dq, None)
 
     @staticmethod
     def backward(ctx, dy, dy32, _dprobs):
@@ -1606,25 +1695,25 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
             return _fp32().cross_attn_ln_bwd(ctx, dy, dy32)
         if ctx.q_pre and ctx.kv_pre and ctx.slots is not None:
             return CrossAttnLN._backward_shared(ctx, dy, dy32)
-        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, kpm, mbits = ctx.saved_tensors
+        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
         B, Lq, Lk, d, H, hd, p, seed, site, b_off = ctx.cfg
-        AB, ALq, ALk, cu, RL, rows = ctx.packed
+        ar = ctx.rows
         dev = xq2.device
         dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(B * Lq, d)
         p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
         sink = GradSink(ctx.params)
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * RL,
+        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
                                                    outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=rows)
+                                                   accumulate=acc, x32=x32v, rows=ar.rows)
         dw_out = sink.buf(p_w_out)
         linear_dw(dg, o, dw_out, acc)
         do = linear_dx(dg, w_out16)
         dq = torch.empty((B * Lq, d), dtype=BF16, device=dev)
-        dkv = (torch.zeros if getattr(ctx, "kv_surplus", False) else torch.empty)((B * Lk, 2 * d), dtype=BF16, device=dev)
+        dkv = (torch.zeros if ar.kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=BF16, device=dev)
         db_in = sink.buf(p_b_in)
-        folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, AB, H, ALq, ALk, hd, kpm, p, seed,
-                          site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=cu)
+        folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed,
+                          site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=ar.cu)
         dw_in = sink.buf(p_w_in)
         linear_dw(dq, xq2, dw_in[:d], acc)
         if not folded:
@@ -1645,12 +1734,12 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
             if not acc:
                 dw_in[d:].zero_()
             sink.done(skip=(p_w_in,))
-            return (dxq, None, None, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 8 + (dkv, None, None, None)
+            return (dxq, None, None, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 9 + (dkv, None, None, None)
         linear_dw(dkv, xkv2, dw_in[d:], acc)
         dxkv = linear_dx(dkv, w_in16[d:])
         sink.done()
         return (dxq, None, dxkv.view(B, Lk, d), r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma),
-                r(dbeta)) + (None,) * 12
+                r(dbeta)) + (None,) * 13
 
 
 class GradJoin:
@@ -1698,8 +1787,6 @@ SHARED_PROJ = True         # one N = 3d projection GEMM per shared encoder input
 
 def shared_proj():
     return SHARED_PROJ
-
-
 
 
 def grad_join(n=2, always=False):
@@ -1892,8 +1979,11 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
     """y = LN(x + drop(W2 . drop_mid(relu(W1 x + b1)) + b2))"""
 
     @staticmethod
-    def forward(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq=None):
-        """seq: the Seq of packed rows (x is [1, N_valid, d]): keys the LayerNorm dropout by the rows of the padded layout"""
+    def forward(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq):
+        """seq: the Seq of x's rows; packed (x is [1, N_valid, d]) it keys the LayerNorm dropout by the rows of the padded layout"""
+        seq.holds(x)
+        if seq.packed and p_mid > 0:
+            raise ValueError("FFNLN: packed rows with a mid-FFN dropout are not built (the encoder's FFNs have none)")
         if precision() == "fp32":
             return _fp32().ffn_ln(ctx, x, x32, w1, b1, w2, b2, gamma, beta, sh, p, p_mid, seed, site, b_off, seq)
         _require_fp32_masters(w1, b1, w2, b2, gamma, beta)
@@ -1913,21 +2003,12 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
                 DROP_LOG.append(("rows", seed, site + 2, M, h.shape[1], float(p_mid), b_off * L))
             _lib.call("hriemo_dropout_bf16", _p(h), _p(hd_), M, h.shape[1], float(p_mid), seed, _p(seed_word(h.device)),
                       site + 2, b_off * L, _stream())
-        RL, rows = (seq.L, seq.idx) if seq is not None else (L, None)
-        if seq is not None and p_mid > 0:
-            raise ValueError("FFNLN: packed rows with a mid-FFN dropout are not built (the encoder's FFNs have none)")
-        ctx.rowkey = (RL, rows)
-        if fuse_ln(M, d):
-            g, y, y32, mean, rstd = proj_add_ln_fwd(hd_, w2_16, b2, x2, x32v, gamma, beta, p, seed, site + 1, b_off * RL, TWIN, rows)
-            mx = []
-        else:
-            g = proj_fwd(Operand(hd_, mx_of(hd_)), sh, w2, w2_16, b2)
-            y, y32, mean, rstd, *mx = add_ln_fwd(g, x2, gamma, beta, p, seed, site + 1, b_off * RL, rows=rows, x32=x32v, want32=TWIN,
-                                                 want_mx=want_mx_copy(M, d))
+        g, y, y32, mean, rstd, mx = _proj_ln(hd_, sh, w2, w2_16, b2, x2, x32v, gamma, beta, p, seed, site + 1, b_off * seq.L, seq.idx)
         ctx.save_for_backward(x2, x32v, h, hd_, g, mean, rstd, w1_16, w2_16, gamma)
         ctx.cfg = (B, L, d, p, p_mid, seed, site, b_off)
+        ctx.seq = seq
         ctx.params = (w1, b1, w2, b2, gamma, beta)
-        return tag_mx(y.view(B, L, d), mx[0] if mx else None), (y32.view(B, L, d) if y32 is not None else None)
+        return tag_mx(y.view(B, L, d), mx), (y32.view(B, L, d) if y32 is not None else None)
 
     @staticmethod
     def backward(ctx, dy, dy32):
@@ -1941,10 +2022,9 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
         p_w1, p_b1, p_w2, p_b2, p_gamma, p_beta = ctx.params
         sink = GradSink(ctx.params)
         acc = sink.fused
-        RL, rows = ctx.rowkey
-        ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * RL,
+        ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * ctx.seq.L,
                                                 outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b2)),
-                                                accumulate=acc, x32=x32v, rows=rows)
+                                                accumulate=acc, x32=x32v, rows=ctx.seq.idx)
         dw2 = sink.buf(p_w2)
         linear_dw(dg, hd_, dw2, acc)
         db1 = sink.buf(p_b1)
@@ -1968,129 +2048,100 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
 
 class BetaGateFn(_GradModeAware, torch.autograd.Function):
     """(h_fusion, beta) = BetaGate(h_a, h_t, masks)  -- models/beta_gate_tacfn.py:68-118
-    plan = (Seq audio, Seq text, Seq fused): the packed form.  h_a / h_t (and twins) are the encoder's packed rows [1, N, d], h_fusion
-    comes back as the packed fused memory [1, N_f, d] (sample b: min(la, lt) rows, surplus rows zero) and backward returns the
-    packed dX of both modalities -- the hriemo_*_packed kernels in place of the padded ones, everything else (gate MLP, GradSink,
-    deferred reduces, pair / two-stream variants) is the same code."""
+    sa / st / sf: the Seq of h_a's rows, of h_t's rows and of the fused memory's -- all padded ([B, L_a, d], [B, L_t, d], h_fusion
+    [B, L_t, d]) or all packed (the encoder's packed rows [1, N, d]; h_fusion comes back as the packed fused memory [1, N_f, d], sample
+    b: min(la, lt) rows, surplus rows zero, and backward returns the packed dX of both modalities).  sa and st carry the padding
+    masks in both forms (Seq.with_kpm): the valid counts are read from them."""
 
     @staticmethod
-    def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan=None):
-        if precision() == "fp32":            # -> (h_fusion as the fp32 tensor itself, beta)
-            return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, kpm_a, kpm_t, plan)
-        _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
-        _require_gpu(h_a)
-        h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
-        if plan is not None:
-            sa, sq_t, sf = plan
-            B, La, Lt, d = sa.Breal, sa.L, sq_t.L, h_a.shape[-1]
-            if h_a.shape[1] != sa.N or h_t.shape[1] != sq_t.N:
-                raise ValueError(f"BetaGate: packed rows {h_a.shape[1]} / {h_t.shape[1]} do not match the plan ({sa.N} / {sq_t.N})")
-        else:
-            B, La, d = h_a.shape
-            Lt = h_t.shape[1]
+    def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st, sf):
+        if not (sa.packed == st.packed == sf.packed):
+            raise ValueError("BetaGate: the three layouts must be all padded or all packed")
+        B, La, Lt, d = sa.Breal, sa.L, st.L, h_a.shape[-1]
+        Ra, Rt = h_a.shape[0] * h_a.shape[1], h_t.shape[0] * h_t.shape[1]
+        if Ra != sa.N or Rt != st.N:
+            raise ValueError(f"BetaGate: packed rows {Ra} / {Rt} do not match the plan ({sa.N} / {st.N})")
         L = La if La == Lt else Lt                      # :98-104 (align to the text length)
         if La < L:
             raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
+        if precision() == "fp32":            # -> (h_fusion as the fp32 tensor itself, beta)
+            return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st, sf)
+        _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
+        _require_gpu(h_a)
+        h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
         dev = h_a.device
         xa, xt = _contig_bf16(h_a), _contig_bf16(h_t)
         f32 = dict(dtype=torch.float32, device=dev)
         L_ = _lib.lib()
         nca, nct = L_.hriemo_pool_chunks(La), L_.hriemo_pool_chunks(Lt)
-        # rows of the two modalities and of the fused buffers (An, Tn, H)
-        Ra, Rt, fshape = (sa.N, sq_t.N, (1, sf.N, d)) if plan is not None else (B * La, B * Lt, (B, L, d))
-        An = torch.empty(fshape, dtype=BF16, device=dev)
-        Tn = torch.empty(fshape, dtype=BF16, device=dev)
+        An = torch.empty(sf.shape(d), dtype=BF16, device=dev)
+        Tn = torch.empty(sf.shape(d), dtype=BF16, device=dev)
         mean_a, rstd_a = torch.empty(Ra, **f32), torch.empty(Ra, **f32)
         mean_t, rstd_t = torch.empty(Rt, **f32), torch.empty(Rt, **f32)
         pa, pt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
-        st = _stream()
-
-        def ln_pool(x, x32, kpm, seq, gamma, beta_, Yn, mean, rstd, part, Lx):
-            if plan is not None:
-                _lib.call("hriemo_ln_pool_fwd_packed", _p(x), _p(x32), _p(seq.cu), seq.B, seq.N, _p(gamma), _p(beta_), _p(Yn), _p(mean),
-                          _p(rstd), _p(part), Lx, _p(sf.cu), sf.N, B, d, _EPS, _stream())
-            else:
-                _lib.call("hriemo_ln_pool_fwd", _p(x), _p(x32), _p(kpm), _p(gamma), _p(beta_), _p(Yn), _p(mean), _p(rstd), _p(part),
-                          B, Lx, L, d, _EPS, _stream())
-
-        seq_a, seq_t = (sa, sq_t) if plan is not None else (None, None)
+        st_ = _stream()
+        side_a = (xa, h_a32, sa, ga, ba, An, mean_a, rstd_a, pa)
+        side_t = (xt, h_t32, st, gt, bt, Tn, mean_t, rstd_t, pt)
         # the two modalities' LayerNorm + pooling are independent: the (small) text one runs on the side stream beside the audio one
         main = torch.cuda.current_stream(dev)
         side = side_stream(dev) if GATE_TWO_STREAMS else None
         if GATE_PAIR and L_.hriemo_ln_pool_pair_supported(d):
             # both modalities from one launch: no fork / join around the step (two graph edges and 10-27 us of idle device each)
-            if plan is not None:
-                _lib.call("hriemo_ln_pool_fwd_packed_pair",
-                          _p(xa), _p(h_a32), _p(sa.cu), sa.B, sa.N, _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa), La,
-                          _p(xt), _p(h_t32), _p(sq_t.cu), sq_t.B, sq_t.N, _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt), Lt,
-                          _p(sf.cu), sf.N, B, d, _EPS, st)
-            else:
-                _lib.call("hriemo_ln_pool_fwd_pair", _p(xa), _p(h_a32), _p(kpm_a), _p(ga), _p(ba), _p(An), _p(mean_a), _p(rstd_a), _p(pa), La,
-                          _p(xt), _p(h_t32), _p(kpm_t), _p(gt), _p(bt), _p(Tn), _p(mean_t), _p(rstd_t), _p(pt), Lt, B, L, d, _EPS, st)
+            ln_pool_fwd_pair(side_a, side_t, sf, d)
         elif side is not None and side != main:
             fork(side, main)
             with torch.cuda.stream(side):
-                ln_pool(xt, h_t32, kpm_t, seq_t, gt, bt, Tn, mean_t, rstd_t, pt, Lt)
-            ln_pool(xa, h_a32, kpm_a, seq_a, ga, ba, An, mean_a, rstd_a, pa, La)
+                ln_pool_fwd(*side_t, sf, d)
+            ln_pool_fwd(*side_a, sf, d)
             main.wait_stream(side)
             if not CTX.capturing:
-                for t_ in (xt, h_t32, kpm_t, Tn, mean_t, rstd_t, pt):
+                for t_ in (xt, h_t32, st.kpm, Tn, mean_t, rstd_t, pt):
                     share(t_, side)
         else:
-            ln_pool(xa, h_a32, kpm_a, seq_a, ga, ba, An, mean_a, rstd_a, pa, La)
-            ln_pool(xt, h_t32, kpm_t, seq_t, gt, bt, Tn, mean_t, rstd_t, pt, Lt)
+            ln_pool_fwd(*side_a, sf, d)
+            ln_pool_fwd(*side_t, sf, d)
         gin = torch.empty((B, 4 * d), dtype=BF16, device=dev)
         a_pool, t_pool = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
         cnt = torch.empty((B, 2), **f32)
-        _lib.call("hriemo_gate_input", _p(pa), _p(pt), _p(kpm_a), _p(kpm_t), B, La, Lt, d, _p(gin), _p(a_pool),
-                  _p(t_pool), _p(cnt), st)
+        _lib.call("hriemo_gate_input", _p(pa), _p(pt), _p(sa.kpm), _p(st.kpm), B, La, Lt, d, _p(gin), _p(a_pool),
+                  _p(t_pool), _p(cnt), st_)
         w1_16, w2_16 = sh.get(w1), sh.get(w2)
         hid = linear_fwd(gin, w1_16, b1, relu=True)
         pre = linear_fwd(hid, w2_16, b2, out_f32=True)
         w = torch.empty((B, d), **f32)
         beta = torch.empty((B, 1), **f32)
-        _lib.call("hriemo_sigmoid_beta", _p(pre), _p(w), _p(beta), B, d, st)
-        H = torch.empty(fshape, dtype=BF16, device=dev)
-        if plan is not None:
-            _lib.call("hriemo_fuse_fwd_packed", _p(w), _p(An), _p(Tn), _p(H), _p(sf.cu), sf.N, B, L, d, st)
-        else:
-            _lib.call("hriemo_fuse_fwd", _p(w), _p(An), _p(Tn), _p(H), B, L, d, st)
+        _lib.call("hriemo_sigmoid_beta", _p(pre), _p(w), _p(beta), B, d, st_)
+        H = torch.empty(sf.shape(d), dtype=BF16, device=dev)
+        fuse_fwd(w, An, Tn, H, sf, d)
         ctx.save_for_backward(xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16,
-                              w2_16, ga, gt, kpm_a, kpm_t, h_a32, h_t32)
-        ctx.cfg = (B, La, Lt, L, d)
-        ctx.plan = plan
+                              w2_16, ga, gt, h_a32, h_t32)
+        ctx.seqs = (sa, st, sf)
         ctx.params = (ga, ba, gt, bt, w1, b1, w2, b2)
         return H, beta
 
     @staticmethod
     def backward(ctx, dH, dbeta):
         if getattr(ctx, "fp32", False):
-            return _fp32().beta_gate_bwd(ctx, dH, dbeta) + (None,)          # (the plan slot)
-        (xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt, kpm_a,
-         kpm_t, h_a32, h_t32) = ctx.saved_tensors
-        B, La, Lt, L, d = ctx.cfg
+            return _fp32().beta_gate_bwd(ctx, dH, dbeta)
+        (xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt,
+         h_a32, h_t32) = ctx.saved_tensors
+        sa, st, sf = ctx.seqs
+        B, La, Lt, L, d = sa.Breal, sa.L, st.L, st.L, xa.shape[-1]
         dev = xa.device
         f32 = dict(dtype=torch.float32, device=dev)
-        st = _stream()
+        st_ = _stream()
         L_ = _lib.lib()
         p_ga, p_ba, p_gt, p_bt, p_w1, p_b1, p_w2, p_b2 = ctx.params
         # parameter gradients go straight into .grad when the parameters were opted in (dp.GradBuckets): no autograd accumulate
         # launches on the serial chain between the decoder's and the encoder's backward
         sink = GradSink(ctx.params)
         acc = sink.fused
-        plan = ctx.plan
-        if plan is not None:
-            sa, sq_t, sf = plan
         dH2 = _contig_bf16(dH) if dH is not None else torch.zeros(An.shape, dtype=BF16, device=dev)
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
         part = torch.empty((B, L_.hriemo_pool_chunks(L), d), **f32)
-        if plan is not None:
-            _lib.call("hriemo_fuse_bwd_dw_packed", _p(dH2), _p(An), _p(Tn), _p(part), _p(sf.cu), sf.N, B, L, d, st)
-        else:
-            _lib.call("hriemo_fuse_bwd_dw", _p(dH2), _p(An), _p(Tn), _p(part), B, L, d, st)
+        fuse_bwd_dw(dH2, An, Tn, part, sf, d)
         dpre = torch.empty((B, d), dtype=BF16, device=dev)
-        _lib.call("hriemo_gate_dpre", _p(part), L, _p(dbeta2), _p(w), _p(dpre), B, d, st)
-        Hd = hid.shape[1]
+        _lib.call("hriemo_gate_dpre", _p(part), L, _p(dbeta2), _p(w), _p(dpre), B, d, st_)
         dw2 = sink.buf(p_w2)
         linear_dw(dpre, hid, dw2, acc)
         db2 = sink.buf(p_b2)
@@ -2102,32 +2153,27 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         colsum(dhid, db1, acc)
         dgin = linear_dx(dhid, w1_16)
         da, dt = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
-        _lib.call("hriemo_gate_input_bwd", _p(dgin), _p(a_pool), _p(t_pool), _p(cnt), _p(da), _p(dt), B, d, st)
-        dxa = torch.empty((1, sa.N, d) if plan is not None else (B, La, d), dtype=BF16, device=dev)
-        dxt = torch.empty((1, sq_t.N, d) if plan is not None else (B, Lt, d), dtype=BF16, device=dev)
+        _lib.call("hriemo_gate_input_bwd", _p(dgin), _p(a_pool), _p(t_pool), _p(cnt), _p(da), _p(dt), B, d, st_)
+        dxa = torch.empty(sa.shape(d), dtype=BF16, device=dev)
+        dxt = torch.empty(st.shape(d), dtype=BF16, device=dev)
         dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
         # LayerNorm-affine gradients: finished by the launch-boundary reduce when they accumulate into .grad inside backward (the
         # kernel's partial sums then live in a buffer of their own instead of the shared workspace), else by the call's own reduce
         defer = acc and DEFER_REDUCE and _in_backward()
         nba, nbt = L_.hriemo_ln_pool_bwd_workspace_bytes(B, La, d), L_.hriemo_ln_pool_bwd_workspace_bytes(B, Lt, d)
 
-        def ln_pool_bwd(is_a, dpool, kpm, x, x32, gamma, mean, rstd, dx, dgam, dbet, Lx, nbytes):
+        def one_side(is_a, dpool, x, x32, sx, gamma, mean, rstd, dx, dgam, dbet, nbytes):
             wsx = torch.empty(nbytes // 4 + 16, **f32) if defer else workspace(nbytes, dev, slot=1)
-            outs_ = (None, None, 1) if defer else (_p(dgam), _p(dbet), int(acc))
-            if plan is not None:
-                seq = sa if is_a else sq_t
-                _lib.call("hriemo_ln_pool_bwd_packed", _p(dH2), _p(sf.cu), sf.N, _p(w), is_a, _p(dpool), _p(x), _p(x32), _p(seq.cu), seq.B,
-                          seq.N, _p(gamma), _p(mean), _p(rstd), _p(dx), *outs_, B, Lx, d, _p(wsx), _stream())
-            else:
-                _lib.call("hriemo_ln_pool_bwd", _p(dH2), L, _p(w), is_a, _p(dpool), _p(kpm), _p(x), _p(x32), _p(gamma), _p(mean),
-                          _p(rstd), _p(dx), *outs_, B, Lx, d, _p(wsx), _stream())
+            outs_ = (None, None, 1) if defer else (dgam, dbet, int(acc))
+            ln_pool_bwd(dH2, sf, w, is_a, dpool, x, x32, sx, gamma, mean, rstd, dx, *outs_, wsx, d)
             if defer:
-                _deferred.add(wsx, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lx), d, 2, [dgam, dbet], True)
+                _deferred.add(wsx, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(sx.L), d, 2, [dgam, dbet], True)
 
+        side_a = (da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa)
+        side_t = (dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt)
         main = torch.cuda.current_stream(dev)
         side = side_stream(dev) if GATE_TWO_STREAMS else None
         if GATE_PAIR and L_.hriemo_ln_pool_pair_supported(d):
-            nca_, nct_ = L_.hriemo_ln_pool_bwd_chunks(La), L_.hriemo_ln_pool_bwd_chunks(Lt)
             if defer:
                 wsa, wst = torch.empty(nba // 4 + 16, **f32), torch.empty(nbt // 4 + 16, **f32)
                 outs = (None,) * 4
@@ -2135,33 +2181,23 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
                 wsa = workspace(nba + nbt + 256, dev, slot=1)
                 wst = wsa[(nba // 4 + 63) // 64 * 64:]
                 outs = (dga, dba, dgt, dbt)
-            if plan is not None:
-                _lib.call("hriemo_ln_pool_bwd_packed_pair", _p(dH2), _p(sf.cu), sf.N, _p(w),
-                          _p(da), _p(xa), _p(h_a32), _p(sa.cu), sa.B, sa.N, _p(ga), _p(mean_a), _p(rstd_a), _p(dxa), _p(outs[0]), _p(outs[1]),
-                          La, _p(wsa),
-                          _p(dt), _p(xt), _p(h_t32), _p(sq_t.cu), sq_t.B, sq_t.N, _p(gt), _p(mean_t), _p(rstd_t), _p(dxt), _p(outs[2]),
-                          _p(outs[3]), Lt, _p(wst), int(acc), B, d, _stream())
-            else:
-                _lib.call("hriemo_ln_pool_bwd_pair", _p(dH2), L, _p(w),
-                          _p(da), _p(kpm_a), _p(xa), _p(h_a32), _p(ga), _p(mean_a), _p(rstd_a), _p(dxa), _p(outs[0]), _p(outs[1]), La, _p(wsa),
-                          _p(dt), _p(kpm_t), _p(xt), _p(h_t32), _p(gt), _p(mean_t), _p(rstd_t), _p(dxt), _p(outs[2]), _p(outs[3]), Lt, _p(wst),
-                          int(acc), B, d, _stream())
+            ln_pool_bwd_pair(dH2, sf, w, (wsa,) + side_a + outs[:2], (wst,) + side_t + outs[2:], int(acc), d)
             if defer:
-                _deferred.add(wsa, 2 * d, B * nca_, d, 2, [dga, dba], True)
-                _deferred.add(wst, 2 * d, B * nct_, d, 2, [dgt, dbt], True)
+                _deferred.add(wsa, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(La), d, 2, [dga, dba], True)
+                _deferred.add(wst, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lt), d, 2, [dgt, dbt], True)
         elif side is not None and side != main:
             # text on the side stream (its own workspace there), audio on this one; joined before the gradients are handed back
             fork(side, main)
             with torch.cuda.stream(side):
-                ln_pool_bwd(0, dt, kpm_t, xt, h_t32, gt, mean_t, rstd_t, dxt, dgt, dbt, Lt, nbt)
-            ln_pool_bwd(1, da, kpm_a, xa, h_a32, ga, mean_a, rstd_a, dxa, dga, dba, La, nba)
+                one_side(0, *side_t, dgt, dbt, nbt)
+            one_side(1, *side_a, dga, dba, nba)
             main.wait_stream(side)
             if not CTX.capturing:
                 for t_ in (dH2, w, dt, dxt, dgt, dbt):
                     share(t_, side)
         else:
-            ln_pool_bwd(1, da, kpm_a, xa, h_a32, ga, mean_a, rstd_a, dxa, dga, dba, La, nba)
-            ln_pool_bwd(0, dt, kpm_t, xt, h_t32, gt, mean_t, rstd_t, dxt, dgt, dbt, Lt, nbt)
+            one_side(1, *side_a, dga, dba, nba)
+            one_side(0, *side_t, dgt, dbt, nbt)
         sink.done()
         r = sink.ret
         return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None, None
@@ -2207,7 +2243,7 @@ class LegacyBetaGateFn(torch.autograd.Function):
         T = xt
         wfull = beta.expand(B, d).contiguous()
         H = torch.empty((B, L, d), dtype=BF16, device=dev)
-        _lib.call("hriemo_fuse_fwd", _p(wfull), _p(A), _p(T), _p(H), B, L, d, st)
+        fuse_fwd(wfull, A, T, H, Seq.padded(B, L), d)
         ctx.save_for_backward(A, T, cnt_a, cnt_t, kpm_a, kpm_t, a_pool, t_pool, gin, hid, beta, w1_16, w2f)
         ctx.cfg = (B, La, Lt, L, d)
         return H, beta
@@ -2223,7 +2259,7 @@ class LegacyBetaGateFn(torch.autograd.Function):
         dH2 = _contig_bf16(dH) if dH is not None else torch.zeros((B, L, d), dtype=BF16, device=dev)
         nc = L_.hriemo_pool_chunks(L)
         part = torch.empty((B, nc, d), **f32)
-        _lib.call("hriemo_fuse_bwd_dw", _p(dH2), _p(A), _p(T), _p(part), B, L, d, st)
+        fuse_bwd_dw(dH2, A, T, part, Seq.padded(B, L), d)
         dbeta_h = torch.empty(B, **f32)
         _lib.call("hriemo_rowsum_f32", _p(part), _p(dbeta_h), B, nc * d, st)               # d loss / d beta through the fusion
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None

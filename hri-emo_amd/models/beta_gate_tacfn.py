@@ -17,23 +17,21 @@ class BetaGate(nn.Module):
         self.mlp = nn.Sequential(nn.Linear(d_model * 4, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, d_model))
         self._sh = _ops.Shadows()
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, plan=None):
+    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, seqs):
         """h_fusion comes back bf16 only (fp32 mode: fp32): it is consumed as a GEMM operand (the decoder's memory).
-        plan = (Seq audio, Seq text, Seq fused): a / t are the encoder's packed rows and h_fusion is the packed fused memory."""
-        if plan is not None:
-            B, La, Lt = plan[0].Breal, plan[0].L, plan[1].L
-        else:
-            B, La, _ = a.shape
-            Lt = t.shape[1]
-        kpm_a, kpm_t = _ops.mask_u8(mask_a, B, La), _ops.mask_u8(mask_t, B, Lt)
+        seqs = (Seq audio, Seq text, Seq fused), the layouts of a, of t and of h_fusion: padded, or the packed plan -- a / t are then
+        the encoder's packed rows and h_fusion is the packed fused memory.  The masks ride on the first two in both forms."""
+        sa, st, sf = seqs
         # (fp32 mode: the same Function; h_fusion then IS the fp32 tensor, read as such by the decoder and seen by autograd)
         return _ops.BetaGateFn.apply(a, a32, t, t32, self.norm_a.weight, self.norm_a.bias, self.norm_t.weight,
                                      self.norm_t.bias, self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight,
-                                     self.mlp[2].bias, self._sh, kpm_a, kpm_t, plan)
+                                     self.mlp[2].bias, self._sh, sa.with_kpm(mask_a), st.with_kpm(mask_t), sf)
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None):
         out_dtype = h_a.dtype
         a, a32 = _ops.as_pair(h_a)
         t, t32 = _ops.as_pair(h_t)
-        h_fusion, beta = self._fwd_pair(a, a32, t, t32, mask_a, mask_t)
+        B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
+        seqs = (_ops.Seq.padded(B, La), _ops.Seq.padded(B, Lt), _ops.Seq.padded(B, Lt))
+        h_fusion, beta = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)
         return h_fusion.to(out_dtype), beta

@@ -32,24 +32,24 @@ class CrossModalBlock(nn.Module):
         _ops._require_gpu(a)
         B, La, _ = a.shape
         Lt = t.shape[1]
-        kpm_a, kpm_t = _ops.mask_u8(mask_a, B, La), _ops.mask_u8(mask_t, B, Lt)
+        sa, st = _ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t)
         p = self.p if self.training else 0.0
         seed = _ops.next_seed(self.training and p > 0)
         s, H, sh, bo = self._site, self.n_heads, self._sh, self.batch_offset
 
-        def cross(xq, xq32, xkv, mha, ln, kpm, site):
+        def cross(xq, xq32, xkv, mha, ln, seq_q, seq_k, site):
             y, y32, _ = _ops.CrossAttnLN.apply(xq, xq32, xkv, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                               mha.out_proj.bias, ln.weight, ln.bias, sh, H, kpm, p, seed, site, bo, False)
+                                               mha.out_proj.bias, ln.weight, ln.bias, sh, H, seq_q, seq_k, p, seed, site, bo, False)
             return y, y32
 
-        def ffn(x, x32, f, ln, site):
+        def ffn(x, x32, f, ln, site, seq):
             return _ops.FFNLN.apply(x, x32, f[0].weight, f[0].bias, f[2].weight, f[2].bias, ln.weight, ln.bias, sh, p,
-                                    0.0, seed, site, bo)
+                                    0.0, seed, site, bo, seq)
 
-        x, x32 = cross(a, a32, t, self.attn_a2t, self.norm_a1, kpm_t, s[0])      # :46-50
-        a_o, a_o32 = ffn(x, x32, self.ffn_a, self.norm_a2, s[1])                 # :51
-        x, x32 = cross(t, t32, a, self.attn_t2a, self.norm_t1, kpm_a, s[2])      # :53-57 (original h_a)
-        t_o, t_o32 = ffn(x, x32, self.ffn_t, self.norm_t2, s[3])                 # :58
+        x, x32 = cross(a, a32, t, self.attn_a2t, self.norm_a1, sa, st, s[0])     # :46-50
+        a_o, a_o32 = ffn(x, x32, self.ffn_a, self.norm_a2, s[1], sa)             # :51
+        x, x32 = cross(t, t32, a, self.attn_t2a, self.norm_t1, st, sa, s[2])     # :53-57 (original h_a)
+        t_o, t_o32 = ffn(x, x32, self.ffn_t, self.norm_t2, s[3], st)             # :58
         return a_o, a_o32, t_o, t_o32
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None):

@@ -16,7 +16,6 @@ except ImportError:            # imported as top-level `models` (PYTHONPATH=<rep
     from hri_emo_amd import _ops
 
 
-
 class CrossModalBlock(nn.Module):
     def __init__(self, d_model=768, n_heads=8, dropout=0.1):
         super().__init__()
@@ -38,14 +37,14 @@ class CrossModalBlock(nn.Module):
         self._site = [_ops.new_site_base() for _ in range(6)]
         self.batch_offset = 0          # global index of this shard's first utterance (data parallel)
 
-    def _self(self, x, x32, mha, ln, kpm, p, seed, site, need_w):
+    def _self(self, x, x32, mha, ln, seq, p, seed, site, need_w):
         return _ops.SelfAttnLN.apply(x, x32, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                     mha.out_proj.bias, ln.weight, ln.bias, self._sh, self.n_heads, kpm, p, seed, site,
+                                     mha.out_proj.bias, ln.weight, ln.bias, self._sh, self.n_heads, seq, p, seed, site,
                                      self.batch_offset, need_w)
 
-    def _cross(self, xq, xq32, xkv, mha, ln, kpm, p, seed, site, need_w, kv_pre=None, join_q=None, q_pre=None, slots=None):
+    def _cross(self, xq, xq32, xkv, mha, ln, seq_q, seq_k, p, seed, site, need_w, kv_pre=None, join_q=None, q_pre=None, slots=None):
         return _ops.CrossAttnLN.apply(xq, xq32, xkv, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                      mha.out_proj.bias, ln.weight, ln.bias, self._sh, self.n_heads, kpm, p, seed,
+                                      mha.out_proj.bias, ln.weight, ln.bias, self._sh, self.n_heads, seq_q, seq_k, p, seed,
                                       site, self.batch_offset, need_w, kv_pre, join_q, q_pre, slots)
 
     def _shared_proj(self, x, mha_q, mha_kv, join):
@@ -61,22 +60,14 @@ class CrossModalBlock(nn.Module):
         gradient the OTHER cross-attention returns for the same tensor as its query side in a GradJoin"""
         return _ops.KVProjFn.apply(xkv, mha.in_proj_weight, mha.in_proj_bias, self._sh, join)
 
-    def _ffn(self, x, x32, ffn, ln, p, seed, site, seq=None):
+    def _ffn(self, x, x32, ffn, ln, p, seed, site, seq):
         return _ops.FFNLN.apply(x, x32, ffn[0].weight, ffn[0].bias, ffn[2].weight, ffn[2].bias, ln.weight, ln.bias,
                                 self._sh, p, 0.0, seed, site, self.batch_offset, seq)
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, plan=None):
+    def _fwd_pair(self, a, a32, t, t32, sa, st, need):
         """(bf16, fp32-twin) pairs in and out; returns (a, a32, t, t32, maps|None).
-        plan = (Seq audio, Seq text): a / t hold the packed valid rows ([1, N, d], _ops.pack_pair) and the attention kernels get
-        cu_seqlens instead of padding masks."""
-        B, La, _ = a.shape
-        Lt = t.shape[1]
-        if plan is not None:
-            kpm_a, kpm_t = plan                 # self-attention: the Seq itself; cross-attention: (query side, key side)
-            kpm_a2t, kpm_t2a = (plan[0], plan[1]), (plan[1], plan[0])
-        else:
-            kpm_a, kpm_t = _ops.mask_u8(mask_a, B, La), _ops.mask_u8(mask_t, B, Lt)
-            kpm_a2t, kpm_t2a = kpm_t, kpm_a
+        sa / st: the _ops.Seq of a's and of t's rows -- padded [B, L, d] with the padding masks, or the packed valid rows
+        ([1, N, d], _ops.pack_pair), for which the attention kernels get cu_seqlens instead of padding masks."""
         p = self.p if self.training else 0.0
         seed = _ops.next_seed(self.training and p > 0)
         s = self._site
@@ -100,33 +91,33 @@ class CrossModalBlock(nn.Module):
         d = a.shape[2]
         shared = use_kv and _ops.shared_proj()
         if shared and side is None:
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, kpm_a, p, seed, s[0], need)   # :74-81
-            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, kpm_t, p, seed, s[1], need)   # :85-92
+            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)   # :74-81
+            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)   # :85-92
             ja, jt = join_for(a_s), join_for(t_s)
             q_a2t, kv_t2a, sga = self._shared_proj(a_s, self.attn_a2t, self.attn_t2a, ja)
             q_t2a, kv_a2t, sgt = self._shared_proj(t_s, self.attn_t2a, self.attn_a2t, jt)
-            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, kpm_a2t, p, seed, s[2], need,
+            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
                                         kv_a2t, ja, q_a2t, (sga.slot(0, d), sgt.slot(d, 3 * d)))                   # :98-105
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], plan[0] if plan is not None else None)
-            x, x32, w_t2a = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, kpm_t2a, p, seed, s[4], need,
+            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
+            x, x32, w_t2a = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
                                         kv_t2a, jt, q_t2a, (sgt.slot(0, d), sga.slot(d, 3 * d)))                   # :111-118
-            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], plan[1] if plan is not None else None)
+            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)
         elif shared:
             # two streams, one GEMM per shared input: each branch projects its own self-attention output to [Q | K, V] on its own
             # stream (no dependence on the other branch yet), THEN the branches exchange the K | V halves and run the cores
             # (the audio branch -- three times the rows, the critical path -- is ENQUEUED first at every fork: the order of capture
             # decides which branch the graph runtime starts first)
             _ops.fork(side, main)
-            for x_ in (t, t32, kpm_t, kpm_a):
+            for x_ in (t, t32, st, sa):
                 _ops.share(x_, side)
 
             def text_self():
                 with torch.cuda.stream(side):
-                    t_s_, t_s32_, w_t_ = self._self(t, t32, self.self_attn_t, self.self_norm_t, kpm_t, p, seed, s[1], need)
+                    t_s_, t_s32_, w_t_ = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)
                     jt_ = join_for(t_s_)
                     return (t_s_, t_s32_, w_t_, jt_) + self._shared_proj(t_s_, self.attn_t2a, self.attn_a2t, jt_)
 
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, kpm_a, p, seed, s[0], need)
+            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)
             ja = join_for(a_s)
             q_a2t, kv_t2a, sga = self._shared_proj(a_s, self.attn_a2t, self.attn_t2a, ja)
             t_s, t_s32, w_t, jt, q_t2a, kv_a2t, sgt = text_self()
@@ -137,29 +128,29 @@ class CrossModalBlock(nn.Module):
 
             def text_cross():
                 with torch.cuda.stream(side):
-                    x_, x32_, w_ = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, kpm_t2a, p, seed, s[4], need,
+                    x_, x32_, w_ = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
                                                kv_t2a, jt, q_t2a, (sgt.slot(0, d), sga.slot(d, 3 * d)))
-                    return self._ffn(x_, x32_, self.ffn_t, self.norm_t2, p, seed, s[5], plan[1] if plan is not None else None) + (w_,)
+                    return self._ffn(x_, x32_, self.ffn_t, self.norm_t2, p, seed, s[5], st) + (w_,)
 
-            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, kpm_a2t, p, seed, s[2], need,
+            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
                                         kv_a2t, ja, q_a2t, (sga.slot(0, d), sgt.slot(d, 3 * d)))
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], plan[0] if plan is not None else None)
+            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
             t_cm, t_cm32, w_t2a = text_cross()
             main.wait_stream(side)
             for x_ in (t_cm, t_cm32, w_t, w_t2a):
                 _ops.share(x_, main)
         elif side is None:
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, kpm_a, p, seed, s[0], need)   # :74-81
-            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, kpm_t, p, seed, s[1], need)   # :85-92
+            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)   # :74-81
+            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)   # :85-92
             ja, jt = join_for(a_s), join_for(t_s)
             kv_t2a = self._kv(a_s, self.attn_t2a, ja) if use_kv else None
             kv_a2t = self._kv(t_s, self.attn_a2t, jt) if use_kv else None
-            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, kpm_a2t, p, seed, s[2], need,
+            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
                                         kv_a2t, ja)                                                                # :98-105
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], plan[0] if plan is not None else None)                              # :106
-            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, kpm_t2a, p, seed, s[4], need,
+            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)                              # :106
+            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
                                         kv_t2a, jt)                                                                # :111-118
-            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], plan[1] if plan is not None else None)                              # :119
+            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)                              # :119
         else:
             # The audio and text branches only meet at the two cross-attentions (each reads the OTHER branch's
             # self-attention output), so the text branch runs on a second stream: its small grids (B*T_t rows)
@@ -167,12 +158,12 @@ class CrossModalBlock(nn.Module):
             # streams are recorded on the consumer stream (allocator safety); autograd replays the same streams
             # in backward.
             _ops.fork(side, main)
-            for x_ in (t, t32, kpm_t, kpm_a):
+            for x_ in (t, t32, st, sa):
                 _ops.share(x_, side)
             # (audio first at every fork, the reference's order of sub-layers: cross_modal_block_tacfn.py:74-119)
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, kpm_a, p, seed, s[0], need)
+            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)
             with torch.cuda.stream(side):
-                t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, kpm_t, p, seed, s[1], need)
+                t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)
             main.wait_stream(side)
             _ops.fork(side, main)
             _ops.share(t_s, main)
@@ -186,13 +177,13 @@ class CrossModalBlock(nn.Module):
                 with torch.cuda.stream(side):
                     kv_t2a = self._kv(a_s, self.attn_t2a, ja)
                 kv_a2t = self._kv(t_s, self.attn_a2t, jt)
-            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, kpm_a2t, p, seed, s[2], need,
+            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
                                         kv_a2t, ja)
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], plan[0] if plan is not None else None)
+            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
             with torch.cuda.stream(side):
-                x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, kpm_t2a, p, seed, s[4], need,
+                x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
                                             kv_t2a, jt)
-                t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], plan[1] if plan is not None else None)
+                t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)
             main.wait_stream(side)
             for x_ in (t_cm, t_cm32, w_t, w_t2a):
                 _ops.share(x_, main)
@@ -203,7 +194,8 @@ class CrossModalBlock(nn.Module):
         out_dtype = h_a.dtype          # outputs come back in the caller's dtype
         a, a32 = _ops.as_pair(h_a)
         t, t32 = _ops.as_pair(h_t)
-        a, a32, t, t32, maps = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, bool(return_attention))
+        sa, st = _ops.Seq.padded(a.shape[0], a.shape[1], mask_a), _ops.Seq.padded(t.shape[0], t.shape[1], mask_t)
+        a, a32, t, t32, maps = self._fwd_pair(a, a32, t, t32, sa, st, bool(return_attention))
         h_a_cm, h_t_cm = _ops.from_pair(a, a32, out_dtype), _ops.from_pair(t, t32, out_dtype)
         if return_attention:
             return h_a_cm, h_t_cm, maps
@@ -215,40 +207,42 @@ class CrossModalTransformer(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([CrossModalBlock(d_model, n_heads, dropout) for _ in range(num_layers)])
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=None):
-        """tail: a list the caller hands in to take the packed tail (_ops.PACKED_TAIL).  When the encoder ran packed, its outputs
-        then STAY packed ([1, N, d] pairs) and the plan (Seq audio, Seq text, Seq fused) is appended to the list -- the gate and
-        the decoder read the packed rows, nothing is scattered back.  Without it (forward() below, whose public output is
-        padded) the outputs are unpacked as before."""
+    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=False):
+        """-> (a, a32, t, t32, maps, (sa, st, sf)): the outputs, the _ops.Seq of their rows and the Seq of the fused memory the gate
+        makes of them.  tail: the caller can take the packed tail (_ops.PACKED_TAIL).  When the encoder ran packed, its outputs then
+        STAY packed ([1, N, d] pairs) and the layouts are the plan (Seq audio, Seq text, Seq fused) -- the gate and the decoder read
+        the packed rows, nothing is scattered back.  Otherwise (and always for forward() below, whose public output is padded) the
+        outputs are unpacked as before and the layouts are the padded ones."""
         all_layers_attn = []
+        B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
         plan = None
         _ops.FLUSH_SITES.add(self.layers[0]._site[1])        # layer-0 text self-attention: the last text-branch backward (_ops._DeferredWgrad)
         if _ops.varlen() and not need and mask_a is not None and mask_t is not None:
             # SURVEY 8(f) rank 4: the encoder on the valid rows only (prefix masks, as the collate builds them); anything else
             # takes the padded path.  dp.DataParallelStep injects bucketed plans whose lengths are device data (_ops.CTX.seq_override).
             if _ops.CTX.seq_override is not None:
-                plan3 = tuple(_ops.CTX.seq_override)
+                plan = tuple(_ops.CTX.seq_override)
             else:
-                plan3 = _ops.seq_plans(mask_a, mask_t, a.shape[0], a.shape[1], t.shape[1])
-            if plan3 is not None:
-                sa, st = plan = plan3[:2]
-                (a, a32), (t, t32) = _ops.pack_pair(a, a32, sa), _ops.pack_pair(t, t32, st)
-        for i, layer in enumerate(self.layers):
-            a, a32, t, t32, maps = layer._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, plan)
+                plan = _ops.seq_plans(mask_a, mask_t, B, La, Lt)
+            if plan is not None:
+                (a, a32), (t, t32) = _ops.pack_pair(a, a32, plan[0]), _ops.pack_pair(t, t32, plan[1])
+        for layer in self.layers:
+            # (padded: every layer converts the masks itself, as it always did -- a view for bool masks)
+            sa, st = plan[:2] if plan is not None else (_ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))
+            a, a32, t, t32, maps = layer._fwd_pair(a, a32, t, t32, sa, st, need)
             if need:
                 all_layers_attn.append(maps)
         if plan is not None:
-            if tail is not None and len(plan3) == 3 and _ops.packed_tail():
-                tail.append(plan3)
-            else:
-                (a, a32), (t, t32) = _ops.unpack_pair(a, a32, plan[0]), _ops.unpack_pair(t, t32, plan[1])
-        return a, a32, t, t32, all_layers_attn
+            if tail and len(plan) == 3 and _ops.packed_tail():
+                return a, a32, t, t32, all_layers_attn, plan
+            (a, a32), (t, t32) = _ops.unpack_pair(a, a32, plan[0]), _ops.unpack_pair(t, t32, plan[1])
+        return a, a32, t, t32, all_layers_attn, (_ops.Seq.padded(B, La), _ops.Seq.padded(B, Lt), _ops.Seq.padded(B, Lt))
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
         out_dtype = h_a.dtype
         a, a32 = _ops.as_pair(h_a)
         t, t32 = _ops.as_pair(h_t)
-        a, a32, t, t32, maps = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, bool(return_attention))
+        a, a32, t, t32, maps, _ = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, bool(return_attention))
         h_a, h_t = _ops.from_pair(a, a32, out_dtype), _ops.from_pair(t, t32, out_dtype)
         if return_attention:
             return h_a, h_t, maps

@@ -40,29 +40,26 @@ class ExplainableDecoderLayer(nn.Module):
         self._site = [_ops.new_site_base() for _ in range(3)]
         self.batch_offset = 0
 
-    def _self_block(self, tgt, tgt32):
-        """the query self-attention sub-layer (:42-43); -> (tgt, tgt32, the layer's dropout seed)"""
+    def _self_block(self, tgt, tgt32, sp):
+        """the query self-attention sub-layer (:42-43) on the queries' padded layout sp; -> (tgt, tgt32, the layer's dropout seed)"""
         p = self.p if self.training else 0.0
         seed = _ops.next_seed(self.training and p > 0)
         sa = self.self_attn
         tgt, tgt32, _ = _ops.SelfAttnLN.apply(tgt, tgt32, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight,
                                               sa.out_proj.bias, self.norm1.weight, self.norm1.bias, self._sh,
-                                              self.nhead, None, p, seed, self._site[0], self.batch_offset, False)     # :42-43
+                                              self.nhead, sp, p, seed, self._site[0], self.batch_offset, False)       # :42-43
         return tgt, tgt32, seed
 
-    def _fwd_pair(self, tgt, tgt32, memory, memory_key_padding_mask, need, kv_pre=None, kv_ready=None):
-        """memory_key_padding_mask may be the fused _ops.Seq: memory is then the packed fused memory [1, N_f, d] and the
-        cross-attention runs on cu_seqlens (N_e query rows per sample, the fused lengths as keys)."""
-        packed = isinstance(memory_key_padding_mask, _ops.Seq)
+    def _fwd_pair(self, tgt, tgt32, memory, sm, need, kv_pre=None, kv_ready=None):
+        """sm: the _ops.Seq of the memory's rows -- padded [B, L_f, d] with its mask, or the fused plan: memory is then the packed
+        fused memory [1, N_f, d] and the cross-attention runs on cu_seqlens (N_e query rows per sample, the fused lengths as keys)."""
+        packed = sm.packed
         Bq, Nq, dq = tgt.shape
-        if packed:
-            kpm = (_ops.query_seq(Bq, Nq, tgt.device), memory_key_padding_mask)
-        else:
-            B, L, _ = memory.shape
-            kpm = _ops.mask_u8(memory_key_padding_mask, B, L)
+        sp = _ops.Seq.padded(Bq, Nq)                                        # the queries' own layout (no mask) ...
+        sq = _ops.query_seq(Bq, Nq, tgt.device) if packed else sp           # ... and as the cross-attention on `memory` sees it
         p = self.p if self.training else 0.0
         ca, s = self.cross_attn, self._site
-        tgt, tgt32, seed = self._self_block(tgt, tgt32)
+        tgt, tgt32, seed = self._self_block(tgt, tgt32, sp)
         if kv_ready is not None:          # K | V of the memory were projected on the side stream (EmotionDecoder._fwd)
             torch.cuda.current_stream(memory.device).wait_event(kv_ready)
         if packed:
@@ -71,13 +68,13 @@ class ExplainableDecoderLayer(nn.Module):
             tgt, tgt32 = tgt.view(1, Bq * Nq, dq), (tgt32.view(1, Bq * Nq, dq) if tgt32 is not None else None)
         tgt, tgt32, w = _ops.CrossAttnLN.apply(tgt, tgt32, memory, ca.in_proj_weight, ca.in_proj_bias,
                                                ca.out_proj.weight, ca.out_proj.bias, self.norm2.weight,
-                                               self.norm2.bias, self._sh, self.nhead, kpm, p, seed, s[1],
+                                               self.norm2.bias, self._sh, self.nhead, sq, sm, p, seed, s[1],
                                                self.batch_offset, need, kv_pre)                               # :48-55
         if packed:
             tgt, tgt32 = tgt.view(Bq, Nq, dq), (tgt32.view(Bq, Nq, dq) if tgt32 is not None else None)
         tgt, tgt32 = _ops.FFNLN.apply(tgt, tgt32, self.linear1.weight, self.linear1.bias, self.linear2.weight,
                                       self.linear2.bias, self.norm3.weight, self.norm3.bias, self._sh, p, p, seed,
-                                      s[2], self.batch_offset)                                                # :58-59
+                                      s[2], self.batch_offset, sp)                                            # :58-59
         return tgt, tgt32, w
 
     def forward(self, tgt, memory, memory_key_padding_mask=None, return_attention=False):
@@ -87,7 +84,8 @@ class ExplainableDecoderLayer(nn.Module):
         if _ops.precision() == "fp32":
             from hri_emo_amd import _fp32
             mem = _fp32.f32_of(mem)
-        t16, t32, w = self._fwd_pair(t16, t32, mem, memory_key_padding_mask, bool(return_attention))
+        sm = _ops.Seq.padded(mem.shape[0], mem.shape[1], memory_key_padding_mask)
+        t16, t32, w = self._fwd_pair(t16, t32, mem, sm, bool(return_attention))
         tgt = _ops.from_pair(t16, t32, out_dtype)
         return (tgt, w) if return_attention else (tgt, None)
 
@@ -111,12 +109,10 @@ class EmotionDecoder(nn.Module):
         out32 = self.emotion_queries.detach().float().unsqueeze(0).expand(B, -1, -1).contiguous() if _ops.TWIN else None
         return out, out32
 
-    def _fwd(self, memory16, memory_key_padding_mask, need, out_dtype):
-        """memory_key_padding_mask: the [B, L_f] mask of a padded memory [B, L_f, d], or the fused _ops.Seq of a packed memory
-        [1, N_f, d] (the K | V projections then run over the N_f packed rows)"""
-        packed = isinstance(memory_key_padding_mask, _ops.Seq)
-        B = memory_key_padding_mask.Breal if packed else memory16.size(0)
-        out, out32 = self._queries(B)
+    def _fwd(self, memory16, sm, need, out_dtype):
+        """sm: the _ops.Seq of the memory's rows -- a padded memory [B, L_f, d] with its [B, L_f] mask, or the fused plan of a packed
+        memory [1, N_f, d] (the K | V projections then run over the N_f packed rows)"""
+        out, out32 = self._queries(sm.Breal)
         all_layers_attn = []
         if _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):
             # fp8 GEMM mode: every layer projects the same memory to K | V -- quantise it once
@@ -142,7 +138,7 @@ class EmotionDecoder(nn.Module):
             for kv in kvs:
                 _ops.share(kv, main)
         for i, layer in enumerate(self.layers):
-            out, out32, attn_map = layer._fwd_pair(out, out32, memory16, memory_key_padding_mask, need, kvs[i],
+            out, out32, attn_map = layer._fwd_pair(out, out32, memory16, sm, need, kvs[i],
                                                    ready if i == 0 else None)
             if need and attn_map is not None:
                 all_layers_attn.append(attn_map)
@@ -153,7 +149,8 @@ class EmotionDecoder(nn.Module):
         return z, logits, all_layers_attn
 
     def forward(self, memory, memory_key_padding_mask=None, return_attention=False):
-        z, logits, maps = self._fwd(_memory16(memory), memory_key_padding_mask, bool(return_attention), memory.dtype)
+        sm = _ops.Seq.padded(memory.shape[0], memory.shape[1], memory_key_padding_mask)
+        z, logits, maps = self._fwd(_memory16(memory), sm, bool(return_attention), memory.dtype)
         if return_attention:
             return z, logits, maps
         return z, logits

@@ -34,8 +34,8 @@ class FusionClassifier(nn.Module):
         h_a, h_t = self._ensure_3d(h_a), self._ensure_3d(h_t)
         a, a32 = _ops.as_pair(h_a)
         t, t32 = _ops.as_pair(h_t)
-        a, a32, t, t32, _ = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, False)      # :139
-        h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t)                 # :142
+        a, a32, t, t32, _, seqs = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, False)      # :139
+        h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)                 # :142
         h_fusion_pooled = h_fusion.float().mean(dim=1)                                            # :145
         logits = self.classifier(h_fusion_pooled)                                                 # :148
         return logits, beta, h_fusion_pooled.to(h_a.dtype if h_a.dtype != torch.bfloat16 else torch.float32)

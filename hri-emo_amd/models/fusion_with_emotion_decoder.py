@@ -88,27 +88,23 @@ class FusionWithEmotionDecoder(nn.Module):
         _ops.begin_step()
         # the decoder's memory mask needs the two padding masks only (L_fused = T_t, beta_gate_tacfn.py:98-116): built here, not on
         # the decoder's serial chain behind the gate
-        # (not needed when the tail stays packed: the fused Seq stands in for it; masks without a plan build it late)
+        # (not needed when the tail stays packed: the fused Seq carries the lengths; masks without a plan build it late)
         may_pack = _ops.varlen() and not need and mask_a is not None and mask_t is not None and _ops.packed_tail()
         fused_early = None if may_pack else self._build_fused_mask(mask_a, mask_t, h_t.size(1))
         ready = self._prefetch_shadows(a.device)
         _ops.CTX.join_scope += 1          # logits, beta and z all depend on both branches: the encoder's gradient joins are safe
-        tail = []                         # takes the packed plan when the encoder ran packed and the tail may stay packed
-        try:
-            a, a32, t, t32, encoder_attns = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, tail)
+        try:                              # seqs: the layouts of a, t and the fused memory (the packed plan when the tail stays packed)
+            a, a32, t, t32, encoder_attns, seqs = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, tail=True)
         finally:
             _ops.CTX.join_scope -= 1
         if ready is not None:
             torch.cuda.current_stream(a.device).wait_event(ready)
-        if tail:
-            # packed tail: the gate reads the packed rows, the decoder a packed fused memory with the fused Seq in its mask slot
-            h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, tail[0])
-            fused_mask = tail[0][2]
-        else:
-            h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t)
-            fused_mask = fused_early if (fused_early is not None and h_fusion.size(1) == h_t.size(1)) else \
-                self._build_fused_mask(mask_a, mask_t, h_fusion.size(1))
-        z, logits, decoder_attns = self.emotion_decoder._fwd(h_fusion, fused_mask, need, out_dtype)
+        h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)
+        sm = seqs[2]                      # packed tail: the gate read the packed rows, the decoder reads a packed fused memory
+        if not sm.packed:
+            sm = sm.with_kpm(fused_early if (fused_early is not None and h_fusion.size(1) == h_t.size(1)) else
+                             self._build_fused_mask(mask_a, mask_t, h_fusion.size(1)))
+        z, logits, decoder_attns = self.emotion_decoder._fwd(h_fusion, sm, need, out_dtype)
         if return_attention:
             return logits, beta, z, {"encoder": encoder_attns, "decoder": decoder_attns}
         return logits, beta, z

@@ -89,3 +89,69 @@ def test_the_tail_unpacks_outside_the_bf16_path():
         _ops.set_precision(prec)
         _ops.set_gemm_mode(mode)
         _ops.PACKED_TAIL = tail
+
+
+# ----------------------------------------------------------------------------- the layout value (Seq) and attn_rows
+def test_padded_layout():
+    import pytest
+    from hri_emo_amd import _ops
+    _, m_t = _masks()
+    s = _ops.Seq.padded(B, LT, m_t)
+    assert (s.cu, s.idx, s.B, s.Breal, s.L, s.Lmax, s.N, s.surplus) == (None, None, 5, 5, 40, 40, 200, False)
+    assert s.kpm.dtype == torch.uint8 and tuple(s.kpm.shape) == (5, 40) and torch.equal(s.kpm.bool(), m_t)
+    assert s.kpm.data_ptr() == m_t.data_ptr()                    # a bool mask is viewed, not copied
+    assert not s.packed and s.shape(16) == (5, 40, 16)
+    assert _ops.Seq.padded(B, LT).kpm is None
+    with pytest.raises(ValueError, match="key_padding_mask shape"):
+        _ops.Seq.padded(B, LA, m_t)
+    with pytest.raises(ValueError, match="rows of its layout"):
+        s.holds(torch.zeros(B, LA, 16))
+    s.holds(torch.zeros(B, LT, 16))
+
+
+def test_attn_rows_of_the_five_layouts():
+    import pytest
+    from hri_emo_amd import _ops
+    m_a, m_t = _masks()
+    # padded self-attention (text) and padded cross-attention (audio queries, text keys: the keys' mask)
+    pa, pt = _ops.Seq.padded(B, LA, m_a), _ops.Seq.padded(B, LT, m_t)
+    assert _ops.attn_rows(pt, pt, False) == (5, 40, 40, pt.kpm, None, 40, None, False)
+    assert _ops.attn_rows(pt, pt, True) == (5, 40, 40, pt.kpm, None, 40, None, False)          # maps: the padded path exports them
+    assert _ops.attn_rows(pa, pt, False) == (5, 70, 40, pt.kpm, None, 70, None, False)
+    # packed self-attention from seq_plan
+    sa, st, sf = _ops.seq_plans(m_a, m_t, B, LA, LT)
+    assert sa.packed and sa.kpm is None and sa.shape(16) == (1, sum(LENS_A), 16)
+    assert _ops.attn_rows(sa, sa, False) == (5, 70, 70, None, (sa.cu, sa.cu), 70, sa.idx, False)
+    assert _ops.attn_rows(st, st, False) == (5, 40, 40, None, (st.cu, st.cu), 40, st.idx, False)
+    # packed cross-attention, both directions
+    assert _ops.attn_rows(sa, st, False) == (5, 70, 40, None, (sa.cu, st.cu), 70, sa.idx, False)
+    assert _ops.attn_rows(st, sa, False) == (5, 40, 70, None, (st.cu, sa.cu), 40, st.idx, False)
+    # bucket plan: the filler rows are one more sequence
+    rows = 128
+    cu = torch.tensor(_cum(LENS_T) + [rows], dtype=torch.int32)
+    sb = _ops.seq_bucket(cu, B, LT, rows)
+    assert _ops.attn_rows(sb, sb, False) == (6, 40, 40, None, (cu, cu), 40, sb.idx, False)
+    # the decoder: N_e = 6 query rows per sample on the fused memory of a bucket, whose surplus rows are no sequence
+    cu_f = torch.tensor(_cum(LENS_F) + [rows], dtype=torch.int32)
+    sq, sbf = _ops.query_seq(B, 6, torch.device("cpu")), _ops.seq_bucket_fused(cu_f, B, LT, rows)
+    assert _ops.attn_rows(sq, sbf, False) == (5, 6, 40, None, (sq.cu, cu_f), 6, None, True)
+    assert _ops.attn_rows(sq, sf, False) == (5, 6, 40, None, (sq.cu, sf.cu), 6, None, False)
+    # the two refusals live here and nowhere else
+    for q, k in ((sa, sa), (sa, st), (sq, sbf)):
+        with pytest.raises(ValueError, match="attention maps are exported by the padded path only"):
+            _ops.attn_rows(q, k, True)
+    for q, k in ((sa, pt), (pa, st), (sa.with_kpm(m_a), st), (sa, st.with_kpm(m_t))):
+        with pytest.raises(ValueError, match="packed sequences carry their lengths; no key_padding_mask"):
+            _ops.attn_rows(q, k, False)
+
+
+def test_a_plan_with_the_masks_riding_along():
+    """the gate's copies (Seq.with_kpm): every field of the plan, plus the padded mask its valid counts are read from"""
+    from hri_emo_amd import _ops
+    m_a, m_t = _masks()
+    sa = _ops.seq_plan(m_a, B, LA)
+    g = sa.with_kpm(m_a)
+    assert (g.cu, g.idx, g.B, g.Breal, g.L, g.Lmax, g.N, g.surplus) == (sa.cu, sa.idx, sa.B, sa.Breal, sa.L, sa.Lmax, sa.N, sa.surplus)
+    assert g.kpm.dtype == torch.uint8 and torch.equal(g.kpm.bool(), m_a) and sa.kpm is None
+    p = _ops.Seq.padded(B, LT).with_kpm(m_t)
+    assert not p.packed and torch.equal(p.kpm.bool(), m_t)
