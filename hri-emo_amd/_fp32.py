@@ -195,7 +195,13 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None, 
               dv.stride(0), _ops._p(delta), B, H, Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
 
 
-def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None):
+def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None, cu=None, out_l=None):
+    """cu / out_l as _ops.attn_probs: the padded map [B, out_l[0], out_l[1]] of packed rows"""
+    if cu is not None:
+        p = _new((B,) + tuple(out_l), q)
+        _lib.call("hriemo_attn_probs_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(cu[0]), _ops._p(cu[1]),
+                  _ops._p(lse), _ops._p(p), B, H, Lq, Lk, out_l[0], out_l[1], hd, *_drop_args(drop, q.device), _ops._stream())
+        return p
     p = _new((B, Lq, Lk), q)
     _lib.call("hriemo_attn_probs_f32", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(kpm), _ops._p(lse), _ops._p(p), B, H,
               Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
@@ -297,7 +303,7 @@ def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq,
     o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
     g = linear(o, sh, w_out, b_out)
     y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=ar.rows)
-    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn) if need_w else None
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn, cu=ar.cu, out_l=(seq.L, seq.L)) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)
@@ -350,7 +356,7 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
     o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
     g = linear(o, sh, w_out, b_out)
     y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res, rows=ar.rows)
-    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn) if need_w else None
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn, cu=ar.cu, out_l=(seq_q.L, seq_k.L)) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)

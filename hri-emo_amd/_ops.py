@@ -885,7 +885,15 @@ def attn_bwd(q, k, v, o, do, dq, dk, dv, lse, B, H, Lq, Lk, hd, kpm, p, seed, si
     return fold
 
 
-def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off):
+def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off, cu=None, out_l=None):
+    """head-averaged probabilities [B, Lq, Lk].  cu = (cu_seqlens_q, cu_seqlens_k): q / k hold packed rows, Lq / Lk are the longest
+    sequences and out_l = (L_q, L_k) the padded lengths of the two layouts: the padded map [B, L_q, L_k] comes back, zeros in the
+    PAD key columns and the PAD query rows (every element is written by the kernel)"""
+    if cu is not None:
+        out = torch.empty((B,) + tuple(out_l), dtype=torch.float32, device=q.device)
+        _lib.call("hriemo_attn_probs_varlen", _p(q), q.stride(0), _p(k), k.stride(0), _p(cu[0]), _p(cu[1]), _p(lse), _p(out), B, H,
+                  Lq, Lk, out_l[0], out_l[1], hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _stream())
+        return out
     out = torch.empty((B, Lq, Lk), dtype=torch.float32, device=q.device)
     _lib.call("hriemo_attn_probs", _p(q), q.stride(0), _p(k), k.stride(0), _p(kpm), _p(lse), _p(out), B, H, Lq, Lk,
               hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _stream())
@@ -1249,6 +1257,22 @@ PACKED_TAIL = False
 PACKED_TAIL_FP32 = False
 
 
+# Attention maps (return_attention=True) from the packed path: the export runs on cu_seqlens (hriemo_attn_probs_varlen,
+# hriemo_attn_probs_f32_varlen) and hands back the padded maps, so asking for the maps no longer sends the forward to the padded
+# layout.  False: the maps are exported by the padded path only (the launches from before the packed export).  Opt-in; a module
+# constant with a setter, not an environment switch.
+PACKED_MAPS = False
+
+
+def set_varlen_maps(on):
+    global PACKED_MAPS
+    PACKED_MAPS = bool(on)
+
+
+def varlen_maps():
+    return bool(PACKED_MAPS)
+
+
 def packed_tail():
     """the tail stays packed: bf16 GEMM operands (the MX-fp8 mode unpacks behind the encoder) and the switch of the precision
     mode -- PACKED_TAIL for bf16, PACKED_TAIL_FP32 for fp32"""
@@ -1310,10 +1334,12 @@ AttnRows = namedtuple("AttnRows", "B Lq Lk kpm cu stride rows kv_surplus")
 
 def attn_rows(seq_q, seq_k, need_w):
     """AttnRows of a sub-layer whose queries are laid out as seq_q and whose keys as seq_k (the same Seq for a self-attention).
-    Packed: the attention sees Seq.B sequences of up to Seq.Lmax rows, the LayerNorm dropout stays keyed by the padded rows."""
+    Packed: the attention sees Seq.B sequences of up to Seq.Lmax rows, the LayerNorm dropout stays keyed by the padded rows.
+    need_w on packed rows: only with the packed export switched on (set_varlen_maps) and a plan without a filler sequence."""
     if not (seq_q.packed or seq_k.packed):
         return AttnRows(seq_q.B, seq_q.L, seq_k.L, seq_k.kpm, None, seq_q.L, None, False)
-    if need_w:
+    if need_w and not (varlen_maps() and seq_q.B == seq_q.Breal and seq_k.B == seq_k.Breal):
+        # (with the packed export on, a bucketed plan is still refused: its filler sequence has no sample to export)
         raise ValueError("attention maps are exported by the padded path only")
     if not (seq_q.packed and seq_k.packed) or seq_q.kpm is not None or seq_k.kpm is not None:
         raise ValueError("attn_fwd: packed sequences carry their lengths; no key_padding_mask")
@@ -1557,7 +1583,7 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
             attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
         g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
                                              ar.rows)
-        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off) if need_w else None
+        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, (seq.L, seq.L)) if need_w else None
         ctx.save_for_backward(x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
         ctx.cfg = (B, L, d, H, hd, p, seed, site, b_off)
         ctx.rows = ar
@@ -1641,7 +1667,7 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
             attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
         g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, xq2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
                                              ar.rows)
-        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off) if need_w else None
+        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, (seq_q.L, seq_k.L)) if need_w else None
         ctx.save_for_backward(xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
         ctx.cfg = (B, Lq, Lk, d, H, hd, p, seed, site, b_off)
         ctx.rows = ar

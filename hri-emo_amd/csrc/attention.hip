@@ -1500,6 +1500,101 @@ __global__ __launch_bounds__(64) void attn_probs_kernel(const AttnArgs a) {
   }
 }
 
+// The export on packed (varlen) rows, on the matrix cores (hriemo_attn_probs_varlen): sample b's queries are rows cu_q[b] ..
+// cu_q[b+1]-1 of Q, its keys rows cu_k[b] .. cu_k[b+1]-1 of K, lse keeps the padded [B, H, max_lq] slots of the varlen forward,
+// and the output is the PADDED map [B, out_lq, out_lk], every element written (no memset in front): probabilities where query
+// and key are valid, exact zeros in the key columns and the query rows past the sample's lengths.
+// Block = 4 waves x 16 queries, PROBS_KT key tiles of 64; key tiles outer, heads inner, the K tile of one head in LDS one tile
+// ahead (the forward's staging and LDS image).  Scores are produced UN-transposed, S = Q.K^T (A = Q rows, B = K rows): lane
+// (i, g) holds S[query 4g + r][key 16n + i], so a store instruction of the wave writes 64-byte runs along the keys of four query
+// rows and a block 512-byte runs -- the map is the only large HBM stream here.  Rows of K past the sample's last key are never
+// fetched (tile_fetch's row bound), so the surplus rows of a fused bucket stay unread.
+#define PROBS_KT 2
+struct ProbsArgs {
+  const bf16_t *Q, *K;
+  long ldq, ldk;
+  const int *cu_q, *cu_k;
+  const float* lse;
+  float* probs;
+  int H, max_lq, max_lk, out_lq, out_lk;
+  float scale;
+  uint32_t thr16; float inv_keep; uint64_t seed; const unsigned long long* seed_dev; uint32_t site; int b_offset;
+};
+template <int HD>
+__global__ __launch_bounds__(256) void attn_probs_mfma_kernel(const ProbsArgs a) {
+  using G = AttnGeom<HD>;
+  constexpr int KS = G::KS, STRIDE = G::STRIDE;
+  __shared__ __attribute__((aligned(16))) char Kt[64 * STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
+  const int b = blockIdx.z;
+  // the lengths are device data: clamped to what sized the buffers, so a stale cu cannot send a block out of bounds
+  const int rq = a.cu_q[b], rk = a.cu_k[b];
+  const int Lq = max(min(a.cu_q[b + 1] - rq, a.max_lq), 0), Lk = max(min(a.cu_k[b + 1] - rk, a.max_lk), 0);
+  const int qb = blockIdx.x * 64, q0 = qb + wave * 16;
+  const int kt0 = blockIdx.y * PROBS_KT, kt1 = min(kt0 + PROBS_KT, (a.out_lk + 63) >> 6);
+  const int nlive = qb < Lq ? min(kt1, (Lk + 63) >> 6) : kt0;       // key tiles [kt0, nlive) hold probabilities, the rest zeros
+  const float sl2 = a.scale * LOG2E, invH = 1.f / (float)a.H;
+  const uint64_t seed = a.thr16 != 0 ? eff_seed(a.seed, a.seed_dev) : 0ull;
+  const bf16_t* Kb = a.K + (long)rk * a.ldk;
+  float* pb = a.probs + (long)b * a.out_lq * a.out_lk;
+
+  TileRegs<HD, 64, 256> kr;
+  if (kt0 < nlive) tile_fetch<HD, 64, 256>(kr, Kb, a.ldk, kt0 * 64, Lk, tid);
+  for (int kt = kt0; kt < kt1; ++kt) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (kt < nlive) {                          // block-uniform
+      for (int h = 0; h < a.H; ++h) {
+        // this head's 16 query rows as A fragments and their lse (rows past the sample's end: its last row, masked at the store)
+        bf16x8 qf[KS];
+        const bf16_t* qp = a.Q + (long)(rq + min(q0 + i, Lq - 1)) * a.ldq + h * HD;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const int e = ks * 32 + 8 * g;
+          qf[ks] = (e < HD) ? *(const bf16x8*)(qp + e) : zero8();
+        }
+        float nl[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) nl[r] = -LOG2E * a.lse[((long)b * a.H + h) * a.max_lq + min(q0 + 4 * g + r, Lq - 1)];
+        __syncthreads();
+        tile_commit<HD, 64, 256>(kr, Kt, tid);
+        __syncthreads();
+        if (h + 1 < a.H) tile_fetch<HD, 64, 256>(kr, Kb + (h + 1) * HD, a.ldk, kt * 64, Lk, tid);
+        else if (kt + 1 < nlive) tile_fetch<HD, 64, 256>(kr, Kb, a.ldk, (kt + 1) * 64, Lk, tid);
+        if (q0 >= Lq) continue;                // wave-uniform: a whole 16-row tile past the sample's end (the barriers are above)
+        const uint32_t key32 = a.thr16 != 0 ? site_key(seed, a.site, (uint32_t)((a.b_offset + b) * a.H + h)) : 0u;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+          f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks)
+            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ks], row_frag(Kt, STRIDE, n * 16 + i, ks * 4 + g), s, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float p = EXP2(fmaf(s[r], sl2, nl[r]));
+            // (training mode: the reference returns the weights AFTER its dropout; keyed by position within the sample, as the forward)
+            if (a.thr16 != 0)
+              p = keep16(key32, (uint32_t)(q0 + 4 * g + r), (uint32_t)(kt * 64 + n * 16 + i), a.thr16) ? p * a.inv_keep : 0.f;
+            acc[n][r] += p;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + 4 * g + r;
+      if (q >= a.out_lq) continue;
+      float* pp = pb + (long)q * a.out_lk;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int key = kt * 64 + n * 16 + i;
+        if (key < a.out_lk) pp[key] = (q < Lq && key < Lk) ? acc[n][r] * invH : 0.f;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host
 static int cu_count() {
   static int n = 0;
@@ -1837,5 +1932,33 @@ extern "C" int hriemo_attn_probs(const void* Q, long ldq, const void* K, long ld
     hipLaunchKernelGGL((attn_probs_kernel<decltype(hd)::value>), dim3((Lk + 63) / 64, (Lq + 7) / 8, B), dim3(64), 0, st, a);
   });
   HRIEMO_LAUNCH_CHECK("attn_probs_kernel");
+  return 0;
+}
+
+// The export on packed rows (attn_probs_mfma_kernel): the padded map [B, out_lq, out_lk] of the varlen forward's operands and lse
+extern "C" int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q,
+                                        const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q,
+                                        int max_len_k, int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
+                                        const unsigned long long* seed_dev, unsigned site, int b_offset, hipStream_t st) {
+  HRIEMO_CHECK(Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr, "attn_probs_varlen: empty problem");
+  if (check_shape(B, H, max_len_q, max_len_k, head_dim)) return 1;
+  HRIEMO_CHECK(B <= 65535, "attn_probs_varlen: B=%d exceeds the grid", B);
+  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_probs_varlen: cu_seqlens_q and cu_seqlens_k must be given together");
+  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "attn_probs_varlen: the map [%d, %d] is smaller than the longest sequences [%d, %d]",
+               out_lq, out_lk, max_len_q, max_len_k);
+  HRIEMO_CHECK(ldq % 8 == 0 && ldk % 8 == 0, "attn_probs_varlen: leading dims must be multiples of 8");
+  HRIEMO_CHECK(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)probs % 4) == 0 && ((uintptr_t)lse % 4) == 0,
+               "attn_probs_varlen: unaligned Q/K/lse/probs");
+  HRIEMO_CHECK(p_drop >= 0.f && p_drop < 1.f, "attn_probs_varlen: dropout p=%f", (double)p_drop);
+  const DropCfg d = make_drop(p_drop, seed, site);
+  ProbsArgs a = {};
+  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.ldq = ldq; a.ldk = ldk;
+  a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.lse = lse; a.probs = probs;
+  a.H = H; a.max_lq = max_len_q; a.max_lk = max_len_k; a.out_lq = out_lq; a.out_lk = out_lk;
+  a.scale = 1.0f / sqrtf((float)head_dim);
+  a.thr16 = d.thr16; a.inv_keep = d.inv_keep; a.seed = seed; a.seed_dev = seed_dev; a.site = site; a.b_offset = b_offset;
+  const dim3 grid(tiles(out_lq, 64), tiles(out_lk, 64 * PROBS_KT), B);
+  with_head_dim(head_dim, [&](auto hd) { hipLaunchKernelGGL((attn_probs_mfma_kernel<decltype(hd)::value>), grid, dim3(256), 0, st, a); });
+  HRIEMO_LAUNCH_CHECK("attn_probs_mfma_kernel");
   return 0;
 }

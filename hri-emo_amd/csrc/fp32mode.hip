@@ -557,6 +557,75 @@ __global__ __launch_bounds__(256) void attn_probs_f32_kernel(const float* __rest
 }
 
 
+// The same export on packed (varlen) rows (hriemo_attn_probs_f32_varlen): sample b = rows cu_q[b] .. cu_q[b+1]-1 of Q and cu_k[b] ..
+// cu_k[b+1]-1 of K, lse in the padded [B, H, max_lq] slots of the varlen forward; the output is the PADDED map [B, out_lq, out_lk]
+// and every element of it is written -- probabilities where query and key are valid, exact zeros in the key columns and the query
+// rows past the sample's lengths (no memset in front).  Rows of K past the sample's last key are never read.
+template <int HD>
+__global__ __launch_bounds__(256) void attn_probs_f32_varlen_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
+                                                                    const int* __restrict__ cu_q, const int* __restrict__ cu_k,
+                                                                    const float* __restrict__ lse, float* __restrict__ probs, int H, int max_lq,
+                                                                    int max_lk, int out_lq, int out_lk, float scale, AttnDrop dr) {
+  constexpr int LDR = HD + 4;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* Ks = (float*)smem_raw;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+  const int b = blockIdx.y;
+  // the lengths are device data: clamped to what sized the buffers
+  const int rq = cu_q[b], rk = cu_k[b];
+  const int Lq = max(min(cu_q[b + 1] - rq, max_lq), 0), Lk = max(min(cu_k[b + 1] - rk, max_lk), 0);
+  const int qb = blockIdx.x * 64, q0 = qb + wave * 16;
+  const bool live = qb < Lq;                    // block-uniform: some query row of this block belongs to the sample
+  const int q = min(q0 + i, Lq - 1);
+  const float invH = 1.f / (float)H;
+  for (int k0 = 0; k0 < out_lk; k0 += 64) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (live && k0 < Lk) {
+      for (int h = 0; h < H; ++h) {
+        __syncthreads();
+        const float* Kb = K + (long)rk * ldk + h * HD;
+        for (int e = tid; e < 64 * (HD / 4); e += 256) {
+          const int r = e / (HD / 4), c = (e - r * (HD / 4)) * 4;
+          const int key = k0 + r;
+          f32x4 kv = {0.f, 0.f, 0.f, 0.f};
+          if (key < Lk) kv = *(const f32x4*)(Kb + (long)key * ldk + c);
+          *(f32x4*)(Ks + r * LDR + c) = kv;
+        }
+        __syncthreads();
+        const float* qp = Q + (long)(rq + q) * ldq + h * HD;
+        const float ls = lse[((long)b * H + h) * max_lq + q];
+        const uint32_t dkey = dr.thr16 != 0 ? site_key(eff_seed(dr.seed, dr.seed_dev), dr.site, (uint32_t)((dr.b_offset + b) * H + h)) : 0u;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+          f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < HD / 4; ++ks)
+            s = __builtin_amdgcn_mfma_f32_16x16x4f32(Ks[(16 * n + i) * LDR + 4 * ks + g], qp[4 * ks + g] * scale, s, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pv = expf(s[r] - ls);
+            if (dr.thr16 == 0) acc[n][r] += pv;
+            else acc[n][r] += keep16(dkey, (uint32_t)(q0 + i), (uint32_t)(k0 + 16 * n + 4 * g + r), dr.thr16) ? pv * dr.inv_keep : 0.f;
+          }
+        }
+      }
+    }
+    if (q0 + i < out_lq) {
+      float* pp = probs + ((long)b * out_lq + q0 + i) * out_lk + k0;
+      const bool qv = q0 + i < Lq;
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = 16 * n + 4 * g + r;
+          if (k0 + key < out_lk) pp[key] = (qv && k0 + key < Lk) ? acc[n][r] * invH : 0.f;
+        }
+    }
+  }
+}
+
 // ===================================================================================================== backward (round 4)
 // ------------------------------------------------------------------------------------------- operand splitting, general form
 // form 0: Y[M][3K] = [hi | mid | hi]   form 1: Y[M][3K] = [hi | hi | mid]      (contraction along the columns of X)
@@ -1261,6 +1330,33 @@ extern "C" int hriemo_attn_probs_f32(const float* Q, long ldq, const float* K, l
   DISPATCH_HD_F32(head_dim, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("attn_probs_f32_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_attn_probs_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                            const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
+                                            int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
+                                            int b_offset, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && H > 0 && max_len_q > 0 && max_len_k > 0 && Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr,
+               "attn_probs_f32_varlen: empty problem");
+  HRIEMO_CHECK(B <= 65535, "attn_probs_f32_varlen: B=%d exceeds the grid", B);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "attn_probs_f32_varlen: dropout p=%f", (double)p);
+  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_probs_f32_varlen: cu_seqlens_q and cu_seqlens_k must be given together");
+  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "attn_probs_f32_varlen: the map [%d, %d] is smaller than the longest sequences [%d, %d]",
+               out_lq, out_lk, max_len_q, max_len_k);
+  const AttnDrop dr = make_attn_drop(p, seed, seed_dev, site, b_offset);
+  HRIEMO_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0, "attn_probs_f32_varlen: operands must be 16-byte aligned");
+  const float scale = 1.0f / sqrtf((float)head_dim);
+  const dim3 grid((out_lq + 63) / 64, B);
+#define CALL(HD)                                                                                                                           \
+  {                                                                                                                                        \
+    const int lds = 64 * (HD + 4) * 4;                                                                                                     \
+    hipLaunchKernelGGL((attn_probs_f32_varlen_kernel<HD>), grid, dim3(256), lds, st, Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, H, \
+                       max_len_q, max_len_k, out_lq, out_lk, scale, dr);                                                                   \
+  }
+  DISPATCH_HD_F32(head_dim, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("attn_probs_f32_varlen_kernel");
   return 0;
 }
 

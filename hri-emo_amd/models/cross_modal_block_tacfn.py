@@ -217,7 +217,7 @@ class CrossModalTransformer(nn.Module):
         B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
         plan = None
         _ops.FLUSH_SITES.add(self.layers[0]._site[1])        # layer-0 text self-attention: the last text-branch backward (_ops._DeferredWgrad)
-        if _ops.varlen() and not need and mask_a is not None and mask_t is not None:
+        if _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None:
             # the encoder on the valid rows only (prefix masks, as the collate builds them); anything else
             # takes the padded path.  dp.DataParallelStep injects bucketed plans whose lengths are device data (_ops.CTX.seq_override).
             if _ops.CTX.seq_override is not None:

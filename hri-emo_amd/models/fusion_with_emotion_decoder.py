@@ -89,7 +89,7 @@ class FusionWithEmotionDecoder(nn.Module):
         # the decoder's memory mask needs the two padding masks only (L_fused = T_t, beta_gate_tacfn.py:98-116): built here, not on
         # the decoder's serial chain behind the gate
         # (not needed when the tail stays packed: the fused Seq carries the lengths; masks without a plan build it late)
-        may_pack = _ops.varlen() and not need and mask_a is not None and mask_t is not None and _ops.packed_tail()
+        may_pack = _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None and _ops.packed_tail()
         fused_early = None if may_pack else self._build_fused_mask(mask_a, mask_t, h_t.size(1))
         ready = self._prefetch_shadows(a.device)
         _ops.CTX.join_scope += 1          # logits, beta and z all depend on both branches: the encoder's gradient joins are safe

@@ -179,6 +179,21 @@ int hriemo_attn_probs(const void* Q, long ldq, const void* K, long ldk, const un
                       const float* lse, float* probs, int B, int H, int Lq, int Lk, int head_dim, float p_drop,
                       unsigned long long seed, const unsigned long long* seed_dev, unsigned site, int b_offset,
                       hriemo_stream_t stream);
+/* The export on packed (varlen) rows, on the matrix cores (v_mfma_f32_16x16x32_bf16): Q / K hold the packed rows of
+ * hriemo_attn_fwd_varlen (sample b = rows cu_seqlens_q[b] .. cu_seqlens_q[b+1]-1 of Q, cu_seqlens_k likewise of K; int32 [B+1],
+ * device memory, every length >= 1; own leading dimensions), lse is what that forward wrote ([B, H, max_len_q], padded indexing),
+ * dropout (p_drop > 0) replays its mask (keyed by position within the sample).  probs is the PADDED map [B, out_lq, out_lk] fp32,
+ * out_lq >= max_len_q, out_lk >= max_len_k (the padded lengths of the two layouts), and EVERY element of it is written, so no
+ * memset precedes the call: probabilities where query and key are valid, exact 0.0 in the key columns at or past the sample's
+ * key length (as hriemo_attn_probs does under a key_padding_mask) and exact 0.0 in the query rows at or past the sample's query
+ * length.  That last part is the one difference to the padded export: hriemo_attn_probs computes the PAD query rows (a softmax
+ * over the valid keys, which nothing reads), the packed path never has those rows.  Rows of K at or past cu_seqlens_k[B] (the
+ * surplus rows of a fused bucket) are never read.  Non-zero (hriemo_last_error) for an empty problem, a head_dim that is not built,
+ * unaligned operands, out_lq < max_len_q or out_lk < max_len_k, and a missing cu_seqlens pointer. */
+int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                             const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
+                             int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
+                             int b_offset, hriemo_stream_t stream);
 
 /* ---- y = LayerNorm(x + dropout(g)), eps, affine (X may be NULL: plain LayerNorm of g).
  * The residual stream has an optional fp32 twin: X32 (read instead of the bf16 X when non-NULL) and Y32
@@ -504,6 +519,12 @@ int hriemo_attn_bwd_f32_varlen(const float* Q, long ldq, const float* K, long ld
                                long lddq, float* dK, long lddk, float* dV, long lddv, float* delta, int B, int H, int max_len_q,
                                int max_len_k, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
                                unsigned site, int b_offset, hriemo_stream_t stream);
+/*  - hriemo_attn_probs_f32_varlen: hriemo_attn_probs_f32 on those packed rows, the contract of hriemo_attn_probs_varlen (padded map
+ *    [B, out_lq, out_lk], every element written, zeros in PAD key columns and PAD query rows, no row of K past cu_seqlens_k[B] read). */
+int hriemo_attn_probs_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                 const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
+                                 int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
+                                 int b_offset, hriemo_stream_t stream);
 int hriemo_add_ln_f32_rows(const float* G, const float* X, const float* gamma, const float* beta, float* Y32, void* Y16, int M, int d,
                            float eps, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
                            long row_offset, const long long* row_index, hriemo_stream_t stream);
