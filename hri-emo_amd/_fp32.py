@@ -289,49 +289,58 @@ def _drops(p, seed, site, b_off, rows_per_sample):
     return (p, seed, site, b_off), (p, seed, site + 1, b_off * rows_per_sample)
 
 
+def _attn_ln(ctx, head, q, k, v, xf, ar, H, hd, params, drops, need_w, out_l, shape):
+    """both attention sub-layers behind their in-projections (as _ops._attn_ln_fwd): core, out-projection, residual + LayerNorm,
+    the map if asked for; a recording node saves `head` (the in-projection's tensors), then o, lse, g.  xf: the residual rows;
+    params = (w_in, b_in, w_out, b_out, gamma, beta, sh); drops = _drops(...) -> the Function's results, y shaped `shape`"""
+    w_out, b_out, gamma, beta, sh = params[2:]
+    rec = recording(ctx)
+    o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=drops[0], cu=ar.cu)
+    g = linear(o, sh, w_out, b_out)
+    y16, y32 = add_ln(g, xf, gamma, beta, drop=drops[1], rows=ar.rows)
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=drops[0], cu=ar.cu, out_l=out_l) if need_w else None
+    ctx.fp32 = True
+    if rec:
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*head, o, lse, g)
+        ctx.rows, ctx.f32_drop, ctx.f32_params = ar, drops, params
+        if pr is not None:
+            ctx.mark_non_differentiable(pr)
+    return y16.view(shape), y32.view(shape), pr
+
+
+def _attn_ln_bwd(ctx, dy, dy32, xf, o, g):
+    """how both attention backwards open: LayerNorm + residual, then the out-projection
+    -> (dS: the residual path's gradient, dO: the attention output's, dw_out, db_out, dgamma, dbeta)"""
+    w_out, gamma, sh = ctx.f32_params[2], ctx.f32_params[4], ctx.f32_params[6]
+    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(_total(dy, dy32, xf.shape), g, xf, gamma, drop=ctx.f32_drop[1], rows=ctx.rows.rows)
+    dw_out = linear_dw(dg, o)
+    return ds, linear_dx(dg, sh, w_out), dw_out, db_out, dgamma, dbeta
+
+
 def self_attn_ln(ctx, x, x32, w_in, b_in, w_out, b_out, gamma, beta, sh, H, seq, need_w, p=0.0, seed=0, site=0, b_off=0):
     _ops._require_fp32_masters(w_in, b_in, w_out, b_out, gamma, beta)
     _ops._require_gpu(x)
     B, L, d = x.shape
     hd = _ops._heads(d, H)
-    rec = recording(ctx)
     ar = _ops.attn_rows(seq, seq, need_w)
-    d_attn, d_res = _drops(p, seed, site, b_off, ar.stride)
     xf = _twin(x, x32).view(B * L, d)
     qkv = linear(xf, sh, w_in, b_in)
-    q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
-    g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xf, gamma, beta, drop=d_res, rows=ar.rows)
-    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn, cu=ar.cu, out_l=(seq.L, seq.L)) if need_w else None
-    ctx.fp32 = True
-    if rec:
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xf, qkv, o, lse, g)
-        ctx.f32_cfg = (B, L, d, H, hd)
-        ctx.rows = ar
-        ctx.f32_drop = (d_attn, d_res)
-        ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
-        ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
-        if pr is not None:
-            ctx.mark_non_differentiable(pr)
-    return y16.view(B, L, d), y32.view(B, L, d), pr
+    ctx.f32_cfg = (B, L, d, H, hd)
+    ctx.f32_from_twin, ctx.f32_x_dtype = x32 is not None, x.dtype
+    return _attn_ln(ctx, (xf, qkv), qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], xf, ar, H, hd, (w_in, b_in, w_out, b_out, gamma, beta, sh),
+                    _drops(p, seed, site, b_off, ar.stride), need_w, (seq.L, seq.L), (B, L, d))
 
 
 def self_attn_ln_bwd(ctx, dy, dy32):
     xf, qkv, o, lse, g = ctx.saved_tensors
     B, L, d, H, hd = ctx.f32_cfg
     ar = ctx.rows
-    w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
-    M = B * L
-    d_attn, d_res = ctx.f32_drop
-    dyt = _total(dy, dy32, (M, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xf, gamma, drop=d_res, rows=ar.rows)
-    dw_out = linear_dw(dg, o)
-    do = linear_dx(dg, sh, w_out)
-    dqkv = _new((M, 3 * d), xf)
+    w_in, sh = ctx.f32_params[0], ctx.f32_params[6]
+    ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, dy, dy32, xf, o, g)
+    dqkv = _new((B * L, 3 * d), xf)
     attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, lse, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], ar.B, H, ar.Lq, ar.Lk, hd,
-             ar.kpm, drop=d_attn, cu=ar.cu)
+             ar.kpm, drop=ctx.f32_drop[0], cu=ar.cu)
     dw_in = linear_dw(dqkv, xf)
     db_in = colsum(dqkv)
     dx = linear_dx(dqkv, sh, w_in, into=ds)            # + the residual path's gradient
@@ -345,47 +354,28 @@ def cross_attn_ln(ctx, xq, xq32, xkv, w_in, b_in, w_out, b_out, gamma, beta, sh,
     B, Lq, d = xq.shape
     Lk = xkv.shape[1]
     hd = _ops._heads(d, H)
-    rec = recording(ctx)
     ar = _ops.attn_rows(seq_q, seq_k, need_w)
-    d_attn, d_res = _drops(p, seed, site, b_off, ar.stride)
     xqf = _twin(xq, xq32).view(B * Lq, d)
     xkvf = _c(f32_of(xkv)).view(B * Lk, d)
     q = linear(xqf, sh, w_in, b_in, rows=(0, d))
     kv = linear(xkvf, sh, w_in, b_in, rows=(d, 3 * d))
-    k, v = kv[:, :d], kv[:, d:]
-    o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=d_attn, cu=ar.cu)
-    g = linear(o, sh, w_out, b_out)
-    y16, y32 = add_ln(g, xqf, gamma, beta, drop=d_res, rows=ar.rows)
-    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=d_attn, cu=ar.cu, out_l=(seq_q.L, seq_k.L)) if need_w else None
-    ctx.fp32 = True
-    if rec:
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xqf, xkvf, q, kv, o, lse, g)
-        ctx.f32_cfg = (B, Lq, Lk, d, H, hd)
-        ctx.rows = ar
-        ctx.f32_drop = (d_attn, d_res)
-        ctx.f32_params = (w_in, b_in, w_out, b_out, gamma, beta, sh)
-        ctx.f32_from_twin, ctx.f32_x_dtype, ctx.f32_kv_dtype = xq32 is not None, xq.dtype, xkv.dtype
-        if pr is not None:
-            ctx.mark_non_differentiable(pr)
-    return y16.view(B, Lq, d), y32.view(B, Lq, d), pr
+    ctx.f32_cfg = (B, Lq, Lk, d, H, hd)
+    ctx.f32_from_twin, ctx.f32_x_dtype, ctx.f32_kv_dtype = xq32 is not None, xq.dtype, xkv.dtype
+    return _attn_ln(ctx, (xqf, xkvf, q, kv), q, kv[:, :d], kv[:, d:], xqf, ar, H, hd, (w_in, b_in, w_out, b_out, gamma, beta, sh),
+                    _drops(p, seed, site, b_off, ar.stride), need_w, (seq_q.L, seq_k.L), (B, Lq, d))
 
 
 def cross_attn_ln_bwd(ctx, dy, dy32):
     xqf, xkvf, q, kv, o, lse, g = ctx.saved_tensors
     B, Lq, Lk, d, H, hd = ctx.f32_cfg
     ar = ctx.rows
-    w_in, b_in, w_out, b_out, gamma, beta, sh = ctx.f32_params
-    d_attn, d_res = ctx.f32_drop
-    dyt = _total(dy, dy32, (B * Lq, d))
-    ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dyt, g, xqf, gamma, drop=d_res, rows=ar.rows)
-    dw_out = linear_dw(dg, o)
-    do = linear_dx(dg, sh, w_out)
+    w_in, sh = ctx.f32_params[0], ctx.f32_params[6]
+    ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, dy, dy32, xqf, o, g)
     dq = _new((B * Lq, d), xqf)
     # packed memory with surplus rows (the fused bucket plan): the varlen backward writes the rows of the B real sequences only,
     # the K | V weight-gradient GEMM and colsum read every row
     dkv = (torch.zeros if ar.kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=F32, device=xqf.device)
-    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, drop=d_attn, cu=ar.cu)
+    attn_bwd(q, kv[:, :d], kv[:, d:], o, do, lse, dq, dkv[:, :d], dkv[:, d:], ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, drop=ctx.f32_drop[0], cu=ar.cu)
     dw_in = _new((3 * d, d), xqf)
     dw_in[:d].copy_(linear_dw(dq, xqf))
     dw_in[d:].copy_(linear_dw(dkv, xkvf))

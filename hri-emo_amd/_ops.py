@@ -166,6 +166,33 @@ def share(t, stream):
     return t
 
 
+class TextBranch:
+    """The text branch of a fusion block beside its audio branch: on `side` (side_stream()) while the audio branch runs on `main`,
+    or, with side None, in line on main -- then all three operations do nothing and the block reads as one sequence of calls.
+    Every fork starts at main (fork() refuses a nested one during capture), so a branch is joined before it is forked again."""
+
+    def __init__(self, side, main):
+        self.side, self.main = side, main
+
+    def fork(self, *handed):
+        """the branch starts behind everything enqueued on main; `handed`: what it will read of main's tensors (or Seqs)"""
+        if self.side is not None:
+            fork(self.side, self.main)
+            for x in handed:
+                share(x, self.side)
+
+    def run(self):
+        """`with branch.run():` -- the calls inside are enqueued on the branch"""
+        return torch.cuda.stream(self.side)          # (a no-op context for None)
+
+    def join(self, *back):
+        """main goes on behind the branch; `back`: what main will read of the branch's tensors"""
+        if self.side is not None:
+            self.main.wait_stream(self.side)
+            for x in back:
+                share(x, self.main)
+
+
 _site_counter = itertools.count(1)
 
 
@@ -1557,6 +1584,50 @@ def _proj_ln(a, sh, w, w16, b, x2, x32v, gamma, beta, p, seed, site, row_off, ro
     return g, y, y32, mean, rstd, (mx[0] if mx else None)
 
 
+def _attn_ln_fwd(ctx, head, q, k, v, x2, x32v, ar, H, hd, sh, w_in16, w_out16, drop, need_w, out_l, shape):
+    """What both attention sub-layers do behind their in-projections: the attention core (its dropout keep-mask as bit words
+    exactly when the backward is the single-pass kernel: attn_mask_bits), out-projection + dropout + residual + LayerNorm
+    (_proj_ln), the head-averaged map if asked for, and the node's bookkeeping.  x2 / x32v: the residual rows [M, d] and their
+    fp32 twin; drop = (p, seed, site, b_off); out_l: the padded lengths of a packed map; ctx.params = (w_in, b_in, w_out, b_out,
+    gamma, beta) as set by the caller.  Saved for the backward: `head` (the in-projection's tensors), then o, lse, g, mean, rstd,
+    w_in16, w_out16, gamma, mask bits.  -> the Function's results (y, y32 | None, probs | None), y shaped `shape`."""
+    p, seed, site, b_off = drop
+    _, _, w_out, b_out, gamma, beta = ctx.params
+    o, lse, *mbits = attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off,
+                              want_bits=attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq), cu=ar.cu)
+    g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
+                                         ar.rows)
+    probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, out_l) if need_w else None
+    ctx.save_for_backward(*head, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits[0] if mbits else None)
+    ctx.rows = ar
+    ctx.mark_non_differentiable(*([probs] if probs is not None else []))
+    return tag_mx(y.view(shape), mx), (y32.view(shape) if y32 is not None else None), probs
+
+
+def _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site, row_off, rows):
+    """How every sub-layer's backward opens: the gradients of its output pair summed, the GradSink of `params` = (..., bias of the
+    last Linear, gamma, beta), LayerNorm + residual + dropout backward into the sink's buffers.
+    -> (sink, dS: the residual path's gradient, dG: the last Linear's output gradient, dgamma, dbeta, dbias)"""
+    dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(x2.shape)
+    sink = GradSink(params)
+    return (sink,) + add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site, row_off,
+                                outs=(sink.buf(params[-2]), sink.buf(params[-1]), sink.buf(params[-3])),
+                                accumulate=sink.fused, x32=x32v, rows=rows)
+
+
+def _attn_ln_bwd(ctx, params, dy, dy32, x2, x32v, tail):
+    """_ln_bwd and the out-projection's backward of an attention sub-layer; params = (..., w_out, b_out, gamma, beta), tail: the
+    saved tensors behind the in-projection's (_attn_ln_fwd).
+    -> (sink, dS, dO: the attention output's gradient, dw_out, db_out, dgamma, dbeta)"""
+    o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = tail
+    p, seed, site, b_off = ctx.cfg[-4:]
+    sink, ds, dg, dgamma, dbeta, db_out = _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site + 1,
+                                                  b_off * ctx.rows.stride, ctx.rows.rows)
+    dw_out = sink.buf(params[-4])
+    linear_dw(dg, o, dw_out, sink.fused)
+    return sink, ds, linear_dx(dg, w_out16), dw_out, db_out, dgamma, dbeta
+
+
 class SelfAttnLN(_GradModeAware, torch.autograd.Function):
     """y = LN(x + drop(out_proj(MHA_core(in_proj(x))))) ; returns (y, probs|None)"""
 
@@ -1577,40 +1648,24 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
         x32 = _c32(x32)
         x32v = x32.view(M, d) if x32 is not None else None
         w_in16, w_out16 = sh.get(w_in), sh.get(w_out)
-        qkv = proj_fwd(Operand(x2, mx_of(x)), sh, w_in, w_in16, b_in)
-        q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-        o, lse, mbits = attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, want_bits=True, cu=ar.cu) if attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq) else \
-            attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
-        g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
-                                             ar.rows)
-        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, (seq.L, seq.L)) if need_w else None
-        ctx.save_for_backward(x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
         ctx.cfg = (B, L, d, H, hd, p, seed, site, b_off)
-        ctx.rows = ar
         ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
-        ctx.mark_non_differentiable(*( [probs] if probs is not None else []))
-        return tag_mx(y.view(B, L, d), mx), (y32.view(B, L, d) if y32 is not None else None), probs
+        qkv = proj_fwd(Operand(x2, mx_of(x)), sh, w_in, w_in16, b_in)
+        return _attn_ln_fwd(ctx, (x2, x32v, qkv), qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], x2, x32v, ar, H, hd, sh, w_in16,
+                            w_out16, (p, seed, site, b_off), need_w, (seq.L, seq.L), (B, L, d))
 
     @staticmethod
     def backward(ctx, dy, dy32, _dprobs):
         if getattr(ctx, "fp32", False):
             return _fp32().self_attn_ln_bwd(ctx, dy, dy32)
-        x2, x32v, qkv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
+        x2, x32v, qkv, o, lse, _, _, _, w_in16, _, _, mbits = saved = ctx.saved_tensors
         B, L, d, H, hd, p, seed, site, b_off = ctx.cfg
         ar = ctx.rows
         M = B * L
-        dev = x2.device
-        dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(M, d)
-        p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
-        sink = GradSink(ctx.params)
+        p_w_in, p_b_in = ctx.params[:2]
+        sink, ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, ctx.params, dy, dy32, x2, x32v, saved[-9:])
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
-                                                   outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=ar.rows)
-        dw_out = sink.buf(p_w_out)
-        linear_dw(dg, o, dw_out, acc)
-        do = linear_dx(dg, w_out16)
-        dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
+        dqkv = torch.empty((M, 3 * d), dtype=BF16, device=x2.device)
         db_in = sink.buf(p_b_in)
         folded = attn_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], o, do, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:],
                           lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits,
@@ -1638,7 +1693,11 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
         weight-gradient and dX then belong to that Function, this one returns dK | dV for it.
         q_pre: likewise the Q projection of xq (SharedProjFn: one GEMM per shared input); this Function then only returns dQ for it
         and hands the residual-path gradient of xq to join_q.  slots = (SharedGrad of dQ, SharedGrad of dK|dV): where the attention
-        backward writes those gradients, so that they arrive at the projection's backward as column slices of ONE buffer."""
+        backward writes those gradients, so that they arrive at the projection's backward as column slices of ONE buffer.
+        This node owns its Q projection unless q_pre is given and its K | V projection unless kv_pre is; the combinations in use
+        are: neither given, kv_pre, and kv_pre + q_pre + slots (both projections belong to SharedProjFn nodes)."""
+        if (q_pre is None) != (slots is None) or (q_pre is not None and kv_pre is None):
+            raise ValueError("CrossAttnLN: q_pre and slots come together, and only with kv_pre (both projections made by SharedProjFn)")
         seq_q.holds(xq)
         seq_k.holds(xkv)
         if precision() == "fp32":
@@ -1654,118 +1713,69 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
         xq2 = _contig_bf16(xq).view(B * Lq, d)
         xq32 = _c32(xq32)
         x32v = xq32.view(B * Lq, d) if xq32 is not None else None
+        ctx.cfg = (B, Lq, Lk, d, H, hd, p, seed, site, b_off)
+        ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
+        ctx.own_q, ctx.own_kv, ctx.slots, ctx.join_q = q_pre is None, kv_pre is None, slots, join_q
         w_out16 = sh.get(w_out)
-        w_in16 = sh.get(w_in) if (q_pre is None or kv_pre is None) else None
+        w_in16 = sh.get(w_in) if (ctx.own_q or ctx.own_kv) else None
         q = q_pre if q_pre is not None else proj_fwd(Operand(xq2, mx_of(xq)), sh, w_in, w_in16, b_in, rows=(0, d))
         if kv_pre is not None:
             xkv2, kv = None, kv_pre
         else:
             xkv2 = _contig_bf16(xkv).view(B * Lk, d)
             kv = proj_fwd(Operand(xkv2, mx_of(xkv)), sh, w_in, w_in16, b_in, rows=(d, 3 * d))
-        k, v = kv[:, :d], kv[:, d:]
-        o, lse, mbits = attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, want_bits=True, cu=ar.cu) if attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq) else \
-            attn_fwd(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed, site, b_off, cu=ar.cu) + (None,)
-        g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, xq2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
-                                             ar.rows)
-        probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, (seq_q.L, seq_k.L)) if need_w else None
-        ctx.save_for_backward(xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits)
-        ctx.cfg = (B, Lq, Lk, d, H, hd, p, seed, site, b_off)
-        ctx.rows = ar
-        ctx.kv_pre = kv_pre is not None
-        ctx.q_pre = q_pre is not None
-        ctx.slots = slots
-        ctx.join_q = join_q
-        ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
-        ctx.mark_non_differentiable(*([probs] if probs is not None else []))
-        return tag_mx(y.view(B, Lq, d), mx), (y32.view(B, Lq, d) if y32 is not None else None), probs
-
-    @staticmethod
-    def _backward_shared(ctx, dy, dy32):
-        """q_pre and kv_pre: both projections belong to SharedProjFn nodes.  Left here: LayerNorm / out-projection backward, the
-        attention core's backward (dQ, dK|dV written into the projections' shared gradient buffers, in-projection bias gradients
-        from its column sums), and the residual-path gradient of xq, deposited for the projection's dX GEMM."""
-        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
-        B, Lq, Lk, d, H, hd, p, seed, site, b_off = ctx.cfg
-        ar = ctx.rows
-        dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(B * Lq, d)
-        p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
-        sink = GradSink((p_b_in, p_w_out, p_b_out, p_gamma, p_beta))
-        acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
-                                                   outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=ar.rows)
-        dw_out = sink.buf(p_w_out)
-        linear_dw(dg, o, dw_out, acc)
-        do = linear_dx(dg, w_out16)
-        sq, skv = ctx.slots
-        dq, dkv = sq.buf(), skv.buf()
-        db_in = sink.buf(p_b_in)
-        folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed,
-                          site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=ar.cu)
-        if not folded:
-            colsum(dq, db_in[:d], acc)
-            colsum(dkv, db_in[d:], acc)
-        dxq = ds
-        if ctx.join_q is not None:
-            ctx.join_q.arrive()
-            ctx.join_q.deposit(ds)            # the projection's dX GEMM adds it in its epilogue
-            dxq = None
-        sink.done()
-        r = sink.ret
-        return (dxq.view(B, Lq, d) if dxq is not None else None, None, None, None, r(db_in), r(dw_out), r(db_out), r(dgamma),
-                r(dbeta)) + (None,) * 9 + (dkv, None, dq, None)
+        return _attn_ln_fwd(ctx, (xq2, x32v, xkv2, q, kv), q, kv[:, :d], kv[:, d:], xq2, x32v, ar, H, hd, sh, w_in16,
+                            w_out16, (p, seed, site, b_off), need_w, (seq_q.L, seq_k.L), (B, Lq, d))
 
     @staticmethod
     def backward(ctx, dy, dy32, _dprobs):
+        """One body for the three owners of the projections.  Always here: LayerNorm / out-projection backward, the attention core's
+        backward with the in-projection's bias gradients from its column sums, and the residual-path gradient of xq.  A projection
+        this node owns gets its weight gradient and dX here; one it does not own gets dQ / dK | dV returned for its node (written
+        straight into the SharedProjFn nodes' gradient buffers: slots), which also writes and reports its rows of dW_in."""
         if getattr(ctx, "fp32", False):
             return _fp32().cross_attn_ln_bwd(ctx, dy, dy32)
-        if ctx.q_pre and ctx.kv_pre and ctx.slots is not None:
-            return CrossAttnLN._backward_shared(ctx, dy, dy32)
-        xq2, x32v, xkv2, q, kv, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = ctx.saved_tensors
+        xq2, x32v, xkv2, q, kv, o, lse, _, _, _, w_in16, _, _, mbits = saved = ctx.saved_tensors
         B, Lq, Lk, d, H, hd, p, seed, site, b_off = ctx.cfg
         ar = ctx.rows
-        dev = xq2.device
-        dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(B * Lq, d)
-        p_w_in, p_b_in, p_w_out, p_b_out, p_gamma, p_beta = ctx.params
-        sink = GradSink(ctx.params)
+        own_q, own_kv = ctx.own_q, ctx.own_kv
+        p_w_in, p_b_in = ctx.params[:2]
+        sink, ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, ctx.params if own_q else ctx.params[1:], dy, dy32, xq2, x32v, saved[-9:])
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db_out = add_ln_bwd(dy2, g, xq2, gamma, mean, rstd, p, seed, site + 1, b_off * ar.stride,
-                                                   outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b_out)),
-                                                   accumulate=acc, x32=x32v, rows=ar.rows)
-        dw_out = sink.buf(p_w_out)
-        linear_dw(dg, o, dw_out, acc)
-        do = linear_dx(dg, w_out16)
-        dq = torch.empty((B * Lq, d), dtype=BF16, device=dev)
-        dkv = (torch.zeros if ar.kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=BF16, device=dev)
+        if own_q:
+            dq = torch.empty((B * Lq, d), dtype=BF16, device=xq2.device)
+            dkv = (torch.zeros if ar.kv_surplus else torch.empty)((B * Lk, 2 * d), dtype=BF16, device=xq2.device)
+        else:
+            dq, dkv = ctx.slots[0].buf(), ctx.slots[1].buf()
         db_in = sink.buf(p_b_in)
         folded = attn_bwd(q, kv[:, :d], kv[:, d:], o, do, dq, dkv[:, :d], dkv[:, d:], lse, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, p, seed,
                           site, b_off, bias_grad=(db_in[:d], db_in[d:], acc), mask_bits=mbits, cu=ar.cu)
-        dw_in = sink.buf(p_w_in)
-        linear_dw(dq, xq2, dw_in[:d], acc)
+        dw_in = None
+        if own_q:
+            dw_in = sink.buf(p_w_in)
+            linear_dw(dq, xq2, dw_in[:d], acc)
         if not folded:
             colsum(dq, db_in[:d], acc)
             colsum(dkv, db_in[d:], acc)
-        dxq = linear_dx(dq, w_in16[:d], epi=3, aux=ds)
+        dxq = linear_dx(dq, w_in16[:d], epi=3, aux=ds) if own_q else ds
         if ctx.join_q is not None:            # xq has another consumer (GradJoin): deposit for it, or finish the sum if it came first
-            last, dep = ctx.join_q.arrive()
+            last, dep = ctx.join_q.arrive()   # (the Q projection's own node folds the deposit into its dX GEMM's epilogue)
             if dep is not None:
                 dxq = dxq + dep.view(B * Lq, d)          # this GEMM's aux slot carries the residual gradient: explicit add
             if not last:
                 ctx.join_q.deposit(dxq)
                 dxq = None
         dxq = dxq.view(B, Lq, d) if dxq is not None else None
+        dxkv = None
+        if own_kv:
+            linear_dw(dkv, xkv2, dw_in[d:], acc)
+            dxkv = linear_dx(dkv, w_in16[d:]).view(B, Lk, d)
+        elif own_q and not acc:
+            dw_in[d:].zero_()                 # KVProjFn adds its rows of dW_in
+        sink.done(skip=() if own_kv else (p_w_in,))          # (and reports the parameter)
         r = sink.ret
-        if ctx.kv_pre:
-            # the K | V projection belongs to KVProjFn: it gets dK | dV, adds its rows of dW_in and reports the parameter
-            if not acc:
-                dw_in[d:].zero_()
-            sink.done(skip=(p_w_in,))
-            return (dxq, None, None, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 9 + (dkv, None, None, None)
-        linear_dw(dkv, xkv2, dw_in[d:], acc)
-        dxkv = linear_dx(dkv, w_in16[d:])
-        sink.done()
-        return (dxq, None, dxkv.view(B, Lk, d), r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma),
-                r(dbeta)) + (None,) * 13
+        return (dxq, None, dxkv, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 9 + \
+            (None if own_kv else dkv, None, None if own_q else dq, None)
 
 
 class GradJoin:
@@ -2044,13 +2054,10 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
         B, L, d, p, p_mid, seed, site, b_off = ctx.cfg
         M, F = h.shape
         dev = x2.device
-        dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(M, d)
-        p_w1, p_b1, p_w2, p_b2, p_gamma, p_beta = ctx.params
-        sink = GradSink(ctx.params)
+        p_w1, p_b1, p_w2 = ctx.params[:3]
+        sink, ds, dg, dgamma, dbeta, db2 = _ln_bwd(ctx.params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site + 1,
+                                                   b_off * ctx.seq.L, ctx.seq.idx)
         acc = sink.fused
-        ds, dg, dgamma, dbeta, db2 = add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site + 1, b_off * ctx.seq.L,
-                                                outs=(sink.buf(p_gamma), sink.buf(p_beta), sink.buf(p_b2)),
-                                                accumulate=acc, x32=x32v, rows=ctx.seq.idx)
         dw2 = sink.buf(p_w2)
         linear_dw(dg, hd_, dw2, acc)
         db1 = sink.buf(p_b1)

@@ -85,108 +85,52 @@ class CrossModalBlock(nn.Module):
         # A join exists only where BOTH consumers are certain to get a backward node that must produce the shared activation's
         # gradient, i.e. where that activation requires grad: with a frozen cross-attention and inputs that need no gradient the
         # partner's node never runs and a deposit would be stranded (autograd then sums whatever gradients there are).
-        ja = jt = None
         use_kv = not fp32
         join_for = lambda x: _ops.grad_join(2) if (use_kv and x.requires_grad) else None          # noqa: E731
         d = a.shape[2]
         shared = use_kv and _ops.shared_proj()
-        if shared and side is None:
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)   # :74-81
-            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)   # :85-92
-            ja, jt = join_for(a_s), join_for(t_s)
+        # The audio and text branches only meet at the two cross-attentions (each reads the OTHER branch's self-attention output),
+        # so the text branch runs on a second stream (_ops.TextBranch; in line on main without one): its small grids (B*T_t rows)
+        # fill the CUs the audio branch leaves idle.  Tensors that cross streams are recorded on the consumer stream (allocator
+        # safety); autograd replays the same streams in backward.  The audio branch -- three times the rows, the critical path --
+        # is ENQUEUED first at every fork (the reference's order of sub-layers, :74-119): the order of capture decides which
+        # branch the graph runtime starts first.
+        tb = _ops.TextBranch(side, main)
+        tb.fork(t, t32, st, sa)
+        # stage 1, nothing of the other branch needed yet: self-attention and, shared, ONE N = 3d GEMM that projects its output to
+        # [Q of the branch's own cross-attention | K, V of the other one]
+        q_a2t = q_t2a = kv_t2a = kv_a2t = slots_a = slots_t = None
+        a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)         # :74-81
+        ja = join_for(a_s)
+        if shared:
             q_a2t, kv_t2a, sga = self._shared_proj(a_s, self.attn_a2t, self.attn_t2a, ja)
-            q_t2a, kv_a2t, sgt = self._shared_proj(t_s, self.attn_t2a, self.attn_a2t, jt)
-            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
-                                        kv_a2t, ja, q_a2t, (sga.slot(0, d), sgt.slot(d, 3 * d)))                   # :98-105
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
-            x, x32, w_t2a = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
-                                        kv_t2a, jt, q_t2a, (sgt.slot(0, d), sga.slot(d, 3 * d)))                   # :111-118
-            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)
-        elif shared:
-            # two streams, one GEMM per shared input: each branch projects its own self-attention output to [Q | K, V] on its own
-            # stream (no dependence on the other branch yet), THEN the branches exchange the K | V halves and run the cores
-            # (the audio branch -- three times the rows, the critical path -- is ENQUEUED first at every fork: the order of capture
-            # decides which branch the graph runtime starts first)
-            _ops.fork(side, main)
-            for x_ in (t, t32, st, sa):
-                _ops.share(x_, side)
-
-            def text_self():
-                with torch.cuda.stream(side):
-                    t_s_, t_s32_, w_t_ = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)
-                    jt_ = join_for(t_s_)
-                    return (t_s_, t_s32_, w_t_, jt_) + self._shared_proj(t_s_, self.attn_t2a, self.attn_a2t, jt_)
-
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)
-            ja = join_for(a_s)
-            q_a2t, kv_t2a, sga = self._shared_proj(a_s, self.attn_a2t, self.attn_t2a, ja)
-            t_s, t_s32, w_t, jt, q_t2a, kv_a2t, sgt = text_self()
-            main.wait_stream(side)
-            _ops.fork(side, main)
-            _ops.share(kv_a2t, main)
-            _ops.share(kv_t2a, side)
-
-            def text_cross():
-                with torch.cuda.stream(side):
-                    x_, x32_, w_ = self._cross(t_s, t_s32, a_s, self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
-                                               kv_t2a, jt, q_t2a, (sgt.slot(0, d), sga.slot(d, 3 * d)))
-                    return self._ffn(x_, x32_, self.ffn_t, self.norm_t2, p, seed, s[5], st) + (w_,)
-
-            x, x32, w_a2t = self._cross(a_s, a_s32, t_s, self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
-                                        kv_a2t, ja, q_a2t, (sga.slot(0, d), sgt.slot(d, 3 * d)))
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
-            t_cm, t_cm32, w_t2a = text_cross()
-            main.wait_stream(side)
-            for x_ in (t_cm, t_cm32, w_t, w_t2a):
-                _ops.share(x_, main)
-        elif side is None:
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)   # :74-81
-            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)   # :85-92
-            ja, jt = join_for(a_s), join_for(t_s)
-            kv_t2a = self._kv(a_s, self.attn_t2a, ja) if use_kv else None
-            kv_a2t = self._kv(t_s, self.attn_a2t, jt) if use_kv else None
-            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
-                                        kv_a2t, ja)                                                                # :98-105
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)                              # :106
-            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
-                                        kv_t2a, jt)                                                                # :111-118
-            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)                              # :119
+        with tb.run():
+            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)     # :85-92
+            jt = join_for(t_s)
+            if shared:
+                q_t2a, kv_a2t, sgt = self._shared_proj(t_s, self.attn_t2a, self.attn_a2t, jt)
+        # the exchange: the K | V halves cross streams, or the self-attention outputs do (in fp32 mode their twins too) and each
+        # stream projects the K | V of the cross-attention it runs
+        if shared:
+            tb.join(kv_a2t)
+            tb.fork(kv_t2a)
+            slots_a, slots_t = (sga.slot(0, d), sgt.slot(d, 3 * d)), (sgt.slot(0, d), sga.slot(d, 3 * d))
         else:
-            # The audio and text branches only meet at the two cross-attentions (each reads the OTHER branch's
-            # self-attention output), so the text branch runs on a second stream: its small grids (B*T_t rows)
-            # fill the CUs the audio branch leaves idle.  Fork/join with stream waits; tensors that cross
-            # streams are recorded on the consumer stream (allocator safety); autograd replays the same streams
-            # in backward.
-            _ops.fork(side, main)
-            for x_ in (t, t32, st, sa):
-                _ops.share(x_, side)
-            # (audio first at every fork, the reference's order of sub-layers: cross_modal_block_tacfn.py:74-119)
-            a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)
-            with torch.cuda.stream(side):
-                t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)
-            main.wait_stream(side)
-            _ops.fork(side, main)
-            _ops.share(t_s, main)
-            _ops.share(a_s, side)
-            if fp32:
-                _ops.share(t_s32, main)
-                _ops.share(a_s32, side)
-            kv_t2a = kv_a2t = None
-            ja, jt = join_for(a_s), join_for(t_s)
+            tb.join(t_s, t_s32 if fp32 else None)
+            tb.fork(a_s, a_s32 if fp32 else None)
             if use_kv:
-                with torch.cuda.stream(side):
+                with tb.run():
                     kv_t2a = self._kv(a_s, self.attn_t2a, ja)
                 kv_a2t = self._kv(t_s, self.attn_a2t, jt)
-            x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
-                                        kv_a2t, ja)
-            a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)
-            with torch.cuda.stream(side):
-                x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
-                                            kv_t2a, jt)
-                t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)
-            main.wait_stream(side)
-            for x_ in (t_cm, t_cm32, w_t, w_t2a):
-                _ops.share(x_, main)
+        # stage 2: cross-attention + FFN
+        x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
+                                    kv_a2t, ja, q_a2t, slots_a)                                                    # :98-105
+        a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)                              # :106
+        with tb.run():
+            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
+                                        kv_t2a, jt, q_t2a, slots_t)                                                # :111-118
+            t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)                          # :119
+        tb.join(t_cm, t_cm32, w_t, w_t2a)
         maps = {"audio_self": w_a, "text_self": w_t, "audio_queries_text": w_a2t, "text_queries_audio": w_t2a} if need else None
         return a_cm, a_cm32, t_cm, t_cm32, maps
 

@@ -872,6 +872,117 @@ def test_shared_input_projection_equals_separate_projections(H, monkeypatch, two
             assert float((p.grad - q.grad).norm()) <= 1e-2 * max(float(q.grad.norm()), 1e-20), n
 
 
+def _spied_block_step(H, monkeypatch, blk, batch, two_streams):
+    """one training step (forward + backward on both outputs, dropout seeded) of a stand-alone block with _lib.call spied, after a
+    warm-up step of the same arm (weight shadows, workspaces).  -> (calls, outputs, parameter gradients); a call is recorded as
+    (entry point, every non-pointer argument but the stream and the null-ness of every pointer, 'main' | 'side' | 'other': the
+    stream argument, 'main' | 'side' | None: the stream its sub-layer belongs on).  The last is known for every forward launch (the
+    block's sub-layer methods are wrapped) and for the backward launches that carry a dropout site."""
+    from hri_emo_amd import _lib, _ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    monkeypatch.setattr(_ops, "TWO_STREAMS", True)
+    handles = {torch.cuda.current_stream(dev).cuda_stream: "main", _ops.side_stream(dev).cuda_stream: "side"}
+    monkeypatch.setattr(_ops, "TWO_STREAMS", two_streams)
+    monkeypatch.setattr(_ops.CTX, "join_scope", 1)       # both outputs are trained: the gradient joins of the fusion model's forward
+    text = {blk._site[i] for i in (1, 4, 5)}
+    audio = {blk._site[i] for i in (0, 2, 3)}
+    by_site = lambda site: "side" if (site & ~3) in text else ("main" if (site & ~3) in audio else None)      # noqa: E731
+    calls, label, real = [], [None], _lib.call
+
+    def spy(name, *args):
+        codes = _lib._SIGS[name][0]
+        assert codes[-1] == "p" and len(codes) == len(args), name
+        fixed = tuple((a is not None and a != 0) if c == "p" else a for c, a in zip(codes[:-1], args[:-1]))
+        want = label[0]
+        if want is None and "I" in codes:
+            want = by_site(args[codes.index("I")])
+        calls.append((name, fixed, handles.get(args[-1] or 0, "other"), want))
+        return real(name, *args)
+
+    def labelled(fn, want_of):
+        def run(*args, **kw):
+            label[0] = want_of(*args)
+            try:
+                return fn(*args, **kw)
+            finally:
+                label[0] = None
+        return run
+
+    def step():
+        blk.zero_grad(set_to_none=True)
+        torch.manual_seed(77)                            # the block draws its dropout seed from torch's CPU generator
+        oa, ot = blk(*batch)
+        (oa.float().pow(2).mean() + ot.float().pow(2).mean()).backward()
+        torch.cuda.synchronize()
+        return (oa.detach().clone(), ot.detach().clone()), {n: q.grad.detach().float().clone() for n, q in blk.named_parameters()}
+
+    step()
+    with monkeypatch.context() as mp:
+        mp.setattr(_lib, "call", spy)
+        mp.setattr(blk, "_self", labelled(blk._self, lambda *a: by_site(a[7])))
+        mp.setattr(blk, "_cross", labelled(blk._cross, lambda *a: by_site(a[9])))
+        mp.setattr(blk, "_ffn", labelled(blk._ffn, lambda *a: by_site(a[6])))
+        mp.setattr(blk, "_kv", labelled(blk._kv, lambda x, mha, join: "side" if mha is blk.attn_t2a else "main"))
+        mp.setattr(blk, "_shared_proj", labelled(blk._shared_proj, lambda x, mha_q, mha_kv, join: "side" if mha_q is blk.attn_t2a else "main"))
+        outs, grads = step()
+    return calls, outs, grads
+
+
+def _assert_one_dataflow(one, two):
+    """the launches of the one-stream arm and of the two-stream arm of one block: the same sequence, placed as the block says"""
+    assert [c[:2] for c in one] == [c[:2] for c in two], "the one-stream arm enqueues another sequence than the two-stream arm"
+    assert not [c for c in one if c[2] == "side"], "the one-stream arm names the side stream"
+    placed = [c for c in two if c[3] is not None]
+    assert [c for c in placed if c[2] != c[3]] == [], "a sub-layer's launch is not on its branch's stream"
+    assert {c[3] for c in placed} == {"main", "side"} and "other" not in {c[2] for c in two}
+    for name in ("hriemo_attn_bwd", "hriemo_add_ln_bwd_rows", "hriemo_attn_bwd_f32", "hriemo_add_ln_bwd_f32"):
+        if any(c[0] == name for c in two):           # the backward was placed too (its launches that carry a site)
+            assert {c[3] for c in placed if c[0] == name} == {"main", "side"}, name
+
+
+@pytest.mark.parametrize("shared", [True, False])
+def test_block_is_one_dataflow_on_one_stream_or_two(H, monkeypatch, shared):
+    """CrossModalBlock._fwd_pair is ONE sequence of calls; the text branch's are enqueued on the side stream (_ops.TextBranch) or,
+    with HRIEMO_TWO_STREAMS=0, in line.  Both arms of both projection layouts (SHARED_PROJ): the same launches in the same order
+    with the same arguments, the text sub-layers (and, not shared, the t2a K | V projection) on the side stream and the audio
+    ones on main, no side stream in the one-stream arm, bit-equal outputs, and the same parameter gradients (the launches are the
+    same and every destination has one writer, so they are expected to be bit-equal; held to the neighbouring tests' bound)."""
+    from hri_emo_amd import _ops
+    monkeypatch.setattr(_ops, "SHARED_PROJ", shared)
+    torch.manual_seed(13)
+    blk = H.CrossModalBlock(256, 8, 0.1).cuda().train()
+    batch = tuple(cu(x) for x in _rand_batch(4, 90, 36, 256, 37))
+    two, outs2, grads2 = _spied_block_step(H, monkeypatch, blk, batch, True)
+    one, outs1, grads1 = _spied_block_step(H, monkeypatch, blk, batch, False)
+    assert any(c[0] == "hriemo_gemm_bf16" and c[3] == "side" for c in two)          # the K | V / shared projection is labelled
+    assert ("hriemo_gemm_bf16_split" in {c[0] for c in two}) == shared               # (SharedProjFn's weight gradients)
+    _assert_one_dataflow(one, two)
+    for a_, b_ in zip(outs1, outs2):
+        assert torch.equal(a_, b_)
+    worst = max(float((grads1[n] - grads2[n]).norm() / grads2[n].norm().clamp_min(1e-20)) for n in grads2)
+    print(f"shared={shared}: {len(two)} launches, {sum(c[2] == 'side' for c in two)} on the side stream; worst relative gradient "
+          f"difference between the stream arms {worst:.3e}")
+    assert worst <= 1e-2, worst
+
+
+def test_block_is_one_dataflow_in_fp32_mode(H, monkeypatch):
+    """the same order and placement in the fp32 mode (no K | V nodes, no shared projection: the self-attention outputs and their
+    fp32 twins cross streams)"""
+    from hri_emo_amd import _ops
+    torch.manual_seed(13)
+    blk = H.CrossModalBlock(256, 8, 0.1).cuda().train()
+    batch = tuple(cu(x) for x in _rand_batch(4, 90, 36, 256, 37))
+    prev = _ops.precision()
+    _ops.set_precision("fp32")
+    try:
+        two = _spied_block_step(H, monkeypatch, blk, batch, True)[0]
+        one = _spied_block_step(H, monkeypatch, blk, batch, False)[0]
+    finally:
+        _ops.set_precision(prev)
+    assert any(c[0] == "hriemo_attn_fwd_f32" for c in two)
+    _assert_one_dataflow(one, two)
+
+
 def test_partial_fine_tuning_with_a_frozen_cross_attention(H, monkeypatch):
     """a join is only created where both consumers of a shared activation get a backward node.  Layer 0 frozen except
     its audio->text cross-attention, inputs without gradient: the t2a K|V projection node never exists, and the a2t core must

@@ -155,3 +155,35 @@ def test_a_plan_with_the_masks_riding_along():
     assert g.kpm.dtype == torch.uint8 and torch.equal(g.kpm.bool(), m_a) and sa.kpm is None
     p = _ops.Seq.padded(B, LT).with_kpm(m_t)
     assert not p.packed and torch.equal(p.kpm.bool(), m_t)
+
+
+def test_cross_attention_refuses_half_given_shared_projections(monkeypatch):
+    """CrossAttnLN owns its Q projection unless q_pre is given and its K | V projection unless kv_pre is; q_pre comes from a
+    SharedProjFn node together with the gradient slots and the K | V half, so q_pre without slots, slots without q_pre and q_pre
+    without kv_pre are refused in forward, before anything touches the device (CPU tensors here, and no library call)."""
+    import pytest
+    from hri_emo_amd import _lib, _ops
+
+    def no_call(*a, **k):
+        raise AssertionError("the library was called")
+
+    monkeypatch.setattr(_lib, "call", no_call)
+    monkeypatch.setattr(_lib, "lib", no_call)
+    d, nh = 32, 2
+    xq, xkv = torch.randn(2, 3, d), torch.randn(2, 5, d)
+    w_in, b_in, w_out, b_out = torch.randn(3 * d, d), torch.zeros(3 * d), torch.randn(d, d), torch.zeros(d)
+    gamma, beta = torch.ones(d), torch.zeros(d)
+    sq, sk = _ops.Seq.padded(2, 3), _ops.Seq.padded(2, 5)
+    q_pre, kv_pre = torch.randn(6, d), torch.randn(10, 2 * d)
+    slots = (object(), object())          # (never looked into: the refusal comes first)
+
+    def apply(**kw):
+        opt = dict(kv_pre=None, join_q=None, q_pre=None, slots=None)
+        opt.update(kw)
+        return _ops.CrossAttnLN.apply(xq, None, xkv, w_in, b_in, w_out, b_out, gamma, beta, _ops.Shadows(), nh, sq, sk, 0.0, 0, 4, 0, False,
+                                      opt["kv_pre"], opt["join_q"], opt["q_pre"], opt["slots"])
+
+    with torch.no_grad():
+        for kw in (dict(q_pre=q_pre, kv_pre=kv_pre), dict(slots=slots, kv_pre=kv_pre), dict(q_pre=q_pre, slots=slots)):
+            with pytest.raises(ValueError, match="q_pre and slots"):
+                apply(**kw)
