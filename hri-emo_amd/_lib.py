@@ -29,6 +29,7 @@ _SIGS = {
     "hriemo_attn_fwd_q": ("plplplplppiiiiifQpIipplplp", "i"),
     "hriemo_attn_bwd": ("plplplplplplplplpppiiiiifQpIipppp", "i"),
     "hriemo_attn_fwd_varlen": ("plplplplpppiiiiifQpIipp", "i"),
+    "hriemo_attn_fwd_q_varlen": ("plplplplpppiiiiifQpIipplpllp", "i"),
     "hriemo_attn_bwd_varlen": ("plplplplplplplplppppiiiiifQpIipppp", "i"),
     "hriemo_attn_mask_bytes": ("iiii", "l"),
     "hriemo_attn_bwd_single_pass": ("iiii", "i"),
@@ -120,6 +121,7 @@ _SIGS = {
     "hriemo_ln_pool_fwd_packed": ("pppiippppppipiiifp", "i"),
     "hriemo_ln_pool_fwd_packed_pair": ("pppiippppppi" * 2 + "piiifp", "i"),
     "hriemo_fuse_fwd_packed": ("pppppiiiip", "i"),
+    "hriemo_fuse_fwd_packed_q": ("pppppiiiipplp", "i"),
     "hriemo_fuse_bwd_dw_packed": ("pppppiiiip", "i"),
     "hriemo_ln_pool_bwd_packed": ("ppipippppiipppppp" + "iiiipp", "i"),
     "hriemo_ln_pool_bwd_packed_pair": ("ppip" + "ppppiippppppip" * 2 + "iiip", "i"),

@@ -843,6 +843,12 @@ def attn_mask_bits(B, H, Lk, hd, Lq=None):
     return bool(_lib.lib().hriemo_attn_bwd_single_pass(B, H, Lk, hd))
 
 
+# fp8 GEMM mode on packed rows: the attention forward leaves the MX-fp8 copy of O itself (hriemo_attn_fwd_q_varlen), as the padded
+# launch does.  False: the previous launches (hriemo_attn_fwd_varlen, then hriemo_quant_mx8 in front of the out-projection) -- the
+# A/B handle; the results are bit-identical.
+ATTN_Q_VARLEN = True
+
+
 def attn_fwd(q, k, v, B, H, Lq, Lk, hd, kpm, p, seed, site, b_off, want_bits=False, cu=None):
     """-> (o, lse) or, with want_bits, (o, lse, mask_bits|None): the dropout keep-mask as bit words for the backward.
     cu = (cu_seqlens_q, cu_seqlens_k) int32 device tensors: q / k / v hold packed rows, Lq / Lk are the longest sequences, kpm is None"""
@@ -853,14 +859,20 @@ def attn_fwd(q, k, v, B, H, Lq, Lk, hd, kpm, p, seed, site, b_off, want_bits=Fal
     mb = None
     if want_bits and p > 0:
         mb = torch.empty(_lib.lib().hriemo_attn_mask_bytes(B, H, Lq, Lk) // 8, dtype=torch.int64, device=q.device)
-    if cu is None and hd % 32 == 0 and want_mx_copy(q.shape[0], H * hd):
+    if (cu is None or ATTN_Q_VARLEN) and hd % 32 == 0 and want_mx_copy(q.shape[0], H * hd):
         # fp8 GEMM mode: the out-projection's operand leaves the attention kernel already quantised (tagged onto o)
-        ld = _lib.lib().hriemo_mx8_scale_ld(q.shape[0])
-        oq = torch.empty((q.shape[0], H * hd), dtype=torch.uint8, device=q.device)
+        n = q.shape[0]
+        ld = _lib.lib().hriemo_mx8_scale_ld(n)
+        oq = torch.empty((n, H * hd), dtype=torch.uint8, device=q.device)
         so = torch.empty((H * hd // 32, ld), dtype=torch.uint8, device=q.device)
-        _lib.call("hriemo_attn_fwd_q", _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
-                  _p(kpm), _p(lse), B, H, Lq, Lk, hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _p(mb), _p(oq), H * hd,
-                  _p(so), ld, _stream())
+        if cu is not None:        # packed rows: the scale byte of packed row r is column r
+            _lib.call("hriemo_attn_fwd_q_varlen", _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
+                      _p(cu[0]), _p(cu[1]), _p(lse), B, H, Lq, Lk, hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _p(mb),
+                      _p(oq), H * hd, _p(so), ld, n, _stream())
+        else:
+            _lib.call("hriemo_attn_fwd_q", _p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0),
+                      _p(kpm), _p(lse), B, H, Lq, Lk, hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _p(mb), _p(oq), H * hd,
+                      _p(so), ld, _stream())
         tag_mx(o, (oq, so))
         return (o, lse, mb) if want_bits else (o, lse)
     if cu is not None:
@@ -1010,8 +1022,16 @@ def ln_pool_fwd_pair(a, t, sf, d):
 
 
 def fuse_fwd(w, An, Tn, H, sf, d):
-    """H = w * An + (1 - w) * Tn on the rows of the fused layout (the surplus rows of a packed one: zeros)"""
-    if sf.packed:
+    """H = w * An + (1 - w) * Tn on the rows of the fused layout (the surplus rows of a packed one: zeros).  fp8 GEMM mode on the
+    packed layout: the same launch leaves the MX-fp8 copy of H (the decoder's memory operand), tagged onto H (tag_mx)"""
+    if sf.packed and want_mx_copy(sf.N, d):
+        ld = _lib.lib().hriemo_mx8_scale_ld(sf.N)
+        hq = torch.empty((sf.N, d), dtype=torch.uint8, device=H.device)
+        hs = torch.empty((d // 32, ld), dtype=torch.uint8, device=H.device)
+        _lib.call("hriemo_fuse_fwd_packed_q", _p(w), _p(An), _p(Tn), _p(H), _p(sf.cu), sf.N, sf.Breal, sf.L, d, _p(hq), _p(hs), ld,
+                  _stream())
+        tag_mx(H, (hq, hs))
+    elif sf.packed:
         _lib.call("hriemo_fuse_fwd_packed", _p(w), _p(An), _p(Tn), _p(H), _p(sf.cu), sf.N, sf.Breal, sf.L, d, _stream())
     else:
         _lib.call("hriemo_fuse_fwd", _p(w), _p(An), _p(Tn), _p(H), sf.B, sf.L, d, _stream())
@@ -1282,6 +1302,10 @@ PACKED_TAIL = False
 # alone must keep meaning "the bf16 tail" (with only PACKED_TAIL set, the fp32 mode issues exactly its previous launches) and
 # because each arm becomes the default only after its own measurement (scripts_dev/ab_packed_tail.sh fp32).
 PACKED_TAIL_FP32 = False
+# And for the MX-fp8 GEMM mode (bf16 precision): the gate's fuse kernel leaves the quantised memory (hriemo_fuse_fwd_packed_q), the
+# decoder's K | V projections run in fp8 over the N_f packed rows.  Its own switch for the same two reasons
+# (scripts_dev/ab_packed_tail.sh mx8).
+PACKED_TAIL_MX8 = False
 
 
 # Attention maps (return_attention=True) from the packed path: the export runs on cu_seqlens (hriemo_attn_probs_varlen,
@@ -1301,10 +1325,10 @@ def varlen_maps():
 
 
 def packed_tail():
-    """the tail stays packed: bf16 GEMM operands (the MX-fp8 mode unpacks behind the encoder) and the switch of the precision
-    mode -- PACKED_TAIL for bf16, PACKED_TAIL_FP32 for fp32"""
-    if gemm_mode() != "bf16":
-        return False
+    """the tail stays packed: the switch of the mode in force -- PACKED_TAIL for bf16 operands in bf16 precision, PACKED_TAIL_FP32
+    for the fp32 precision (bf16 GEMM mode), PACKED_TAIL_MX8 for MX-fp8 operands in bf16 precision"""
+    if gemm_mode() == "mx_fp8":
+        return bool(PACKED_TAIL_MX8 and precision() == "bf16")
     return bool(PACKED_TAIL_FP32) if precision() == "fp32" else bool(PACKED_TAIL and precision() == "bf16")
 
 

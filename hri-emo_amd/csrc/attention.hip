@@ -50,7 +50,8 @@ struct AttnArgs {
   // stride of the lse / delta / mask-word side buffers, which keep their padded [B,H,Lq] indexing).  Every length >= 1.
   const int* cu_q;
   const int* cu_k;
-  // optional MX-fp8 copy of O for the out-projection GEMM (cfg 5's fp8 mode): bytes [B*Lq][ldoq] + E8M0 scales [H*HD/32][ldso]
+  // optional MX-fp8 copy of O for the out-projection GEMM (cfg 5's fp8 mode): bytes [B*Lq][ldoq] + E8M0 scales [H*HD/32][ldso];
+  // packed sequences: bytes [n_rows][ldoq], the scale byte of packed row r in column r
   uint8_t* Oq; long ldoq;
   uint8_t* So; long ldso;
 };
@@ -77,6 +78,7 @@ __device__ __forceinline__ AttnArgs localize(const AttnArgs& a0, int b, int h) {
     if (a.lse != nullptr) a.lse += bh * (a0.Lq - Lq);
     if (a.delta != nullptr) a.delta += bh * (a0.Lq - Lq);
     if (a.mbits != nullptr) a.mbits += bh * ((long)a0.Lq * ((a0.Lk + 63) >> 6) - (long)Lq * ((Lk + 63) >> 6));
+    if (a.Oq != nullptr) { a.Oq += sq * a.ldoq; a.So += sq; }      // the scale byte of packed row r is COLUMN r of So
     a.Lq = Lq; a.Lk = Lk;
     a.kpm = nullptr;
   }
@@ -1763,14 +1765,15 @@ static int attn_fwd_impl(const void* Q, long ldq, const void* K, long ldk, const
                          long ldo, const unsigned char* key_padding_mask, float* lse, int B, int H, int Lq,
                          int Lk, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
                          unsigned site, int b_offset, void* drop_mask_bits, const int* cu_q, const int* cu_k, hipStream_t st,
-                         void* Oq = nullptr, long ldoq = 0, void* So = nullptr, long ldso = 0) {
+                         void* Oq = nullptr, long ldoq = 0, void* So = nullptr, long ldso = 0, long n_rows = 0) {
   AttnArgs a = attn_args(Q, ldq, K, ldk, V, ldv, key_padding_mask, lse, B, H, Lq, Lk, head_dim, p_drop, seed, seed_dev, site, b_offset);
   a.cu_q = cu_q; a.cu_k = cu_k;
   a.O = (bf16_t*)O; a.ldo = ldo;
   a.Oq = (uint8_t*)Oq; a.ldoq = ldoq; a.So = (uint8_t*)So; a.ldso = ldso;
-  HRIEMO_CHECK(Oq == nullptr || (cu_q == nullptr && head_dim % 32 == 0 && So != nullptr && ldoq % 4 == 0 && ((uintptr_t)Oq % 4) == 0 &&
-                                 ldso >= (long)B * Lq),
-               "attn_fwd: the MX-fp8 copy of O needs padded rows, head_dim %% 32 == 0 and a scale buffer of >= B*Lq columns");
+  // rows of Oq / columns of So: B*Lq padded; packed, the host cannot read cu, so the caller states the packed row count
+  HRIEMO_CHECK(Oq == nullptr || (head_dim % 32 == 0 && So != nullptr && ldoq % 4 == 0 && ((uintptr_t)Oq % 4) == 0 &&
+                                 (cu_q == nullptr ? ldso >= (long)B * Lq : (n_rows >= B && n_rows <= (long)B * Lq && ldso >= n_rows))),
+               "attn_fwd: the MX-fp8 copy of O needs head_dim %% 32 == 0 and a scale buffer of >= B*Lq (packed: n_rows) columns");
   a.mbits = (unsigned long long*)drop_mask_bits;
   if (check_common(a, head_dim) || check_packed(a)) return 1;
   HRIEMO_CHECK(ldo % 4 == 0 && ((uintptr_t)O % 8) == 0 && ((uintptr_t)drop_mask_bits % 8) == 0, "attn_fwd: unaligned O / mask bits");
@@ -1815,6 +1818,18 @@ extern "C" int hriemo_attn_fwd_varlen(const void* Q, long ldq, const void* K, lo
   HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_fwd_varlen: cu_seqlens missing");
   return attn_fwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, lse, B, H, max_len_q, max_len_k, head_dim, p_drop, seed, seed_dev,
                        site, b_offset, drop_mask_bits, cu_seqlens_q, cu_seqlens_k, st);
+}
+// hriemo_attn_fwd_varlen that also leaves the MX-fp8 form of the packed O: bytes Oq[n_rows][ldoq], E8M0 scales So[H*hd/32][ldso]
+// with the scale byte of packed row r in column r (bit-identical to hriemo_quant_mx8 of the packed O); n_rows = cu_seqlens_q[B]
+extern "C" int hriemo_attn_fwd_q_varlen(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O,
+                                        long ldo, const int* cu_seqlens_q, const int* cu_seqlens_k, float* lse, int B, int H,
+                                        int max_len_q, int max_len_k, int head_dim, float p_drop, unsigned long long seed,
+                                        const unsigned long long* seed_dev, unsigned site, int b_offset, void* drop_mask_bits,
+                                        void* Oq, long ldoq, void* So, long ldso, long n_rows, hipStream_t st) {
+  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_fwd_q_varlen: cu_seqlens missing");
+  HRIEMO_CHECK(Oq != nullptr, "attn_fwd_q_varlen: Oq required");
+  return attn_fwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, lse, B, H, max_len_q, max_len_k, head_dim, p_drop, seed, seed_dev,
+                       site, b_offset, drop_mask_bits, cu_seqlens_q, cu_seqlens_k, st, Oq, ldoq, So, ldso, n_rows);
 }
 
 static int attn_bwd_impl(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,

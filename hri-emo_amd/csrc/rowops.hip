@@ -891,30 +891,54 @@ __global__ void fuse_fwd_kernel(const float* __restrict__ w, const bf16_t* __res
 // the same on the packed fused layout [n_f, d] (A, T, H alike): block (32-row chunk, sample b) walks rows cu_f[b] + l, the gate
 // weights of its sample in registers; grid y = B + 1: slice B zeroes the surplus rows cu_f[B] .. n_f-1 (the decoder's K | V
 // weight-gradient GEMM multiplies every row of H)
-template <int NCH>
+// MXQ (fp8 GEMM mode, d % 32 == 0): also the MX-fp8 form of H for the decoder's memory K | V projection -- bytes Hq[n_f][d], E8M0
+// scales Hs[d/32][lds], the scale byte of row r in column r.  A lane owns 8 columns, a 32-column block is four adjacent lanes
+// (mx8_block); the ROUNDED bf16 values are quantised, so the copy is hriemo_quant_mx8(H) bit for bit; surplus rows: zero bytes
+// and zero scale bytes (what the quantiser gives for zero rows).
+template <int NCH, bool MXQ = false>
 __global__ __launch_bounds__(256) void fuse_fwd_packed_kernel(const float* __restrict__ w, const bf16_t* __restrict__ A, const bf16_t* __restrict__ T,
-                                                              bf16_t* __restrict__ H, const int* __restrict__ cu_f, int n_f, int B, int L, int d) {
+                                                              bf16_t* __restrict__ H, const int* __restrict__ cu_f, int n_f, int B, int L, int d,
+                                                              uint8_t* __restrict__ Hq = nullptr, uint8_t* __restrict__ Hs = nullptr, long lds = 0) {
+  typedef __attribute__((ext_vector_type(2))) int i32x2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = d >> 3;
   if (b == B) {
-    zero_rows16(H, min(max(cu_f[B], 0), n_f), n_f, gridDim.x * 4, chunk * 4 + wave, d, lane);
+    const long r0 = min(max(cu_f[B], 0), n_f);
+    zero_rows16(H, r0, n_f, gridDim.x * 4, chunk * 4 + wave, d, lane);
+    if (MXQ)
+      for (long r = r0 + chunk * 4 + wave; r < n_f; r += gridDim.x * 4) {
+        for (int o = lane * 8; o < d; o += 64 * 8) *(i32x2*)(Hq + r * d + o) = i32x2{0, 0};
+        for (int k = lane; k < (d >> 5); k += 64) Hs[(long)k * lds + r] = 0;
+      }
     return;
   }
   const PackedSpan sf = packed_span(cu_f, b, L, n_f);
   float wv[NCH][8];
   load_cols<NCH>(w + (long)b * d, nchunk, lane, wv);
-  for (int l = chunk * 32 + wave; l < min(sf.len, chunk * 32 + 32); l += 4) {
+  for (int l = chunk * 32 + wave; l < min(sf.len, chunk * 32 + 32); l += 4) {       // wave-uniform: every lane reaches mx8_block
     const long row = (long)sf.c0 + l;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
+      float o[8];
+      bf16x8 h = bf16x8{};
       if (ch < nchunk) {
-        float a[8], t[8], o[8];
+        float a[8], t[8];
         bf8_to_f32(*(const bf16x8*)(A + row * d + ch * 8), a);
         bf8_to_f32(*(const bf16x8*)(T + row * d + ch * 8), t);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = wv[c][j] * a[j] + (1.f - wv[c][j]) * t[j];
-        *(bf16x8*)(H + row * d + ch * 8) = f32_to_bf8(o);
+        h = f32_to_bf8(o);
+        *(bf16x8*)(H + row * d + ch * 8) = h;
+      }
+      if (MXQ) {
+        int e;
+        bf8_to_f32(h, o);
+        const i32x2 q = mx8_block(o, e);
+        if (ch < nchunk) {
+          *(i32x2*)(Hq + row * d + ch * 8) = q;
+          if ((lane & 3) == 0) Hs[(long)(ch >> 2) * lds + row] = (uint8_t)e;
+        }
       }
     }
   }
@@ -2012,11 +2036,29 @@ extern "C" int hriemo_fuse_fwd_packed(const float* w, const void* A, const void*
   if (check_packed("fuse_fwd_packed", nullptr, 0, 0, cu_fused, n_fused, B, L, d)) return 1;
   const int nc = (L + 31) / 32;
   hriemo_prof_begin(HP_ROWOPS, st);
-#define CALL(N) hipLaunchKernelGGL((fuse_fwd_packed_kernel<N>), dim3(nc, B + 1), dim3(256), 0, st, w, (const bf16_t*)A, (const bf16_t*)T, (bf16_t*)H, cu_fused, n_fused, B, L, d)
+#define CALL(N) hipLaunchKernelGGL((fuse_fwd_packed_kernel<N, false>), dim3(nc, B + 1), dim3(256), 0, st, w, (const bf16_t*)A, (const bf16_t*)T, (bf16_t*)H, cu_fused, n_fused, B, L, d, (uint8_t*)nullptr, (uint8_t*)nullptr, 0L)
   DISPATCH_NCH(d, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("fuse_fwd_packed_kernel");
   hriemo_prof_end(HP_ROWOPS, st, 3.0 * n_fused * d * 2);
+  return 0;
+}
+
+// hriemo_fuse_fwd_packed that also leaves the MX-fp8 form of H (bytes Hq[n_fused][d], E8M0 scales Hs[d/32][lds], the scale byte of
+// row r in column r): the operand of the decoder's memory K | V projection in the fp8 GEMM mode, bit-identical to
+// hriemo_quant_mx8(H); surplus rows: zero bytes, zero scale bytes
+extern "C" int hriemo_fuse_fwd_packed_q(const float* w, const void* A, const void* T, void* H, const int* cu_fused, int n_fused, int B,
+                                        int L, int d, void* Hq, void* Hs, long lds, hipStream_t st) {
+  if (check_packed("fuse_fwd_packed_q", nullptr, 0, 0, cu_fused, n_fused, B, L, d)) return 1;
+  HRIEMO_CHECK(d % 32 == 0 && Hq != nullptr && Hs != nullptr && lds >= n_fused && ((uintptr_t)Hq % 8) == 0,
+               "fuse_fwd_packed_q: needs d %% 32 == 0 (d=%d), Hq / Hs and a scale buffer of >= n_fused columns", d);
+  const int nc = (L + 31) / 32;
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N) hipLaunchKernelGGL((fuse_fwd_packed_kernel<N, true>), dim3(nc, B + 1), dim3(256), 0, st, w, (const bf16_t*)A, (const bf16_t*)T, (bf16_t*)H, cu_fused, n_fused, B, L, d, (uint8_t*)Hq, (uint8_t*)Hs, lds)
+  DISPATCH_NCH(d, CALL)
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("fuse_fwd_packed_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, 3.0 * n_fused * d * 2 + (double)n_fused * d);
   return 0;
 }
 

@@ -65,13 +65,14 @@ class ExplainableDecoderLayer(nn.Module):
         if packed:
             # the queries are not ragged: their packed rows ARE the padded rows ([1, B*N_e, d]), so the dropout row keys of this
             # sub-layer's LayerNorm stay those of the padded path
-            tgt, tgt32 = tgt.view(1, Bq * Nq, dq), (tgt32.view(1, Bq * Nq, dq) if tgt32 is not None else None)
+            # (a view is a new tensor: the MX-fp8 copy a LayerNorm attached to its output is per row, so it rides along)
+            tgt, tgt32 = _ops.tag_mx(tgt.view(1, Bq * Nq, dq), _ops.mx_of(tgt)), (tgt32.view(1, Bq * Nq, dq) if tgt32 is not None else None)
         tgt, tgt32, w = _ops.CrossAttnLN.apply(tgt, tgt32, memory, ca.in_proj_weight, ca.in_proj_bias,
                                                ca.out_proj.weight, ca.out_proj.bias, self.norm2.weight,
                                                self.norm2.bias, self._sh, self.nhead, sq, sm, p, seed, s[1],
                                                self.batch_offset, need, kv_pre)                               # :48-55
         if packed:
-            tgt, tgt32 = tgt.view(Bq, Nq, dq), (tgt32.view(Bq, Nq, dq) if tgt32 is not None else None)
+            tgt, tgt32 = _ops.tag_mx(tgt.view(Bq, Nq, dq), _ops.mx_of(tgt)), (tgt32.view(Bq, Nq, dq) if tgt32 is not None else None)
         tgt, tgt32 = _ops.FFNLN.apply(tgt, tgt32, self.linear1.weight, self.linear1.bias, self.linear2.weight,
                                       self.linear2.bias, self.norm3.weight, self.norm3.bias, self._sh, p, p, seed,
                                       s[2], self.batch_offset, sp)                                            # :58-59
@@ -114,8 +115,9 @@ class EmotionDecoder(nn.Module):
         memory [1, N_f, d] (the K | V projections then run over the N_f packed rows)"""
         out, out32 = self._queries(sm.Breal)
         all_layers_attn = []
-        if _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):
-            # fp8 GEMM mode: every layer projects the same memory to K | V -- quantise it once
+        if _ops.mx_of(memory16) is None and _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):
+            # fp8 GEMM mode: every layer projects the same memory to K | V -- quantise it once (a packed memory arrives with the
+            # copy the gate's fuse kernel left: nothing to do)
             m2 = memory16 if memory16.is_contiguous() else memory16.contiguous()
             memory16 = _ops.tag_mx(m2, _ops.quant_mx8(m2.view(-1, m2.shape[2])))
         if _ops.precision() == "fp32":

@@ -159,6 +159,15 @@ int hriemo_attn_fwd_varlen(const void* Q, long ldq, const void* K, long ldk, con
                            const int* cu_seqlens_q, const int* cu_seqlens_k, float* lse, int B, int H, int max_len_q,
                            int max_len_k, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
                            unsigned site, int b_offset, void* drop_mask_bits, hriemo_stream_t stream);
+/* hriemo_attn_fwd_varlen whose epilogue also writes the MX-fp8 form of the packed O: bytes Oq[n_rows][ldoq], E8M0 scales
+ * So[H*hd/32][ldso] with the scale byte of packed row r in column r (ldso >= n_rows, a multiple of 256), bit-identical to
+ * hriemo_quant_mx8 of the packed O; O and lse are those of hriemo_attn_fwd_varlen bit for bit.  n_rows = cu_seqlens_q[B], the packed
+ * row count of Q / O (the host cannot read cu_seqlens).  head_dim % 32 == 0. */
+int hriemo_attn_fwd_q_varlen(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
+                             const int* cu_seqlens_q, const int* cu_seqlens_k, float* lse, int B, int H, int max_len_q,
+                             int max_len_k, int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev,
+                             unsigned site, int b_offset, void* drop_mask_bits, void* Oq, long ldoq, void* So, long ldso,
+                             long n_rows, hriemo_stream_t stream);
 int hriemo_attn_bwd_varlen(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, const void* O, long ldo,
                            const void* dO, long lddo, void* dQ, long lddq, void* dK, long lddk, void* dV, long lddv,
                            const int* cu_seqlens_q, const int* cu_seqlens_k, const float* lse, float* delta, int B, int H,
@@ -401,6 +410,11 @@ int hriemo_ln_pool_fwd_packed_pair(const void* Xa, const float* Xa32, const int*
 /* H = w * A + (1 - w) * T on the packed fused rows (the sample of a row comes from cu_fused); dw partials of the same rows */
 int hriemo_fuse_fwd_packed(const float* w, const void* A, const void* T, void* H, const int* cu_fused, int n_fused, int B, int L, int d,
                            hriemo_stream_t stream);
+/* hriemo_fuse_fwd_packed that also leaves the MX-fp8 form of H for the decoder's memory K | V projection (fp8 GEMM mode): bytes
+ * Hq[n_fused][d], E8M0 scales Hs[d/32][lds] with the scale byte of row r in column r (lds >= n_fused, a multiple of 256),
+ * bit-identical to hriemo_quant_mx8(H); the surplus rows get zero bytes and zero scale bytes.  d % 32 == 0. */
+int hriemo_fuse_fwd_packed_q(const float* w, const void* A, const void* T, void* H, const int* cu_fused, int n_fused, int B, int L, int d,
+                             void* Hq, void* Hs, long lds, hriemo_stream_t stream);
 int hriemo_fuse_bwd_dw_packed(const void* dH, const void* A, const void* T, float* partials, const int* cu_fused, int n_fused, int B,
                               int L, int d, hriemo_stream_t stream);
 int hriemo_ln_pool_bwd_packed(const void* dH, const int* cu_fused, int n_fused, const float* w, int is_a, const float* dpool,
