@@ -66,6 +66,7 @@ _SIGS = {
     "hriemo_gate_dpre_f32_packed": ("ppippiippiipppiiip", "i"),
     "hriemo_gate_dy_f32_packed": ("ppipippipiiiip", "i"),
     "hriemo_attn_probs": ("plplpppiiiiifQpIip", "i"),
+    "hriemo_attn_probs_mfma": ("plplpppiiiiifQpIip", "i"),
     "hriemo_attn_probs_varlen": ("plplppppiiiiiiifQpIip", "i"),
     "hriemo_attn_probs_f32_varlen": ("plplppppiiiiiiifQpIip", "i"),
     "hriemo_add_ln_fwd": ("pppppppppiiffQpIlp", "i"),

@@ -934,7 +934,7 @@ def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off, cu=None, 
                   Lq, Lk, out_l[0], out_l[1], hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _stream())
         return out
     out = torch.empty((B, Lq, Lk), dtype=torch.float32, device=q.device)
-    _lib.call("hriemo_attn_probs", _p(q), q.stride(0), _p(k), k.stride(0), _p(kpm), _p(lse), _p(out), B, H, Lq, Lk,
+    _lib.call("hriemo_attn_probs_mfma" if MFMA_MAPS else "hriemo_attn_probs", _p(q), q.stride(0), _p(k), k.stride(0), _p(kpm), _p(lse), _p(out), B, H, Lq, Lk,
               hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _stream())
     return out
 
@@ -1322,6 +1322,24 @@ def set_varlen_maps(on):
 
 def varlen_maps():
     return bool(PACKED_MAPS)
+
+
+# Attention maps of PADDED rows from the matrix cores: attn_probs picks hriemo_attn_probs_mfma (the contract of hriemo_attn_probs
+# under any key-padding mask: PAD query rows computed, PAD key columns exact zeros, an all-PAD sample NaN; the result is equal up
+# to fp32 summation order) wherever it would launch the VALU export -- every encoder site, the decoder's padded maps (those of
+# varlen + packed maps with the packed tail off included), the legacy block, the classifier's transformer.  False: exactly the
+# launches from before.  The fp32 precision is unaffected: _fp32.probs already runs an fp32 MFMA loop.  Opt-in; a module constant
+# with a setter, not an environment switch.
+MFMA_MAPS = False
+
+
+def set_mfma_maps(on):
+    global MFMA_MAPS
+    MFMA_MAPS = bool(on)
+
+
+def mfma_maps():
+    return bool(MFMA_MAPS)
 
 
 def packed_tail():

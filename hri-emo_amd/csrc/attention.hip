@@ -1597,6 +1597,131 @@ __global__ __launch_bounds__(256) void attn_probs_mfma_kernel(const ProbsArgs a)
   }
 }
 
+// The same export on PADDED rows under any key-padding mask (hriemo_attn_probs_mfma): the contract of attn_probs_kernel above on the
+// schedule of attn_probs_mfma_kernel.  Sample b owns rows b*Lq .. b*Lq+Lq-1 of Q and b*Lk .. b*Lk+Lk-1 of K, lse is [B, H, Lq], the
+// map the dense [B, Lq, Lk], every element of it written.  What differs from the packed kernel:
+//  * the key mask is bytes [B, Lk] of any pattern (or NULL).  Each wave reads the 64 mask bytes of a key tile once, one per lane,
+//    and keeps them as a ballot word: bit k = key 64*tile + k is valid (keys at or past Lk are PAD).  The words are equal in all
+//    four waves, so "word == 0" -- a DEAD tile, nothing but PAD keys -- is block-uniform: such a tile fetches nothing, runs no MFMA
+//    and no barrier.  A PAD key's probability is the constant 0 by a select on its bit, never the exponential of a masked score,
+//    so NaN / Inf in a PAD row of K end in their own column of S and nowhere else;
+//  * PAD query rows do not exist here: every row of the map is a softmax over the valid keys (the reference masks keys only);
+//  * a query whose lse is -inf (all keys PAD) is NaN in every column, PAD columns and dropped elements included: the select comes
+//    last, as in attn_probs_kernel, and it is a select -- exp2(fma(s, c, +inf)) would be +inf.  A sample that is all PAD has dead
+//    tiles only, so a dead tile takes the rule from the lse alone;
+//  * the K tile fetch is bounded by the sample's Lk (tile_fetch's row bound): rows past it are zeros from the range check, never
+//    the next sample's.
+struct ProbsPadArgs {
+  const bf16_t *Q, *K;
+  long ldq, ldk;
+  const uint8_t* kpm;
+  const float* lse;
+  float* probs;
+  int H, Lq, Lk;
+  float scale;
+  uint32_t thr16; float inv_keep; uint64_t seed; const unsigned long long* seed_dev; uint32_t site; int b_offset;
+};
+template <int HD>
+__global__ __launch_bounds__(256) void attn_probs_mfma_pad_kernel(const ProbsPadArgs a) {
+  using G = AttnGeom<HD>;
+  constexpr int KS = G::KS, STRIDE = G::STRIDE;
+  __shared__ __attribute__((aligned(16))) char Kt[64 * STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
+  const int b = blockIdx.z, Lq = a.Lq, Lk = a.Lk;
+  const int q0 = blockIdx.x * 64 + wave * 16;
+  const int kt0 = blockIdx.y * PROBS_KT, kt1 = min(kt0 + PROBS_KT, (Lk + 63) >> 6);
+  const float sl2 = a.scale * LOG2E, invH = 1.f / (float)a.H;
+  const uint64_t seed = a.thr16 != 0 ? eff_seed(a.seed, a.seed_dev) : 0ull;
+  const bf16_t* Kb = a.K + (long)b * Lk * a.ldk;
+  const bf16_t* Qb = a.Q + (long)b * Lq * a.ldq;
+  const float* lb = a.lse + (long)b * a.H * Lq;
+  float* pb = a.probs + (long)b * Lq * Lk;
+
+  // the valid-key words of this block's tiles (wave-uniform, the same in every wave)
+  unsigned long long valid[PROBS_KT];
+#pragma unroll
+  for (int t = 0; t < PROBS_KT; ++t) {
+    const int key = (kt0 + t) * 64 + lane;
+    valid[t] = __builtin_amdgcn_ballot_w64(key < Lk && (a.kpm == nullptr || a.kpm[(long)b * Lk + key] == 0));
+  }
+  TileRegs<HD, 64, 256> kr;
+  {
+    int t = 0;
+    while (t < PROBS_KT && valid[t] == 0) ++t;           // the first live tile of the block, if there is one
+    if (t < PROBS_KT) tile_fetch<HD, 64, 256>(kr, Kb, a.ldk, (kt0 + t) * 64, Lk, tid);
+  }
+#pragma unroll
+  for (int t = 0; t < PROBS_KT; ++t) {
+    const int kt = kt0 + t;
+    if (kt >= kt1) break;
+    f32x4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (valid[t] != 0) {                       // block-uniform: every barrier below is reached by all 256 threads
+      int tn = t + 1;
+      while (tn < PROBS_KT && valid[tn] == 0) ++tn;          // the next live tile
+      bool padk[4];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) padk[n] = ((valid[t] >> (n * 16 + i)) & 1ull) == 0;
+      for (int h = 0; h < a.H; ++h) {
+        // this head's 16 query rows as A fragments and their lse (rows past Lq: the sample's last row, masked at the store)
+        bf16x8 qf[KS];
+        const bf16_t* qp = Qb + (long)min(q0 + i, Lq - 1) * a.ldq + h * HD;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const int e = ks * 32 + 8 * g;
+          qf[ks] = (e < HD) ? *(const bf16x8*)(qp + e) : zero8();
+        }
+        float nl[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) nl[r] = -LOG2E * lb[(long)h * Lq + min(q0 + 4 * g + r, Lq - 1)];
+        __syncthreads();
+        tile_commit<HD, 64, 256>(kr, Kt, tid);
+        __syncthreads();
+        if (h + 1 < a.H) tile_fetch<HD, 64, 256>(kr, Kb + (h + 1) * HD, a.ldk, kt * 64, Lk, tid);
+        else if (tn < PROBS_KT) tile_fetch<HD, 64, 256>(kr, Kb, a.ldk, (kt0 + tn) * 64, Lk, tid);
+        if (q0 >= Lq) continue;                // wave-uniform: a whole 16-row tile past Lq (the barriers are above)
+        const uint32_t key32 = a.thr16 != 0 ? site_key(seed, a.site, (uint32_t)((a.b_offset + b) * a.H + h)) : 0u;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+          f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks)
+            s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ks], row_frag(Kt, STRIDE, n * 16 + i, ks * 4 + g), s, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float p = padk[n] ? 0.f : EXP2(fmaf(s[r], sl2, nl[r]));
+            // (training mode: the reference returns the weights AFTER its dropout; keyed by the padded indices, as the forward)
+            if (a.thr16 != 0)
+              p = keep16(key32, (uint32_t)(q0 + 4 * g + r), (uint32_t)(kt * 64 + n * 16 + i), a.thr16) ? p * a.inv_keep : 0.f;
+            if (nl[r] == INFINITY) p = __builtin_nanf("");          // lse = -inf: NaN like the reference, behind the dropout select
+            acc[n][r] += p;
+          }
+        }
+      }
+    } else if (q0 < Lq) {                      // a dead tile: zeros, or NaN where a head's lse says that every key is PAD
+      for (int h = 0; h < a.H; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (lb[(long)h * Lq + min(q0 + 4 * g + r, Lq - 1)] == -INFINITY) {
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n][r] = __builtin_nanf("");
+          }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + 4 * g + r;
+      if (q >= Lq) continue;
+      float* pp = pb + (long)q * Lk;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int key = kt * 64 + n * 16 + i;
+        if (key < Lk) pp[key] = acc[n][r] * invH;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host
 static int cu_count() {
   static int n = 0;
@@ -1975,5 +2100,30 @@ extern "C" int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, 
   const dim3 grid(tiles(out_lq, 64), tiles(out_lk, 64 * PROBS_KT), B);
   with_head_dim(head_dim, [&](auto hd) { hipLaunchKernelGGL((attn_probs_mfma_kernel<decltype(hd)::value>), grid, dim3(256), 0, st, a); });
   HRIEMO_LAUNCH_CHECK("attn_probs_mfma_kernel");
+  return 0;
+}
+
+// The padded export on the matrix cores (attn_probs_mfma_pad_kernel): the arguments and the result of hriemo_attn_probs
+extern "C" int hriemo_attn_probs_mfma(const void* Q, long ldq, const void* K, long ldk, const unsigned char* key_padding_mask,
+                                      const float* lse, float* probs, int B, int H, int Lq, int Lk, int head_dim, float p_drop,
+                                      unsigned long long seed, const unsigned long long* seed_dev, unsigned site, int b_offset,
+                                      hipStream_t st) {
+  HRIEMO_CHECK(Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr, "attn_probs_mfma: empty problem");
+  if (check_shape(B, H, Lq, Lk, head_dim)) return 1;
+  HRIEMO_CHECK(B <= 65535, "attn_probs_mfma: B=%d exceeds the grid", B);
+  HRIEMO_CHECK(ldq % 8 == 0 && ldk % 8 == 0, "attn_probs_mfma: leading dims must be multiples of 8");
+  HRIEMO_CHECK(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)probs % 4) == 0 && ((uintptr_t)lse % 4) == 0,
+               "attn_probs_mfma: unaligned Q/K/lse/probs");
+  HRIEMO_CHECK(p_drop >= 0.f && p_drop < 1.f, "attn_probs_mfma: dropout p=%f", (double)p_drop);
+  const DropCfg d = make_drop(p_drop, seed, site);
+  ProbsPadArgs a = {};
+  a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.ldq = ldq; a.ldk = ldk;
+  a.kpm = key_padding_mask; a.lse = lse; a.probs = probs;
+  a.H = H; a.Lq = Lq; a.Lk = Lk;
+  a.scale = 1.0f / sqrtf((float)head_dim);
+  a.thr16 = d.thr16; a.inv_keep = d.inv_keep; a.seed = seed; a.seed_dev = seed_dev; a.site = site; a.b_offset = b_offset;
+  const dim3 grid(tiles(Lq, 64), tiles(Lk, 64 * PROBS_KT), B);
+  with_head_dim(head_dim, [&](auto hd) { hipLaunchKernelGGL((attn_probs_mfma_pad_kernel<decltype(hd)::value>), grid, dim3(256), 0, st, a); });
+  HRIEMO_LAUNCH_CHECK("attn_probs_mfma_pad_kernel");
   return 0;
 }

@@ -203,6 +203,20 @@ int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, long ldk, c
                              const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
                              int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
                              int b_offset, hriemo_stream_t stream);
+/* hriemo_attn_probs on the matrix cores (v_mfma_f32_16x16x32_bf16): the same arguments and the same padded layout -- sample b owns
+ * rows b*Lq .. b*Lq+Lq-1 of Q and b*Lk .. b*Lk+Lk-1 of K, lse is the [B, H, Lq] of hriemo_attn_fwd, probs the dense map
+ * [B, Lq, Lk] fp32, of which EVERY element is written and nothing outside it.  key_padding_mask is uint8 [B, Lk], non-zero = PAD,
+ * any pattern (not only prefixes), or NULL.  A PAD key's column is exact 0.0, chosen by a select: NaN / Inf in a PAD key's row
+ * of K reach no output element.  PAD query rows are computed like any other row (the reference masks keys, not queries).  A
+ * query whose lse is -inf (every key of the sample PAD) is NaN in its whole row, PAD columns and dropped elements included.
+ * Dropout (p_drop > 0) replays the forward's mask, keyed by the padded indices.  Rows of K past a sample's Lk are never read, and
+ * a 64-key tile whose keys are all PAD costs no fetch and no MFMA work.  The result is hriemo_attn_probs's up to fp32 summation
+ * order.  Non-zero (hriemo_last_error), and nothing launched, for an empty problem or a NULL Q / K / lse / probs, a head_dim that
+ * is not built, leading dimensions that are not multiples of 8, unaligned operands, p_drop outside [0, 1) and B > 65535. */
+int hriemo_attn_probs_mfma(const void* Q, long ldq, const void* K, long ldk, const unsigned char* key_padding_mask,
+                           const float* lse, float* probs, int B, int H, int Lq, int Lk, int head_dim, float p_drop,
+                           unsigned long long seed, const unsigned long long* seed_dev, unsigned site, int b_offset,
+                           hriemo_stream_t stream);
 
 /* ---- y = LayerNorm(x + dropout(g)), eps, affine (X may be NULL: plain LayerNorm of g).
  * The residual stream has an optional fp32 twin: X32 (read instead of the bf16 X when non-NULL) and Y32
