@@ -55,12 +55,18 @@ def inv_keep(p):
     return 1.0 / (1.0 - thr16(p) / 65536.0)
 
 
-def rows_mask(seed, site, M, N, p, row_offset=0):
-    """keep-mask [M,N] of add_ln / dropout kernels"""
+def rows_mask_at(seed, site, row_keys, N, p):
+    """keep-mask [len(row_keys), N] of the add_ln / dropout kernels for rows whose dropout hash is keyed by row_keys (the kernels'
+    row_offset + row, or row_offset + row_index[row]; taken modulo 2^32 as the kernels take it)"""
     k = site_key(seed, site, 0)
-    r = np.arange(M, dtype=np.uint64)[:, None] + np.uint64(row_offset)
+    r = (np.asarray(row_keys, dtype=np.int64) & np.int64(0xFFFFFFFF)).astype(np.uint64)[:, None]
     c = np.arange(N, dtype=np.uint64)[None, :]
     return keep(k, r, c, p)
+
+
+def rows_mask(seed, site, M, N, p, row_offset=0):
+    """keep-mask [M,N] of add_ln / dropout kernels"""
+    return rows_mask_at(seed, site, np.arange(M, dtype=np.int64) + int(row_offset), N, p)
 
 
 def attn_mask(seed, site, B, H, Lq, Lk, p, b_offset=0):
