@@ -343,8 +343,11 @@ def self_attn_ln_bwd(ctx, dy, dy32):
              ar.kpm, drop=ctx.f32_drop[0], cu=ar.cu)
     dw_in = linear_dw(dqkv, xf)
     db_in = colsum(dqkv)
-    dx = linear_dx(dqkv, sh, w_in, into=ds)            # + the residual path's gradient
-    gx = _route(ctx, dx, 0, 1, (B, L, d))
+    # the first encoder layer's x is the model's input: no dX GEMM where autograd asks for neither its gradient nor its twin's
+    gx = (None, None)
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or _ops.FORCE_INPUT_GRAD:
+        dx = linear_dx(dqkv, sh, w_in, into=ds)        # + the residual path's gradient
+        gx = _route(ctx, dx, 0, 1, (B, L, d))
     return (gx[0], gx[1], dw_in, db_in, dw_out, db_out, dgamma, dbeta) + (None,) * 8
 
 

@@ -1136,6 +1136,7 @@ DEFER_SMALL_DW = True
 GROUP_SMALL_DW = True      # the queued weight gradients leave as one grouped GEMM launch
 SMALL_DW_ROWS = 1024
 FLUSH_SITES = set()                # dropout-site ids of the sub-layers whose backward ends a model's text branch (one per CrossModalTransformer)
+FORCE_INPUT_GRAD = False           # tests: SelfAttnLN.backward computes its input gradient even where autograd does not ask for it
 _hook_predicates = []              # one per live dp.GradBuckets with gradient-ready hooks (register_hook_predicate)
 
 
@@ -1646,25 +1647,25 @@ def _attn_ln_fwd(ctx, head, q, k, v, x2, x32v, ar, H, hd, sh, w_in16, w_out16, d
     return tag_mx(y.view(shape), mx), (y32.view(shape) if y32 is not None else None), probs
 
 
-def _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site, row_off, rows):
+def _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site, row_off, rows, want_dx=True):
     """How every sub-layer's backward opens: the gradients of its output pair summed, the GradSink of `params` = (..., bias of the
     last Linear, gamma, beta), LayerNorm + residual + dropout backward into the sink's buffers.
-    -> (sink, dS: the residual path's gradient, dG: the last Linear's output gradient, dgamma, dbeta, dbias)"""
+    -> (sink, dS: the residual path's gradient (None unless want_dx), dG: the last Linear's output gradient, dgamma, dbeta, dbias)"""
     dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(x2.shape)
     sink = GradSink(params)
-    return (sink,) + add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site, row_off,
+    return (sink,) + add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site, row_off, want_dx=want_dx,
                                 outs=(sink.buf(params[-2]), sink.buf(params[-1]), sink.buf(params[-3])),
                                 accumulate=sink.fused, x32=x32v, rows=rows)
 
 
-def _attn_ln_bwd(ctx, params, dy, dy32, x2, x32v, tail):
+def _attn_ln_bwd(ctx, params, dy, dy32, x2, x32v, tail, want_dx=True):
     """_ln_bwd and the out-projection's backward of an attention sub-layer; params = (..., w_out, b_out, gamma, beta), tail: the
     saved tensors behind the in-projection's (_attn_ln_fwd).
-    -> (sink, dS, dO: the attention output's gradient, dw_out, db_out, dgamma, dbeta)"""
+    -> (sink, dS (None unless want_dx), dO: the attention output's gradient, dw_out, db_out, dgamma, dbeta)"""
     o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = tail
     p, seed, site, b_off = ctx.cfg[-4:]
     sink, ds, dg, dgamma, dbeta, db_out = _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site + 1,
-                                                  b_off * ctx.rows.stride, ctx.rows.rows)
+                                                  b_off * ctx.rows.stride, ctx.rows.rows, want_dx)
     dw_out = sink.buf(params[-4])
     linear_dw(dg, o, dw_out, sink.fused)
     return sink, ds, linear_dx(dg, w_out16), dw_out, db_out, dgamma, dbeta
@@ -1705,7 +1706,10 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
         ar = ctx.rows
         M = B * L
         p_w_in, p_b_in = ctx.params[:2]
-        sink, ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, ctx.params, dy, dy32, x2, x32v, saved[-9:])
+        # x is the model's input in the first encoder layer: where autograd asks for neither x's nor its twin's gradient, the
+        # residual gradient dS (its only reader is the dX GEMM below) and that GEMM are not computed at all
+        want_dx = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or FORCE_INPUT_GRAD
+        sink, ds, do, dw_out, db_out, dgamma, dbeta = _attn_ln_bwd(ctx, ctx.params, dy, dy32, x2, x32v, saved[-9:], want_dx)
         acc = sink.fused
         dqkv = torch.empty((M, 3 * d), dtype=BF16, device=x2.device)
         db_in = sink.buf(p_b_in)
@@ -1716,12 +1720,12 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
         linear_dw(dqkv, x2, dw_in, acc)
         if not folded:
             colsum(dqkv, db_in, acc)
-        dx = linear_dx(dqkv, w_in16, epi=3, aux=ds)
+        dx = linear_dx(dqkv, w_in16, epi=3, aux=ds).view(B, L, d) if want_dx else None
         sink.done()
         if site in FLUSH_SITES:
             _small_dw.flush()                 # the text branch's backward ends here: queued decoder / gate weight gradients go out now
         r = sink.ret
-        return (dx.view(B, L, d), None, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 8
+        return (dx, None, r(dw_in), r(db_in), r(dw_out), r(db_out), r(dgamma), r(dbeta)) + (None,) * 8
 
 
 class CrossAttnLN(_GradModeAware, torch.autograd.Function):

@@ -365,7 +365,9 @@ __global__ __launch_bounds__(256, (NQ <= 2 ? 6 : NQ == 3 ? 5 : 4)) void add_ln_f
   }
 }
 
-template <int NQ>
+// WDX = false: nobody reads the residual gradient (the sub-layer's input needs no gradient), dX is not stored; a compile-time
+// arm, so the loop stays free of branches around memory operations.  dG, the partials and the grid are the same either way.
+template <int NQ, bool WDX = true>
 __global__ __launch_bounds__(256, (NQ <= 2 ? 4 : NQ == 3 ? 3 : 2)) void add_ln_bwd_q_kernel(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ G,
                                                            const float* __restrict__ X32, const float* __restrict__ gamma,
                                                            const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(256, (NQ <= 2 ? 4 : NQ == 3 ? 3 : 2)) void add_ln_b
           dsb[j] = (bf16_t)ds;
           dgb[j] = (bf16_t)dg;
         }
-        *(bf16x4*)(dX + row * d + qo[c]) = dsb;
+        if constexpr (WDX) *(bf16x4*)(dX + row * d + qo[c]) = dsb;
         *(bf16x4*)(dG + row * d + qo[c]) = dgb;
       }
 #pragma unroll
@@ -1372,6 +1374,10 @@ static int add_ln_bwd_impl(const void* dY, const void* G, const void* X, const f
   if (dG == nullptr && p_drop == 0.f && dX != nullptr && use_quad(d) && X32 != nullptr) dG = dX;      // no dropout: dG == dX, one tensor, equal bytes twice
   if (use_quad(d) && X32 != nullptr && dX != nullptr && dG != nullptr) {
 #define CALL(N) hipLaunchKernelGGL((add_ln_bwd_q_kernel<N>), dim3(nb), dim3(256), 3 * d * 4, st, (const bf16_t*)dY, (const bf16_t*)G, X32, gamma, mean, rstd, (bf16_t*)dX, (bf16_t*)dG, workspace, M, d, dr, row_offset)
+    DISPATCH_NQ(d, CALL)
+#undef CALL
+  } else if (use_quad(d) && X32 != nullptr && dG != nullptr) {      // dX == NULL: same kernel, same grid (lnb_cap), no dX store
+#define CALL(N) hipLaunchKernelGGL((add_ln_bwd_q_kernel<N, false>), dim3(nb), dim3(256), 3 * d * 4, st, (const bf16_t*)dY, (const bf16_t*)G, X32, gamma, mean, rstd, (bf16_t*)nullptr, (bf16_t*)dG, workspace, M, d, dr, row_offset)
     DISPATCH_NQ(d, CALL)
 #undef CALL
   } else {

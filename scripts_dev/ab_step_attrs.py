@@ -1,6 +1,7 @@
 """Same-process A/B of host-side switches (attributes of hri_emo_amd._ops) on the captured cfg-2 step: one capture per variant,
-replays interleaved.  usage: ab_step_attrs.py base GATE_TWO_STREAMS=False SMALL_DW_ROWS=8192,GROUP_SMALL_DW=False ...
-('base' = the defaults; a variant is a comma-separated list of NAME=python-literal)"""
+replays interleaved.  usage: ab_step_attrs.py [--workload cfg4] base GATE_TWO_STREAMS=False SMALL_DW_ROWS=8192,GROUP_SMALL_DW=False ...
+('base' = the defaults; a variant is a comma-separated list of NAME=python-literal; --workload: one of bench.WORKLOADS instead of
+cfg2.  HRIEMO_LIB=<path> runs the same comparison on another build of the library, e.g. the parent commit's.)"""
 import ast, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hri_emo_amd as H
@@ -9,7 +10,15 @@ from hri_emo_amd.dp import DataParallelStep
 from hri_emo_amd.train import fusion_step_loss
 import bench
 dev = torch.device("cuda", 0)
-variants = sys.argv[1:] or ["base"]
+args = sys.argv[1:]
+workload = "cfg2"
+if args[:1] == ["--workload"]:
+    workload, args = args[1], args[2:]
+wl = bench.WORKLOADS[workload]
+bench.CFG = dict(wl["model"], beta_hidden=256, dropout=0.1)
+bench.T_A, bench.T_T = wl["T_a"], wl["T_t"]
+H.set_gemm_mode(wl["gemm"])
+variants = args or ["base"]
 
 
 def parse(v):
@@ -24,8 +33,8 @@ for v in variants:
     torch.manual_seed(1234)
     model = H.FusionWithEmotionDecoder(**bench.CFG).to(dev).train()
     dp = DataParallelStep(model, fusion_step_loss, overlap=False)
-    dp.set_global_batch(64)
-    batch = bench.synth(64, 0, dev)
+    dp.set_global_batch(wl["batch"])
+    batch = bench.synth(wl["batch"], 0, dev)
     dp.step(*batch)
     dp.capture(*batch)
     steps[v] = (dp, batch)
@@ -43,4 +52,4 @@ for rnd in range(5):
         res[v].append(e0.elapsed_time(e1) / 30)
 for v in variants:
     r = sorted(res[v])
-    print(f"{v:48s} median {r[2]:.3f} ms  (" + " ".join(f"{x:.3f}" for x in res[v]) + ")", flush=True)
+    print(f"{workload} {v:48s} median {r[2]:.3f} ms  max-min {r[-1] - r[0]:.3f}  (" + " ".join(f"{x:.3f}" for x in res[v]) + ")", flush=True)
