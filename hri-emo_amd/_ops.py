@@ -1595,6 +1595,165 @@ def unpack_pair(p16, p32, seq):
     return UnpackFn.apply(p16, p32, seq)
 
 
+# ----------------------------------------------------------------------------- module inputs in one launch (hriemo_ingest_rows)
+# The front door of every model: the caller's tensor (fp32 / bf16 / fp16) -> the (bf16, fp32-twin) pair the first encoder layer
+# reads, gathered straight into the packed rows where the encoder packs, with seq.idx and -- in MX-fp8 mode -- the quantised copy
+# of the rows from the same launch.  Replaces as_pair's torch casts + hriemo_pack_rows (+ the first layer's hriemo_quant_mx8): PAD
+# rows are neither read nor converted.  Opt-in (set_ingest) until the step has been measured against the launches it replaces
+# (scripts_dev/bench_ingest.py); forward_packed (rows that arrive packed) uses the kernel regardless.
+INGEST_ROWS = False
+_XT = {torch.float32: 0, BF16: 1, torch.float16: 2}       # x_dtype of hriemo_ingest_rows
+
+
+def set_ingest(on):
+    global INGEST_ROWS
+    INGEST_ROWS = bool(on)
+
+
+def ingest():
+    return bool(INGEST_ROWS)
+
+
+def ingestible(*xs):
+    """the module entries take these tensors through hriemo_ingest_rows (switch on, a source dtype the kernel converts)"""
+    return bool(INGEST_ROWS) and all(x.dtype in _XT for x in xs)
+
+
+def _ingest_rows(x, seq, src_packed, want16=True, want32=False):
+    """x: the padded [Breal, L, d] tensor, or (src_packed) the packed [rows, d] one -> (bf16 rows | None, fp32 twin | None, MX-fp8
+    copy (bytes, scales) | None -- made when want_mx_copy(seq.N, d)) in the layout of `seq` ([1, N, d] packed: fills seq.idx,
+    surplus rows zero; a padded Seq: [Breal, L, d], the rows stay where they are)."""
+    _require_gpu(x)
+    d = x.shape[-1]
+    if not (x.is_contiguous() and x.data_ptr() % 16 == 0):
+        x = x.contiguous()
+    N, shape = seq.N, seq.shape(d)
+    p16 = torch.empty(shape, dtype=BF16, device=x.device) if want16 else None
+    p32 = torch.empty(shape, dtype=torch.float32, device=x.device) if want32 else None
+    q = sc = None
+    ld = 0
+    if want_mx_copy(N, d):
+        ld = _lib.lib().hriemo_mx8_scale_ld(N)
+        q = torch.empty((N, d), dtype=torch.uint8, device=x.device)
+        sc = torch.empty((d // 32, ld), dtype=torch.uint8, device=x.device)
+    _lib.call("hriemo_ingest_rows", _p(x), _XT[x.dtype], d, _p(seq.cu), int(bool(src_packed)), seq.Breal, seq.L, d, N, _p(p16), _p(p32),
+              _p(q), _p(sc), ld, _p(seq.idx), _stream())
+    return p16, p32, ((q, sc) if q is not None else None)
+
+
+class IngestFn(torch.autograd.Function):
+    """x (fp32 / bf16 / fp16) -> the (bf16, fp32 twin | None) pair of its rows laid out as `seq`: ONE launch (hriemo_ingest_rows).
+    seq packed: x is the padded [Breal, L, d] tensor (gathered; what as_pair + PackFn give) or, src_packed, the valid rows
+    [N, d] back to back; also fills seq.idx.  seq padded: x [B, L, d] keeps its layout (what as_pair gives).  The twin is None
+    where as_pair's is (bf16 sources, HRIEMO_FP32_TWIN=0); in MX-fp8 mode the quantised copy rides on the bf16 member (tag_mx).
+    Backward: the pair's gradients scattered back to x's layout (hriemo_unpack_rows for a gathered source), each cast to x's
+    dtype and summed there -- what autograd computes for as_pair + PackFn."""
+
+    @staticmethod
+    def forward(ctx, x, seq, src_packed=False):
+        ctx.set_materialize_grads(False)
+        if x.dtype not in _XT:
+            raise TypeError(f"ingest: inputs of dtype {x.dtype} (expected float32, bfloat16 or float16)")
+        d = x.shape[-1]
+        if src_packed:
+            if not seq.packed or x.dim() != 2 or (seq.B == seq.Breal and x.shape[0] != seq.N):
+                raise ValueError(f"ingest: packed rows of shape {tuple(x.shape)} do not match the {seq.N} rows of their plan")
+        elif x.dim() != 3 or tuple(x.shape[:2]) != (seq.Breal, seq.L):
+            raise ValueError(f"ingest: activation of shape {tuple(x.shape)} is not the padded [{seq.Breal}, {seq.L}] layout of its plan")
+        ctx.seq, ctx.src_packed, ctx.shape, ctx.dtype = seq, bool(src_packed), tuple(x.shape), x.dtype
+        p16, p32, mx = _ingest_rows(x, seq, src_packed, want32=TWIN and x.dtype != BF16)
+        return tag_mx(p16, mx), p32
+
+    @staticmethod
+    def backward(ctx, d16, d32):
+        if not ctx.needs_input_grad[0] or (d16 is None and d32 is None):
+            return None, None, None
+        seq, d = ctx.seq, ctx.shape[-1]
+        if seq.packed and not ctx.src_packed:
+            d16, d32 = _unpack_pair(d16, d32, seq, d)
+        g = None
+        for y in (d16, d32):
+            if y is not None:
+                y = y.reshape(-1, d)[:ctx.shape[0]] if ctx.src_packed else y
+                y = y.to(ctx.dtype)
+                g = y if g is None else g + y
+        return g.reshape(ctx.shape), None, None
+
+
+def ingest_pair(x, seq, src_packed=False):
+    """IngestFn; a bf16 tensor that keeps its padded layout is its own pair (as_pair): no launch unless the MX-fp8 copy is wanted,
+    which then rides on a fresh view of x"""
+    if x.dtype == BF16 and not seq.packed:
+        if not want_mx_copy(seq.N, x.shape[-1]):
+            return x, None
+        return tag_mx(x.view(x.shape), _ingest_rows(x.detach(), seq, False, want16=False)[2]), None
+    return IngestFn.apply(x, seq, src_packed)
+
+
+def entry_pair(x):
+    """as_pair at a module entry that keeps the padded layout; with INGEST_ROWS on, its one-launch form"""
+    if x.dim() != 3 or not ingestible(x):
+        return as_pair(x)
+    return ingest_pair(x, Seq.padded(x.shape[0], x.shape[1]))
+
+
+def packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to=None, same_width=True):
+    """Argument check of forward_packed, on the host only: -> (audio lengths, text lengths) as Python lists and (L_a, L_t).
+    ValueError for lengths outside [1, L], rows that do not add up to the lengths or tensors of the wrong form; RuntimeError for
+    L_t > L_a (the reference's gate slices h_a[:, :L_t], beta_gate_tacfn.py:98-112).  same_width False: the two modalities may differ
+    in width (the MOSEI wrapper, in front of its projections)."""
+    la, lt = ([int(v) for v in (l.tolist() if isinstance(l, torch.Tensor) else l)] for l in (lengths_a, lengths_t))
+    for l in (lengths_a, lengths_t):
+        if isinstance(l, torch.Tensor) and l.is_cuda:
+            raise ValueError("forward_packed: lengths are host sequences or CPU int tensors (no device read)")
+    if len(la) == 0 or len(la) != len(lt):
+        raise ValueError(f"forward_packed: {len(la)} audio and {len(lt)} text lengths")
+    La, Lt = (max(la), max(lt)) if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
+    for name, ls, L in (("audio", la, La), ("text", lt, Lt)):
+        bad = [v for v in ls if v < 1 or v > L]
+        if bad:
+            raise ValueError(f"forward_packed: {name} length {bad[0]} outside [1, {L}]")
+    for name, rows, ls in (("rows_a", rows_a, la), ("rows_t", rows_t, lt)):
+        if rows.dim() != 2 or rows.shape[0] != sum(ls):
+            raise ValueError(f"forward_packed: {name} of shape {tuple(rows.shape)} is not [sum(lengths) = {sum(ls)}, d]")
+        if rows.dtype not in _XT:
+            raise ValueError(f"forward_packed: {name} of dtype {rows.dtype} (expected float32, bfloat16 or float16)")
+    if (same_width and rows_a.shape[1] != rows_t.shape[1]) or rows_a.dtype != rows_t.dtype or rows_a.device != rows_t.device:
+        raise ValueError("forward_packed: rows_a and rows_t differ in width, dtype or device")
+    if Lt > La:
+        raise RuntimeError(f"forward_packed: L_t={Lt} > L_a={La}: the gate fuses over the text length and needs L_a >= L_t")
+    return la, lt, (La, Lt)
+
+
+_LENGTH_PLANS = {}
+
+
+def plans_from_lengths(la, lt, La, Lt, device):
+    """(Seq audio, Seq text, Seq fused) and the padded bool masks (True = PAD) [B, La], [B, Lt] of a batch given by its lengths (host
+    lists): what seq_plans makes of the masks, without a device -> host read.  idx of the two modality plans is written by the
+    ingest launch (hriemo_ingest_rows' row_index)."""
+    key = (tuple(la), tuple(lt), La, Lt, str(device))
+    hit = _LENGTH_PLANS.get(key)
+    if hit is not None:
+        return hit
+    B = len(la)
+
+    def plan(ls, L, Lmax, with_idx):
+        cu = torch.zeros(B + 1, dtype=torch.int32)
+        cu[1:] = torch.cumsum(torch.tensor(ls, dtype=torch.int64), 0)
+        n = int(cu[B])
+        return Seq(cu.to(device), torch.empty(n, dtype=torch.int64, device=device) if with_idx else None, B, L, Lmax, n)
+
+    lf = [min(x, y) for x, y in zip(la, lt)]
+    Lf = min(La, Lt)
+    plans = (plan(la, La, max(la), True), plan(lt, Lt, max(lt), True), plan(lf, Lf, Lf, False))     # (fused: Lmax as fused_seq)
+    masks = tuple((torch.arange(L)[None, :] >= torch.tensor(ls)[:, None]).to(device) for ls, L in ((la, La), (lt, Lt)))
+    if len(_LENGTH_PLANS) > 64:
+        _LENGTH_PLANS.clear()
+    _LENGTH_PLANS[key] = (plans, masks)
+    return plans, masks
+
+
 # ----------------------------------------------------------------------------- sub-layer Functions
 class _GradModeAware:
     """Function.forward always runs with grad mode off, and ctx.needs_input_grad mirrors the inputs' requires_grad even under

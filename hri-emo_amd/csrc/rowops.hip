@@ -1618,6 +1618,133 @@ extern "C" int hriemo_unpack_rows(const void* P16, const float* P32, const int* 
   return 0;
 }
 
+// ---- module inputs: ONE launch from the caller's tensor to everything the first encoder layer reads ----------------------------
+// X (fp32 / bf16 / fp16, row stride ldx) -> the bf16 rows P16 (round to nearest even), their exact fp32 twin P32, with MXQ the
+// MX-fp8 form of the ROUNDED bf16 rows (bytes Pq[n_rows][d], E8M0 scales Ps[d/32][lds], the scale byte of row r in column r:
+// hriemo_quant_mx8(P16) bit for bit) and the padded row of every packed row (what pack_rows_kernel emits).  Rows as in
+// pack_rows_kernel (one wave per destination row, the search over cu); the source is the padded [B, L, d] tensor (gathered), the
+// already packed [cu[B], d] rows (src_packed) or, without cu, the rows themselves.  A row of no sequence is never read and written
+// as zeros (zero bytes, zero scale bytes).  A lane owns the 8-column chunks lane, lane + 64, ... (a 32-column MX block = four
+// adjacent lanes, mx8_block): all of a row's 16-byte loads are issued before the first convert, every output leaves from
+// registers (rows wider than 2048 columns take further passes of 2048).  XT (0 fp32, 1 bf16, 2 fp16) and MXQ are compile-time, so the
+// plain instantiations carry no fp8 code.
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+template <int XT, int NCH, bool MXQ>
+__global__ __launch_bounds__(256) void ingest_rows_kernel(const void* __restrict__ X, long ldx, const int* __restrict__ cu, int src_packed,
+                                                          int B, int L, int d, int n_rows, bf16_t* __restrict__ P16, float* __restrict__ P32,
+                                                          uint8_t* __restrict__ Pq, uint8_t* __restrict__ Ps, long lds,
+                                                          long long* __restrict__ rows) {
+  typedef __attribute__((ext_vector_type(2))) int i32x2;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wave-uniform: the search is scalar loads
+  if (r >= n_rows) return;
+  const int nchunk = d >> 3;
+  long src = r;
+  bool real = true;
+  if (cu != nullptr) {
+    int lo = 0, hi = B;                     // largest b in [0, B] with cu[b] <= r  (b == B: beyond the last sequence)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (cu[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    const int b = lo, l = r - cu[b];
+    const long padded = (long)b * L + l;
+    real = b < B && l >= 0 && (src_packed != 0 || l < L);
+    src = src_packed != 0 ? (long)r : padded;
+    if (rows != nullptr && lane == 0) rows[r] = padded;
+  }
+  constexpr int ESZ = XT == 0 ? 4 : 2;
+  const char* xrow = (const char*)X + src * ldx * ESZ;
+  for (int cb = 0; cb < nchunk; cb += 64 * NCH) {      // one pass = 512 * NCH columns (d <= 2048: a single pass)
+    f32x4 w0[NCH], w1[XT == 0 ? NCH : 1];          // the raw 16-byte words of the row: fp32 takes two per chunk
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = cb + lane + 64 * c;
+      w0[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (XT == 0) w1[XT == 0 ? c : 0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (real && ch < nchunk) {
+        w0[c] = *(const f32x4*)(xrow + (long)ch * 8 * ESZ);
+        if (XT == 0) w1[XT == 0 ? c : 0] = *(const f32x4*)(xrow + (long)ch * 8 * ESZ + 16);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = cb + lane + 64 * c;
+      float f[8];
+      bf16x8 h;
+      if (XT == 0) {
+        const f32x4 a = w0[c], b4 = w1[XT == 0 ? c : 0];
+        f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b4[0]; f[5] = b4[1]; f[6] = b4[2]; f[7] = b4[3];
+        h = f32_to_bf8(f);
+      } else if (XT == 1) {
+        h = __builtin_bit_cast(bf16x8, w0[c]);       // a bf16 source is copied, not converted
+        bf8_to_f32(h, f);
+      } else {
+        const f16x8 v = __builtin_bit_cast(f16x8, w0[c]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
+        h = f32_to_bf8(f);
+      }
+      const long off = (long)r * d + ch * 8;
+      if (ch < nchunk) {
+        if (P32 != nullptr) {
+          *(f32x4*)(P32 + off) = (f32x4){f[0], f[1], f[2], f[3]};
+          *(f32x4*)(P32 + off + 4) = (f32x4){f[4], f[5], f[6], f[7]};
+        }
+        if (P16 != nullptr) *(bf16x8*)(P16 + off) = h;
+      }
+      if (MXQ) {                                     // every lane reaches mx8_block (r and `real` are wave-uniform)
+        int e;
+        float o[8];
+        bf8_to_f32(h, o);
+        const i32x2 q = mx8_block(o, e);
+        if (ch < nchunk) {
+          *(i32x2*)(Pq + off) = q;
+          if ((lane & 3) == 0) Ps[(long)(ch >> 2) * lds + r] = (uint8_t)e;
+        }
+      }
+    }
+  }
+}
+
+extern "C" int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const int* cu_seqlens, int src_packed, int B, int L, int d,
+                                  int n_rows, void* P16, float* P32, void* Pq, void* Ps, long lds, long long* row_index, hipStream_t st) {
+  HRIEMO_CHECK(X != nullptr && B > 0 && L > 0 && d > 0 && n_rows > 0, "ingest_rows: empty shape (B=%d L=%d d=%d n_rows=%d)", B, L, d, n_rows);
+  HRIEMO_CHECK(d % 8 == 0, "ingest_rows: d=%d must be a multiple of 8", d);
+  HRIEMO_CHECK(x_dtype >= 0 && x_dtype <= 2, "ingest_rows: unknown x_dtype %d (0 fp32, 1 bf16, 2 fp16)", x_dtype);
+  HRIEMO_CHECK(P16 != nullptr || P32 != nullptr || Pq != nullptr, "ingest_rows: no output given");
+  HRIEMO_CHECK(Pq != nullptr || Ps == nullptr, "ingest_rows: scales without the fp8 bytes");
+  if (Pq != nullptr) {
+    HRIEMO_CHECK(Ps != nullptr && d % 32 == 0, "ingest_rows: the MX-fp8 copy needs its scale buffer and d %% 32 == 0 (d=%d)", d);
+    HRIEMO_CHECK(lds >= n_rows && lds % 256 == 0, "ingest_rows: scale rows must be padded to a multiple of 256 (lds=%ld, n_rows=%d)", lds, n_rows);
+  }
+  if (cu_seqlens == nullptr) {
+    HRIEMO_CHECK(row_index == nullptr && src_packed == 0, "ingest_rows: row_index / src_packed need cu_seqlens");
+    HRIEMO_CHECK((long)n_rows == (long)B * L, "ingest_rows: without cu_seqlens n_rows=%d must be B*L=%ld", n_rows, (long)B * L);
+  }
+  const int esz = x_dtype == 0 ? 4 : 2;
+  HRIEMO_CHECK(ldx >= d && (ldx * esz) % 16 == 0, "ingest_rows: source row stride %ld (d=%d) must be >= d and a multiple of 16 bytes", ldx, d);
+  HRIEMO_CHECK(((uintptr_t)X % 16) == 0 && ((uintptr_t)P16 % 16) == 0 && ((uintptr_t)P32 % 16) == 0 && ((uintptr_t)Pq % 16) == 0 &&
+               ((uintptr_t)Ps % 16) == 0 && ((uintptr_t)row_index % 8) == 0, "ingest_rows: unaligned operand");
+  const int nch = (d / 8 + 63) / 64;
+  const dim3 grid((n_rows + 3) / 4);
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define ICALL(T, N, Q) hipLaunchKernelGGL((ingest_rows_kernel<T, N, Q>), grid, dim3(256), 0, st, X, ldx, cu_seqlens, src_packed, B, L, d, n_rows, \
+                                          (bf16_t*)P16, P32, (uint8_t*)Pq, (uint8_t*)Ps, lds, row_index)
+#define INCH(T, Q)                              \
+  if (nch <= 1) { ICALL(T, 1, Q); }             \
+  else if (nch <= 2) { ICALL(T, 2, Q); }        \
+  else { ICALL(T, 4, Q); }
+#define IMXQ(T) if (Pq != nullptr) { INCH(T, true) } else { INCH(T, false) }
+  if (x_dtype == 0) { IMXQ(0) } else if (x_dtype == 1) { IMXQ(1) } else { IMXQ(2) }
+#undef IMXQ
+#undef INCH
+#undef ICALL
+  HRIEMO_LAUNCH_CHECK("ingest_rows_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)n_rows * d * (esz + (P16 ? 2.0 : 0.0) + (P32 ? 4.0 : 0.0) + (Pq ? 1.0 + 1.0 / 32 : 0.0)));
+  return 0;
+}
+
 extern "C" int hriemo_expand_rows(const float* q, void* out, float* out32, int B, long n, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && n > 0, "expand: empty");
   long g = ((long)B * n + 255) / 256;

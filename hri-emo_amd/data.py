@@ -42,6 +42,23 @@ def collate_seq_batch(batch, loss_type="multi_label", pad_to=None):
     return h_a, m_a, h_t, m_t, labels
 
 
+def collate_seq_packed(batch, loss_type="multi_label"):
+    """The samples of collate_seq_batch for a model's forward_packed: -> (rows_a [sum(lengths_a), d], lengths_a [B] int64,
+    rows_t [sum(lengths_t), d], lengths_t [B] int64, labels) -- the valid rows (mask False) of every utterance back to back, nothing
+    padded on the host and no PAD row on its way to the device.  The padded batch collate_seq_batch builds, gathered at its valid
+    rows, is exactly (rows_a, rows_t); pad_to of forward_packed defaults to the lengths collate_seq_batch would pad to when every
+    utterance's stored rows are valid."""
+    rows_a = torch.cat([xa[~ka] for xa, ka, _, _, _ in batch], dim=0)
+    rows_t = torch.cat([xt[~kt] for _, _, xt, kt, _ in batch], dim=0)
+    len_a = torch.tensor([int((~ka).sum()) for _, ka, _, _, _ in batch], dtype=torch.int64)
+    len_t = torch.tensor([int((~kt).sum()) for _, _, _, kt, _ in batch], dtype=torch.int64)
+    if loss_type == "single_label":
+        labels = torch.tensor([s[4] for s in batch], dtype=torch.long)
+    else:
+        labels = torch.stack([s[4] for s in batch], dim=0)
+    return rows_a, len_a, rows_t, len_t, labels
+
+
 def _valid_extent(mask):
     """1 + index of the last position that is valid for at least one sample (0 if everything is PAD)."""
     any_valid = (~mask).any(dim=0)

@@ -54,8 +54,8 @@ class CrossModalBlock(nn.Module):
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None):
         out_dtype = h_a.dtype
-        a, a32 = _ops.as_pair(h_a)
-        t, t32 = _ops.as_pair(h_t)
+        a, a32 = _ops.entry_pair(h_a)
+        t, t32 = _ops.entry_pair(h_t)
         a, a32, t, t32 = self._fwd_pair(a, a32, t, t32, mask_a, mask_t)
         return _ops.from_pair(a, a32, out_dtype), _ops.from_pair(t, t32, out_dtype)
 
@@ -67,8 +67,8 @@ class CrossModalTransformer(nn.Module):
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None):
         out_dtype = h_a.dtype
-        a, a32 = _ops.as_pair(h_a)
-        t, t32 = _ops.as_pair(h_t)
+        a, a32 = _ops.entry_pair(h_a)
+        t, t32 = _ops.entry_pair(h_t)
         for layer in self.layers:
             a, a32, t, t32 = layer._fwd_pair(a, a32, t, t32, mask_a, mask_t)
         return _ops.from_pair(a, a32, out_dtype), _ops.from_pair(t, t32, out_dtype)

@@ -151,17 +151,20 @@ class CrossModalTransformer(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([CrossModalBlock(d_model, n_heads, dropout) for _ in range(num_layers)])
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=False):
+    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=False, raw=False, plan=None):
         """-> (a, a32, t, t32, maps, (sa, st, sf)): the outputs, the _ops.Seq of their rows and the Seq of the fused memory the gate
         makes of them.  tail: the caller can take the packed tail (_ops.PACKED_TAIL).  When the encoder ran packed, its outputs then
         STAY packed ([1, N, d] pairs) and the layouts are the plan (Seq audio, Seq text, Seq fused) -- the gate and the decoder read
         the packed rows, nothing is scattered back.  Otherwise (and always for forward() below, whose public output is padded) the
-        outputs are unpacked as before and the layouts are the padded ones."""
+        outputs are unpacked as before and the layouts are the padded ones.
+        raw (_ops.INGEST_ROWS): a / t are still the caller's tensors (a32 / t32 None); ONE launch each makes the pairs here, gathered
+        straight into the packed rows where the encoder packs (_ops.ingest_pair).  plan: the caller's packed plan, a / t are already
+        its packed pairs (forward_packed): the encoder runs packed whatever set_varlen says."""
         all_layers_attn = []
-        B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
-        plan = None
+        given = plan is not None
+        B, La, Lt = (plan[0].Breal, plan[0].L, plan[1].L) if given else (a.shape[0], a.shape[1], t.shape[1])
         _ops.FLUSH_SITES.add(self.layers[0]._site[1])        # layer-0 text self-attention: the last text-branch backward (_ops._DeferredWgrad)
-        if _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None:
+        if not given and _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None:
             # SURVEY 8(f) rank 4: the encoder on the valid rows only (prefix masks, as the collate builds them); anything else
             # takes the padded path.  dp.DataParallelStep injects bucketed plans whose lengths are device data (_ops.CTX.seq_override).
             if _ops.CTX.seq_override is not None:
@@ -169,7 +172,12 @@ class CrossModalTransformer(nn.Module):
             else:
                 plan = _ops.seq_plans(mask_a, mask_t, B, La, Lt)
             if plan is not None:
-                (a, a32), (t, t32) = _ops.pack_pair(a, a32, plan[0]), _ops.pack_pair(t, t32, plan[1])
+                if raw:
+                    (a, a32), (t, t32) = _ops.ingest_pair(a, plan[0]), _ops.ingest_pair(t, plan[1])
+                else:
+                    (a, a32), (t, t32) = _ops.pack_pair(a, a32, plan[0]), _ops.pack_pair(t, t32, plan[1])
+        if raw and plan is None:
+            (a, a32), (t, t32) = _ops.ingest_pair(a, _ops.Seq.padded(B, La)), _ops.ingest_pair(t, _ops.Seq.padded(B, Lt))
         for layer in self.layers:
             # (padded: every layer converts the masks itself, as it always did -- a view for bool masks)
             sa, st = plan[:2] if plan is not None else (_ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))
@@ -184,9 +192,10 @@ class CrossModalTransformer(nn.Module):
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
         out_dtype = h_a.dtype
-        a, a32 = _ops.as_pair(h_a)
-        t, t32 = _ops.as_pair(h_t)
-        a, a32, t, t32, maps, _ = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, bool(return_attention))
+        raw = h_a.dim() == 3 and h_t.dim() == 3 and _ops.ingestible(h_a, h_t)
+        a, a32 = (h_a, None) if raw else _ops.as_pair(h_a)
+        t, t32 = (h_t, None) if raw else _ops.as_pair(h_t)
+        a, a32, t, t32, maps, _ = self._fwd_pair(a, a32, t, t32, mask_a, mask_t, bool(return_attention), raw=raw)
         h_a, h_t = _ops.from_pair(a, a32, out_dtype), _ops.from_pair(t, t32, out_dtype)
         if return_attention:
             return h_a, h_t, maps

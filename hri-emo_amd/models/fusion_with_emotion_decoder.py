@@ -80,21 +80,44 @@ class FusionWithEmotionDecoder(nn.Module):
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
         h_a, h_t = self._ensure_3d(h_a), self._ensure_3d(h_t)
-        out_dtype = h_a.dtype
-        need = bool(return_attention)
         # one cast at the boundary; between the sub-modules activations travel as (bf16, fp32-twin) pairs
-        a, a32 = _ops.as_pair(h_a)
-        t, t32 = _ops.as_pair(h_t)
+        # (_ops.INGEST_ROWS: the pairs are made by the encoder's entry, one launch each, packed where it packs)
+        raw = _ops.ingestible(h_a, h_t)
+        a, a32 = (h_a, None) if raw else _ops.as_pair(h_a)
+        t, t32 = (h_t, None) if raw else _ops.as_pair(h_t)
+        return self._run(a, a32, t, t32, mask_a, mask_t, h_t.size(1), h_a.dtype, return_attention, raw=raw)
+
+    def forward_packed(self, rows_a, rows_t, lengths_a, lengths_t, pad_to=None, return_attention=False):
+        """forward for a batch that is already ragged: rows_a / rows_t [sum(lengths), d] (fp32, bf16 or fp16) hold the valid rows of
+        all utterances back to back, lengths_a / lengths_t are host sequences or CPU int tensors.  pad_to = (L_a, L_t), default the
+        batch maxima: the padded lengths the reference's collate would produce -- they key the dropout hash and size the returned
+        attention maps.  One launch per modality takes the rows in (hriemo_ingest_rows); the encoder always runs packed, whatever
+        set_varlen says; packed_tail() decides whether the gate and the decoder stay packed; return_attention needs
+        set_varlen_maps(True).  Returns what forward returns for the padded batch and its masks."""
+        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to)
+        if return_attention and not _ops.varlen_maps():
+            raise ValueError("forward_packed: attention maps of packed rows need set_varlen_maps(True)")
+        _ops._require_gpu(rows_a)
+        plan, (mask_a, mask_t) = _ops.plans_from_lengths(la, lt, La, Lt, rows_a.device)
+        a, a32 = _ops.ingest_pair(rows_a, plan[0], src_packed=True)
+        t, t32 = _ops.ingest_pair(rows_t, plan[1], src_packed=True)
+        return self._run(a, a32, t, t32, mask_a, mask_t, Lt, rows_a.dtype, return_attention, plan=plan)
+
+    def _run(self, a, a32, t, t32, mask_a, mask_t, Lt, out_dtype, return_attention, raw=False, plan=None):
+        """the model behind its entry: a / t as pairs (raw: still the caller's tensors; plan: the packed pairs of that plan)"""
+        need = bool(return_attention)
         _ops.begin_step()
         # the decoder's memory mask needs the two padding masks only (L_fused = T_t, beta_gate_tacfn.py:98-116): built here, not on
         # the decoder's serial chain behind the gate
         # (not needed when the tail stays packed: the fused Seq carries the lengths; masks without a plan build it late)
-        may_pack = _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None and _ops.packed_tail()
-        fused_early = None if may_pack else self._build_fused_mask(mask_a, mask_t, h_t.size(1))
+        may_pack = (plan is not None or (_ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None
+                                         and mask_t is not None)) and _ops.packed_tail()
+        fused_early = None if may_pack else self._build_fused_mask(mask_a, mask_t, Lt)
         ready = self._prefetch_shadows(a.device)
         _ops.CTX.join_scope += 1          # logits, beta and z all depend on both branches: the encoder's gradient joins are safe
         try:                              # seqs: the layouts of a, t and the fused memory (the packed plan when the tail stays packed)
-            a, a32, t, t32, encoder_attns, seqs = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, tail=True)
+            a, a32, t, t32, encoder_attns, seqs = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, need, tail=True, raw=raw,
+                                                                             plan=plan)
         finally:
             _ops.CTX.join_scope -= 1
         if ready is not None:
@@ -102,7 +125,7 @@ class FusionWithEmotionDecoder(nn.Module):
         h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)
         sm = seqs[2]                      # packed tail: the gate read the packed rows, the decoder reads a packed fused memory
         if not sm.packed:
-            sm = sm.with_kpm(fused_early if (fused_early is not None and h_fusion.size(1) == h_t.size(1)) else
+            sm = sm.with_kpm(fused_early if (fused_early is not None and h_fusion.size(1) == Lt) else
                              self._build_fused_mask(mask_a, mask_t, h_fusion.size(1)))
         z, logits, decoder_attns = self.emotion_decoder._fwd(h_fusion, sm, need, out_dtype)
         if return_attention:

@@ -32,3 +32,11 @@ class MoseiFusionWithEmotionDecoder(nn.Module):
         h_a_proj = _ops.LinearFn.apply(h_a, self.audio_proj.weight, self.audio_proj.bias, self._sh)   # :63
         h_t_proj = _ops.LinearFn.apply(h_t, self.text_proj.weight, self.text_proj.bias, self._sh)     # :65
         return self.backbone(h_a_proj, h_t_proj, mask_a, mask_t, return_attention=return_attention)   # :68-79
+
+    def forward_packed(self, rows_a, rows_t, lengths_a, lengths_t, pad_to=None, return_attention=False):
+        """forward for ragged data (FusionWithEmotionDecoder.forward_packed): rows_a [sum(lengths_a), d_audio] and rows_t
+        [sum(lengths_t), d_text]; the two input projections run over the valid rows only"""
+        _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=False)
+        a = _ops.LinearFn.apply(rows_a, self.audio_proj.weight, self.audio_proj.bias, self._sh)
+        t = _ops.LinearFn.apply(rows_t, self.text_proj.weight, self.text_proj.bias, self._sh)
+        return self.backbone.forward_packed(a, t, lengths_a, lengths_t, pad_to=pad_to, return_attention=return_attention)

@@ -256,6 +256,27 @@ int hriemo_pack_rows(const void* X16, const float* X32, const int* cu_seqlens, i
                      long long* row_index, hriemo_stream_t stream);
 int hriemo_unpack_rows(const void* P16, const float* P32, const int* cu_seqlens, int B, int L, int d, void* Y16, float* Y32,
                        hriemo_stream_t stream);
+/* Module inputs in one launch: the caller's tensor X (x_dtype 0 fp32, 1 bf16, 2 fp16; row stride ldx elements) -> the rows the
+ * first encoder layer reads.  Destination rows r in [0, n_rows):
+ *  - with cu_seqlens (int32 [B+1], device): b = the largest index with cu[b] <= r, l = r - cu[b]; the row is real when b < B (then
+ *    l < cu[b+1] - cu[b]); rows from cu[B] on are the surplus of a bucket plan.  src_packed = 0: X is the padded [B, L, d] tensor,
+ *    the source row is b*L + l (hriemo_pack_rows' gather).  src_packed = 1: X is already packed [cu[B], d], the source row is r.
+ *  - cu_seqlens = NULL: the padded layout is kept, n_rows must equal B*L, the source row is r, row_index must be NULL.
+ * Outputs, each optional, at least one given:
+ *  - P32 [n_rows][d]: the exact fp32 value of the source element;  P16 [n_rows][d]: its round-to-nearest-even bf16 (a bf16 source
+ *    is copied);
+ *  - Pq / Ps: the MX-fp8 form of the ROUNDED bf16 values, bit-identical to hriemo_quant_mx8 of P16: e4m3 bytes [n_rows][d], E8M0
+ *    scales [d/32][lds] with the scale byte of row r in column r; lds >= n_rows and a multiple of 256 (hriemo_mx8_scale_ld),
+ *    d % 32 == 0; columns >= n_rows of Ps are not written;
+ *  - row_index[r] (int64 [n_rows]): b*L + l, exactly what hriemo_pack_rows writes.
+ * Surplus rows get zeros in P16 and P32, zero bytes in Pq and zero scale bytes in Ps.  A source row that is not real (a PAD row of
+ * a padded source, a row past cu[B] of a packed one) is never read.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): an empty shape; d % 8 != 0; Pq without Ps (or Ps
+ * without Pq) or with d % 32 != 0; lds < n_rows or lds % 256 != 0; a base pointer that is not 16-byte aligned; ldx < d or a
+ * source row stride that is not a multiple of 16 bytes; an unknown x_dtype; row_index or src_packed without cu_seqlens; no
+ * output at all. */
+int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const int* cu_seqlens, int src_packed, int B, int L, int d, int n_rows,
+                       void* P16, float* P32, void* Pq, void* Ps, long lds, long long* row_index, hriemo_stream_t stream);
 long hriemo_add_ln_bwd_workspace_bytes(int M, int d);
 int hriemo_add_ln_bwd(const void* dY, const void* G, const void* X, const float* X32, const float* gamma, const float* mean,
                       const float* rstd, void* dX, void* dG, float* dgamma, float* dbeta, float* dbias, int accumulate,
