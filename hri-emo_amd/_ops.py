@@ -1754,6 +1754,22 @@ def plans_from_lengths(la, lt, La, Lt, device):
     return plans, masks
 
 
+def seq_tables(lens, La, Lt, rows=(0, 0), cu=(None, None, None), masks=(None, None, None)):
+    """The tables of a ragged batch from its lengths in DEVICE memory, ONE launch (hriemo_seq_tables): lens int32 [2, B] (audio row,
+    text row; already checked on the host, packed_lengths) -> cu = (cu_a, cu_t, cu_f) int32 [B+2] each, closed by the bucket row
+    counts rows = (audio, text), and masks = (mask_a [B, La], mask_t [B, Lt], mask_f [B, Lt]) uint8, 1 = PAD.  Every output is
+    optional; the ones given are overwritten in place, so a captured step that starts with this launch follows the lengths."""
+    _require_gpu(lens)
+    B = lens.shape[1]
+    if lens.dtype != torch.int32 or lens.dim() != 2 or lens.shape[0] != 2 or not lens.is_contiguous():
+        raise ValueError(f"seq_tables: lengths of shape {tuple(lens.shape)} / {lens.dtype} (expected contiguous int32 [2, B])")
+    for t, n, size in zip(tuple(cu) + tuple(masks), (B + 2,) * 3 + (B * La, B * Lt, B * Lt), (4,) * 3 + (1,) * 3):
+        if t is not None and not (t.is_contiguous() and t.numel() == n and t.element_size() == size):
+            raise ValueError(f"seq_tables: an output of shape {tuple(t.shape)} / {t.dtype} does not hold its {n} elements")
+    _lib.call("hriemo_seq_tables", _p(lens[0]), _p(lens[1]), B, int(La), int(Lt), int(rows[0]), int(rows[1]), _p(cu[0]), _p(cu[1]), _p(cu[2]),
+              _p(masks[0]), _p(masks[1]), _p(masks[2]), _stream())
+
+
 # ----------------------------------------------------------------------------- sub-layer Functions
 class _GradModeAware:
     """Function.forward always runs with grad mode off, and ctx.needs_input_grad mirrors the inputs' requires_grad even under

@@ -1745,6 +1745,122 @@ extern "C" int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const in
   return 0;
 }
 
+// ---- the sequence tables of a ragged batch: ONE launch from the lengths to everything a packed step reads -----------------------
+// la / lt (int32 [B], device; clamped to [1, La] / [1, Lt] for memory safety) -> cu_a, cu_t, cu_f (int32 [B+2] = [0, inclusive
+// prefix sums ..., the bucket's row count]; fused length = min of the two) and the dense uint8 key-padding masks [B, La], [B, Lt],
+// [B, Lt] (1 = PAD).  Block 0 does the three prefix sums: 256 sequences per trip, an inclusive scan inside every wave by shuffles,
+// the four wave totals and the running carry through 12 + 3 LDS words.  Blocks 1.. write the masks straight from the lengths, four
+// bytes per lane: the masks laid end to end are cut into the 32-bit words of each mask's own (rounded-down) base address, a word
+// that lies inside its mask leaves as one store, the words across a mask's two ends byte by byte -- nothing outside is touched.
+__device__ __forceinline__ int seq_len_clamped(const int* __restrict__ p, int b, int L) { return min(max(p[b], 1), L); }
+__device__ __forceinline__ void seq_mask_words(uint8_t* __restrict__ M, const int* __restrict__ la, const int* __restrict__ lt, int B, int L,
+                                               int La, int Lt, long w0, long wstep) {
+  // lt == nullptr: the mask of `la` over L columns; else the fused mask (min of the two lengths) over L = Lt columns
+  const long total = (long)B * L;
+  const int shift = (int)((uintptr_t)M & 3);
+  uint8_t* base = M - shift;
+  const long nwords = (total + shift + 3) >> 2;
+  for (long w = w0; w < nwords; w += wstep) {
+    const long j0 = w * 4 - shift;                     // mask element of the word's first byte (< 0: in front of the mask)
+    unsigned word = 0;
+    const bool whole = j0 >= 0 && j0 + 4 <= total;
+    const long jf = j0 > 0 ? j0 : 0;                   // one division per word: (b, l) of its first element inside the mask
+    int b = (int)(jf / L), l = (int)(jf - (long)b * L);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long j = j0 + k;
+      if (j < 0 || j >= total) continue;
+      int len = seq_len_clamped(la, b, La);
+      if (lt != nullptr) len = min(len, seq_len_clamped(lt, b, Lt));
+      const unsigned pad = l >= len ? 1u : 0u;
+      if (whole) word |= pad << (8 * k);
+      else base[w * 4 + k] = (uint8_t)pad;
+      if (++l == L) { l = 0; ++b; }
+    }
+    if (whole) *(unsigned*)(base + w * 4) = word;
+  }
+}
+__global__ __launch_bounds__(256) void seq_tables_kernel(const int* __restrict__ la, const int* __restrict__ lt, int B, int La, int Lt,
+                                                         int n_rows_a, int n_rows_t, int* __restrict__ cu_a, int* __restrict__ cu_t,
+                                                         int* __restrict__ cu_f, uint8_t* __restrict__ mask_a, uint8_t* __restrict__ mask_t,
+                                                         uint8_t* __restrict__ mask_f, int scan_blocks) {
+  if ((int)blockIdx.x < scan_blocks) {                 // (scan_blocks is 0 or 1)
+    __shared__ int wtot[3][4];
+    __shared__ int carry[3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < 3) carry[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+      if (cu_a != nullptr) { cu_a[0] = 0; cu_a[B + 1] = n_rows_a; }
+      if (cu_t != nullptr) { cu_t[0] = 0; cu_t[B + 1] = n_rows_t; }
+      if (cu_f != nullptr) { cu_f[0] = 0; cu_f[B + 1] = n_rows_t; }
+    }
+    for (int b0 = 0; b0 < B; b0 += 256) {
+      const int b = b0 + threadIdx.x;
+      int v[3] = {0, 0, 0};
+      if (b < B) {
+        v[0] = seq_len_clamped(la, b, La);
+        v[1] = seq_len_clamped(lt, b, Lt);
+        v[2] = min(v[0], v[1]);
+      }
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {               // inclusive scan inside the wave
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const int up = __shfl_up(v[k], o);
+          if (lane >= o) v[k] += up;
+        }
+      }
+      __syncthreads();                                 // the previous trip's reads of wtot / carry are done
+      if (lane == 63) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wtot[k][wave] = v[k];
+      }
+      __syncthreads();
+      int add[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        add[k] = carry[k];
+        for (int w = 0; w < wave; ++w) add[k] += wtot[k][w];
+      }
+      if (b < B) {
+        if (cu_a != nullptr) cu_a[b + 1] = v[0] + add[0];
+        if (cu_t != nullptr) cu_t[b + 1] = v[1] + add[1];
+        if (cu_f != nullptr) cu_f[b + 1] = v[2] + add[2];
+      }
+      __syncthreads();                                 // everyone has read the carry
+      if (threadIdx.x < 3) carry[threadIdx.x] += wtot[threadIdx.x][0] + wtot[threadIdx.x][1] + wtot[threadIdx.x][2] + wtot[threadIdx.x][3];
+    }
+    return;
+  }
+  const long w0 = (long)((int)blockIdx.x - scan_blocks) * 256 + threadIdx.x;
+  const long wstep = (long)((int)gridDim.x - scan_blocks) * 256;
+  if (mask_a != nullptr) seq_mask_words(mask_a, la, nullptr, B, La, La, Lt, w0, wstep);
+  if (mask_t != nullptr) seq_mask_words(mask_t, lt, nullptr, B, Lt, Lt, Lt, w0, wstep);
+  if (mask_f != nullptr) seq_mask_words(mask_f, la, lt, B, Lt, La, Lt, w0, wstep);
+}
+extern "C" int hriemo_seq_tables(const int* lengths_a, const int* lengths_t, int B, int La, int Lt, int n_rows_a, int n_rows_t, int* cu_a,
+                                 int* cu_t, int* cu_f, unsigned char* mask_a, unsigned char* mask_t, unsigned char* mask_f, hipStream_t st) {
+  HRIEMO_CHECK(B >= 1 && La >= 1 && Lt >= 1 && Lt <= La, "seq_tables: bad shape (B=%d La=%d Lt=%d; L_t <= L_a)", B, La, Lt);
+  HRIEMO_CHECK(lengths_a != nullptr && lengths_t != nullptr, "seq_tables: both length arrays are needed");
+  HRIEMO_CHECK(cu_a != nullptr || cu_t != nullptr || cu_f != nullptr || mask_a != nullptr || mask_t != nullptr || mask_f != nullptr,
+               "seq_tables: no output given");
+  HRIEMO_CHECK(cu_a == nullptr || n_rows_a > 0, "seq_tables: cu_a needs the audio bucket's row count (n_rows_a=%d)", n_rows_a);
+  HRIEMO_CHECK((cu_t == nullptr && cu_f == nullptr) || n_rows_t > 0, "seq_tables: cu_t / cu_f need the text bucket's row count (n_rows_t=%d)", n_rows_t);
+  HRIEMO_CHECK(((uintptr_t)lengths_a % 4) == 0 && ((uintptr_t)lengths_t % 4) == 0 && ((uintptr_t)cu_a % 4) == 0 && ((uintptr_t)cu_t % 4) == 0 &&
+               ((uintptr_t)cu_f % 4) == 0, "seq_tables: unaligned int32 operand");
+  const int scan_blocks = (cu_a != nullptr || cu_t != nullptr || cu_f != nullptr) ? 1 : 0;
+  int mask_blocks = 0;
+  if (mask_a != nullptr || mask_t != nullptr || mask_f != nullptr) {
+    const long words = ((long)B * La + 6) / 4;         // the longest mask in 32-bit words (an unaligned base adds up to one)
+    const long blocks = (words + 255) / 256;
+    mask_blocks = (int)(blocks < 256 ? blocks : 256);
+  }
+  hipLaunchKernelGGL(seq_tables_kernel, dim3(scan_blocks + mask_blocks), dim3(256), 0, st, lengths_a, lengths_t, B, La, Lt, n_rows_a, n_rows_t,
+                     cu_a, cu_t, cu_f, mask_a, mask_t, mask_f, scan_blocks);
+  HRIEMO_LAUNCH_CHECK("seq_tables_kernel");
+  return 0;
+}
+
 extern "C" int hriemo_expand_rows(const float* q, void* out, float* out32, int B, long n, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && n > 0, "expand: empty");
   long g = ((long)B * n + 255) / 256;

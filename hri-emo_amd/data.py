@@ -107,11 +107,19 @@ class DevicePrefetcher:
     (tests, gloo rehearsals).  ``mask_slots=(i, j)``: the tuple entries that are the audio / text padding masks -- the batch is
     handed out with one more element, ``(audio lengths, text lengths)`` as Python lists counted on the HOST copy of the masks, which
     is what ``DataParallelStep.step(..., lengths=)`` wants in packed (varlen) mode instead of reading the masks back from the
-    device."""
+    device.
 
-    def __init__(self, loader, device, depth=2, convert=None, dtypes=None, mask_slots=None):
+    ``ragged={slot: capacity_rows}``: the tuple entries whose FIRST dimension changes from batch to batch (the packed rows of
+    ``collate_seq_packed``).  Their pinned staging and device buffers are allocated once, ``capacity_rows`` long (B * L covers any
+    batch); a batch copies only its own ``n`` rows and is handed out as the ``[:n]`` view of the device buffer, so the buffers --
+    and their addresses -- stay put while the row count changes with every batch.  Entries not named keep the behaviour above
+    (buffers per shape).  An entry that is no tensor (the lengths as Python lists, which ``DataParallelStep.step_packed`` wants
+    on the host) passes through like None."""
+
+    def __init__(self, loader, device, depth=2, convert=None, dtypes=None, mask_slots=None, ragged=None):
         self.loader, self.device, self.depth = loader, torch.device(device), max(2, int(depth))
         self.convert, self.dtypes, self.mask_slots = convert, dtypes, mask_slots
+        self.ragged = {int(k): int(v) for k, v in (ragged or {}).items()}
         self.cuda = self.device.type == "cuda"
         self._ring = [None] * self.depth          # slot -> {"host": [...], "dev": [...], "copied": event, "released": event}
         self._copy_stream = torch.cuda.Stream(device=self.device) if self.cuda else None
@@ -129,29 +137,43 @@ class DevicePrefetcher:
         if not self.cuda:
             return tensors + extra, None
         ent = self._ring[slot]
-        shapes = [None if t is None else (tuple(t.shape), t.dtype) for t in tensors]
+        is_t = [isinstance(t, torch.Tensor) for t in tensors]
+        for i, cap in self.ragged.items():
+            if is_t[i] and tensors[i].shape[0] > cap:
+                raise ValueError(f"DevicePrefetcher: entry {i} has {tensors[i].shape[0]} rows, its ragged capacity is {cap}")
+        # a ragged entry is keyed (and its buffers are sized) by its capacity, not by the batch's row count
+        full = [None if not ok else ((self.ragged[i],) + tuple(t.shape[1:]) if i in self.ragged else tuple(t.shape))
+                for i, (t, ok) in enumerate(zip(tensors, is_t))]
+        shapes = [None if f is None else (f, t.dtype) for f, t in zip(full, tensors)]
         if ent is None or ent["shapes"] != shapes:
             ent = {"shapes": shapes,
-                   "host": [None if t is None else torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in tensors],
-                   "dev": [None if t is None else torch.empty(t.shape, dtype=t.dtype, device=self.device) for t in tensors],
+                   "host": [None if f is None else torch.empty(f, dtype=t.dtype).pin_memory() for f, t in zip(full, tensors)],
+                   "dev": [None if f is None else torch.empty(f, dtype=t.dtype, device=self.device) for f, t in zip(full, tensors)],
                    "copied": torch.cuda.Event(), "released": None}
             self._ring[slot] = ent
         if ent["released"] is not None:
             ent["released"].synchronize()          # the step that read this slot's device buffers has finished
-        src = []
-        for h, t in zip(ent["host"], tensors):
-            if t is None or t.is_pinned():         # a loader with pin_memory=True hands pinned tensors over: copied from there
+        src, out = [], []
+        for i, (h, d_, t) in enumerate(zip(ent["host"], ent["dev"], tensors)):
+            if not is_t[i]:
+                src.append(None)
+                out.append(t)
+                continue
+            if i in self.ragged:                   # this batch's rows only; the views keep the buffers' base addresses
+                h, d_ = h[:t.shape[0]], d_[:t.shape[0]]
+            if t.is_pinned():                      # a loader with pin_memory=True hands pinned tensors over: copied from there
                 src.append(t)
             else:
                 h.copy_(t)                         # pageable -> pinned staging (host memcpy)
                 src.append(h)
+            out.append(d_)
         ent["src"] = src                           # referenced until the slot is staged again: the copy below is asynchronous
         with torch.cuda.stream(self._copy_stream):
-            for h, d_ in zip(src, ent["dev"]):
+            for h, d_ in zip(src, out):
                 if h is not None:
                     d_.copy_(h, non_blocking=True)
             ent["copied"].record(self._copy_stream)
-        return tuple(ent["dev"]) + extra, ent
+        return tuple(out) + extra, ent
 
     def __iter__(self):
         it = iter(self.loader)

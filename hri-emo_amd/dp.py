@@ -27,6 +27,16 @@ _VARLEN_BUCKETS = max(1, int(os.environ.get("HRIEMO_VARLEN_BUCKETS", "64")))
 _VARLEN_MAX_GRAPHS = max(1, int(os.environ.get("HRIEMO_VARLEN_MAX_GRAPHS", "48")))
 
 
+def bucket_rows(n, B, L):
+    """Row count of the packed (varlen) bucket that holds `n` valid rows of a modality padded to [B, L]: the next multiple of the
+    granule g = max(8, B*L / _VARLEN_BUCKETS rounded down to a multiple of 8), g capped at L -- always > n (the surplus rows form
+    ONE extra sequence, which is never empty and never longer than L).  The one place this arithmetic lives: the mask-fed
+    (_packed_key) and the ragged (step_packed) front doors of DataParallelStep both call it."""
+    g = max(8, (B * L) // _VARLEN_BUCKETS // 8 * 8)
+    g = min(g, L)                         # the surplus rows are ONE sequence of at most L rows
+    return (n // g + 1) * g               # > n: the extra sequence is never empty
+
+
 class GradBuckets:
     """comm_dtype: torch.float32 (default: the flat buffer is all-reduced in place) or torch.bfloat16: every bucket is cast to a
     bf16 staging buffer (half the bytes on the xGMI links: 109 MB instead of 218 MB per step at cfg 2), summed by the collective in
@@ -292,8 +302,19 @@ class DataParallelStep:
             self.model.set_batch_offset(lo)
         return lo, hi
 
-    def _fwd_bwd(self, h_a, h_t, m_a, m_t, y, zero=True, scale=None):
+    def _fwd_bwd(self, h_a, h_t, m_a, m_t, y, zero=True, scale=None, ragged=None):
+        """ragged = (audio lengths, text lengths, pad_to): h_a / h_t are a ragged batch's own rows (the eager forward_packed step).
+        After capture_packed, without `ragged`: h_a / h_t are the static row sources and the step starts with hriemo_seq_tables."""
         from . import _ops
+        front = self._pb.get("front") if (self._pb is not None and ragged is None) else None
+        if front is not None:
+            # the first launch of the packed arm, warm-up passes included: the lengths [2, B] -> the three cu_seqlens of the bucket
+            # in force and the three masks; everything behind it reads those static buffers
+            seqs = _ops.CTX.seq_override
+            if seqs is None:
+                raise RuntimeError("DataParallelStep: after capture_packed() the static rows are fed by step_packed() only")
+            _ops.seq_tables(front["lens"], self._pb["La"], self._pb["Lt"], rows=(seqs[0].N, seqs[1].N),
+                            cu=(self._pb["cu_a"], self._pb["cu_t"], self._pb["cu_f"]), masks=front["masks"])
         # collectives launched from the gradient-ready hooks run BESIDE backward (eagerly, or baked into a capture): the loader /
         # consumer GEMMs then draw their tiles from the work queue (a block whose CU a collective holds late draws fewer); with
         # the chip to itself they walk statically, which is 5-8 % faster per launch alone and equal inside the step (DESIGN.md 3.1)
@@ -304,7 +325,12 @@ class DataParallelStep:
             _ops.gemm_contended(bool(self.force_queue), force=True)
         if zero:
             self.buckets.zero_grad()
-        logits, beta, _ = self.model(h_a, h_t, m_a, m_t)
+        if ragged is not None:
+            logits, beta, _ = self.model.forward_packed(h_a, h_t, ragged[0], ragged[1], pad_to=ragged[2])
+        elif front is not None:
+            logits, beta, _ = self.model._forward_rows(h_a, h_t, tuple(seqs), front["bool"], (self._pb["La"], self._pb["Lt"]))
+        else:
+            logits, beta, _ = self.model(h_a, h_t, m_a, m_t)
         loss = self.loss_fn(logits, beta, y)
         if scale is not None:
             loss = loss * scale
@@ -398,6 +424,133 @@ class DataParallelStep:
         if collectives:
             self.buckets.suspended = True         # from now on hooks fire only inside replays (they are baked into the graph)
 
+    @_in_step_context
+    def capture_packed(self, rows_a, rows_t, lengths_a, lengths_t, y, pad_to, optimizer=None, collectives=False):
+        """capture() for batches that arrive ragged (data.collate_seq_packed): rows_a / rows_t [sum(lengths), d] (fp32, bf16 or fp16; on
+        the device or in pinned host memory) hold the valid rows of all utterances back to back, lengths_a / lengths_t are host
+        sequences or CPU int tensors, pad_to = (L_a, L_t) the padded lengths: they size the static buffers, key the dropout hash and fix
+        the gate's L.  pad_to and the number of utterances are fixed from here on; ``step_packed`` then serves every batch.
+
+        Static state: one row source per modality in the rows' dtype, zero-initialised and as long as the LARGEST bucket (a full
+        batch of B*L rows still gets its surplus sequence, bucket_rows); the lengths as ONE int32 [2, B] block on the device with a
+        pinned host twin; the three cu_seqlens buffers and three mask buffers of packed mode; y.  The captured step starts with
+        hriemo_seq_tables, which derives the cu_seqlens and the masks from the lengths block, then runs the model's forward_packed
+        body on a bucket plan (hriemo_ingest_rows on the packed source): no padded tensor exists on the host or on the device, and
+        the lengths cross to the device once.  Behind the front door everything is the mask-fed packed step: the bucket graphs
+        (one per (audio rows, text rows) bucket, LRU-capped, one memory pool), packed_tail(), fp32 precision, mx_fp8,
+        optimizer=DeviceAdamW.  The encoder runs packed whatever set_varlen says, as in forward_packed.  collectives=True at world
+        size > 1 is refused for the reason capture() gives in packed mode."""
+        from . import _ops
+        if not hasattr(self.model, "_forward_rows"):
+            raise TypeError("capture_packed: the model has no forward_packed entry")
+        same_width = not hasattr(self.model, "audio_proj")
+        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
+        if pad_to is None:
+            raise ValueError("capture_packed: pad_to=(L_a, L_t) is required")
+        dev = next(self.model.parameters()).device
+        _ops._require_gpu(next(self.model.parameters()))
+        if optimizer is not None:
+            from .optim import DeviceAdamW
+            if not isinstance(optimizer, DeviceAdamW) or optimizer.buckets is not self.buckets:
+                raise TypeError("capture_packed(optimizer=...) takes an optim.DeviceAdamW built on this step's buckets")
+            if self.world > 1:
+                raise RuntimeError("capture_packed(optimizer=...) at world size > 1: the gradient exchange after the replay would run "
+                                   "behind the captured update (packed mode captures no collectives)")
+        if collectives and self.world > 1:
+            raise RuntimeError("capture_packed(collectives=True): ranks meet new buckets at different steps and a bucket's capture runs "
+                               "eager warm-up exchanges -- capture without collectives (exchange after the replay)")
+        if collectives and not self.buckets._hooks:
+            raise RuntimeError("capture_packed(collectives=True) needs the gradient-ready hooks: GradBuckets(force_exchange=True)")
+        if not collectives and self.buckets._hooks and not self.buckets.suspended:
+            raise RuntimeError("capture_packed() needs GradBuckets(overlap=False) or buckets.suspended = True")
+        if collectives:
+            self.buckets.suspended = False
+        self.release_graph()
+        self._collectives = bool(collectives)
+        self._optimizer = optimizer
+        B = len(la)
+        cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
+        src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
+        src_t = torch.zeros(cap_t, rows_t.shape[1], dtype=rows_t.dtype, device=dev)
+        self._static = [src_a, src_t, None, None, y.to(dev, copy=True)]
+        masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
+        cu = lambda: torch.zeros(B + 2, dtype=torch.int32, device=dev)     # noqa: E731
+        self._pb = {"graphs": collections.OrderedDict(), "B": B, "La": La, "Lt": Lt, "cu_a": cu(), "cu_t": cu(), "cu_f": cu(),
+                    "front": {"lens": torch.ones(2, B, dtype=torch.int32, device=dev), "lens_host": torch.ones(2, B, dtype=torch.int32).pin_memory(),
+                              "lens_copied": None, "masks": masks, "bool": tuple(m.view(torch.bool) for m in masks),
+                              "same_width": same_width}}
+        key = self._load_packed(rows_a, rows_t, la, lt, y)
+        rec = self._packed_graph(key)
+        self._graph, self._static_loss, self._keep = rec["graph"], rec["loss"], []
+        self._packed = True
+        self._mask_seen = {}
+        self._replay = True
+        self._exchange_in_graph = bool(collectives)
+        if collectives:
+            self.buckets.suspended = True
+
+    def _load_packed(self, rows_a, rows_t, la, lt, y):
+        """a checked ragged batch into the static state -> its bucket key: the rows to the head of each source, zeros from there to
+        the bucket's end (the MOSEI projections read every bucket row), the lengths as one [2, B] block through the pinned twin, y"""
+        pb = self._pb
+        front, B = pb["front"], pb["B"]
+        key = (bucket_rows(sum(la), B, pb["La"]), bucket_rows(sum(lt), B, pb["Lt"]))
+        for src, rows, n, n_rows in ((self._static[0], rows_a, sum(la), key[0]), (self._static[1], rows_t, sum(lt), key[1])):
+            if rows.data_ptr() != src.data_ptr():
+                src[:n].copy_(rows, non_blocking=True)
+            src[n:n_rows].zero_()
+        if front["lens_copied"] is not None:
+            front["lens_copied"].synchronize()        # the previous batch's lengths have left the pinned twin
+        front["lens_host"].copy_(torch.tensor([la, lt], dtype=torch.int32))
+        front["lens"].copy_(front["lens_host"], non_blocking=True)
+        front["lens_copied"] = torch.cuda.Event()
+        front["lens_copied"].record()
+        if y.data_ptr() != self._static[4].data_ptr():
+            self._static[4].copy_(y, non_blocking=True)
+        return key
+
+    @_in_step_context
+    def step_packed(self, rows_a, rows_t, lengths_a, lengths_t, y):
+        """One trainer step on a ragged batch (capture_packed): the arguments are checked on the host (_ops.packed_lengths; a
+        ValueError leaves the static state untouched), the rows, the lengths block and y are copied into the static buffers, the
+        batch's bucket graph is picked -- or captured on the spot -- and replayed.  A batch with another number of utterances than
+        captured is refused: drop it, or run it with use_graph(False), which makes this the eager forward_packed step."""
+        from . import _ops
+        front = self._pb.get("front") if self._pb is not None else None
+        if front is None:
+            raise RuntimeError("step_packed needs capture_packed() first")
+        pb = self._pb
+        B, pad = pb["B"], (pb["La"], pb["Lt"])
+        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front["same_width"])
+        replay = self._graph is not None and getattr(self, "_replay", True)
+        if replay:
+            if len(la) != B:
+                raise ValueError(f"step_packed: a batch of {len(la)} utterances; the captured step holds B = {B} (drop the batch or run it "
+                                 "with use_graph(False))")
+            for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
+                if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
+                    raise ValueError(f"step_packed: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
+            if tuple(y.shape) != tuple(self._static[4].shape):
+                raise ValueError(f"step_packed: targets of shape {tuple(y.shape)}; captured with {tuple(self._static[4].shape)}")
+            if self._optimizer is not None:
+                self._optimizer._upload_hyper()
+            key = self._load_packed(rows_a, rows_t, la, lt, y)
+            rec = self._packed_graph(key)                 # captures on the static state (already this batch) if the bucket is new
+            rec["graph"].replay()
+            if not self._exchange_in_graph:
+                self.buckets.finish()
+            if self._optimizer is not None:
+                _ops.bump_weights_epoch()
+                self._optimizer._opt_called = True
+            return rec["loss"]
+        dev = self._static[0].device
+        loss = self._fwd_bwd(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), None, None, y.to(dev, non_blocking=True),
+                             ragged=(la, lt, pad))
+        self.buckets.finish()
+        if self._optimizer is not None:
+            self._optimizer.step()
+        return loss
+
     # ---- packed (varlen) bucket graphs
     def _packed_key(self, m_a, m_t, lengths):
         """host-side: the batch's cu_seqlens written to the static device buffers + the bucket (rows audio, rows text) it needs"""
@@ -421,10 +574,7 @@ class DataParallelStep:
         out = []
         lf = [min(x, y) for x, y in zip(la, lt)]      # the fused memory of a sample: the reference ORs the two prefix masks
         for lens, L, buf in ((la, La, pb["cu_a"]), (lt, Lt, pb["cu_t"])):
-            g = max(8, (B * L) // _VARLEN_BUCKETS // 8 * 8)
-            g = min(g, L)                         # the surplus rows are ONE sequence of at most L rows
-            n = sum(lens)
-            rows = (n // g + 1) * g               # > n: the extra sequence is never empty
+            rows = bucket_rows(sum(lens), B, L)
             cu = [0]
             for x in lens:
                 cu.append(cu[-1] + x)
@@ -553,6 +703,8 @@ class DataParallelStep:
             graph, loss = self._graph, self._static_loss
             if self._optimizer is not None:
                 self._optimizer._upload_hyper()           # host -> device only; the replay reads lr & co. from that block
+            if self._pb is not None and "front" in self._pb:
+                raise RuntimeError("DataParallelStep: this step was captured by capture_packed(); feed it with step_packed()")
             if self._pb is not None:
                 # packed mode: any padding masks of the captured shapes; the lengths travel as device data (cu_seqlens), the row
                 # counts pick the bucket graph (captured now if this bucket was not seen before)

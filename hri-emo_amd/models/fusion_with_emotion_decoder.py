@@ -98,13 +98,23 @@ class FusionWithEmotionDecoder(nn.Module):
         if return_attention and not _ops.varlen_maps():
             raise ValueError("forward_packed: attention maps of packed rows need set_varlen_maps(True)")
         _ops._require_gpu(rows_a)
-        plan, (mask_a, mask_t) = _ops.plans_from_lengths(la, lt, La, Lt, rows_a.device)
+        plan, masks = _ops.plans_from_lengths(la, lt, La, Lt, rows_a.device)
+        return self._forward_rows(rows_a, rows_t, plan, masks, (La, Lt), return_attention)
+
+    def _forward_rows(self, rows_a, rows_t, plan, masks, pad, return_attention=False):
+        """forward_packed behind its argument check: the packed rows, their plan (Seq audio, Seq text, Seq fused), the padded bool
+        masks (mask_a [B, L_a], mask_t [B, L_t] and optionally the fused mask [B, L_t], which then stands in for _build_fused_mask
+        when the tail is unpacked) and pad = (L_a, L_t).  dp.DataParallelStep.step_packed calls it with a BUCKET plan (_ops.seq_bucket,
+        _ops.seq_bucket_fused) and masks in device memory that hriemo_seq_tables wrote: rows_a / rows_t may then hold more rows than
+        the batch has (the ingest launch never reads past cu[B])."""
         a, a32 = _ops.ingest_pair(rows_a, plan[0], src_packed=True)
         t, t32 = _ops.ingest_pair(rows_t, plan[1], src_packed=True)
-        return self._run(a, a32, t, t32, mask_a, mask_t, Lt, rows_a.dtype, return_attention, plan=plan)
+        return self._run(a, a32, t, t32, masks[0], masks[1], pad[1], rows_a.dtype, return_attention, plan=plan,
+                         fused_mask=masks[2] if len(masks) > 2 else None)
 
-    def _run(self, a, a32, t, t32, mask_a, mask_t, Lt, out_dtype, return_attention, raw=False, plan=None):
-        """the model behind its entry: a / t as pairs (raw: still the caller's tensors; plan: the packed pairs of that plan)"""
+    def _run(self, a, a32, t, t32, mask_a, mask_t, Lt, out_dtype, return_attention, raw=False, plan=None, fused_mask=None):
+        """the model behind its entry: a / t as pairs (raw: still the caller's tensors; plan: the packed pairs of that plan;
+        fused_mask: the decoder's memory mask [B, L_t] where the caller has it already)"""
         need = bool(return_attention)
         _ops.begin_step()
         # the decoder's memory mask needs the two padding masks only (L_fused = T_t, beta_gate_tacfn.py:98-116): built here, not on
@@ -112,7 +122,7 @@ class FusionWithEmotionDecoder(nn.Module):
         # (not needed when the tail stays packed: the fused Seq carries the lengths; masks without a plan build it late)
         may_pack = (plan is not None or (_ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None
                                          and mask_t is not None)) and _ops.packed_tail()
-        fused_early = None if may_pack else self._build_fused_mask(mask_a, mask_t, Lt)
+        fused_early = None if may_pack else (fused_mask if fused_mask is not None else self._build_fused_mask(mask_a, mask_t, Lt))
         ready = self._prefetch_shadows(a.device)
         _ops.CTX.join_scope += 1          # logits, beta and z all depend on both branches: the encoder's gradient joins are safe
         try:                              # seqs: the layouts of a, t and the fused memory (the packed plan when the tail stays packed)
@@ -124,7 +134,9 @@ class FusionWithEmotionDecoder(nn.Module):
             torch.cuda.current_stream(a.device).wait_event(ready)
         h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)
         sm = seqs[2]                      # packed tail: the gate read the packed rows, the decoder reads a packed fused memory
-        if not sm.packed:
+        if not sm.packed and fused_mask is not None:
+            sm = sm.with_kpm(fused_mask)
+        elif not sm.packed:
             sm = sm.with_kpm(fused_early if (fused_early is not None and h_fusion.size(1) == Lt) else
                              self._build_fused_mask(mask_a, mask_t, h_fusion.size(1)))
         z, logits, decoder_attns = self.emotion_decoder._fwd(h_fusion, sm, need, out_dtype)

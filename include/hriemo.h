@@ -277,6 +277,21 @@ int hriemo_unpack_rows(const void* P16, const float* P32, const int* cu_seqlens,
  * output at all. */
 int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const int* cu_seqlens, int src_packed, int B, int L, int d, int n_rows,
                        void* P16, float* P32, void* Pq, void* Ps, long lds, long long* row_index, hriemo_stream_t stream);
+/* The sequence tables of a ragged batch in one launch: the lengths (int32 [B] each, DEVICE memory) -> every table a packed step
+ * reads, so the lengths are ONE piece of device data and a captured step derives the rest itself.  The kernel clamps a length to
+ * [1, La] / [1, Lt] for memory safety only (the host has refused anything else).  Outputs, each optional, at least one given:
+ *  - cu_a, cu_t (int32 [B+2]): [0, inclusive prefix sums of the lengths ..., n_rows_x] -- the cu_seqlens of a bucket plan whose
+ *    row count is n_rows_x (hriemo_pack_rows / hriemo_ingest_rows read entries 0..B, the attention kernels all B+2);
+ *  - cu_f (int32 [B+2]): the same over lf[b] = min(la[b], lt[b]) (the fused memory), last entry n_rows_t: the fused plan rides in
+ *    the text bucket;
+ *  - mask_a [B, La], mask_t [B, Lt], mask_f [B, Lt]: dense bytes, 1 = PAD: mask_x[b, l] = l >= length_x[b], mask_f[b, l] = l >= lf[b]
+ *    (the OR of the two prefix masks cut to L_t).  Any byte alignment.
+ * Every element of every given output is written, nothing outside it.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): B < 1, La < 1, Lt < 1 or Lt > La; a NULL lengths pointer; no output
+ * at all; n_rows_a <= 0 with cu_a, n_rows_t <= 0 with cu_t or cu_f; an int32 operand that is not 4-byte aligned. */
+int hriemo_seq_tables(const int* lengths_a, const int* lengths_t, int B, int La, int Lt, int n_rows_a, int n_rows_t, int* cu_a,
+                      int* cu_t, int* cu_f, unsigned char* mask_a, unsigned char* mask_t, unsigned char* mask_f,
+                      hriemo_stream_t stream);
 long hriemo_add_ln_bwd_workspace_bytes(int M, int d);
 int hriemo_add_ln_bwd(const void* dY, const void* G, const void* X, const float* X32, const float* gamma, const float* mean,
                       const float* rstd, void* dX, void* dG, float* dgamma, float* dbeta, float* dbias, int accumulate,
