@@ -106,11 +106,15 @@ _SIGS = {
     "hriemo_adamw_flat": ("pppplfffffifpp", "i"),
     "hriemo_optim_finalize": ("pippppp", "i"),
     "hriemo_adamw_flat_dev": ("pppplppp", "i"),
+    "hriemo_grad_begin": ("plpp", "i"),
+    "hriemo_optim_finalize_ctl": ("pipppppp", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),
     "hriemo_fusion_loss": ("ppppiiiffpppp", "i"),
     "hriemo_fusion_loss_ce": ("pppiiiffpppp", "i"),
+    "hriemo_fusion_loss_n": ("ppppiiiffppppp", "i"),
+    "hriemo_fusion_loss_ce_n": ("pppiiiffppppp", "i"),
     "hriemo_scalar_gate_dx": ("pipippppiiip", "i"),
     "hriemo_fuse_bwd_dw": ("ppppiiip", "i"),
     "hriemo_gate_dpre": ("pippp" + "iip", "i"),

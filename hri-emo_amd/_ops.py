@@ -2543,14 +2543,28 @@ class LegacyBetaGateFn(torch.autograd.Function):
         return dxa, dxt, dw1, db1, dw2, db2, None, None, None
 
 
+def _n_valid_word(n_valid, like):
+    """the optional trailing argument of the loss Functions -> one int32 word on `like`'s device, or None"""
+    if not n_valid or n_valid[0] is None:
+        return None
+    nv = n_valid[0]
+    if not (isinstance(nv, torch.Tensor) and nv.dtype == torch.int32 and nv.numel() == 1 and nv.device == like.device):
+        raise TypeError("n_valid is a 0-dim or 1-element int32 tensor on the logits' device (the count is device data: a captured "
+                        f"step reads it on every replay), got {nv!r}")
+    return nv
+
+
 class FusionLossFn(torch.autograd.Function):
     """Trainer loss with its gradients from ONE kernel (hriemo_fusion_loss): mean BCEWithLogits(logits, targets; pos_weight) +
     reg(beta).  reg_mode 1 = -coef*mean(beta(1-beta)) (train_fusion_seq_level_decoder.py:318-326), 2 = +coef*entropy(beta)
-    (train_mosei_fusion_seq_level_decoder.py:340-347,385-386); `scale` = 1/grad_accum (:387)."""
+    (train_mosei_fusion_seq_level_decoder.py:340-347,385-386); `scale` = 1/grad_accum (:387).  An eighth argument n_valid (one int32
+    on the device) routes to hriemo_fusion_loss_n: only the first n_valid samples count, the others get zero gradients."""
 
     @staticmethod
-    def forward(ctx, logits, beta, targets, pos_weight, reg_mode, reg_coef, scale):
+    def forward(ctx, logits, beta, targets, pos_weight, reg_mode, reg_coef, scale, *n_valid):
         _require_gpu(logits)
+        nv = _n_valid_word(n_valid, logits)
+        ctx.n_extra = len(n_valid)
         B, Ne = logits.shape
         x, y = logits.contiguous().float(), targets.contiguous().float()
         bt = beta.contiguous().float().view(B) if beta is not None else None
@@ -2558,8 +2572,12 @@ class FusionLossFn(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dx = torch.empty((B, Ne), dtype=torch.float32, device=x.device)
         db = torch.empty(B, dtype=torch.float32, device=x.device) if bt is not None else None
-        _lib.call("hriemo_fusion_loss", _p(x), _p(y), _p(pw), _p(bt), B, Ne, int(reg_mode) if bt is not None else 0, float(reg_coef),
-                  float(scale), _p(loss), _p(dx), _p(db), _stream())
+        if nv is None:
+            _lib.call("hriemo_fusion_loss", _p(x), _p(y), _p(pw), _p(bt), B, Ne, int(reg_mode) if bt is not None else 0, float(reg_coef),
+                      float(scale), _p(loss), _p(dx), _p(db), _stream())
+        else:
+            _lib.call("hriemo_fusion_loss_n", _p(x), _p(y), _p(pw), _p(bt), B, Ne, int(reg_mode) if bt is not None else 0, float(reg_coef),
+                      float(scale), _p(loss), _p(dx), _p(db), _p(nv), _stream())
         ctx.save_for_backward(dx, db)
         ctx.shapes = (logits.shape, beta.shape if beta is not None else None, logits.dtype, beta.dtype if beta is not None else None)
         return loss.view(())
@@ -2568,20 +2586,23 @@ class FusionLossFn(torch.autograd.Function):
     def backward(ctx, g):
         dx, db = ctx.saved_tensors
         ls, bs, ld, bd = ctx.shapes
+        rest = (None,) * (5 + ctx.n_extra)
         if _is_one(g):                       # loss.backward(gradient=_ops.one(device)): the kernel's gradients are the answer
-            return dx.to(ld).view(ls), (db.to(bd).view(bs) if db is not None else None), None, None, None, None, None
+            return (dx.to(ld).view(ls), (db.to(bd).view(bs) if db is not None else None)) + rest
         gl = (dx * g).to(ld).view(ls)
         gb = (db * g).to(bd).view(bs) if db is not None else None
-        return gl, gb, None, None, None, None, None
+        return (gl, gb) + rest
 
 
 class FusionLossCEFn(torch.autograd.Function):
     """Single-label trainer loss (train_fusion_seq_level_decoder.py:312-314,325-326,413-414): CrossEntropyLoss(logits, labels) +
-    reg(beta), value and gradients from ONE kernel (hriemo_fusion_loss_ce)."""
+    reg(beta), value and gradients from ONE kernel (hriemo_fusion_loss_ce; with a seventh argument n_valid, hriemo_fusion_loss_ce_n)."""
 
     @staticmethod
-    def forward(ctx, logits, beta, labels, reg_mode, reg_coef, scale):
+    def forward(ctx, logits, beta, labels, reg_mode, reg_coef, scale, *n_valid):
         _require_gpu(logits)
+        nv = _n_valid_word(n_valid, logits)
+        ctx.n_extra = len(n_valid)
         B, C = logits.shape
         x = logits.contiguous().float()
         lb = labels.contiguous().to(torch.int64)
@@ -2589,8 +2610,12 @@ class FusionLossCEFn(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dx = torch.empty((B, C), dtype=torch.float32, device=x.device)
         db = torch.empty(B, dtype=torch.float32, device=x.device) if bt is not None else None
-        _lib.call("hriemo_fusion_loss_ce", _p(x), _p(lb), _p(bt), B, C, int(reg_mode) if bt is not None else 0, float(reg_coef),
-                  float(scale), _p(loss), _p(dx), _p(db), _stream())
+        if nv is None:
+            _lib.call("hriemo_fusion_loss_ce", _p(x), _p(lb), _p(bt), B, C, int(reg_mode) if bt is not None else 0, float(reg_coef),
+                      float(scale), _p(loss), _p(dx), _p(db), _stream())
+        else:
+            _lib.call("hriemo_fusion_loss_ce_n", _p(x), _p(lb), _p(bt), B, C, int(reg_mode) if bt is not None else 0, float(reg_coef),
+                      float(scale), _p(loss), _p(dx), _p(db), _p(nv), _stream())
         ctx.save_for_backward(dx, db)
         ctx.shapes = (logits.shape, beta.shape if beta is not None else None, logits.dtype, beta.dtype if beta is not None else None)
         return loss.view(())
@@ -2599,11 +2624,12 @@ class FusionLossCEFn(torch.autograd.Function):
     def backward(ctx, g):
         dx, db = ctx.saved_tensors
         ls, bs, ld, bd = ctx.shapes
+        rest = (None,) * (4 + ctx.n_extra)
         if _is_one(g):
-            return dx.to(ld).view(ls), (db.to(bd).view(bs) if db is not None else None), None, None, None, None
+            return (dx.to(ld).view(ls), (db.to(bd).view(bs) if db is not None else None)) + rest
         gl = (dx * g).to(ld).view(ls)
         gb = (db * g).to(bd).view(bs) if db is not None else None
-        return gl, gb, None, None, None, None
+        return (gl, gb) + rest
 
 
 class LinearFn(_GradModeAware, torch.autograd.Function):

@@ -5,19 +5,32 @@
 //   state[8]  written by the device: step, skip, coef, step_size = lr / bc1, 1 / sqrt(bc2), decay = 1 - lr * wd,
 //                                    grad_norm (pre-clip, unscaled), skipped (number of skipped steps)
 // A step is hriemo_sumsq_f32 (rowops.hip) -> hriemo_optim_finalize (one block) -> hriemo_adamw_flat_dev (streaming).
+// Gradient accumulation inside a captured step (dp.capture_packed(grad_accum=k)) adds the step-control block
+//   ctl[4]    written by the host (int32): n_valid (read by the masked losses, loss.hip), first, last, one spare word
+// hriemo_grad_begin zeroes the flat gradient buffer when ctl.first is set and leaves every bit of it in place otherwise;
+// hriemo_optim_finalize_ctl holds the update (state.skip = 1, nothing else) on every micro-step but the one with ctl.last set.
 #include "common.h"
 
 enum { HY_LR = 0, HY_BETA1, HY_BETA2, HY_EPS, HY_WD, HY_MAX_NORM };
 enum { ST_STEP = 0, ST_SKIP, ST_COEF, ST_STEP_SIZE, ST_ISB2, ST_DECAY, ST_GRAD_NORM, ST_SKIPPED };
+enum { CTL_N_VALID = 0, CTL_FIRST, CTL_LAST };
 
 // One block.  Sums the sumsq_f32 partials in a fixed order (deterministic), forms the unscaled gradient norm, decides whether
 // the step is skipped (GradScaler found an inf / the norm is not finite: torch's GradScaler.step and the reference trainer's
 // NaN guard, without the host reading anything back) and leaves every per-step scalar of the update in state[]: the only
 // powf of the optimizer runs here, once, not per element.
+// HOLD (hriemo_optim_finalize_ctl): a micro-step of an accumulation group that is not its last one (ctl.last == 0) sets
+// state.skip so that adamw_flat_dev_kernel returns early, and touches nothing else: step, skipped and grad_norm stay those of the last
+// real step -- a held micro-step is not a skipped step.  With ctl.last != 0 the kernel runs the instructions of the plain one.
+template <bool HOLD>
 __global__ __launch_bounds__(256) void optim_finalize_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
                                                              const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
-                                                             float* __restrict__ state) {
+                                                             float* __restrict__ state, const int* __restrict__ ctl) {
   __shared__ float red[4];
+  if (HOLD && ctl[CTL_LAST] == 0) {                // block-uniform: nobody reaches the barrier below
+    if (threadIdx.x == 0) state[ST_SKIP] = 1.f;
+    return;
+  }
   float s = 0.f;
   for (int i = threadIdx.x; i < nblocks; i += 256) s += partial[i];
   s = wave_sum(s);
@@ -71,12 +84,43 @@ __global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__
   }
 }
 
+// The conditional start of an accumulation group: ctl.first != 0 -> +0 over flat[0, n) (16-byte stores, grid capped like the update's);
+// ctl.first == 0 -> the kernel returns without a load or a store, so NaN payloads, -0 and denormals of the running sum survive.
+__global__ __launch_bounds__(256) void grad_begin_kernel(float* __restrict__ flat, long n, const int* __restrict__ ctl) {
+  if (ctl[CTL_FIRST] == 0) return;
+  const long nv = n >> 2;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) *(f32x4*)(flat + i * 4) = zero;
+}
+
+extern "C" int hriemo_grad_begin(float* flat, long n, const int* ctl, hipStream_t st) {
+  HRIEMO_CHECK(flat != nullptr && n > 0 && n % 4 == 0, "grad_begin: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(((uintptr_t)flat % 16) == 0, "grad_begin: unaligned buffer");
+  HRIEMO_CHECK(ctl != nullptr && ((uintptr_t)ctl % 4) == 0, "grad_begin: ctl is the int32 step-control block in device memory");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  hipLaunchKernelGGL(grad_begin_kernel, dim3((int)gsz), dim3(256), 0, st, flat, n, ctl);
+  HRIEMO_LAUNCH_CHECK("grad_begin_kernel");
+  return 0;
+}
+
 extern "C" int hriemo_optim_finalize(const float* partial, int nblocks, const float* hyper, const float* grad_scale, const float* found_inf,
                                      float* state, hipStream_t st) {
   HRIEMO_CHECK(partial != nullptr && hyper != nullptr && state != nullptr, "optim_finalize: partial, hyper and state are required");
   HRIEMO_CHECK(nblocks > 0 && nblocks <= 4096, "optim_finalize: nblocks=%d out of range (1..4096)", nblocks);
-  hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, grad_scale, found_inf, state);
+  hipLaunchKernelGGL(optim_finalize_kernel<false>, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, grad_scale, found_inf, state,
+                     (const int*)nullptr);
   HRIEMO_LAUNCH_CHECK("optim_finalize_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_optim_finalize_ctl(const float* partial, int nblocks, const float* hyper, const float* grad_scale,
+                                         const float* found_inf, float* state, const int* ctl, hipStream_t st) {
+  HRIEMO_CHECK(partial != nullptr && hyper != nullptr && state != nullptr, "optim_finalize_ctl: partial, hyper and state are required");
+  HRIEMO_CHECK(nblocks > 0 && nblocks <= 4096, "optim_finalize_ctl: nblocks=%d out of range (1..4096)", nblocks);
+  HRIEMO_CHECK(ctl != nullptr && ((uintptr_t)ctl % 4) == 0, "optim_finalize_ctl: ctl is the int32 step-control block in device memory");
+  hipLaunchKernelGGL(optim_finalize_kernel<true>, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, grad_scale, found_inf, state, ctl);
+  HRIEMO_LAUNCH_CHECK("optim_finalize_kernel<hold>");
   return 0;
 }
 

@@ -113,7 +113,8 @@ class DevicePrefetcher:
     ``collate_seq_packed``).  Their pinned staging and device buffers are allocated once, ``capacity_rows`` long (B * L covers any
     batch); a batch copies only its own ``n`` rows and is handed out as the ``[:n]`` view of the device buffer, so the buffers --
     and their addresses -- stay put while the row count changes with every batch.  Entries not named keep the behaviour above
-    (buffers per shape).  An entry that is no tensor (the lengths as Python lists, which ``DataParallelStep.step_packed`` wants
+    (buffers per shape, except that a batch whose entry is SHORTER in the first dimension only -- the labels of an epoch's short last
+    batch -- is staged in the same buffers and handed out as their ``[:n]`` view).  An entry that is no tensor (the lengths as Python lists, which ``DataParallelStep.step_packed`` wants
     on the host) passes through like None."""
 
     def __init__(self, loader, device, depth=2, convert=None, dtypes=None, mask_slots=None, ragged=None):
@@ -145,7 +146,17 @@ class DevicePrefetcher:
         full = [None if not ok else ((self.ragged[i],) + tuple(t.shape[1:]) if i in self.ragged else tuple(t.shape))
                 for i, (t, ok) in enumerate(zip(tensors, is_t))]
         shapes = [None if f is None else (f, t.dtype) for f, t in zip(full, tensors)]
-        if ent is None or ent["shapes"] != shapes:
+
+        def holds(have, want):
+            """a buffer set serves every batch whose entries differ from it in the FIRST dimension only and are no longer there: the
+            short last batch of an epoch (its labels and lengths tensors shrink with the number of utterances) is staged in the
+            buffers of the full batches, like a ragged entry in its capacity"""
+            if have is None or want is None:
+                return have is None and want is None
+            (hf, hd), (wf, wd) = have, want
+            return hd == wd and len(hf) == len(wf) and hf[1:] == wf[1:] and (not wf or wf[0] <= hf[0])
+
+        if ent is None or len(ent["shapes"]) != len(shapes) or not all(holds(h, w) for h, w in zip(ent["shapes"], shapes)):
             ent = {"shapes": shapes,
                    "host": [None if f is None else torch.empty(f, dtype=t.dtype).pin_memory() for f, t in zip(full, tensors)],
                    "dev": [None if f is None else torch.empty(f, dtype=t.dtype, device=self.device) for f, t in zip(full, tensors)],
@@ -159,7 +170,7 @@ class DevicePrefetcher:
                 src.append(None)
                 out.append(t)
                 continue
-            if i in self.ragged:                   # this batch's rows only; the views keep the buffers' base addresses
+            if t.dim() and t.shape[0] != h.shape[0]:      # this batch's rows only; the views keep the buffers' base addresses
                 h, d_ = h[:t.shape[0]], d_[:t.shape[0]]
             if t.is_pinned():                      # a loader with pin_memory=True hands pinned tensors over: copied from there
                 src.append(t)

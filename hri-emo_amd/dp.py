@@ -37,6 +37,37 @@ def bucket_rows(n, B, L):
     return (n // g + 1) * g               # > n: the extra sequence is never empty
 
 
+def ghost_plan(la, lt, B, La, Lt):
+    """A short batch of n = len(la) <= B utterances, as a captured step of B utterances sees it (capture_packed(partial_batches=True)):
+    -> (audio lengths, text lengths, bucket key, (own audio rows, own text rows)).  The B - n missing utterances are ghosts of length
+    1 in both modalities -- the shortest sequence every kernel of the step accepts; their rows lie directly behind the batch's own
+    rows, inside the region _load_packed zeroes up to the bucket's end, and the bucket key counts them.  n == B: the batch itself."""
+    own = (sum(la), sum(lt))
+    ghosts = [1] * (B - len(la))
+    la, lt = list(la) + ghosts, list(lt) + ghosts
+    return la, lt, (bucket_rows(sum(la), B, La), bucket_rows(sum(lt), B, Lt)), own
+
+
+def ctl_words(n_valid, first, last):
+    """host image of the step-control block a captured step reads from device memory: int32 {n_valid, first, last, spare}"""
+    return [int(n_valid), 1 if first else 0, 1 if last else 0, 0]
+
+
+def micro_flags(micro, k):
+    """(first, last) of micro-step `micro` in an accumulation group of k: the flat gradient buffer starts from zero on the first,
+    the optimizer (and the exchange outside the graph) runs on the last"""
+    return micro == 0, micro == k - 1
+
+
+def _accepts_n_valid(fn):
+    import inspect
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.name == "n_valid" or p.kind is inspect.Parameter.VAR_KEYWORD for p in params)
+
+
 class GradBuckets:
     """comm_dtype: torch.float32 (default: the flat buffer is all-reduced in place) or torch.bfloat16: every bucket is cast to a
     bf16 staging buffer (half the bytes on the xGMI links: 109 MB instead of 218 MB per step at cfg 2), summed by the collective in
@@ -295,6 +326,7 @@ class DataParallelStep:
         self._pb = None               # packed (varlen) bucket graphs: {(rows audio, rows text): record}, see capture()
         self._pool = None
         self._optimizer = None        # optim.DeviceAdamW whose update closes the captured step (capture(optimizer=...))
+        self._micro = 0               # micro-steps of the open accumulation group (capture_packed(grad_accum=k)): 0 .. k-1
 
     def set_global_batch(self, global_batch):
         lo, hi = shard_bounds(global_batch, self.rank, self.world)
@@ -323,7 +355,13 @@ class DataParallelStep:
             _ops.gemm_contended(bool(b._hooks) and not b.suspended and b.world > 1)
         else:
             _ops.gemm_contended(bool(self.force_queue), force=True)
-        if zero:
+        ctl = front.get("ctl") if front is not None else None
+        if ctl is not None and front["accum"] > 1:
+            # a step captured with gradient accumulation: whether the flat buffer starts from zero is device data (ctl.first)
+            from . import _lib
+            _lib.call("hriemo_grad_begin", self.buckets.flat.data_ptr(), self.buckets.flat.numel(), ctl.data_ptr(), _ops._stream())
+            self.buckets._rebind()
+        elif zero:
             self.buckets.zero_grad()
         if ragged is not None:
             logits, beta, _ = self.model.forward_packed(h_a, h_t, ragged[0], ragged[1], pad_to=ragged[2])
@@ -331,7 +369,10 @@ class DataParallelStep:
             logits, beta, _ = self.model._forward_rows(h_a, h_t, tuple(seqs), front["bool"], (self._pb["La"], self._pb["Lt"]))
         else:
             logits, beta, _ = self.model(h_a, h_t, m_a, m_t)
-        loss = self.loss_fn(logits, beta, y)
+        if ctl is not None and front["partial"]:
+            loss = self.loss_fn(logits, beta, y, n_valid=ctl[:1])      # ctl.n_valid: the ghosts behind it add nothing and get zero gradients
+        else:
+            loss = self.loss_fn(logits, beta, y)
         if scale is not None:
             loss = loss * scale
         if loss.is_cuda and scale is None:
@@ -341,16 +382,25 @@ class DataParallelStep:
         return loss.detach()
 
     @_in_step_context
-    def step_accumulated(self, micro_batches):
+    def step_accumulated(self, micro_batches, pad_to=None):
         """Gradient accumulation (train_mosei_fusion_seq_level_decoder.py:387-396: loss / grad_accum, optimizer every grad_accum
         micro-steps) under data parallelism WITHOUT a gradient exchange per micro-step: the flat buffer is zeroed once, every
         micro-batch accumulates into it (the kernels add in place), gradient-ready notifications stay suspended until the LAST
-        micro-batch, whose backward launches the bucket all-reduces as usual.  Returns the mean of the micro-losses."""
+        micro-batch, whose backward launches the bucket all-reduces as usual.  Returns the mean of the micro-losses.
+        pad_to=(L_a, L_t): the micro-batches are ragged, (rows_a, rows_t, lengths_a, lengths_t, y) each, of any number of
+        utterances, and run through the model's forward_packed (the eager counterpart of capture_packed(grad_accum=k))."""
+        from . import _ops
         k = len(micro_batches)
         was = self.buckets.suspended
         total = None
         for i, mb in enumerate(micro_batches):
             self.buckets.suspended = True if i + 1 < k else was
+            if pad_to is not None:
+                ra, rt, la, lt, y = mb
+                la, lt, pad = _ops.packed_lengths(ra, rt, la, lt, pad_to, same_width=not hasattr(self.model, "audio_proj"))
+                l = self._fwd_bwd(ra, rt, None, None, y, zero=(i == 0), scale=1.0 / k, ragged=(la, lt, pad))
+                total = l if total is None else total + l
+                continue
             l = self._fwd_bwd(*mb, zero=(i == 0), scale=1.0 / k)
             total = l if total is None else total + l
         self.buckets.suspended = was
@@ -425,7 +475,8 @@ class DataParallelStep:
             self.buckets.suspended = True         # from now on hooks fire only inside replays (they are baked into the graph)
 
     @_in_step_context
-    def capture_packed(self, rows_a, rows_t, lengths_a, lengths_t, y, pad_to, optimizer=None, collectives=False):
+    def capture_packed(self, rows_a, rows_t, lengths_a, lengths_t, y, pad_to, optimizer=None, collectives=False, partial_batches=False,
+                       grad_accum=1):
         """capture() for batches that arrive ragged (data.collate_seq_packed): rows_a / rows_t [sum(lengths), d] (fp32, bf16 or fp16; on
         the device or in pinned host memory) hold the valid rows of all utterances back to back, lengths_a / lengths_t are host
         sequences or CPU int tensors, pad_to = (L_a, L_t) the padded lengths: they size the static buffers, key the dropout hash and fix
@@ -439,10 +490,38 @@ class DataParallelStep:
         the lengths cross to the device once.  Behind the front door everything is the mask-fed packed step: the bucket graphs
         (one per (audio rows, text rows) bucket, LRU-capped, one memory pool), packed_tail(), fp32 precision, mx_fp8,
         optimizer=DeviceAdamW.  The encoder runs packed whatever set_varlen says, as in forward_packed.  collectives=True at world
-        size > 1 is refused for the reason capture() gives in packed mode."""
+        size > 1 is refused for the reason capture() gives in packed mode.
+
+        Two opt-in arguments let the captured step run a whole epoch of the reference's trainers (their loaders keep the short last
+        batch; the MOSEI trainer accumulates gradients, train_mosei_fusion_seq_level_decoder.py:383-402).  Both turn a fact of the
+        step that is otherwise baked into the graph into DEVICE data: one int32 step-control block ctl[4] = {n_valid, first, last,
+        spare} with a pinned host twin, uploaded in stream order before every replay like the lengths block.  With neither given the
+        captured step consists of exactly the launches it had before them (memset, hriemo_fusion_loss(_ce), hriemo_optim_finalize).
+
+        partial_batches=True: ``step_packed`` accepts 1 <= n <= B utterances.  The B - n missing ones become GHOSTS on the host:
+        length 1 in both modalities, their rows the zero rows that are written behind the batch's own rows anyway, counted in the
+        bucket key.  ctl.n_valid = n; ``loss_fn`` is called with ``n_valid=`` (a 1-element int32 device tensor) and must ignore the
+        ghosts: hri_emo_amd.train's three losses do (hriemo_fusion_loss_n / _ce_n: means over the first n samples, exactly zero
+        gradients for the ghosts, so nothing of a ghost reaches a parameter gradient).  y is copied into the first n rows of the
+        static targets; rows of an earlier batch may stay behind them.  A ``loss_fn`` without an ``n_valid`` keyword is a TypeError
+        here.  Each rank normalises by its OWN n_valid, as torch's DistributedDataParallel does with a short last batch: the
+        exchange averages per-rank means, it does not re-weight them by sample counts.
+
+        grad_accum=k > 1: the captured step starts with hriemo_grad_begin (zeroes the flat gradient buffer when ctl.first is set,
+        leaves every bit in place otherwise) instead of the memset, and the optimizer's finalize launch becomes
+        hriemo_optim_finalize_ctl (holds the update unless ctl.last is set: parameters, moments, step count, ``skipped`` and
+        ``grad_norm`` stay as they are).  ``step_packed`` counts micro-steps: first on micro-step 0, last on micro-step k - 1; the
+        exchange outside the graph, the weights-epoch bump and the hyper-parameter upload happen for the last micro-step only.  The
+        1/k loss scale stays the caller's, by value (``mosei_step_loss(grad_accum=k)``): it is constant per run.
+        ``flush_accumulated()`` closes a group that the end of an epoch cut short."""
         from . import _ops
         if not hasattr(self.model, "_forward_rows"):
             raise TypeError("capture_packed: the model has no forward_packed entry")
+        if int(grad_accum) != grad_accum or grad_accum < 1:
+            raise ValueError(f"capture_packed: grad_accum = {grad_accum!r} (an integer >= 1)")
+        if partial_batches and not _accepts_n_valid(self.loss_fn):
+            raise TypeError("capture_packed(partial_batches=True): loss_fn takes no n_valid= keyword -- the ghost utterances of a short "
+                            "batch must stay out of the loss (hri_emo_amd.train's losses accept it)")
         same_width = not hasattr(self.model, "audio_proj")
         la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
         if pad_to is None:
@@ -468,6 +547,7 @@ class DataParallelStep:
         self.release_graph()
         self._collectives = bool(collectives)
         self._optimizer = optimizer
+        self._micro = 0
         B = len(la)
         cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
         src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
@@ -478,7 +558,10 @@ class DataParallelStep:
         self._pb = {"graphs": collections.OrderedDict(), "B": B, "La": La, "Lt": Lt, "cu_a": cu(), "cu_t": cu(), "cu_f": cu(),
                     "front": {"lens": torch.ones(2, B, dtype=torch.int32, device=dev), "lens_host": torch.ones(2, B, dtype=torch.int32).pin_memory(),
                               "lens_copied": None, "masks": masks, "bool": tuple(m.view(torch.bool) for m in masks),
-                              "same_width": same_width}}
+                              "same_width": same_width, "partial": bool(partial_batches), "accum": int(grad_accum), "ctl": None}}
+        if partial_batches or grad_accum > 1:
+            self._pb["front"].update(ctl=torch.tensor([B, 1, 1, 0], dtype=torch.int32, device=dev),
+                                     ctl_host=torch.tensor([B, 1, 1, 0], dtype=torch.int32).pin_memory(), ctl_copied=None)
         key = self._load_packed(rows_a, rows_t, la, lt, y)
         rec = self._packed_graph(key)
         self._graph, self._static_loss, self._keep = rec["graph"], rec["loss"], []
@@ -489,13 +572,16 @@ class DataParallelStep:
         if collectives:
             self.buckets.suspended = True
 
-    def _load_packed(self, rows_a, rows_t, la, lt, y):
+    def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
         """a checked ragged batch into the static state -> its bucket key: the rows to the head of each source, zeros from there to
-        the bucket's end (the MOSEI projections read every bucket row), the lengths as one [2, B] block through the pinned twin, y"""
+        the bucket's end (the MOSEI projections read every bucket row), the lengths as one [2, B] block through the pinned twin, y.
+        A short batch (partial_batches) is completed with ghosts first (ghost_plan).  ctl = (first, last): the step-control block
+        goes up with n_valid = the batch's own number of utterances, by the protocol of the lengths block."""
         pb = self._pb
         front, B = pb["front"], pb["B"]
-        key = (bucket_rows(sum(la), B, pb["La"]), bucket_rows(sum(lt), B, pb["Lt"]))
-        for src, rows, n, n_rows in ((self._static[0], rows_a, sum(la), key[0]), (self._static[1], rows_t, sum(lt), key[1])):
+        n_utt = len(la)
+        la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, B, pb["La"], pb["Lt"])
+        for src, rows, n, n_rows in ((self._static[0], rows_a, rows_own_a, key[0]), (self._static[1], rows_t, rows_own_t, key[1])):
             if rows.data_ptr() != src.data_ptr():
                 src[:n].copy_(rows, non_blocking=True)
             src[n:n_rows].zero_()
@@ -505,8 +591,16 @@ class DataParallelStep:
         front["lens"].copy_(front["lens_host"], non_blocking=True)
         front["lens_copied"] = torch.cuda.Event()
         front["lens_copied"].record()
+        if front["ctl"] is not None:
+            first, last = ctl if ctl is not None else (1, 1)
+            if front["ctl_copied"] is not None:
+                front["ctl_copied"].synchronize()
+            front["ctl_host"].copy_(torch.tensor(ctl_words(n_utt, first, last), dtype=torch.int32))
+            front["ctl"].copy_(front["ctl_host"], non_blocking=True)
+            front["ctl_copied"] = torch.cuda.Event()
+            front["ctl_copied"].record()
         if y.data_ptr() != self._static[4].data_ptr():
-            self._static[4].copy_(y, non_blocking=True)
+            self._static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
         return key
 
     @_in_step_context
@@ -514,7 +608,9 @@ class DataParallelStep:
         """One trainer step on a ragged batch (capture_packed): the arguments are checked on the host (_ops.packed_lengths; a
         ValueError leaves the static state untouched), the rows, the lengths block and y are copied into the static buffers, the
         batch's bucket graph is picked -- or captured on the spot -- and replayed.  A batch with another number of utterances than
-        captured is refused: drop it, or run it with use_graph(False), which makes this the eager forward_packed step."""
+        captured is refused: drop it, or run it with use_graph(False), which makes this the eager forward_packed step.  After
+        capture_packed(partial_batches=True) a batch of 1 <= n <= B utterances is served by the same graphs (ghosts, n_valid as
+        device data); after capture_packed(grad_accum=k) every call is one MICRO-step and the k-th one carries the update."""
         from . import _ops
         front = self._pb.get("front") if self._pb is not None else None
         if front is None:
@@ -523,33 +619,77 @@ class DataParallelStep:
         B, pad = pb["B"], (pb["La"], pb["Lt"])
         la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front["same_width"])
         replay = self._graph is not None and getattr(self, "_replay", True)
+        k = front["accum"]
+        first, last = micro_flags(self._micro, k)
         if replay:
-            if len(la) != B:
-                raise ValueError(f"step_packed: a batch of {len(la)} utterances; the captured step holds B = {B} (drop the batch or run it "
-                                 "with use_graph(False))")
+            n = len(la)
+            if n != B and not front["partial"]:
+                raise ValueError(f"step_packed: a batch of {n} utterances; the captured step holds B = {B} (drop the batch, run it "
+                                 "with use_graph(False), or capture with partial_batches=True)")
+            if n > B:
+                raise ValueError(f"step_packed: a batch of {n} utterances; the captured step holds at most B = {B}")
             for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
                 if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
                     raise ValueError(f"step_packed: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
-            if tuple(y.shape) != tuple(self._static[4].shape):
-                raise ValueError(f"step_packed: targets of shape {tuple(y.shape)}; captured with {tuple(self._static[4].shape)}")
-            if self._optimizer is not None:
+            want = (n,) + tuple(self._static[4].shape[1:])
+            if tuple(y.shape) != want:
+                raise ValueError(f"step_packed: targets of shape {tuple(y.shape)}; captured with {tuple(self._static[4].shape)}"
+                                 + (f", this batch needs {want}" if n != B else ""))
+            if self._optimizer is not None and last:
+                # the update of this group reads lr & co. as the scheduler left them after the previous update; a held micro-step
+                # reads none of them (the finalize returns in front of hyper[], the update kernel in front of everything)
                 self._optimizer._upload_hyper()
-            key = self._load_packed(rows_a, rows_t, la, lt, y)
+            key = self._load_packed(rows_a, rows_t, la, lt, y, ctl=(first, last))
             rec = self._packed_graph(key)                 # captures on the static state (already this batch) if the bucket is new
             rec["graph"].replay()
-            if not self._exchange_in_graph:
-                self.buckets.finish()
-            if self._optimizer is not None:
-                _ops.bump_weights_epoch()
-                self._optimizer._opt_called = True
+            self._micro = 0 if last else self._micro + 1
+            if last:
+                if not self._exchange_in_graph:
+                    self.buckets.finish()
+                if self._optimizer is not None:
+                    _ops.bump_weights_epoch()
+                    self._optimizer._opt_called = True
             return rec["loss"]
         dev = self._static[0].device
-        loss = self._fwd_bwd(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), None, None, y.to(dev, non_blocking=True),
-                             ragged=(la, lt, pad))
-        self.buckets.finish()
-        if self._optimizer is not None:
-            self._optimizer.step()
+        was = self.buckets.suspended
+        if not last:
+            self.buckets.suspended = True                 # as step_accumulated: the exchange belongs to the group's last backward
+        try:
+            loss = self._fwd_bwd(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), None, None, y.to(dev, non_blocking=True),
+                                 zero=first, ragged=(la, lt, pad))
+        finally:
+            self.buckets.suspended = was
+        self._micro = 0 if last else self._micro + 1
+        if last:
+            self.buckets.finish()
+            if self._optimizer is not None:
+                self._optimizer.step()
         return loss
+
+    @property
+    def micro_step(self):
+        """micro-steps taken in the open accumulation group (0: none pending)"""
+        return self._micro
+
+    @_in_step_context
+    def flush_accumulated(self):
+        """Close an accumulation group that the end of an epoch cut short (capture_packed(grad_accum=k), fewer than k micro-steps
+        since the last update): the update runs on what HAS been accumulated -- nothing is rerun.  The form chosen is the simplest
+        correct one: no replay with last = 1 and an empty batch, but the gradient exchange (when it is outside the graph) followed
+        by one eager ``DeviceAdamW.step()`` on the flat buffer -- the same three launches the graph holds, with the plain finalize.
+        The sum is NOT rescaled by k / micro-steps: every term carries the caller's 1/k, as in the reference trainer, whose loss
+        scale does not know about the epoch's end either.  Without an optimizer in the graph only the exchange is finished and the
+        caller's own ``opt.step()`` follows.  Returns the number of micro-steps the update covers (0: nothing was pending, nothing
+        is done)."""
+        n = self._micro
+        if n == 0:
+            return 0
+        self._micro = 0
+        if not self._exchange_in_graph or not (self._graph is not None and getattr(self, "_replay", True)):
+            self.buckets.finish()
+        if self._optimizer is not None:
+            self._optimizer.step()                        # uploads hyper[], bumps the weights epoch
+        return n
 
     # ---- packed (varlen) bucket graphs
     def _packed_key(self, m_a, m_t, lengths):
@@ -608,11 +748,17 @@ class DataParallelStep:
             # CPU generator.  Ranks meet new buckets at different steps, so the generator is put back: its stream stays the one
             # the caller (and every other rank) sees, as _ops.next_seed documents.
             rng = torch.get_rng_state() if self._graph is not None else None
+            # inside an accumulation group the warm-up passes run with ctl.first = 0 and would add to the running gradient sum:
+            # it is set aside and put back (a copy of the flat buffer, paid only when a bucket is met for the first time)
+            front = pb.get("front")
+            held = self.buckets.flat.clone() if (front is not None and front["accum"] > 1 and self._micro > 0) else None
             try:
                 graph, loss, keep = self._capture_graph(seqs)
             finally:
                 if rng is not None:
                     torch.set_rng_state(rng)
+                if held is not None:
+                    self.buckets.flat.copy_(held)
             rec = pb["graphs"][key] = {"graph": graph, "loss": loss, "keep": keep, "seqs": seqs}
             log.info("packed step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb["graphs"]))
         else:
@@ -664,7 +810,9 @@ class DataParallelStep:
                     if collectives:
                         self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
                     if self._optimizer is not None:
-                        self._optimizer._enqueue()    # recorded, not run: norm, skip / clip / bias corrections, update
+                        front = self._pb.get("front") if self._pb is not None else None
+                        ctl = front["ctl"] if (front is not None and front["accum"] > 1) else None
+                        self._optimizer._enqueue(ctl=ctl)    # recorded, not run: norm, skip / hold / clip / bias corrections, update
             finally:
                 _ops.CTX.capturing = False
                 _ops.CTX.capture_origin = None

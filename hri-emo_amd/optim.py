@@ -121,14 +121,20 @@ class DeviceAdamW(torch.optim.Optimizer):
             self._hyper.copy_(torch.tensor(img, dtype=torch.float32).pin_memory(), non_blocking=True)
             self._hyper_host = img
 
-    def _enqueue(self, grad_scale=None, found_inf=None):
-        """the three launches on the current stream (eagerly, or while a step is being captured)"""
+    def _enqueue(self, grad_scale=None, found_inf=None, ctl=None):
+        """the three launches on the current stream (eagerly, or while a step is being captured).  ctl: the int32 step-control block
+        of a step captured with gradient accumulation (dp.capture_packed(grad_accum=k)): the finalize launch then holds the update
+        on every micro-step whose ctl.last is 0 -- parameters, moments, step count, skipped and grad_norm stay as they are."""
         g = self.buckets.flat
         n = g.numel()
         st = _stream()
         _lib.call("hriemo_sumsq_f32", _p(g), n, _p(self._partial), self.nblocks, st)
-        _lib.call("hriemo_optim_finalize", _p(self._partial), self.nblocks, _p(self._hyper), _p(grad_scale), _p(found_inf),
-                  _p(self._state), st)
+        if ctl is None:
+            _lib.call("hriemo_optim_finalize", _p(self._partial), self.nblocks, _p(self._hyper), _p(grad_scale), _p(found_inf),
+                      _p(self._state), st)
+        else:
+            _lib.call("hriemo_optim_finalize_ctl", _p(self._partial), self.nblocks, _p(self._hyper), _p(grad_scale), _p(found_inf),
+                      _p(self._state), _p(ctl), st)
         _lib.call("hriemo_adamw_flat_dev", _p(self.flat_p), _p(g), _p(self.m), _p(self.v), n, _p(self._hyper), _p(self._state), st)
 
     def _amp_word(self, name):

@@ -365,6 +365,17 @@ int hriemo_fusion_loss(const float* logits, const float* targets, const float* p
  * instead of reading out of bounds.  Writes loss[1], dlogits[B,C] = (softmax - onehot)/n_labelled * scale, dbeta[B] (may be NULL). */
 int hriemo_fusion_loss_ce(const float* logits, const long long* labels, const float* beta, int B, int C, int reg_mode,
                           float reg_coef, float scale, float* loss, float* dlogits, float* dbeta, hriemo_stream_t stream);
+/* The two losses with the number of samples that count in DEVICE memory (a captured step that serves the short last batch of an
+ * epoch, DataParallelStep.capture_packed(partial_batches=True)): nv = clamp(*n_valid, 1, B) on the device.  Samples b >= nv are
+ * ghosts: their rows of logits, targets / labels and beta are never read (they may hold NaN), they add no loss term, and every
+ * element of their dlogits row and their dbeta is stored as +0.  The BCE mean runs over nv * N_e, the CE mean over the labelled
+ * samples among the first nv, the regulariser mean over nv.  *n_valid == B: bit-identical to the entries above. */
+int hriemo_fusion_loss_n(const float* logits, const float* targets, const float* pos_weight, const float* beta, int B, int Ne,
+                         int reg_mode, float reg_coef, float scale, float* loss, float* dlogits, float* dbeta, const int* n_valid,
+                         hriemo_stream_t stream);
+int hriemo_fusion_loss_ce_n(const float* logits, const long long* labels, const float* beta, int B, int C, int reg_mode,
+                            float reg_coef, float scale, float* loss, float* dlogits, float* dbeta, const int* n_valid,
+                            hriemo_stream_t stream);
 int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, int is_a, const float* dpool, const float* cnt,
                           const unsigned char* mask, void* dX, int B, int L, int d, hriemo_stream_t stream);
 /* Trainer step off the timed path, scripts/fusion/train_fusion_seq_level_decoder.py:332-334: clip_grad_norm_(5.0) +
@@ -391,6 +402,16 @@ int hriemo_optim_finalize(const float* partial, int nblocks, const float* hyper,
                           float* state, hriemo_stream_t stream);
 int hriemo_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* state,
                           hriemo_stream_t stream);
+/* Gradient accumulation inside a captured step (DataParallelStep.capture_packed(grad_accum=k)).  ctl is the step-control block,
+ * int32[4] in device memory, written by the host before every replay: {n_valid, first, last, spare}.
+ * hriemo_grad_begin opens a micro-step: ctl[1] (first) != 0 writes +0 over flat[0, n) (n % 4 == 0, flat 16-byte aligned);
+ * first == 0 leaves every bit of flat in place (nothing is loaded or stored: NaN payloads and -0 survive).
+ * hriemo_optim_finalize_ctl is hriemo_optim_finalize for the micro-step with ctl[2] (last) != 0, bit for bit; with last == 0 it
+ * HOLDS the update: state[1] (skip) = 1 so that hriemo_adamw_flat_dev returns early, and no other word of state changes -- step,
+ * skipped and grad_norm stay as they were. */
+int hriemo_grad_begin(float* flat, long n, const int* ctl, hriemo_stream_t stream);
+int hriemo_optim_finalize_ctl(const float* partial, int nblocks, const float* hyper, const float* grad_scale, const float* found_inf,
+                              float* state, const int* ctl, hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
