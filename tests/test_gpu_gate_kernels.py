@@ -3,8 +3,11 @@
 
 Reference arithmetic: models/beta_gate_tacfn.py:6-24 (masked_mean), :79-84 (LayerNorm + pools), :87-95 (gate input, sigmoid,
 beta), :98-116 (fusion over the first L positions); models/beta_gate.py:6-32,97-112 (legacy scalar gate);
-models/emotion_decoder.py:58 (mid-FFN dropout).  Tolerances are stated per check: fp32 results 1e-5-ish, bf16 outputs one
-bf16 ulp of the value range (2^-8 relative)."""
+models/emotion_decoder.py:58 (mid-FFN dropout).  The chain tests here feed each kernel the previous kernel's output and compare with
+torch fp32 / autograd under coarse tolerances normalised by the tensor's maximum: they check that the kernels compose into the
+model's graph.  The LIMITS of every gate kernel -- float64 references, per-element bounds derived from the reference alone, guarded
+and poisoned buffers, every chunk edge and every dispatch instance -- are test_gpu_gate_variants.py (gate_reference.py,
+test_gate_bound_host.py)."""
 import numpy as np
 import pytest
 import torch
@@ -55,6 +58,7 @@ GATE_CASES = [  # B, La, Lt, d, masked, twin
     (4, 33, 33, 256, False, True),        # equal lengths, no masks (mask pointers NULL)
     (2, 70, 5, 1024, True, True),
     (1, 1, 1, 128, False, False),
+    (2, 37, 21, 1032, True, True),        # d > 1024: the NCH = 4 instances, the backward's constants in registers, no look-ahead row
 ]
 
 
