@@ -11,6 +11,7 @@ collective with the rest of backward.  xGMI is point-to-point (7 links x ~153 GB
 (default 32 MiB) beat many small ones.
 """
 import collections
+import itertools
 import logging
 import os
 
@@ -30,11 +31,41 @@ _VARLEN_MAX_GRAPHS = max(1, int(os.environ.get("HRIEMO_VARLEN_MAX_GRAPHS", "48")
 def bucket_rows(n, B, L):
     """Row count of the packed (varlen) bucket that holds `n` valid rows of a modality padded to [B, L]: the next multiple of the
     granule g = max(8, B*L / _VARLEN_BUCKETS rounded down to a multiple of 8), g capped at L -- always > n (the surplus rows form
-    ONE extra sequence, which is never empty and never longer than L).  The one place this arithmetic lives: the mask-fed
-    (_packed_key) and the ragged (step_packed) front doors of DataParallelStep both call it."""
+    ONE extra sequence, which is never empty and never longer than L).  The one place this arithmetic lives: packed_tables, which
+    the mask-fed (_packed_key) and the ragged (step_packed) front doors of DataParallelStep share, is built on it."""
     g = max(8, (B * L) // _VARLEN_BUCKETS // 8 * 8)
     g = min(g, L)                         # the surplus rows are ONE sequence of at most L rows
     return (n // g + 1) * g               # > n: the extra sequence is never empty
+
+
+def packed_tables(la, lt, B, La, Lt):
+    """Host arithmetic of a packed batch, lists in and lists out: the lengths of B utterances per modality, padded to [B, La] / [B, Lt]
+    -> (bucket key, cu_a, cu_t, cu_f).  key = (audio rows, text rows) of the bucket (bucket_rows); every cu is
+    [0, inclusive prefix sums ..., bucket row count], B + 2 entries: the surplus rows are the last sequence.  cu_f is the fused memory
+    of the packed tail (min of the two lengths per utterance: the reference ORs the two prefix masks); it rides in the text bucket
+    (sum lf <= sum lt < its row count): no bucket dimension, no graph of its own."""
+    key = (bucket_rows(sum(la), B, La), bucket_rows(sum(lt), B, Lt))
+    cu = lambda lens, rows: list(itertools.accumulate(lens, initial=0)) + [rows]          # noqa: E731
+    return key, cu(la, key[0]), cu(lt, key[1]), cu([min(x, y) for x, y in zip(la, lt)], key[1])
+
+
+def mask_lengths(m_a, m_t, lengths, B, La, Lt):
+    """-> (audio lengths, text lengths) as host lists: `lengths` checked, or read from the padding masks (one device -> host read;
+    the masks must be prefix masks with no empty sequence, the collate's form)"""
+    if lengths is not None:
+        la, lt = [int(x) for x in lengths[0]], [int(x) for x in lengths[1]]
+        if len(la) != B or len(lt) != B or min(la) < 1 or min(lt) < 1 or max(la) > La or max(lt) > Lt:
+            raise ValueError("DataParallelStep (packed mode): lengths must hold one value in [1, L] per utterance and modality")
+        return la, lt
+    va, vt = ~m_a.bool(), ~m_t.bool()
+    la, lt = va.sum(1), vt.sum(1)
+    ok = ((va == (torch.arange(La, device=m_a.device)[None, :] < la[:, None])).all()
+          & (vt == (torch.arange(Lt, device=m_t.device)[None, :] < lt[:, None])).all() & (la > 0).all() & (lt > 0).all())
+    host = torch.cat([la, lt, ok.long().view(1)]).tolist()
+    if not host[-1]:
+        raise RuntimeError("DataParallelStep (packed mode): padding masks must mark a suffix of every row and leave at least "
+                           "one valid position -- use_graph(False) runs such a batch on the padded path")
+    return host[:B], host[B:2 * B]
 
 
 def ghost_plan(la, lt, B, La, Lt):
@@ -45,7 +76,7 @@ def ghost_plan(la, lt, B, La, Lt):
     own = (sum(la), sum(lt))
     ghosts = [1] * (B - len(la))
     la, lt = list(la) + ghosts, list(lt) + ghosts
-    return la, lt, (bucket_rows(sum(la), B, La), bucket_rows(sum(lt), B, Lt)), own
+    return la, lt, packed_tables(la, lt, B, La, Lt)[0], own
 
 
 def ctl_words(n_valid, first, last):
@@ -124,6 +155,7 @@ class GradBuckets:
         self.suspended = False      # True: gradient-ready notifications are ignored (rank-local diagnostic steps: no collectives)
         self._works = []
         self._hooks = []
+        self._predicate = None
         if overlap and (self.world > 1 or self.force_exchange):
             from . import _ops
             # an overlapped exchange wants gradients in production order; one predicate per GradBuckets (a second instance --
@@ -139,7 +171,7 @@ class GradBuckets:
         for h in self._hooks:
             h.remove()
         self._hooks = []
-        if getattr(self, "_predicate", None) is not None:
+        if self._predicate is not None:
             _ops.unregister_hook_predicate(self._predicate)
             self._predicate = None
         for p in self.params:
@@ -296,6 +328,74 @@ def _in_step_context(fn):
     return wrapper
 
 
+class _GraphRecord:
+    """One captured graph and what lives exactly as long as it: the loss tensor its replay writes, the buffers its kernels point
+    into (column-sum partials, queued weight-gradient operands), the packed plans of a bucket graph (None: the plain step).  A
+    record has ONE owner -- DataParallelStep._record or a _PackedState.graphs entry -- and dies through release()."""
+    __slots__ = ("graph", "loss", "keep", "seqs")
+
+    def __init__(self, graph, loss, keep, seqs=None):
+        self.graph, self.loss, self.keep, self.seqs = graph, loss, keep, seqs
+
+    def release(self):
+        """the one way down for _ops.GRAPHS_ALIVE (the way up: _capture_graph); the caller has synchronized the device"""
+        from . import _ops
+        self.graph = self.loss = self.keep = self.seqs = None
+        _ops.GRAPHS_ALIVE -= 1
+        if _ops.GRAPHS_ALIVE == 0:
+            del _ops._ws_retired[:]   # no graph points into the outgrown workspaces any more
+
+
+class _HostBlock:
+    """a small int32 block a captured step reads from device memory (`dev`) and its host twin (`host`, pinned beside a GPU)"""
+    __slots__ = ("dev", "host", "copied")
+
+    def __init__(self, values, device):
+        self.dev = torch.tensor(values, dtype=torch.int32, device=device)
+        self.host = torch.tensor(values, dtype=torch.int32, pin_memory=self.dev.is_cuda)
+        self.copied = None           # event behind the latest upload: until it has passed the twin is still being read
+
+    def upload(self, values):
+        """values -> twin -> device, in stream order"""
+        if self.copied is not None:
+            self.copied.synchronize()         # the previous upload has left the pinned twin
+        self.host.copy_(torch.tensor(values, dtype=torch.int32))
+        self.dev.copy_(self.host, non_blocking=True)
+        self.copied = torch.cuda.Event()
+        self.copied.record()
+
+
+class _RaggedFront:
+    """what capture_packed adds in front of the packed step: the lengths as one [2, B] block, the three mask buffers
+    hriemo_seq_tables fills (uint8, and the same memory as bool), and the step-control block {n_valid, first, last, spare} --
+    None unless the step was captured with partial_batches or grad_accum > 1"""
+    __slots__ = ("lens", "masks", "bool", "same_width", "partial", "accum", "ctl")
+
+    def __init__(self, lens, masks, same_width, partial=False, accum=1, ctl=None):
+        self.lens, self.masks, self.bool = lens, masks, tuple(m.view(torch.bool) for m in masks)
+        self.same_width, self.partial, self.accum, self.ctl = same_width, bool(partial), int(accum), ctl
+
+
+# the mask-fed packed step's memory of its last batch: the identity of the mask tensors, their bucket key and cu_seqlens, the masks
+_MaskSeen = collections.namedtuple("_MaskSeen", "ident key cu masks")
+
+
+class _PackedState:
+    """a step captured in packed (varlen) mode: the baked-in shapes, the three cu_seqlens buffers every bucket graph reads, the
+    bucket graphs {(rows audio, rows text): _GraphRecord} in LRU order with their one memory pool, and the ragged front door
+    (capture_packed) or None (mask-fed, capture)"""
+    __slots__ = ("B", "La", "Lt", "cu_a", "cu_t", "cu_f", "graphs", "pool", "front")
+
+    def __init__(self, B, La, Lt, device, front=None):
+        self.B, self.La, self.Lt, self.front = B, La, Lt, front
+        self.cu_a, self.cu_t, self.cu_f = (torch.zeros(B + 2, dtype=torch.int32, device=device) for _ in range(3))
+        self.graphs = collections.OrderedDict()
+        self.pool = None              # the bucket graphs never run concurrently: one pool for all
+
+    def __getitem__(self, name):      # bench.py reads _pb["graphs"]
+        return getattr(self, name)
+
+
 class DataParallelStep:
     """fwd -> loss -> bwd -> gradient all-reduce for one shard; mirrors the order of operations of
     train_one_epoch (scripts/fusion/train_fusion_seq_level_decoder.py:310-334) minus the optimizer.
@@ -313,20 +413,29 @@ class DataParallelStep:
                  launch_from="notify", force_queue=None):
         self.model, self.loss_fn = model, loss_fn
         self.force_queue = force_queue    # None: the loader / consumer GEMMs draw from the work queue when collectives run beside backward; True / False: always / never
-        self._keep = []
-        self._exchange_in_graph = False
+        self._exchange_in_graph = False   # capture(collectives=True): the bucket all-reduces are part of the captured step
+        self._replay = True               # use_graph(False) runs a captured step eagerly
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.buckets = GradBuckets(model.parameters(), bucket_bytes, group, overlap, comm_dtype, force_exchange, launch_from)
         from . import _ops
         self.ctx = _ops.StepContext()      # this step's capture flag / packed plan / join scope: not shared with another model's
-        self._graph = None
-        self._static = None
-        self._static_loss = None
-        self._pb = None               # packed (varlen) bucket graphs: {(rows audio, rows text): record}, see capture()
-        self._pool = None
+        # a captured graph has one owner: _record (the plain step) or _pb.graphs (the packed modes, one record per bucket)
+        self._record = None
+        self._pb = None               # _PackedState of a step captured in packed (varlen) mode, see capture()
+        self._static = None           # the static batch the captured step reads: [h_a, h_t, m_a, m_t, y]
+        self._mask_seen = None        # mask-fed packed step: (mask identity, bucket key, cu_seqlens clones, the masks) of the last step
         self._optimizer = None        # optim.DeviceAdamW whose update closes the captured step (capture(optimizer=...))
         self._micro = 0               # micro-steps of the open accumulation group (capture_packed(grad_accum=k)): 0 .. k-1
+
+    @property
+    def captured(self):
+        """a captured step exists (use_graph decides whether step() replays it)"""
+        return self._record is not None or (self._pb is not None and len(self._pb.graphs) > 0)
+
+    @property
+    def _replaying(self):
+        return self._replay and self.captured
 
     def set_global_batch(self, global_batch):
         lo, hi = shard_bounds(global_batch, self.rank, self.world)
@@ -338,15 +447,15 @@ class DataParallelStep:
         """ragged = (audio lengths, text lengths, pad_to): h_a / h_t are a ragged batch's own rows (the eager forward_packed step).
         After capture_packed, without `ragged`: h_a / h_t are the static row sources and the step starts with hriemo_seq_tables."""
         from . import _ops
-        front = self._pb.get("front") if (self._pb is not None and ragged is None) else None
+        pb = self._pb
+        front = pb.front if (pb is not None and ragged is None) else None
         if front is not None:
             # the first launch of the packed arm, warm-up passes included: the lengths [2, B] -> the three cu_seqlens of the bucket
             # in force and the three masks; everything behind it reads those static buffers
             seqs = _ops.CTX.seq_override
             if seqs is None:
                 raise RuntimeError("DataParallelStep: after capture_packed() the static rows are fed by step_packed() only")
-            _ops.seq_tables(front["lens"], self._pb["La"], self._pb["Lt"], rows=(seqs[0].N, seqs[1].N),
-                            cu=(self._pb["cu_a"], self._pb["cu_t"], self._pb["cu_f"]), masks=front["masks"])
+            _ops.seq_tables(front.lens.dev, pb.La, pb.Lt, rows=(seqs[0].N, seqs[1].N), cu=(pb.cu_a, pb.cu_t, pb.cu_f), masks=front.masks)
         # collectives launched from the gradient-ready hooks run BESIDE backward (eagerly, or baked into a capture): the loader /
         # consumer GEMMs then draw their tiles from the work queue (a block whose CU a collective holds late draws fewer); with
         # the chip to itself they walk statically, which is 5-8 % faster per launch alone and equal inside the step (DESIGN.md 3.1)
@@ -355,8 +464,8 @@ class DataParallelStep:
             _ops.gemm_contended(bool(b._hooks) and not b.suspended and b.world > 1)
         else:
             _ops.gemm_contended(bool(self.force_queue), force=True)
-        ctl = front.get("ctl") if front is not None else None
-        if ctl is not None and front["accum"] > 1:
+        ctl = front.ctl.dev if (front is not None and front.ctl is not None) else None
+        if ctl is not None and front.accum > 1:
             # a step captured with gradient accumulation: whether the flat buffer starts from zero is device data (ctl.first)
             from . import _lib
             _lib.call("hriemo_grad_begin", self.buckets.flat.data_ptr(), self.buckets.flat.numel(), ctl.data_ptr(), _ops._stream())
@@ -366,10 +475,10 @@ class DataParallelStep:
         if ragged is not None:
             logits, beta, _ = self.model.forward_packed(h_a, h_t, ragged[0], ragged[1], pad_to=ragged[2])
         elif front is not None:
-            logits, beta, _ = self.model._forward_rows(h_a, h_t, tuple(seqs), front["bool"], (self._pb["La"], self._pb["Lt"]))
+            logits, beta, _ = self.model._forward_rows(h_a, h_t, tuple(seqs), front.bool, (pb.La, pb.Lt))
         else:
             logits, beta, _ = self.model(h_a, h_t, m_a, m_t)
-        if ctl is not None and front["partial"]:
+        if ctl is not None and front.partial:
             loss = self.loss_fn(logits, beta, y, n_valid=ctl[:1])      # ctl.n_valid: the ghosts behind it add nothing and get zero gradients
         else:
             loss = self.loss_fn(logits, beta, y)
@@ -399,9 +508,8 @@ class DataParallelStep:
                 ra, rt, la, lt, y = mb
                 la, lt, pad = _ops.packed_lengths(ra, rt, la, lt, pad_to, same_width=not hasattr(self.model, "audio_proj"))
                 l = self._fwd_bwd(ra, rt, None, None, y, zero=(i == 0), scale=1.0 / k, ragged=(la, lt, pad))
-                total = l if total is None else total + l
-                continue
-            l = self._fwd_bwd(*mb, zero=(i == 0), scale=1.0 / k)
+            else:
+                l = self._fwd_bwd(*mb, zero=(i == 0), scale=1.0 / k)
             total = l if total is None else total + l
         self.buckets.suspended = was
         self.buckets.finish()
@@ -432,46 +540,46 @@ class DataParallelStep:
         Every scalar of the update is device data, so packed bucket graphs captured later share the one step count.  At world
         size > 1 this needs collectives=True: an exchange after the replay would run behind the update."""
         from . import _ops
+        packed = _ops.varlen() and m_a is not None and m_t is not None
+        self._begin_capture("capture", optimizer, collectives, packed)
+        self._static = [None if t is None else t.clone() for t in (h_a, h_t, m_a, m_t, y)]
+        if packed:
+            self._pb = _PackedState(h_a.shape[0], h_a.shape[1], h_t.shape[1], self._static[0].device)
+            self._packed_graph(self._packed_key(m_a, m_t, lengths))
+        else:
+            self._record = self._capture_graph(None)
+        self._end_capture()
+
+    def _begin_capture(self, entry, optimizer, collectives, packed):
+        """the refusals capture() and capture_packed() share, then the old step goes and the new one's facts are set"""
         if optimizer is not None:
             from .optim import DeviceAdamW
             if not isinstance(optimizer, DeviceAdamW) or optimizer.buckets is not self.buckets:
-                raise TypeError("capture(optimizer=...) takes an optim.DeviceAdamW built on this step's buckets (every scalar of its "
+                raise TypeError(f"{entry}(optimizer=...) takes an optim.DeviceAdamW built on this step's buckets (every scalar of its "
                                 "update is device data; FusedClipAdamW passes lr and the step count by value)")
             if self.world > 1 and not collectives:
-                raise RuntimeError("capture(optimizer=...) at world size > 1 needs collectives=True: the gradient exchange after the "
-                                   "replay would run behind the captured update")
+                raise RuntimeError(f"{entry}(optimizer=...) at world size > 1 needs collectives=True: the gradient exchange after the "
+                                   "replay would run behind the captured update" + (" (and packed mode captures none)" if packed else ""))
+        if packed and collectives and self.world > 1:
+            raise RuntimeError(f"{entry}(collectives=True) in packed (varlen) mode: ranks meet new buckets at different steps and a "
+                               "bucket's capture runs eager warm-up exchanges -- capture without collectives (exchange after the "
+                               "replay) or run the padded path")
         if collectives and not self.buckets._hooks:
-            raise RuntimeError("capture(collectives=True) needs the gradient-ready hooks: GradBuckets(overlap=True) at world size > 1 "
+            raise RuntimeError(f"{entry}(collectives=True) needs the gradient-ready hooks: GradBuckets(overlap=True) at world size > 1 "
                                "(or force_exchange=True)")
         if not collectives and self.buckets._hooks and not self.buckets.suspended:
-            raise RuntimeError("capture() needs GradBuckets(overlap=False) or buckets.suspended = True, or collectives=True to "
+            raise RuntimeError(f"{entry}() needs GradBuckets(overlap=False) or buckets.suspended = True, or collectives=True to "
                                "capture the exchange as well")
         if collectives:
             self.buckets.suspended = False
-        self._static = [None if t is None else t.clone() for t in (h_a, h_t, m_a, m_t, y)]
         self.release_graph()              # a re-capture replaces the old graph(s): their pinned buffers go first
-        self._collectives = bool(collectives)
-        self._optimizer = optimizer
-        if _ops.varlen() and m_a is not None and m_t is not None:
-            if collectives and self.world > 1:
-                raise RuntimeError("capture(collectives=True) in packed (varlen) mode: ranks meet new buckets at different steps and a "
-                                   "bucket's capture runs eager warm-up exchanges -- capture without collectives (exchange after the "
-                                   "replay) or run the padded path")
-            dev = self._static[0].device
-            B, La, Lt = h_a.shape[0], h_a.shape[1], h_t.shape[1]
-            self._pb = {"graphs": collections.OrderedDict(), "B": B, "La": La, "Lt": Lt,
-                        "cu_a": torch.zeros(B + 2, dtype=torch.int32, device=dev), "cu_t": torch.zeros(B + 2, dtype=torch.int32, device=dev),
-                        "cu_f": torch.zeros(B + 2, dtype=torch.int32, device=dev)}
-            key = self._packed_key(m_a, m_t, lengths)
-            rec = self._packed_graph(key)
-            self._graph, self._static_loss, self._keep = rec["graph"], rec["loss"], []
-        else:
-            self._graph, self._static_loss, self._keep = self._capture_graph(None)
-        self._packed = self._pb is not None
-        self._mask_seen = {}
-        self._replay = True
         self._exchange_in_graph = bool(collectives)
-        if collectives:
+        self._optimizer = optimizer
+        self._mask_seen = None
+
+    def _end_capture(self):
+        self._replay = True
+        if self._exchange_in_graph:
             self.buckets.suspended = True         # from now on hooks fire only inside replays (they are baked into the graph)
 
     @_in_step_context
@@ -528,25 +636,7 @@ class DataParallelStep:
             raise ValueError("capture_packed: pad_to=(L_a, L_t) is required")
         dev = next(self.model.parameters()).device
         _ops._require_gpu(next(self.model.parameters()))
-        if optimizer is not None:
-            from .optim import DeviceAdamW
-            if not isinstance(optimizer, DeviceAdamW) or optimizer.buckets is not self.buckets:
-                raise TypeError("capture_packed(optimizer=...) takes an optim.DeviceAdamW built on this step's buckets")
-            if self.world > 1:
-                raise RuntimeError("capture_packed(optimizer=...) at world size > 1: the gradient exchange after the replay would run "
-                                   "behind the captured update (packed mode captures no collectives)")
-        if collectives and self.world > 1:
-            raise RuntimeError("capture_packed(collectives=True): ranks meet new buckets at different steps and a bucket's capture runs "
-                               "eager warm-up exchanges -- capture without collectives (exchange after the replay)")
-        if collectives and not self.buckets._hooks:
-            raise RuntimeError("capture_packed(collectives=True) needs the gradient-ready hooks: GradBuckets(force_exchange=True)")
-        if not collectives and self.buckets._hooks and not self.buckets.suspended:
-            raise RuntimeError("capture_packed() needs GradBuckets(overlap=False) or buckets.suspended = True")
-        if collectives:
-            self.buckets.suspended = False
-        self.release_graph()
-        self._collectives = bool(collectives)
-        self._optimizer = optimizer
+        self._begin_capture("capture_packed", optimizer, collectives, packed=True)
         self._micro = 0
         B = len(la)
         cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
@@ -554,23 +644,11 @@ class DataParallelStep:
         src_t = torch.zeros(cap_t, rows_t.shape[1], dtype=rows_t.dtype, device=dev)
         self._static = [src_a, src_t, None, None, y.to(dev, copy=True)]
         masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
-        cu = lambda: torch.zeros(B + 2, dtype=torch.int32, device=dev)     # noqa: E731
-        self._pb = {"graphs": collections.OrderedDict(), "B": B, "La": La, "Lt": Lt, "cu_a": cu(), "cu_t": cu(), "cu_f": cu(),
-                    "front": {"lens": torch.ones(2, B, dtype=torch.int32, device=dev), "lens_host": torch.ones(2, B, dtype=torch.int32).pin_memory(),
-                              "lens_copied": None, "masks": masks, "bool": tuple(m.view(torch.bool) for m in masks),
-                              "same_width": same_width, "partial": bool(partial_batches), "accum": int(grad_accum), "ctl": None}}
-        if partial_batches or grad_accum > 1:
-            self._pb["front"].update(ctl=torch.tensor([B, 1, 1, 0], dtype=torch.int32, device=dev),
-                                     ctl_host=torch.tensor([B, 1, 1, 0], dtype=torch.int32).pin_memory(), ctl_copied=None)
-        key = self._load_packed(rows_a, rows_t, la, lt, y)
-        rec = self._packed_graph(key)
-        self._graph, self._static_loss, self._keep = rec["graph"], rec["loss"], []
-        self._packed = True
-        self._mask_seen = {}
-        self._replay = True
-        self._exchange_in_graph = bool(collectives)
-        if collectives:
-            self.buckets.suspended = True
+        ctl = _HostBlock(ctl_words(B, 1, 1), dev) if (partial_batches or grad_accum > 1) else None
+        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, same_width, partial_batches, grad_accum, ctl)
+        self._pb = _PackedState(B, La, Lt, dev, front)
+        self._packed_graph(self._load_packed(rows_a, rows_t, la, lt, y))
+        self._end_capture()
 
     def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
         """a checked ragged batch into the static state -> its bucket key: the rows to the head of each source, zeros from there to
@@ -578,27 +656,16 @@ class DataParallelStep:
         A short batch (partial_batches) is completed with ghosts first (ghost_plan).  ctl = (first, last): the step-control block
         goes up with n_valid = the batch's own number of utterances, by the protocol of the lengths block."""
         pb = self._pb
-        front, B = pb["front"], pb["B"]
+        front = pb.front
         n_utt = len(la)
-        la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, B, pb["La"], pb["Lt"])
+        la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, pb.B, pb.La, pb.Lt)
         for src, rows, n, n_rows in ((self._static[0], rows_a, rows_own_a, key[0]), (self._static[1], rows_t, rows_own_t, key[1])):
             if rows.data_ptr() != src.data_ptr():
                 src[:n].copy_(rows, non_blocking=True)
             src[n:n_rows].zero_()
-        if front["lens_copied"] is not None:
-            front["lens_copied"].synchronize()        # the previous batch's lengths have left the pinned twin
-        front["lens_host"].copy_(torch.tensor([la, lt], dtype=torch.int32))
-        front["lens"].copy_(front["lens_host"], non_blocking=True)
-        front["lens_copied"] = torch.cuda.Event()
-        front["lens_copied"].record()
-        if front["ctl"] is not None:
-            first, last = ctl if ctl is not None else (1, 1)
-            if front["ctl_copied"] is not None:
-                front["ctl_copied"].synchronize()
-            front["ctl_host"].copy_(torch.tensor(ctl_words(n_utt, first, last), dtype=torch.int32))
-            front["ctl"].copy_(front["ctl_host"], non_blocking=True)
-            front["ctl_copied"] = torch.cuda.Event()
-            front["ctl_copied"].record()
+        front.lens.upload([la, lt])
+        if front.ctl is not None:
+            front.ctl.upload(ctl_words(n_utt, *(ctl if ctl is not None else (1, 1))))
         if y.data_ptr() != self._static[4].data_ptr():
             self._static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
         return key
@@ -612,18 +679,16 @@ class DataParallelStep:
         capture_packed(partial_batches=True) a batch of 1 <= n <= B utterances is served by the same graphs (ghosts, n_valid as
         device data); after capture_packed(grad_accum=k) every call is one MICRO-step and the k-th one carries the update."""
         from . import _ops
-        front = self._pb.get("front") if self._pb is not None else None
+        pb = self._pb
+        front = pb.front if pb is not None else None
         if front is None:
             raise RuntimeError("step_packed needs capture_packed() first")
-        pb = self._pb
-        B, pad = pb["B"], (pb["La"], pb["Lt"])
-        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front["same_width"])
-        replay = self._graph is not None and getattr(self, "_replay", True)
-        k = front["accum"]
-        first, last = micro_flags(self._micro, k)
-        if replay:
+        B, pad = pb.B, (pb.La, pb.Lt)
+        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front.same_width)
+        first, last = micro_flags(self._micro, front.accum)
+        if self._replaying:
             n = len(la)
-            if n != B and not front["partial"]:
+            if n != B and not front.partial:
                 raise ValueError(f"step_packed: a batch of {n} utterances; the captured step holds B = {B} (drop the batch, run it "
                                  "with use_graph(False), or capture with partial_batches=True)")
             if n > B:
@@ -641,15 +706,11 @@ class DataParallelStep:
                 self._optimizer._upload_hyper()
             key = self._load_packed(rows_a, rows_t, la, lt, y, ctl=(first, last))
             rec = self._packed_graph(key)                 # captures on the static state (already this batch) if the bucket is new
-            rec["graph"].replay()
+            rec.graph.replay()
             self._micro = 0 if last else self._micro + 1
             if last:
-                if not self._exchange_in_graph:
-                    self.buckets.finish()
-                if self._optimizer is not None:
-                    _ops.bump_weights_epoch()
-                    self._optimizer._opt_called = True
-            return rec["loss"]
+                self._after_replay()
+            return rec.loss
         dev = self._static[0].device
         was = self.buckets.suspended
         if not last:
@@ -685,7 +746,7 @@ class DataParallelStep:
         if n == 0:
             return 0
         self._micro = 0
-        if not self._exchange_in_graph or not (self._graph is not None and getattr(self, "_replay", True)):
+        if not self._exchange_in_graph or not self._replaying:
             self.buckets.finish()
         if self._optimizer is not None:
             self._optimizer.step()                        # uploads hyper[], bumps the weights epoch
@@ -695,80 +756,49 @@ class DataParallelStep:
     def _packed_key(self, m_a, m_t, lengths):
         """host-side: the batch's cu_seqlens written to the static device buffers + the bucket (rows audio, rows text) it needs"""
         pb = self._pb
-        B, La, Lt = pb["B"], pb["La"], pb["Lt"]
-        if lengths is None:
-            # one device -> host read per step; masks must be prefix masks with no empty sequence (the collate's form)
-            va, vt = ~m_a.bool(), ~m_t.bool()
-            la, lt = va.sum(1), vt.sum(1)
-            ok = ((va == (torch.arange(La, device=m_a.device)[None, :] < la[:, None])).all()
-                  & (vt == (torch.arange(Lt, device=m_t.device)[None, :] < lt[:, None])).all() & (la > 0).all() & (lt > 0).all())
-            host = torch.cat([la, lt, ok.long().view(1)]).tolist()
-            if not host[-1]:
-                raise RuntimeError("DataParallelStep (packed mode): padding masks must mark a suffix of every row and leave at least "
-                                   "one valid position -- use_graph(False) runs such a batch on the padded path")
-            la, lt = host[:B], host[B:2 * B]
-        else:
-            la, lt = [int(x) for x in lengths[0]], [int(x) for x in lengths[1]]
-            if len(la) != B or len(lt) != B or min(la) < 1 or min(lt) < 1 or max(la) > La or max(lt) > Lt:
-                raise ValueError("DataParallelStep (packed mode): lengths must hold one value in [1, L] per utterance and modality")
-        out = []
-        lf = [min(x, y) for x, y in zip(la, lt)]      # the fused memory of a sample: the reference ORs the two prefix masks
-        for lens, L, buf in ((la, La, pb["cu_a"]), (lt, Lt, pb["cu_t"])):
-            rows = bucket_rows(sum(lens), B, L)
-            cu = [0]
-            for x in lens:
-                cu.append(cu[-1] + x)
-            cu.append(rows)
+        la, lt = mask_lengths(m_a, m_t, lengths, pb.B, pb.La, pb.Lt)
+        key, *tables = packed_tables(la, lt, pb.B, pb.La, pb.Lt)
+        for buf, cu in zip((pb.cu_a, pb.cu_t, pb.cu_f), tables):
             buf.copy_(torch.tensor(cu, dtype=torch.int32))
-            out.append(rows)
-        # the fused plan rides in the text bucket (sum lf <= sum lt < its row count): no bucket dimension, no graph of its own
-        if pb.get("cu_f") is not None:
-            cu = [0]
-            for x in lf:
-                cu.append(cu[-1] + x)
-            cu.append(out[1])
-            pb["cu_f"].copy_(torch.tensor(cu, dtype=torch.int32))
-        return tuple(out)
+        return key
 
     def _packed_graph(self, key):
         from . import _ops
         pb = self._pb
-        rec = pb["graphs"].get(key)
+        rec = pb.graphs.get(key)
         if rec is None:
-            while len(pb["graphs"]) >= _VARLEN_MAX_GRAPHS:
-                # bounded: a corpus with a wide length spread would otherwise accumulate a graph + its buffers per bucket pair
-                old_key, old = pb["graphs"].popitem(last=False)
-                torch.cuda.synchronize()
-                old.clear()
-                _ops.GRAPHS_ALIVE = max(1, _ops.GRAPHS_ALIVE - 1)
-                log.info("packed step: released the graph of bucket %s (cap %d)", old_key, _VARLEN_MAX_GRAPHS)
-            seqs = (_ops.seq_bucket(pb["cu_a"], pb["B"], pb["La"], key[0]), _ops.seq_bucket(pb["cu_t"], pb["B"], pb["Lt"], key[1]),
-                    _ops.seq_bucket_fused(pb["cu_f"], pb["B"], min(pb["La"], pb["Lt"]), key[1]))
             # a bucket met inside step() runs two eager warm-up passes + the capture pass; each draws dropout seeds from torch's
             # CPU generator.  Ranks meet new buckets at different steps, so the generator is put back: its stream stays the one
-            # the caller (and every other rank) sees, as _ops.next_seed documents.
-            rng = torch.get_rng_state() if self._graph is not None else None
+            # the caller (and every other rank) sees, as _ops.next_seed documents.  (The step's first capture keeps its draws.)
+            rng = torch.get_rng_state() if self.captured else None
+            while len(pb.graphs) >= _VARLEN_MAX_GRAPHS:
+                # bounded: a corpus with a wide length spread would otherwise accumulate a graph + its buffers per bucket pair
+                old_key, old = pb.graphs.popitem(last=False)
+                torch.cuda.synchronize()
+                old.release()
+                log.info("packed step: released the graph of bucket %s (cap %d)", old_key, _VARLEN_MAX_GRAPHS)
+            seqs = (_ops.seq_bucket(pb.cu_a, pb.B, pb.La, key[0]), _ops.seq_bucket(pb.cu_t, pb.B, pb.Lt, key[1]),
+                    _ops.seq_bucket_fused(pb.cu_f, pb.B, min(pb.La, pb.Lt), key[1]))
             # inside an accumulation group the warm-up passes run with ctl.first = 0 and would add to the running gradient sum:
             # it is set aside and put back (a copy of the flat buffer, paid only when a bucket is met for the first time)
-            front = pb.get("front")
-            held = self.buckets.flat.clone() if (front is not None and front["accum"] > 1 and self._micro > 0) else None
+            front = pb.front
+            held = self.buckets.flat.clone() if (front is not None and front.accum > 1 and self._micro > 0) else None
             try:
-                graph, loss, keep = self._capture_graph(seqs)
+                rec = pb.graphs[key] = self._capture_graph(seqs)
             finally:
                 if rng is not None:
                     torch.set_rng_state(rng)
                 if held is not None:
                     self.buckets.flat.copy_(held)
-            rec = pb["graphs"][key] = {"graph": graph, "loss": loss, "keep": keep, "seqs": seqs}
-            log.info("packed step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb["graphs"]))
+            log.info("packed step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb.graphs))
         else:
-            pb["graphs"].move_to_end(key)
+            pb.graphs.move_to_end(key)
         return rec
 
     def _capture_graph(self, seqs):
-        """warm-up + capture of one step on self._static; seqs = the packed plans of a bucket graph (or None) -> (graph, loss, keep)"""
+        """warm-up + capture of one step on self._static; seqs = the packed plans of a bucket graph (or None) -> its _GraphRecord"""
         from . import _ops
-        collectives = self._collectives
+        collectives = self._exchange_in_graph
         # ONE capture stream per device for every capture of the process: workspaces are keyed by stream, a fresh stream per
         # capture would allocate (and, with a graph alive, retire instead of free) a fresh 64 MB+ set each time
         dev = self._static[0].device
@@ -794,8 +824,8 @@ class DataParallelStep:
                 import time
                 time.sleep(0.25)
             graph = torch.cuda.CUDAGraph()
-            if seqs is not None and self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()       # the bucket graphs never run concurrently: one pool for all
+            if seqs is not None and self._pb.pool is None:
+                self._pb.pool = torch.cuda.graph_pool_handle()
             _ops.CTX.capturing = True
             _ops.CTX.capture_origin = side        # every helper-stream fork of the step must start here (_ops.fork refuses nested forks)
             _ops.begin_step()
@@ -803,15 +833,15 @@ class DataParallelStep:
                 # capture on the stream the warm-up ran on: its workspaces (keyed by stream) exist already, so nothing the
                 # graph points into comes from the graph's private pool or is first sized during capture.
                 # thread_local: the RCCL watchdog thread may query events while we capture
-                kw = {"pool": self._pool} if seqs is not None else {}
+                kw = {"pool": self._pb.pool} if seqs is not None else {}
                 with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local", **kw):
                     _ops.bump_seed_word(self._static[0].device)
                     loss = self._fwd_bwd(*self._static)
                     if collectives:
                         self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
                     if self._optimizer is not None:
-                        front = self._pb.get("front") if self._pb is not None else None
-                        ctl = front["ctl"] if (front is not None and front["accum"] > 1) else None
+                        front = self._pb.front if self._pb is not None else None
+                        ctl = front.ctl.dev if (front is not None and front.accum > 1) else None
                         self._optimizer._enqueue(ctl=ctl)    # recorded, not run: norm, skip / hold / clip / bias corrections, update
             finally:
                 _ops.CTX.capturing = False
@@ -823,69 +853,63 @@ class DataParallelStep:
         # this graph: they move from the process-wide lists to the graph's owner
         keep = _ops._deferred.keep + _ops._small_dw.keep
         _ops._deferred.keep, _ops._small_dw.keep = [], []
-        return graph, loss, keep
+        return _GraphRecord(graph, loss, keep, seqs)
 
     def release_graph(self):
-        """drop the captured step (before a re-capture, or to free its buffers): the graph, the buffers its kernels point into"""
-        from . import _ops
-        if self._graph is not None:
+        """drop the captured step (before a re-capture, or to free its buffers): the graph(s), the buffers their kernels point into"""
+        if self.captured:
             torch.cuda.synchronize()
-            n = len(self._pb["graphs"]) if self._pb is not None else 1
-            self._graph = None
-            self._keep = []
-            self._pb = None
-            self._optimizer = None
-            _ops.GRAPHS_ALIVE = max(0, _ops.GRAPHS_ALIVE - n)
-            if _ops.GRAPHS_ALIVE == 0:
-                del _ops._ws_retired[:]   # no graph points into the outgrown workspaces any more
+            for rec in ([self._record] if self._record is not None else self._pb.graphs.values()):
+                rec.release()
+            self._record = self._pb = self._optimizer = None
 
     def use_graph(self, on):
         """Switch between the captured replay (gradient exchange after it) and eager launches (exchange from the
         gradient-ready hooks during backward, if installed)."""
-        self._replay = bool(on) and self._graph is not None
+        self._replay = bool(on) and self.captured
         self.buckets.suspended = self._replay     # eager steps: the hooks drive the exchange; replays: it follows / is inside the graph
+
+    def _after_replay(self):
+        """what follows the replay that carries the update: the exchange unless the graph holds it, the optimizer's host side"""
+        if not self._exchange_in_graph:
+            self.buckets.finish()
+        if self._optimizer is not None:
+            from . import _ops
+            _ops.bump_weights_epoch()                 # the replay rewrote the parameters through raw pointers
+            self._optimizer._opt_called = True        # torch's lr schedulers warn about a scheduler.step() before any optimizer step
 
     @_in_step_context
     def step(self, h_a, h_t, m_a, m_t, y, lengths=None):
-        if self._graph is not None and getattr(self, "_replay", True):
-            graph, loss = self._graph, self._static_loss
+        if self._replaying:
+            pb = self._pb
             if self._optimizer is not None:
                 self._optimizer._upload_hyper()           # host -> device only; the replay reads lr & co. from that block
-            if self._pb is not None and "front" in self._pb:
+            if pb is not None and pb.front is not None:
                 raise RuntimeError("DataParallelStep: this step was captured by capture_packed(); feed it with step_packed()")
-            if self._pb is not None:
+            if pb is not None:
                 # packed mode: any padding masks of the captured shapes; the lengths travel as device data (cu_seqlens), the row
                 # counts pick the bucket graph (captured now if this bucket was not seen before)
                 if m_a is None or m_t is None:
                     raise RuntimeError("DataParallelStep (packed mode): both padding masks are needed")
-                seen = (m_a.data_ptr(), m_a._version, m_t.data_ptr(), m_t._version)
-                if lengths is None and self._mask_seen.get("key") == seen:
-                    key = self._mask_seen["val"]          # the same mask tensors as last step: no second device -> host read
-                    for name, saved in zip(("cu_a", "cu_t", "cu_f"), self._mask_seen["cu"]):
-                        self._pb[name].copy_(saved)
+                ident = (m_a.data_ptr(), m_a._version, m_t.data_ptr(), m_t._version)
+                seen = self._mask_seen
+                if lengths is None and seen is not None and seen.ident == ident:
+                    key = seen.key                        # the same mask tensors as last step: no second device -> host read
+                    for buf, saved in zip((pb.cu_a, pb.cu_t, pb.cu_f), seen.cu):
+                        buf.copy_(saved)
                 else:
                     key = self._packed_key(m_a, m_t, lengths)
                     # the entry HOLDS the masks: while it is the cache entry their addresses cannot be handed to the next batch's
                     # masks (same address + version 0 would otherwise pass for "the same tensors" with other lengths inside)
-                    self._mask_seen = {"key": seen, "val": key, "cu": (self._pb["cu_a"].clone(), self._pb["cu_t"].clone(), self._pb["cu_f"].clone()),
-                                       "masks": (m_a, m_t)}
-                for s, t in zip(self._static, (h_a, h_t, m_a, m_t, y)):
-                    if s is not None and t is not None and s.data_ptr() != t.data_ptr():
-                        s.copy_(t)
-                rec = self._packed_graph(key)             # captures on self._static (already this batch) if the bucket is new
-                graph, loss = rec["graph"], rec["loss"]
-            else:
-                for s, t in zip(self._static, (h_a, h_t, m_a, m_t, y)):
-                    if s is not None and t is not None and s.data_ptr() != t.data_ptr():
-                        s.copy_(t)
-            graph.replay()
-            if not self._exchange_in_graph:
-                self.buckets.finish()
-            if self._optimizer is not None:
-                from . import _ops
-                _ops.bump_weights_epoch()                 # the replay rewrote the parameters through raw pointers
-                self._optimizer._opt_called = True        # torch's lr schedulers warn about a scheduler.step() before any optimizer step
-            return loss
+                    self._mask_seen = _MaskSeen(ident, key, (pb.cu_a.clone(), pb.cu_t.clone(), pb.cu_f.clone()), (m_a, m_t))
+            for s, t in zip(self._static, (h_a, h_t, m_a, m_t, y)):
+                if s is not None and t is not None and s.data_ptr() != t.data_ptr():
+                    s.copy_(t)
+            # packed: captures on self._static (already this batch) if the bucket is new
+            rec = self._packed_graph(key) if pb is not None else self._record
+            rec.graph.replay()
+            self._after_replay()
+            return rec.loss
         loss = self._fwd_bwd(h_a, h_t, m_a, m_t, y)
         self.buckets.finish()
         if self._optimizer is not None:

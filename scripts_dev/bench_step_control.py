@@ -85,7 +85,7 @@ def make(k, **kw):
 def prepare(arm, items):
     dp, opt, kw = arm
     for i, (r_a, l_a, r_t, l_t, y) in enumerate(feed(items)):
-        if i == 0 and dp._graph is None:
+        if i == 0 and not dp.captured:
             dp.capture_packed(r_a, r_t, l_a, l_t, y, pad_to=(TA, TT), optimizer=opt, **kw)
         dp.step_packed(r_a, r_t, l_a, l_t, y)
     dp.flush_accumulated()
@@ -132,7 +132,7 @@ def stepper(arm):
 P, Q, Q2 = make(1), make(1, partial_batches=True, grad_accum=2), make(2, partial_batches=True, grad_accum=2)
 for arm in (P, Q, Q2):
     prepare(arm, full)
-Q[0]._pb["front"]["accum"] = 1            # groups of one on the graph captured for accumulation: first = last = 1 on every call
+Q[0]._pb.front.accum = 1            # groups of one on the graph captured for accumulation: first = last = 1 on every call
 prepare(Q, half)                          # the tail's bucket graphs (arm T)
 arms = {"P": stepper(P), "Q": stepper(Q), "Q2": stepper(Q2)}
 for fn in arms.values():
@@ -142,7 +142,7 @@ for r in range(ROUNDS):
     for k, fn in arms.items():
         t[k].append(wall(fn, steps_full, STEPS))
     print(f"full batch: round {r}: " + ", ".join(f"{k} {v[-1]:.3f}" for k, v in t.items()) + " ms/call", flush=True)
-report(f"1. full batch, optimizer in the graph (bucket graphs P {len(P[0]._pb['graphs'])} / Q {len(Q[0]._pb['graphs'])})", t, "P", "call")
+report(f"1. full batch, optimizer in the graph (bucket graphs P {len(P[0]._pb.graphs)} / Q {len(Q[0]._pb.graphs)})", t, "P", "call")
 
 # ---- 2. an epoch's tail: B / 2 utterances
 E = P

@@ -84,7 +84,7 @@ def run(valid):
             dp_b.capture_packed(r_a, r_t, l_a, l_t, y, pad_to=(TA, TT))
         dp_b.step_packed(r_a, r_t, l_a, l_t, y)
     torch.cuda.synchronize()
-    graphs = (len(dp_a._pb["graphs"]), len(dp_b._pb["graphs"]))
+    graphs = (len(dp_a._pb.graphs), len(dp_b._pb.graphs))
     items_a, items_b = [pad[i % NBATCH] for i in range(STEPS)], [rag[i % NBATCH] for i in range(STEPS)]
 
     def wall_a():

@@ -33,10 +33,10 @@ t32 = timeit(lambda: dpa.step(*ba))
 print(f"one step B=32 alone: {t32:.3f} ms -> {32 / t32 * 1e3:.0f} utt/s", flush=True)
 s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
 def both():
-    with torch.cuda.stream(s1): dpa._graph.replay()
-    with torch.cuda.stream(s2): dpb._graph.replay()
+    with torch.cuda.stream(s1): dpa._record.graph.replay()
+    with torch.cuda.stream(s2): dpb._record.graph.replay()
 for stagger in (False, True):
     if stagger:       # offset the second stream by half a step so that tails meet bodies
-        with torch.cuda.stream(s2): dpb._graph.replay()
+        with torch.cuda.stream(s2): dpb._record.graph.replay()
     tb = timeit(both)
     print(f"two B=32 steps concurrently (stagger={stagger}): {tb:.3f} ms per pair -> {64 / tb * 1e3:.0f} utt/s", flush=True)

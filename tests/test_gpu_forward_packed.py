@@ -354,8 +354,8 @@ def test_captured_bucket_graphs_with_the_switch_on(H, monkeypatch):
     for i, batch in enumerate(batches):
         loss = float(dp.step(*batch))
         torch.cuda.synchronize()
-        keys.add(tuple(int(x) for x in (dp._pb["cu_a"][-1], dp._pb["cu_t"][-1])))
-        assert int(dp._pb["cu_a"][-1]) > int(dp._pb["cu_a"][nb]), "the bucket has surplus rows behind the last sample"
+        keys.add(tuple(int(x) for x in (dp._pb.cu_a[-1], dp._pb.cu_t[-1])))
+        assert int(dp._pb.cu_a[-1]) > int(dp._pb.cu_a[nb]), "the bucket has surplus rows behind the last sample"
         rel = float((dp.buckets.flat - ref[i][1]).norm() / ref[i][1].norm())
         print(f"batch {i}: loss {loss:.6f} vs {ref[i][0]:.6f}, flat gradients relative L2 {rel:.2e}")
         assert abs(loss - ref[i][0]) <= 1e-5 * max(1.0, abs(ref[i][0])), (i, loss, ref[i][0])
@@ -365,7 +365,7 @@ def test_captured_bucket_graphs_with_the_switch_on(H, monkeypatch):
     loss = float(dp.step(*batches[0]))
     torch.cuda.synchronize()
     assert loss == once[0] and torch.equal(dp.buckets.flat, once[1]), "a second replay of the first batch"
-    assert len(dp._pb["graphs"]) == len(keys) == 2
+    assert len(dp._pb.graphs) == len(keys) == 2
     names = [n for n, _ in spy.take()]
     assert names.count("hriemo_ingest_rows") >= 2 * len(keys) and "hriemo_pack_rows" not in names
     dp.release_graph()

@@ -450,8 +450,8 @@ def test_captured_bucket_graphs_run_the_fp32_packed_tail(H):
     for i, batch in enumerate(batches):
         loss = float(dp.step(*batch))
         torch.cuda.synchronize()
-        keys.add(tuple(int(x) for x in (dp._pb["cu_a"][-1], dp._pb["cu_t"][-1])))
-        assert int(dp._pb["cu_f"][-1]) == int(dp._pb["cu_t"][-1])
+        keys.add(tuple(int(x) for x in (dp._pb.cu_a[-1], dp._pb.cu_t[-1])))
+        assert int(dp._pb.cu_f[-1]) == int(dp._pb.cu_t[-1])
         assert bool(torch.isfinite(dp.buckets.flat).all()), i
         rel = float((dp.buckets.flat - ref[i][1]).norm() / ref[i][1].norm())
         print(f"batch {i}: loss {loss:.6f} vs {ref[i][0]:.6f}, flat gradients relative L2 {rel:.2e}")
@@ -462,5 +462,5 @@ def test_captured_bucket_graphs_run_the_fp32_packed_tail(H):
     loss = float(dp.step(*batches[0]))
     torch.cuda.synchronize()
     assert loss == first[0] and torch.equal(dp.buckets.flat, first[1]), "a second replay of the first batch"
-    assert len(dp._pb["graphs"]) == len(keys) == 3
+    assert len(dp._pb.graphs) == len(keys) == 3
     dp.release_graph()

@@ -374,14 +374,14 @@ def test_captured_fp32_packed_step_serves_every_batch(H):
     for i, (batch, lens) in enumerate(batches):
         loss = float(dp.step(*batch, lengths=lens if i % 2 else None))
         torch.cuda.synchronize()
-        seen.add(tuple(int(x) for x in (dp._pb["cu_a"][-1], dp._pb["cu_t"][-1])))
+        seen.add(tuple(int(x) for x in (dp._pb.cu_a[-1], dp._pb.cu_t[-1])))
         assert abs(loss - ref[i][0]) <= 1e-5 * max(1.0, abs(ref[i][0])), (i, loss, ref[i][0])
         assert _rel(dp.buckets.flat, ref[i][1]) <= 1e-5, (i, _rel(dp.buckets.flat, ref[i][1]))
         if i == 0:                                    # the replay against the eager packed step on the same bucket plan
             replay_flat = dp.buckets.flat.clone()
-            rec = dp._pb["graphs"][dp._mask_seen["val"]]
+            rec = dp._pb.graphs[dp._mask_seen.key]
             with _ops.use_context(dp.ctx):
-                dp.ctx.seq_override = rec["seqs"]
+                dp.ctx.seq_override = rec.seqs
                 try:
                     eager_b = float(dp._fwd_bwd(*dp._static))
                 finally:
@@ -389,7 +389,7 @@ def test_captured_fp32_packed_step_serves_every_batch(H):
             dp.buckets.finish()
             torch.cuda.synchronize()
             assert eager_b == loss and torch.equal(dp.buckets.flat, replay_flat), (eager_b, loss, _rel(dp.buckets.flat, replay_flat))
-    assert len(dp._pb["graphs"]) == len(seen) >= 3
+    assert len(dp._pb.graphs) == len(seen) >= 3
     dp.release_graph()
     # dropout on: replays of a bucket graph from the same seed word are bit-identical, another seed is another draw
     m, dp = _dp(H, d, ne, 0.1, B)

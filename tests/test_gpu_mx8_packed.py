@@ -466,9 +466,9 @@ def test_captured_bucket_graphs_run_the_packed_fp8_tail(H, monkeypatch):
         for batch in batches + [batches[0]]:
             loss = float(dp.step(*batch))
             torch.cuda.synchronize()
-            keys.add(tuple(int(x) for x in (dp._pb["cu_a"][-1], dp._pb["cu_t"][-1])))
+            keys.add(tuple(int(x) for x in (dp._pb.cu_a[-1], dp._pb.cu_t[-1])))
             res.append((loss, dp.buckets.flat.clone()))
-        n = len(dp._pb["graphs"])
+        n = len(dp._pb.graphs)
         dp.release_graph()
         return res, keys, n
 

@@ -410,7 +410,7 @@ def test_packed_training_loop_with_the_optimizer_in_every_bucket_graph(H):
                 opt.step()
             assert float(opt.device_step) == i + 1.0, (packed, i)
         if packed:
-            assert len(dp._pb["graphs"]) >= 2          # the six batches do not all fall into one bucket
+            assert len(dp._pb.graphs) >= 2          # the six batches do not all fall into one bucket
             dp.release_graph()
         assert float(opt.device_step) == len(loader) and float(opt.skipped) == 0.0
         traj.append(losses)
@@ -434,4 +434,4 @@ def test_capture_with_optimizer_needs_captured_collectives_at_world_2(H):
     dp.world = 1
     with pytest.raises(TypeError):                      # an optimizer whose scalars are host values cannot be recorded
         dp.capture(*batch, optimizer=FusedClipAdamW(dp.buckets))
-    assert dp._graph is None
+    assert not dp.captured

@@ -5,7 +5,6 @@ either source layout, the bucket plans and every table are the same), with the o
 its refusals, and data.DevicePrefetcher(ragged=...).  Shapes: those of test_gpu_forward_packed.py (d128: B = 5, T_a = 70, T_t = 40,
 bucket granule 8 rows); three batches that land in three row-count buckets."""
 import copy
-import types
 
 import pytest
 import torch
@@ -107,25 +106,25 @@ class Spy:
 
 
 def _host_tables(la, lt):
-    """what the host path makes of the lengths: _packed_key's cu_seqlens (on a stub, no GPU) and plans_from_lengths' masks"""
+    """what the host path makes of the lengths: packed_tables' cu_seqlens (the lists _packed_key uploads) and plans_from_lengths' masks"""
     from hri_emo_amd import _ops, dp as dpm
     lt = [int(x) for x in lt]
-    z = lambda: torch.zeros(NB + 2, dtype=torch.int32)       # noqa: E731
-    stub = types.SimpleNamespace(_pb={"B": NB, "La": TA, "Lt": TT, "cu_a": z(), "cu_t": z(), "cu_f": z()})
-    key = dpm.DataParallelStep._packed_key(stub, None, None, (la, lt))
+    key, *cus = dpm.packed_tables(*dpm.mask_lengths(None, None, (la, lt), NB, TA, TT), NB, TA, TT)
+    host = {name: torch.tensor(cu, dtype=torch.int32) for name, cu in zip(("cu_a", "cu_t", "cu_f"), cus)}
     plans, (m_a, m_t) = _ops.plans_from_lengths(la, lt, TA, TT, torch.device("cuda", 0))
-    return key, stub._pb, plans, (m_a, m_t, m_a[:, :TT] | m_t)
+    return key, host, plans, (m_a, m_t, m_a[:, :TT] | m_t)
 
 
 def _assert_tables(dp, la, lt):
     key, host, plans, masks = _host_tables(la, lt)
     pb = dp._pb
     for name, plan in zip(("cu_a", "cu_t", "cu_f"), plans):
-        assert torch.equal(pb[name].cpu(), host[name]), (name, pb[name].tolist(), host[name].tolist())
-        assert torch.equal(pb[name][:NB + 1], plan.cu), name
-    for got, ref, name in zip(pb["front"]["masks"], masks, ("mask_a", "mask_t", "mask_f")):
+        dev = getattr(pb, name)
+        assert torch.equal(dev.cpu(), host[name]), (name, dev.tolist(), host[name].tolist())
+        assert torch.equal(dev[:NB + 1], plan.cu), name
+    for got, ref, name in zip(pb.front.masks, masks, ("mask_a", "mask_t", "mask_f")):
         assert got.dtype == torch.uint8 and torch.equal(got.view(torch.bool), ref), name
-    assert pb["front"]["lens"].tolist() == [list(la), [int(x) for x in lt]]
+    assert pb.front.lens.dev.tolist() == [list(la), [int(x) for x in lt]]
     return key
 
 
@@ -185,7 +184,7 @@ def test_step_packed_against_the_eager_padded_step(H, monkeypatch, precision, ta
     torch.cuda.synchronize()
     assert loss == once[0] and torch.equal(dp.buckets.flat, once[1]), "a second replay of the first batch"
     assert spy.take() == [], "a replay of a known bucket launches nothing from the host"
-    assert len(dp._pb["graphs"]) == len(set(keys)) == 3
+    assert len(dp._pb.graphs) == len(set(keys)) == 3
     # use_graph(False): the eager forward_packed step on the same batch
     dp.use_graph(False)
     eager = float(dp.step_packed(*first))
@@ -221,7 +220,7 @@ def _captured_run(m0, packed, word, opt_steps=0):
         loss = dp.step_packed(*rag) if packed else dp.step(*pad, lengths=(rag[2], rag[3].tolist()))
         torch.cuda.synchronize()
         out.append((loss.clone(), dp.buckets.flat.clone()))
-    n_graphs = len(dp._pb["graphs"])
+    n_graphs = len(dp._pb.graphs)
     params = (before, opt.flat_p.clone(), float(opt.device_step)) if opt_steps else None
     dp.release_graph()
     return out, n_graphs, params
@@ -304,9 +303,9 @@ def test_refusals_leave_the_static_state_untouched(H):
     dp.capture_packed(ra, rt, la, lt, y, pad_to=(TA, TT))
     dp.step_packed(ra, rt, la, lt, y)
     torch.cuda.synchronize()
-    front = dp._pb["front"]
-    state = lambda: [t.clone() for t in (dp._static[0], dp._static[1], dp._static[4], front["lens"], front["lens_host"], dp._pb["cu_a"],      # noqa: E731
-                                         dp._pb["cu_t"], dp._pb["cu_f"]) + front["masks"]]
+    front = dp._pb.front
+    state = lambda: [t.clone() for t in (dp._static[0], dp._static[1], dp._static[4], front.lens.dev, front.lens.host, dp._pb.cu_a,      # noqa: E731
+                                         dp._pb.cu_t, dp._pb.cu_f) + front.masks]
     before = state()
     lt = lt.tolist()
     bad = {
@@ -328,6 +327,83 @@ def test_refusals_leave_the_static_state_untouched(H):
     with pytest.raises(RuntimeError, match="step_packed"):
         dp.step(*_batches()[0][0])
     dp.release_graph()
+
+
+# ----------------------------------------------------------------------------- who owns a captured graph
+def test_bucket_graph_accounting_after_capture_packed(H, monkeypatch):
+    """cap 2, the three batches of three buckets: _ops.GRAPHS_ALIVE counts exactly the entries of the graphs mapping after every
+    step_packed, the evicted (first-captured) bucket's graph object dies with its record, the bucket that comes back reproduces
+    loss and gradients bit for bit, and release_graph() returns the count to where it started"""
+    import gc
+    import weakref
+    from hri_emo_amd import _ops, dp as dpmod
+    monkeypatch.setattr(dpmod, "_VARLEN_MAX_GRAPHS", 2)
+    _tail(True)
+    dp = _dp(_model(H))
+    rags = [rag for _, rag in _batches()]
+    alive0 = _ops.GRAPHS_ALIVE
+    dp.capture_packed(*rags[0], pad_to=(TA, TT))
+    assert _ops.GRAPHS_ALIVE == alive0 + 1 and dp.captured and list(dp._pb.graphs) == [KEYS[0]]
+    graph0 = weakref.ref(dp._pb.graphs[KEYS[0]].graph)
+    first = float(dp.step_packed(*rags[0]))
+    g0 = dp.buckets.flat.clone()
+    for i in (1, 2):
+        dp.step_packed(*rags[i])
+        assert _ops.GRAPHS_ALIVE == alive0 + len(dp._pb.graphs) == alive0 + min(i + 1, 2)
+    assert list(dp._pb.graphs) == [KEYS[1], KEYS[2]], "the first-captured bucket is the one evicted"
+    gc.collect()
+    assert graph0() is None, "the evicted bucket's graph is still alive: something besides the graphs mapping held it"
+    again = float(dp.step_packed(*rags[0]))                # captured afresh, bucket 1 goes
+    torch.cuda.synchronize()
+    assert list(dp._pb.graphs) == [KEYS[2], KEYS[0]] and _ops.GRAPHS_ALIVE == alive0 + 2
+    assert again == first and torch.equal(dp.buckets.flat, g0)
+    dp.release_graph()
+    assert _ops.GRAPHS_ALIVE == alive0 and not dp.captured
+    if alive0 == 0:
+        assert _ops._ws_retired == []
+
+
+def test_two_captured_steps_in_one_process_count_and_release_independently(H):
+    """one DataParallelStep captured plain (padded), one by capture_packed with two bucket graphs: the counter is the sum of their
+    records; releasing either leaves the other's replay bit-identical to its replay before"""
+    from hri_emo_amd import _ops
+    H.set_varlen(False)
+    _tail(True)
+    m0 = _model(H)
+    plain, packed = _dp(copy.deepcopy(m0)), _dp(copy.deepcopy(m0))
+    (pad0, rag0), (_, rag1) = _batches()[:2]
+    alive0 = _ops.GRAPHS_ALIVE
+
+    def replay_plain():
+        loss = plain.step(*pad0)
+        torch.cuda.synchronize()
+        return loss.clone(), plain.buckets.flat.clone()
+
+    def replay_packed():
+        out = []
+        for rag in (rag0, rag1):
+            loss = packed.step_packed(*rag)
+            torch.cuda.synchronize()
+            out += [loss.clone(), packed.buckets.flat.clone()]
+        return out
+
+    plain.capture(*pad0)
+    assert plain._record is not None and plain._pb is None and _ops.GRAPHS_ALIVE == alive0 + 1
+    packed.capture_packed(*rag0, pad_to=(TA, TT))
+    was_packed = replay_packed()
+    assert packed._record is None and len(packed._pb.graphs) == 2 and _ops.GRAPHS_ALIVE == alive0 + 1 + 2
+    replay_plain()
+    plain.release_graph()
+    assert not plain.captured and _ops.GRAPHS_ALIVE == alive0 + len(packed._pb.graphs) == alive0 + 2
+    assert all(torch.equal(a, b) for a, b in zip(replay_packed(), was_packed))
+    plain.capture(*pad0)
+    assert _ops.GRAPHS_ALIVE == alive0 + 3
+    was_plain = replay_plain()
+    packed.release_graph()
+    assert not packed.captured and _ops.GRAPHS_ALIVE == alive0 + 1
+    assert all(torch.equal(a, b) for a, b in zip(replay_plain(), was_plain))
+    plain.release_graph()
+    assert _ops.GRAPHS_ALIVE == alive0
 
 
 # ----------------------------------------------------------------------------- the prefetcher's ragged mode

@@ -103,8 +103,8 @@ def test_short_batch_against_the_eager_step_on_its_own_utterances(H, precision):
     dp.capture_packed(*full, pad_to=(TA, TT), partial_batches=True)
     loss = dp.step_packed(*short)
     torch.cuda.synchronize()
-    front = dp._pb["front"]
-    assert front["ctl"].tolist() == [3, 1, 1, 0] and front["lens"].tolist() == [[70, 33, 32, 1, 1], [40, 1, 32, 1, 1]]
+    front = dp._pb.front
+    assert front.ctl.dev.tolist() == [3, 1, 1, 0] and front.lens.dev.tolist() == [[70, 33, 32, 1, 1], [40, 1, 32, 1, 1]]
     _close(loss, dp.buckets.flat, ref_loss, ref_flat, f"{precision} n = 3")
     worst = max(float((p.grad - q.grad).norm() / q.grad.norm().clamp_min(1e-30)) for p, q in zip(dp.model.parameters(), ref.model.parameters()))
     print(f"{precision}: worst relative L2 of a single parameter's gradient {worst:.2e}")
@@ -177,9 +177,9 @@ def test_short_batch_refusals_leave_the_static_state_untouched(H):
     dp.capture_packed(*full, pad_to=(TA, TT), partial_batches=True)
     dp.step_packed(*full)
     torch.cuda.synchronize()
-    front = dp._pb["front"]
-    state = lambda: [t.clone() for t in (dp._static[0], dp._static[1], dp._static[4], front["lens"], front["lens_host"], front["ctl"],      # noqa: E731
-                                         front["ctl_host"], dp._pb["cu_a"], dp._pb["cu_t"], dp._pb["cu_f"], dp.buckets.flat) + front["masks"]]
+    front = dp._pb.front
+    state = lambda: [t.clone() for t in (dp._static[0], dp._static[1], dp._static[4], front.lens.dev, front.lens.host, front.ctl.dev,      # noqa: E731
+                                         front.ctl.host, dp._pb.cu_a, dp._pb.cu_t, dp._pb.cu_f, dp.buckets.flat) + front.masks]
     before = state()
     bad = {
         "n = 0": (ra[:0], rt[:0], [], [], y[:0]),
@@ -195,7 +195,7 @@ def test_short_batch_refusals_leave_the_static_state_untouched(H):
     dp.release_graph()
     dp = _dp(_model(H))
     dp.capture_packed(*full, pad_to=(TA, TT))
-    assert dp._pb["front"]["ctl"] is None
+    assert dp._pb.front.ctl is None
     with pytest.raises(ValueError, match="B = 5"):
         dp.step_packed(*_head(full, 4))
     dp.release_graph()
@@ -282,7 +282,7 @@ def test_flush_accumulated_updates_on_what_is_there(H):
     assert torch.equal(opt.flat_p, topt.flat_p) and torch.equal(opt.m, topt.m) and torch.equal(opt.v, topt.v)
     dp.step_packed(*b0)
     torch.cuda.synchronize()
-    assert dp._pb["front"]["ctl"].tolist() == [NB, 1, 0, 0] and dp.micro_step == 1 and float(opt.device_step) == 1.0
+    assert dp._pb.front.ctl.dev.tolist() == [NB, 1, 0, 0] and dp.micro_step == 1 and float(opt.device_step) == 1.0
     dp.release_graph()
 
 

@@ -276,11 +276,11 @@ def test_captured_packed_step_serves_every_batch(H):
     for i, (batch, lens) in enumerate(batches):
         loss = float(dp.step(*batch, lengths=lens if i % 2 else None))
         torch.cuda.synchronize()
-        seen.add(tuple(int(x) for x in (dp._pb["cu_a"][-1], dp._pb["cu_t"][-1])))
+        seen.add(tuple(int(x) for x in (dp._pb.cu_a[-1], dp._pb.cu_t[-1])))
         assert abs(loss - ref[i][0]) <= 1e-5 * max(1.0, abs(ref[i][0])), (i, loss, ref[i][0])
         rel = float((dp.buckets.flat - ref[i][1]).norm() / ref[i][1].norm())
         assert rel <= 1e-5, (i, rel)
-    assert len(dp._pb["graphs"]) == len(seen) >= 3            # full-length and very short batches fall into other buckets
+    assert len(dp._pb.graphs) == len(seen) >= 3            # full-length and very short batches fall into other buckets
     loss = float(dp.step(*batches[1][0]))                         # back to a bucket that exists: a replay, same numbers
     assert abs(loss - ref[1][0]) <= 1e-5 * max(1.0, abs(ref[1][0]))
     with pytest.raises(RuntimeError, match="suffix"):
@@ -326,8 +326,12 @@ def test_packed_step_reads_the_lengths_of_a_batch_that_reuses_freed_mask_address
 
 def test_packed_bucket_graphs_are_bounded(H, monkeypatch):
     """one hipGraph per distinct (audio rows, text rows) bucket pair must not grow without bound: beyond the cap the
-    least recently used graph is released, and a bucket that comes back is captured again with the same results"""
-    from hri_emo_amd import dp as dpmod
+    least recently used graph is released, and a bucket that comes back is captured again with the same results.  The graphs
+    mapping is the only owner of a bucket's record (ADVICE dp.py:418): _ops.GRAPHS_ALIVE counts exactly its entries after every
+    step, the evicted bucket's graph object is gone, and release_graph() gives back every count it took."""
+    import gc
+    import weakref
+    from hri_emo_amd import _ops, dp as dpmod
     from hri_emo_amd.train import fusion_step_loss
     monkeypatch.setattr(dpmod, "_VARLEN_MAX_GRAPHS", 2)
     torch.manual_seed(3)
@@ -337,18 +341,31 @@ def test_packed_bucket_graphs_are_bounded(H, monkeypatch):
     dp.set_global_batch(B)
     batches = [_ragged_batch(B, Ta, Tt, d, 4, s_, lo_a, lo_t)[0] for s_, lo_a, lo_t in ((41, 20, 8), (42, 50, 20), (43, 90, 38))]
     H.set_varlen(True)
+    alive0 = _ops.GRAPHS_ALIVE
     dp.capture(*batches[0])
+    assert _ops.GRAPHS_ALIVE == alive0 + 1 and dp.captured
+    (key0, rec0), = dp._pb.graphs.items()
+    graph0 = weakref.ref(rec0.graph)
+    del rec0
     first = float(dp.step(*batches[0]))
+    assert _ops.GRAPHS_ALIVE == alive0 + len(dp._pb.graphs) == alive0 + 1
     g0 = dp.buckets.flat.clone()
     rng = torch.get_rng_state()
     for b in batches[1:]:
         dp.step(*b)                                        # two new buckets: the first one's graph has to go
+        assert _ops.GRAPHS_ALIVE == alive0 + len(dp._pb.graphs)
     assert torch.equal(torch.get_rng_state(), rng)         # bucket captures inside step() leave torch's CPU generator alone
-    assert len(dp._pb["graphs"]) == 2
+    assert len(dp._pb.graphs) == 2 and key0 not in dp._pb.graphs, "the first-captured bucket is the one evicted"
+    gc.collect()
+    assert graph0() is None, "the evicted bucket's graph is still alive: something besides the graphs mapping held it"
     again = float(dp.step(*batches[0]))                    # captured afresh
     torch.cuda.synchronize()
-    assert len(dp._pb["graphs"]) == 2 and again == first and torch.equal(dp.buckets.flat, g0)
+    assert _ops.GRAPHS_ALIVE == alive0 + len(dp._pb.graphs)
+    assert len(dp._pb.graphs) == 2 and again == first and torch.equal(dp.buckets.flat, g0)
     dp.release_graph()
+    assert _ops.GRAPHS_ALIVE == alive0 and not dp.captured and dp._pb is None
+    if alive0 == 0:
+        assert _ops._ws_retired == []
 
 
 def test_captured_packed_step_with_dropout_is_deterministic_per_seed(H):
@@ -415,7 +432,7 @@ def test_packed_training_loop_end_to_end(H):
             losses.append(float(dp.step(h_a, h_t, m_a, m_t, y, lengths=lens) if packed else dp.step(h_a, h_t, m_a, m_t, y)))
             opt.step()
         if packed:
-            assert len(dp._pb["graphs"]) >= 2          # the six batches do not all fall into one bucket
+            assert len(dp._pb.graphs) >= 2          # the six batches do not all fall into one bucket
             dp.release_graph()
         traj.append(losses)
     for a, b in zip(*traj):
@@ -457,7 +474,7 @@ def test_captured_packed_step_edge_length_patterns(H, case):
     for _ in range(2):
         loss = float(dp.step(h_a, h_t, m_a, m_t, y, lengths=(la, lt)))
     torch.cuda.synchronize()
-    rows_a, rows_t = int(dp._pb["cu_a"][-1]), int(dp._pb["cu_t"][-1])
+    rows_a, rows_t = int(dp._pb.cu_a[-1]), int(dp._pb.cu_t[-1])
     assert rows_a > sum(la) and rows_t > sum(lt) and rows_a - sum(la) <= Ta and rows_t - sum(lt) <= Tt, (rows_a, rows_t)
     assert abs(loss - ref_loss) <= 1e-5 * max(1.0, abs(ref_loss)), (case, loss, ref_loss)
     rel = float((dp.buckets.flat - ref).norm() / ref.norm())

@@ -1,6 +1,5 @@
 """Host side of the packed tail (no GPU): the fused sequence plan -- sample b of the fused memory has min(la[b], lt[b]) rows,
 because the reference ORs the two prefix masks cut to the text length (models/fusion_with_emotion_decoder.py:62-79)."""
-import types
 
 import torch
 
@@ -48,20 +47,15 @@ def test_masks_that_are_not_prefixes_give_no_plan():
 
 def test_bucket_fused_plan_rides_in_the_text_bucket():
     from hri_emo_amd import _ops, dp
-    pb = {"B": B, "La": LA, "Lt": LT, "cu_a": torch.zeros(B + 2, dtype=torch.int32), "cu_t": torch.zeros(B + 2, dtype=torch.int32),
-          "cu_f": torch.zeros(B + 2, dtype=torch.int32)}
-    stub = types.SimpleNamespace(_pb=pb)
     m_a, m_t = _masks()
     for lengths in (None, (LENS_A, LENS_T)):
-        pb["cu_f"].zero_()
-        ra, rt = dp.DataParallelStep._packed_key(stub, m_a, m_t, lengths)
-        cu_f = pb["cu_f"].tolist()
+        (ra, rt), _, cu_t, cu_f = dp.packed_tables(*dp.mask_lengths(m_a, m_t, lengths, B, LA, LT), B, LA, LT)
         assert cu_f[:B + 1] == _cum(LENS_F)
-        assert cu_f[B + 1] == rt == pb["cu_t"].tolist()[B + 1] and cu_f[B] < rt          # ends at the text bucket's row count
-    sf = _ops.seq_bucket_fused(pb["cu_f"], B, LT, rt)
+        assert cu_f[B + 1] == rt == cu_t[B + 1] and cu_f[B] < rt          # ends at the text bucket's row count
+    sf = _ops.seq_bucket_fused(torch.tensor(cu_f, dtype=torch.int32), B, LT, rt)
     # the surplus rows form no sequence on the attention side: B sequences, not B + 1, and the plan says that rows are left over
     assert (sf.B, sf.Breal, sf.N, sf.L, sf.Lmax, sf.surplus) == (B, B, rt, LT, LT, True)
-    st = _ops.seq_bucket(pb["cu_t"], B, LT, rt)
+    st = _ops.seq_bucket(torch.tensor(cu_t, dtype=torch.int32), B, LT, rt)
     assert st.B == B + 1 and st.N == sf.N
 
 

@@ -77,14 +77,16 @@ def _stub_step(k, partial, optimizer=True):
     s.ctx = _ops.StepContext()
     s.events = []
     s._static = [torch.zeros(8, 16), torch.zeros(8, 16), None, None, torch.zeros(5, 4)]
-    s._pb = {"B": 5, "La": 7, "Lt": 4, "front": {"same_width": True, "partial": partial, "accum": k, "ctl": object()}}
-    s._graph, s._replay, s._exchange_in_graph, s._micro = object(), True, False, 0
+    front = dp._RaggedFront(lens=None, masks=(), same_width=True, partial=partial, accum=k, ctl=object())
+    s._pb = dp._PackedState(5, 7, 4, "cpu", front)
+    s._record, s._replay, s._exchange_in_graph, s._micro = None, True, False, 0
     s.buckets = _Recorder()
     s.buckets.suspended = False
     s._optimizer = _Recorder() if optimizer else None
     graph = types.SimpleNamespace(replay=lambda: s.events.append("replay"))
+    s._pb.graphs[(8, 8)] = dp._GraphRecord(graph, torch.zeros(()), [])          # the one bucket graph: the step counts as captured
     s._load_packed = lambda ra, rt, la, lt, y, ctl=None: s.events.append(("load", len(la), tuple(bool(c) for c in ctl))) or (8, 8)
-    s._packed_graph = lambda key: {"graph": graph, "loss": torch.zeros(())}
+    s._packed_graph = lambda key: s._pb.graphs[key]
     return s
 
 

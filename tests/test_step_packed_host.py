@@ -1,11 +1,10 @@
 """CPU suite of the ragged front door of the captured step: the shared bucket-row helper against the formula of capture()'s
-docstring and against _packed_key, the new C-ABI entry in the header, the library and the binding, and the ragged mode of
+docstring and against packed_tables, the new C-ABI entry in the header, the library and the binding, and the ragged mode of
 data.DevicePrefetcher on a CPU device."""
 import ctypes
 import os
 import random
 import re
-import types
 
 import torch
 
@@ -40,14 +39,56 @@ def test_bucket_rows_is_the_arithmetic_of_packed_key():
             la, lt = [1] * B, [1] * B
         want = (_formula(sum(la), B, La, dp._VARLEN_BUCKETS), _formula(sum(lt), B, Lt, dp._VARLEN_BUCKETS))
         assert (dp.bucket_rows(sum(la), B, La), dp.bucket_rows(sum(lt), B, Lt)) == want, (B, La, Lt, la, lt)
-        z = lambda: torch.zeros(B + 2, dtype=torch.int32)       # noqa: E731
-        stub = types.SimpleNamespace(_pb={"B": B, "La": La, "Lt": Lt, "cu_a": z(), "cu_t": z(), "cu_f": z()})
-        assert dp.DataParallelStep._packed_key(stub, None, None, (la, lt)) == want
-        assert stub._pb["cu_a"][-1] == want[0] and stub._pb["cu_t"][-1] == want[1] and stub._pb["cu_f"][-1] == want[1]
+        key, cu_a, cu_t, cu_f = dp.packed_tables(*dp.mask_lengths(None, None, (la, lt), B, La, Lt), B, La, Lt)
+        assert key == want
+        assert cu_a[-1] == want[0] and cu_t[-1] == want[1] and cu_f[-1] == want[1]
         for n, rows, L in ((sum(la), want[0], La), (sum(lt), want[1], Lt)):
             assert n < rows and rows - n <= L
         # the static row sources of capture_packed are as long as the largest bucket: every batch's bucket fits
         assert dp.bucket_rows(B * La, B, La) >= want[0] and dp.bucket_rows(B * Lt, B, Lt) >= want[1]
+
+
+def test_packed_tables_against_brute_force_prefix_sums():
+    from hri_emo_amd import dp
+    cases = [([5], [3], 1, 9, 4),                                    # B = 1
+             ([1, 1, 1, 1], [1, 1, 1, 1], 4, 96, 40),                # every length 1
+             ([96] * 4, [40] * 4, 4, 96, 40),                        # every length L: the full batch still gets its surplus sequence
+             ([7, 96, 1, 33], [40, 2, 1, 17], 4, 96, 40),
+             ([3, 400, 250, 1, 399, 17, 64, 128], [128, 1, 77, 5, 9, 100, 64, 2], 8, 400, 128)]
+    for la, lt, B, La, Lt in cases:
+        key, cu_a, cu_t, cu_f = dp.packed_tables(la, lt, B, La, Lt)
+        assert key == (_formula(sum(la), B, La, dp._VARLEN_BUCKETS), _formula(sum(lt), B, Lt, dp._VARLEN_BUCKETS))
+        for cu, lens, rows in ((cu_a, la, key[0]), (cu_t, lt, key[1]), (cu_f, [min(a, t) for a, t in zip(la, lt)], key[1])):
+            assert type(cu) is list and len(cu) == B + 2
+            assert cu[:B + 1] == [sum(lens[:i]) for i in range(B + 1)] and cu[B + 1] == rows
+            assert cu[B] < cu[B + 1], "the surplus sequence is never empty"
+        assert key[0] - cu_a[B] <= La and key[1] - cu_t[B] <= Lt, "and never longer than one padded sequence"
+        assert dp.ghost_plan(la, lt, B, La, Lt)[2] == key, "a full batch: ghost_plan's key is this key"
+    assert dp.packed_tables([96] * 4, [40] * 4, 4, 96, 40)[0] == (dp.bucket_rows(4 * 96, 4, 96), dp.bucket_rows(4 * 40, 4, 40))
+
+
+def test_state_classes_need_no_gpu():
+    from hri_emo_amd import dp
+    lens = dp._HostBlock([[1] * 3] * 2, "cpu")
+    assert lens.dev.tolist() == lens.host.tolist() == [[1, 1, 1], [1, 1, 1]] and lens.dev.dtype == lens.host.dtype == torch.int32
+    masks = tuple(torch.ones(3, L, dtype=torch.uint8) for L in (9, 4, 4))
+    front = dp._RaggedFront(lens, masks, same_width=True, partial=True, accum=2, ctl=dp._HostBlock(dp.ctl_words(3, 1, 1), "cpu"))
+    assert front.ctl.dev.tolist() == [3, 1, 1, 0] and (front.partial, front.accum) == (True, 2)
+    assert all(b.dtype == torch.bool and b.data_ptr() == m.data_ptr() for b, m in zip(front.bool, masks))
+    pb = dp._PackedState(3, 9, 4, "cpu", front)
+    assert pb["graphs"] is pb.graphs and len(pb["graphs"]) == 0 and pb.pool is None and pb.front is front
+    assert [t.tolist() for t in (pb.cu_a, pb.cu_t, pb.cu_f)] == [[0] * 5] * 3 and pb.cu_a.data_ptr() != pb.cu_t.data_ptr()
+    assert dp._PackedState(3, 9, 4, "cpu").front is None
+    rec = dp._GraphRecord(object(), torch.zeros(()), [])
+    pb.graphs[(16, 8)] = rec
+    assert pb["graphs"][(16, 8)] is rec and rec.seqs is None
+    s = object.__new__(dp.DataParallelStep)
+    s._record, s._pb, s._replay = None, None, True
+    assert not s.captured and not s._replaying
+    s._pb = pb
+    assert s.captured and s._replaying
+    s._record, s._pb = rec, None
+    assert s.captured
 
 
 def test_seq_tables_in_header_library_and_binding():
