@@ -115,7 +115,11 @@ _SIGS = {
     "hriemo_fusion_loss_ce": ("pppiiiffpppp", "i"),
     "hriemo_fusion_loss_n": ("ppppiiiffppppp", "i"),
     "hriemo_fusion_loss_ce_n": ("pppiiiffppppp", "i"),
-    "hriemo_scalar_gate_dx": ("pipippppiiip", "i"),
+    "hriemo_stats_update": ("ppppfpipiiippippp", "i"),
+    "hriemo_stats_counts": ("ppiippipp", "i"),
+    "hriemo_stats_auc_tiles": ("i", "i"),
+    "hriemo_stats_auc": ("ppiipppp", "i"),
+    "hriemo_scalar_gate_dx":("pipippppiiip", "i"),
     "hriemo_fuse_bwd_dw": ("ppppiiip", "i"),
     "hriemo_gate_dpre": ("pippp" + "iip", "i"),
     "hriemo_gate_input_bwd": ("ppppppiip", "i"),

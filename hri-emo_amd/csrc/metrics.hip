@@ -1,0 +1,250 @@
+// Epoch statistics of the reference's trainers, kept in device memory so that a captured trainer step never reads anything back:
+//   scripts/fusion/train_fusion_seq_level_decoder.py:300-372         sample-weighted mean loss, accuracy, mean beta
+//   scripts/fusion/train_mosei_fusion_seq_level_decoder.py:119-171,367-495   mean loss (non-finite batches skipped), mean beta,
+//                                                                    micro / macro F1, macro AUC, the 19-threshold calibration sweep
+//   hriemo_stats_update   one block behind the loss launch of a step: appends sigmoid(logits) and [target > 0] of the batch's own
+//                         samples to the epoch's log, adds to the sums and counters
+//   hriemo_stats_counts   tp / fp / fn per class and threshold over the log                     (once per epoch)
+//   hriemo_stats_auc      2 [p_i > p_j] + [p_i == p_j] over all (positive i, negative j) pairs   (once per epoch, the O(N^2) part)
+// The device hands back integers only; every ratio is formed on the host in float64 (train.EpochStats.result).
+// Plain C++, vector stores only.  Built with -fno-slp-vectorize like loss.hip: the scalar tails of the one-block kernel are where
+// hipcc produces the packed fp32 operand-select form `make check-isa` forbids.
+#include "common.h"
+
+// counters[8] (int32) and sums[4] (float64) of one epoch: the layout include/hriemo.h documents
+enum { SC_CURSOR = 0, SC_SAMPLES, SC_BATCHES, SC_SKIPPED, SC_CORRECT, SC_NONFINITE, SC_OVERFLOW, SC_SPARE };
+enum { SS_LOSS = 0, SS_BETA, SS_NBETA, SS_SPARE };
+#define STATS_MAX_THRESHOLDS 64
+#define AUC_TILE 256
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// One block of 256.  Launches are stream-ordered, so this block is the only writer of the cursor, the counters and the sums: no
+// atomics.  Only the first nv = clamp(*n_valid, 1, B) samples are ever loaded (the ghosts of a short batch may hold NaN).
+// SINGLE: labels are int64 class indices, nothing is logged, correct = the FIRST maximal logit's index equals the label
+// (torch.argmax: a NaN counts as maximal).  Otherwise: targets are float [B, C], p = 1 / (1 + expf(-x)) and [target > 0] go to
+// column cursor + b of the class-major log, correct = every label of the sample has [p > 0.5] == [target > 0].
+template <bool SINGLE>
+__global__ __launch_bounds__(256) void stats_update_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const long long* __restrict__ label, const float* __restrict__ loss,
+                                                           float loss_scale, const float* __restrict__ beta, int bps,
+                                                           const int* __restrict__ n_valid, int B, int C, int skip_nonfinite,
+                                                           float* __restrict__ probs, unsigned char* __restrict__ truth, int capacity,
+                                                           int* __restrict__ counters, double* __restrict__ sums) {
+  __shared__ int red_i[2][4];
+  __shared__ double red_d[4];
+  const int nv = n_valid != nullptr ? min(max(n_valid[0], 1), B) : B;
+  const float lv = loss[0];
+  if (skip_nonfinite && !isfinite(lv)) {            // the MOSEI trainer's `continue`: the batch leaves no other trace
+    if (threadIdx.x == 0) counters[SC_SKIPPED] += 1;
+    return;
+  }
+  const int cursor = counters[SC_CURSOR];           // every thread reads it here; thread 0 writes it behind the last barrier
+  const bool fits = SINGLE || (cursor >= 0 && (long)cursor + nv <= (long)capacity);
+  int correct = 0, nonfinite = 0;
+  for (int b = threadIdx.x; b < nv; b += 256) {
+    const float* xr = x + (long)b * C;
+    if (SINGLE) {
+      int best = 0;
+      float bv = xr[0];
+      for (int c = 1; c < C; ++c) {
+        const float v = xr[c];
+        if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
+      }
+      correct += (long long)best == label[b] ? 1 : 0;
+    } else {
+      bool all = true;
+      for (int c = 0; c < C; ++c) {
+        const float xv = xr[c];
+        const float p = 1.f / (1.f + expf(-xv));
+        const bool t = y[(long)b * C + c] > 0.f;
+        all = all && ((p > 0.5f) == t);
+        if (fits) {
+          const long at = (long)c * capacity + cursor + b;
+          probs[at] = p;
+          truth[at] = t ? 1 : 0;
+          nonfinite += isfinite(xv) ? 0 : 1;
+        }
+      }
+      correct += all ? 1 : 0;
+    }
+  }
+  double bsum = 0.0;
+  const int nb = beta != nullptr ? nv * bps : 0;
+  for (int i = threadIdx.x; i < nb; i += 256) bsum += (double)beta[i];
+  correct = wave_sum_i(correct);
+  nonfinite = wave_sum_i(nonfinite);
+  bsum = wave_sum_d(bsum);
+  if ((threadIdx.x & 63) == 0) {
+    red_i[0][threadIdx.x >> 6] = correct;
+    red_i[1][threadIdx.x >> 6] = nonfinite;
+    red_d[threadIdx.x >> 6] = bsum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counters[SC_CORRECT] += (red_i[0][0] + red_i[0][1]) + (red_i[0][2] + red_i[0][3]);
+    counters[SC_NONFINITE] += (red_i[1][0] + red_i[1][1]) + (red_i[1][2] + red_i[1][3]);
+    counters[SC_SAMPLES] += nv;
+    counters[SC_BATCHES] += 1;
+    if (!SINGLE) {
+      if (fits) counters[SC_CURSOR] = cursor + nv;
+      else counters[SC_OVERFLOW] = 1;
+    }
+    sums[SS_LOSS] += (double)lv * (double)loss_scale * (double)nv;
+    if (nb > 0) {
+      sums[SS_BETA] += (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
+      sums[SS_NBETA] += (double)nb;
+    }
+  }
+}
+
+// tp / fp / fn of `p >= thr[s]` per class and threshold over the first n = clamp(cursor, 0, capacity) log entries.  Grid
+// (ceil(capacity / 256), C): one entry per thread, blocks past the cursor exit; a block adds its S * 3 integers to out[C, S, 3]
+// (zeroed by the entry in front of the launch) with integer atomics -- integer sums do not depend on the order.
+__global__ __launch_bounds__(256) void stats_counts_kernel(const float* __restrict__ probs, const unsigned char* __restrict__ truth,
+                                                           int capacity, const int* __restrict__ counters, const float* __restrict__ thr,
+                                                           int S, int* __restrict__ out) {
+  __shared__ int acc[STATS_MAX_THRESHOLDS * 3];
+  const int n = min(max(counters[SC_CURSOR], 0), capacity);
+  if ((int)blockIdx.x * 256 >= n) return;
+  const int c = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < n;
+  const float p = valid ? probs[(long)c * capacity + i] : 0.f;
+  const bool t = valid && truth[(long)c * capacity + i] != 0;
+  for (int k = threadIdx.x; k < S * 3; k += 256) acc[k] = 0;
+  __syncthreads();
+  for (int s = 0; s < S; ++s) {
+    const bool pred = valid && p >= thr[s];
+    const int tp = __popcll(__ballot(pred && t));
+    const int fp = __popcll(__ballot(pred && !t));
+    const int fn = __popcll(__ballot(valid && !pred && t));
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(&acc[s * 3 + 0], tp);
+      atomicAdd(&acc[s * 3 + 1], fp);
+      atomicAdd(&acc[s * 3 + 2], fn);
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < S * 3; k += 256)
+    if (acc[k] != 0) atomicAdd(&out[(long)c * S * 3 + k], acc[k]);
+}
+
+// Mann-Whitney count of one class, twice over so that a tie is an integer: 2 U = sum over (positive i, negative j) of
+// 2 [p_i > p_j] + [p_i == p_j].  Grid (ceil(capacity / 256), C): a block owns 256 rows i and walks every j through LDS, 256 at a
+// time; an entry that is no negative (a positive, or past the cursor) is staged as NaN, against which both comparisons are false.
+// uint32 per thread (<= 2 * capacity), uint64 per block, ONE ordinary store per (class, tile): partial[C, tiles].  A tile past the
+// cursor stores 0.  Tile 0 of every class also stores the class's n_pos, n_neg to npn[C, 2].
+__global__ __launch_bounds__(256) void stats_auc_kernel(const float* __restrict__ probs, const unsigned char* __restrict__ truth,
+                                                        int capacity, const int* __restrict__ counters,
+                                                        unsigned long long* __restrict__ partial, int* __restrict__ npn) {
+  __shared__ float pj[AUC_TILE];
+  __shared__ unsigned long long red[4];
+  __shared__ int red_n[2][4];
+  const int n = min(max(counters[SC_CURSOR], 0), capacity);
+  const int c = blockIdx.y, tiles = gridDim.x;
+  if ((int)blockIdx.x * AUC_TILE >= n && blockIdx.x != 0) {
+    if (threadIdx.x == 0) partial[(long)c * tiles + blockIdx.x] = 0ull;
+    return;
+  }
+  const float* pc = probs + (long)c * capacity;
+  const unsigned char* tc = truth + (long)c * capacity;
+  const int i = blockIdx.x * AUC_TILE + threadIdx.x;
+  const bool pos_i = i < n && tc[i] != 0;
+  const float pi = pos_i ? pc[i] : 0.f;
+  unsigned int cnt = 0;
+  int n_pos = 0, n_neg = 0;
+  for (int j0 = 0; j0 < n; j0 += AUC_TILE) {
+    const int j = j0 + threadIdx.x;
+    const bool in = j < n;
+    const bool tj = in && tc[j] != 0;
+    n_pos += tj ? 1 : 0;
+    n_neg += (in && !tj) ? 1 : 0;
+    __syncthreads();                                 // the previous chunk has been read
+    pj[threadIdx.x] = (in && !tj) ? pc[j] : __builtin_nanf("");
+    __syncthreads();
+    if (pos_i) {
+      const int m = min(AUC_TILE, n - j0);
+      for (int k = 0; k < m; ++k) {
+        const float q = pj[k];
+        cnt += (pi > q ? 2u : 0u) + (pi == q ? 1u : 0u);
+      }
+    }
+  }
+  unsigned long long s = wave_sum_u64((unsigned long long)cnt);
+  n_pos = wave_sum_i(n_pos);
+  n_neg = wave_sum_i(n_neg);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = s;
+    red_n[0][threadIdx.x >> 6] = n_pos;
+    red_n[1][threadIdx.x >> 6] = n_neg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[(long)c * tiles + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (blockIdx.x == 0) {
+      npn[c * 2 + 0] = (red_n[0][0] + red_n[0][1]) + (red_n[0][2] + red_n[0][3]);
+      npn[c * 2 + 1] = (red_n[1][0] + red_n[1][1]) + (red_n[1][2] + red_n[1][3]);
+    }
+  }
+}
+
+extern "C" int hriemo_stats_update(const float* logits, const float* targets, const long long* labels, const float* loss, float loss_scale,
+                                   const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int skip_nonfinite,
+                                   float* probs, unsigned char* truth, int capacity, int* counters, double* sums, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && C > 0 && logits != nullptr && loss != nullptr && counters != nullptr && sums != nullptr, "stats_update: bad arguments");
+  HRIEMO_CHECK((targets != nullptr) != (labels != nullptr), "stats_update: float targets [B, C] (multi-label) or int64 labels [B] (single-label), not both");
+  HRIEMO_CHECK(beta == nullptr || beta_per_sample >= 1, "stats_update: beta_per_sample %d", beta_per_sample);
+  HRIEMO_CHECK(n_valid == nullptr || ((uintptr_t)n_valid % 4) == 0, "stats_update: n_valid is one aligned int32 in device memory");
+  HRIEMO_CHECK(((uintptr_t)counters % 4) == 0 && ((uintptr_t)sums % 8) == 0, "stats_update: counters / sums are not aligned");
+  if (labels != nullptr) {
+    hipLaunchKernelGGL(stats_update_kernel<true>, dim3(1), dim3(256), 0, st, logits, targets, labels, loss, loss_scale, beta, beta_per_sample,
+                       n_valid, B, C, skip_nonfinite, probs, truth, capacity, counters, sums);
+  } else {
+    HRIEMO_CHECK(probs != nullptr && truth != nullptr && capacity > 0, "stats_update: the multi-label kind needs the log (probs, truth, capacity > 0)");
+    hipLaunchKernelGGL(stats_update_kernel<false>, dim3(1), dim3(256), 0, st, logits, targets, labels, loss, loss_scale, beta, beta_per_sample,
+                       n_valid, B, C, skip_nonfinite, probs, truth, capacity, counters, sums);
+  }
+  HRIEMO_LAUNCH_CHECK("stats_update_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_stats_counts(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
+                                   const float* thresholds, int S, int* out, hipStream_t st) {
+  HRIEMO_CHECK(probs != nullptr && truth != nullptr && counters != nullptr && thresholds != nullptr && out != nullptr && capacity > 0 && C > 0,
+               "stats_counts: bad arguments");
+  HRIEMO_CHECK(S >= 1 && S <= STATS_MAX_THRESHOLDS, "stats_counts: %d thresholds (1 .. %d)", S, STATS_MAX_THRESHOLDS);
+  HRIEMO_CHECK(C <= 65535, "stats_counts: %d classes", C);
+  hipError_t e = hipMemsetAsync(out, 0, (size_t)C * S * 3 * sizeof(int), st);
+  HRIEMO_CHECK(e == hipSuccess, "stats_counts: memset failed: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(stats_counts_kernel, dim3((capacity + 255) / 256, C), dim3(256), 0, st, probs, truth, capacity, counters, thresholds, S, out);
+  HRIEMO_LAUNCH_CHECK("stats_counts_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_stats_auc_tiles(int capacity) { return capacity > 0 ? (capacity + AUC_TILE - 1) / AUC_TILE : 0; }
+
+extern "C" int hriemo_stats_auc(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
+                                unsigned long long* partial, int* npn, hipStream_t st) {
+  HRIEMO_CHECK(probs != nullptr && truth != nullptr && counters != nullptr && partial != nullptr && npn != nullptr && capacity > 0 && C > 0,
+               "stats_auc: bad arguments");
+  HRIEMO_CHECK(C <= 65535 && ((uintptr_t)partial % 8) == 0, "stats_auc: %d classes / partial not 8-byte aligned", C);
+  hipLaunchKernelGGL(stats_auc_kernel, dim3(hriemo_stats_auc_tiles(capacity), C), dim3(256), 0, st, probs, truth, capacity, counters, partial, npn);
+  HRIEMO_LAUNCH_CHECK("stats_auc_kernel");
+  return 0;
+}

@@ -427,6 +427,9 @@ class DataParallelStep:
         self._mask_seen = None        # mask-fed packed step: (mask identity, bucket key, cu_seqlens clones, the masks) of the last step
         self._optimizer = None        # optim.DeviceAdamW whose update closes the captured step (capture(optimizer=...))
         self._micro = 0               # micro-steps of the open accumulation group (capture_packed(grad_accum=k)): 0 .. k-1
+        self._stats = None            # train.EpochStats fed by every executed (micro-)step (attach_stats)
+        self._stats_scale = 1.0
+        self._outputs = None          # with statistics attached: what the latest _fwd_bwd pass hands to _update_stats
 
     @property
     def captured(self):
@@ -442,6 +445,28 @@ class DataParallelStep:
         if hasattr(self.model, "set_batch_offset"):
             self.model.set_batch_offset(lo)
         return lo, hi
+
+    def attach_stats(self, stats, loss_scale=1.0):
+        """Feed a ``train.EpochStats`` from this step: every executed trainer step or micro-step -- a replay, an eager step, a
+        micro-batch of step_accumulated -- updates it exactly once, with the pass's logits, beta, targets and loss (and n_valid after
+        capture_packed(partial_batches=True)); nothing is read back.  Call it BEFORE capture() / capture_packed(): the update
+        (hriemo_stats_update, one block) is recorded inside the graph, behind forward + loss + backward and in front of the
+        optimizer's launches.  The warm-up passes of a capture never count -- those of a bucket graph captured in the middle of an
+        epoch included: they run without the update exactly as they run without the optimizer.  loss_scale: what the logged loss is
+        multiplied by -- grad_accum where the loss function divides by it (mosei_step_loss(grad_accum=k)): the reference logs the
+        undivided loss (train_mosei_fusion_seq_level_decoder.py:385-388,406).  stats=None detaches.  Without statistics attached
+        every path launches exactly what it launched before."""
+        if self.captured:
+            raise RuntimeError("attach_stats() comes before capture() / capture_packed(): the update is part of the captured step "
+                               "(release_graph() first to change it)")
+        self._stats, self._stats_scale, self._outputs = stats, float(loss_scale), None
+
+    def _update_stats(self):
+        """one hriemo_stats_update launch on the outputs of the latest _fwd_bwd pass (no-op without statistics attached)"""
+        out, self._outputs = self._outputs, None
+        if self._stats is not None and out is not None:
+            logits, beta, y, loss, n_valid = out
+            self._stats.update(logits, beta, y, loss, n_valid=n_valid, loss_scale=self._stats_scale)
 
     def _fwd_bwd(self, h_a, h_t, m_a, m_t, y, zero=True, scale=None, ragged=None):
         """ragged = (audio lengths, text lengths, pad_to): h_a / h_t are a ragged batch's own rows (the eager forward_packed step).
@@ -482,6 +507,11 @@ class DataParallelStep:
             loss = self.loss_fn(logits, beta, y, n_valid=ctl[:1])      # ctl.n_valid: the ghosts behind it add nothing and get zero gradients
         else:
             loss = self.loss_fn(logits, beta, y)
+        if self._stats is not None:
+            # handed to _update_stats by the caller that executes (or records) a real step; a warm-up pass drops them.  The loss
+            # as loss_fn returned it: step_accumulated's own 1/k below is not part of what the reference logs
+            self._outputs = (logits.detach(), None if beta is None else beta.detach(), y, loss.detach(),
+                             ctl[:1] if (ctl is not None and front.partial) else None)
         if scale is not None:
             loss = loss * scale
         if loss.is_cuda and scale is None:
@@ -510,6 +540,7 @@ class DataParallelStep:
                 l = self._fwd_bwd(ra, rt, None, None, y, zero=(i == 0), scale=1.0 / k, ragged=(la, lt, pad))
             else:
                 l = self._fwd_bwd(*mb, zero=(i == 0), scale=1.0 / k)
+            self._update_stats()
             total = l if total is None else total + l
         self.buckets.suspended = was
         self.buckets.finish()
@@ -720,6 +751,7 @@ class DataParallelStep:
                                  zero=first, ragged=(la, lt, pad))
         finally:
             self.buckets.suspended = was
+        self._update_stats()
         self._micro = 0 if last else self._micro + 1
         if last:
             self.buckets.finish()
@@ -813,6 +845,7 @@ class DataParallelStep:
                     self._fwd_bwd(*self._static)
                     if collectives:
                         self.buckets.finish()         # the warm-up steps exchange eagerly (every rank alike) and leave the buckets reset
+                self._outputs = None                  # warm-up passes never reach the statistics
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             if collectives:
@@ -837,6 +870,7 @@ class DataParallelStep:
                 with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local", **kw):
                     _ops.bump_seed_word(self._static[0].device)
                     loss = self._fwd_bwd(*self._static)
+                    self._update_stats()              # recorded, not run: one block behind backward, in front of the optimizer
                     if collectives:
                         self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
                     if self._optimizer is not None:
@@ -911,6 +945,7 @@ class DataParallelStep:
             self._after_replay()
             return rec.loss
         loss = self._fwd_bwd(h_a, h_t, m_a, m_t, y)
+        self._update_stats()
         self.buckets.finish()
         if self._optimizer is not None:
             self._optimizer.step()                        # use_graph(False): still the whole trainer step

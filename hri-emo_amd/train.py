@@ -6,6 +6,7 @@
   mosei_step_loss         scripts/fusion/train_mosei_fusion_seq_level_decoder.py:340-347,383-387,569:
                           BCEWithLogits(logits, y; pos_weight) + beta_entropy*H(beta), divided by grad_accum
 CPU tensors (the gloo tests drive the CPU oracle through dp.py) take the same formulas in plain torch."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -58,3 +59,253 @@ def mosei_step_loss(logits, beta, targets, pos_weight=None, beta_entropy=0.0, gr
     if beta is not None and beta_entropy > 0:
         loss = loss + beta_entropy * beta_entropy_loss(beta)
     return loss / grad_accum
+
+
+# ---------------------------------------------------------------------------------------------------------------- epoch statistics
+# What the reference's trainers report per epoch, without a read-back per step (hriemo_stats_update / _counts / _auc, csrc/metrics.hip):
+#   train_fusion_seq_level_decoder.py:300-372          sample-weighted mean loss, accuracy, mean beta
+#   train_mosei_fusion_seq_level_decoder.py:119-171,367-495   mean loss (non-finite batches skipped), mean beta, micro / macro F1,
+#                                                      macro AUC, calibrate_thresholds' sweep and the macro F1 at its thresholds
+# The device (and the CPU twin below) produce INTEGERS only: tp / fp / fn per class and threshold, 2U per class (the Mann-Whitney
+# count with ties as halves, doubled), n_pos, n_neg, the counters.  Every ratio is formed here in float64.
+
+SWEEP = tuple(float(t) for t in np.linspace(0.05, 0.95, 19))        # calibrate_thresholds' grid (:165)
+_MAX_THRESHOLDS = 64          # STATS_MAX_THRESHOLDS of csrc/metrics.hip
+_CTR = ("cursor", "n_samples", "n_batches", "n_skipped", "n_correct", "n_nonfinite", "overflow")
+
+
+def thresholds_up(thresholds):
+    """float64 thresholds -> float32, each the SMALLEST fp32 value >= its threshold.  The reference compares fp32 probabilities with
+    float64 thresholds (numpy promotes p); p >= t64 holds exactly when p >= that fp32 value, so an fp32 comparison against the
+    rounded-up threshold takes the reference's decision for the same p."""
+    t = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+    r = t.astype(np.float32)
+    low = r.astype(np.float64) < t
+    r[low] = np.nextafter(r[low], np.float32(np.inf))
+    return r
+
+
+def _f1(tp, fp, fn):
+    """2 tp / (2 tp + fp + fn) in float64, 0 where the denominator is 0 (f1_score(..., zero_division=0))"""
+    tp, den = np.asarray(tp, dtype=np.float64), 2.0 * np.asarray(tp, dtype=np.float64) + np.asarray(fp, dtype=np.float64) + np.asarray(fn, dtype=np.float64)
+    return np.where(den > 0, 2.0 * tp / np.where(den > 0, den, 1.0), 0.0)
+
+
+class EpochStats:
+    """The statistics of one training or validation epoch, accumulated where the step runs.
+
+    EpochStats(num_outputs, capacity, kind="multi_label" | "single_label", skip_nonfinite=False, device=...): `capacity` is the
+    number of samples the epoch's log holds (multi-label: sigmoid(logits) as fp32 [C, capacity] and [target > 0] as uint8);
+    skip_nonfinite is the MOSEI trainer's `continue` on a NaN / Inf loss (:390-393, :452-454): such a batch only counts in n_skipped.
+
+    update(logits, beta, targets, loss, n_valid=None, loss_scale=1.0) enqueues ONE launch (hriemo_stats_update) on the current stream
+    and reads nothing back; it can be recorded into a captured step (dp.DataParallelStep.attach_stats).  targets: float [B, C]
+    (multi-label; a label counts as positive when > 0, so the MOSEI trainer's raw and normalised targets give the same bits) or
+    int64 [B] (single-label).  loss: the scalar the loss wrote; loss_scale undoes a 1/grad_accum inside it (the reference logs the raw
+    loss).  n_valid: None or a 1-element int32 tensor on the device (a Python int on the CPU path too): only the first
+    clamp(n_valid, 1, B) samples count, whatever the rows behind them hold.
+
+    result(thresholds=None): two launches over the log (hriemo_stats_counts, hriemo_stats_auc), ONE read-back, and the ratios in
+    float64: avg_loss = |sum_loss / max(1, n_samples)|, accuracy (multi-label: every label of the sample has [p > 0.5] == [target >
+    0]; single-label: first argmax == label), mean_beta, n_samples, n_batches, n_skipped; multi-label also micro_f1, macro_f1,
+    per_class_f1 (prediction p >= 0.5), macro_auc (mean over the classes that have both kinds, 0.0 without one),
+    calibrated_thresholds (float32 [C]; per class the first threshold of the sweep -- default SWEEP, np.linspace(0.05, 0.95, 19) --
+    with strictly greater F1, start 0.5 / -1 as calibrate_thresholds), macro_f1_calibrated, and the integers themselves: tp, fp, fn
+    [C] at 0.5, sweep_counts [C, S, 3], auc_2u, n_pos, n_neg [C].  RuntimeError if the log overflowed, ValueError if non-finite
+    logits were logged.
+
+    Thresholds: the kernels compare fp32 p with thresholds_up(t), which is the reference's `p >= t` for float64 t.  The calibrated
+    thresholds are returned as the reference returns them, rounded to NEAREST fp32; macro_f1_calibrated is read from the sweep's own
+    counts at the chosen grid points, while the reference compares a second time against those rounded values.  The two differ
+    only where a probability lies within one fp32 ulp of a grid threshold.
+
+    CPU tensors take the same definitions in plain torch / numpy (the log lives in host memory).  Statistics are per rank."""
+
+    def __init__(self, num_outputs, capacity, kind="multi_label", skip_nonfinite=False, device="cuda"):
+        if kind not in ("multi_label", "single_label"):
+            raise ValueError("EpochStats: kind is 'multi_label' or 'single_label'")
+        if int(num_outputs) < 1 or int(capacity) < 1:
+            raise ValueError("EpochStats: num_outputs and capacity are positive")
+        self.C, self.capacity, self.kind, self.skip_nonfinite = int(num_outputs), int(capacity), kind, bool(skip_nonfinite)
+        self.device = torch.device(device)
+        self.multi = kind == "multi_label"
+        C, dev = self.C, self.device
+        self.tiles = (self.capacity + 255) // 256            # hriemo_stats_auc_tiles
+        # everything result() reads back is ONE buffer: counters int32[8] | sums float64[4] | npn int32[C, 2] | counts
+        # int32[C, 64, 3] | auc partials uint64[C, tiles]; every part starts 8-byte aligned
+        o_npn = 64
+        o_cnt = o_npn + 8 * C
+        o_auc = o_cnt + 4 * C * _MAX_THRESHOLDS * 3
+        self._small = torch.zeros(o_auc + 8 * C * self.tiles, dtype=torch.uint8, device=dev)
+        self._parts = (o_npn, o_cnt, o_auc)
+        self.counters, self.sums, self._npn, self._counts, self._partial = self._views(self._small)
+        if self.multi:
+            self.probs = torch.zeros(C, self.capacity, dtype=torch.float32, device=dev)
+            self.truth = torch.zeros(C, self.capacity, dtype=torch.uint8, device=dev)
+        else:
+            self.probs = self.truth = None
+        self._thr = torch.zeros(_MAX_THRESHOLDS, dtype=torch.float32, device=dev)
+
+    def _views(self, buf):
+        o_npn, o_cnt, o_auc = self._parts
+        return (buf[:32].view(torch.int32), buf[32:64].view(torch.float64), buf[o_npn:o_cnt].view(torch.int32).view(self.C, 2),
+                buf[o_cnt:o_auc].view(torch.int32), buf[o_auc:].view(torch.int64).view(self.C, self.tiles))
+
+    def reset(self):
+        """a new epoch: counters and sums to zero (the log needs no clearing: only entries in front of the cursor are ever read)"""
+        self._small[:64].zero_()
+
+    # ---- update
+    def _check(self, logits, beta, targets, loss):
+        if logits.dim() != 2 or logits.shape[1] != self.C:
+            raise ValueError(f"EpochStats.update: logits of shape {tuple(logits.shape)}; expected [B, {self.C}]")
+        B = logits.shape[0]
+        want = (B, self.C) if self.multi else (B,)
+        if tuple(targets.shape) != want:
+            raise ValueError(f"EpochStats.update: targets of shape {tuple(targets.shape)}; the {self.kind} kind takes {want}")
+        if beta is not None and (beta.numel() == 0 or beta.numel() % B != 0):
+            raise ValueError(f"EpochStats.update: beta of {beta.numel()} values for {B} samples")
+        if loss.numel() != 1:
+            raise ValueError("EpochStats.update: loss is one scalar")
+        return B
+
+    def update(self, logits, beta, targets, loss, n_valid=None, loss_scale=1.0):
+        B = self._check(logits, beta, targets, loss)
+        if not logits.is_cuda:
+            return self._update_cpu(logits, beta, targets, loss, n_valid, float(loss_scale), B)
+        from . import _lib, _ops
+        p = _ops._p
+        nv = _ops._n_valid_word((n_valid,), logits)
+        x = logits.detach().contiguous().float()
+        y = targets.detach().contiguous()
+        y = y.float() if self.multi else y.to(torch.int64)
+        bt = beta.detach().contiguous().float() if beta is not None else None
+        lv = loss.detach().reshape(1).float()
+        _lib.call("hriemo_stats_update", p(x), p(y) if self.multi else None, None if self.multi else p(y), p(lv), float(loss_scale),
+                  p(bt), bt.numel() // B if bt is not None else 0, p(nv), B, self.C, int(self.skip_nonfinite), p(self.probs), p(self.truth),
+                  self.capacity, p(self.counters), p(self.sums), _ops._stream())
+
+    def _update_cpu(self, logits, beta, targets, loss, n_valid, loss_scale, B):
+        import math
+        nv = B if n_valid is None else min(max(int(n_valid), 1), B)
+        ctr, lv = self.counters, float(loss)
+        if self.skip_nonfinite and not math.isfinite(lv):
+            ctr[3] += 1
+            return
+        x = logits.detach()[:nv].float()
+        if self.multi:
+            # float64, rounded to fp32: torch's fp32 CPU sigmoid sends the last numel % 16 elements of a tensor down a scalar path
+            # that can differ by an ulp, and two equal logits in two batches must tie in the AUC
+            pr, t = torch.sigmoid(x.double()).float(), targets.detach()[:nv] > 0
+            ctr[4] += int(((pr > 0.5) == t).all(dim=1).sum())
+            cur = int(ctr[0])
+            if cur + nv <= self.capacity:
+                self.probs[:, cur:cur + nv] = pr.t()
+                self.truth[:, cur:cur + nv] = t.t().to(torch.uint8)
+                ctr[5] += int((~torch.isfinite(x)).sum())
+                ctr[0] = cur + nv
+            else:
+                ctr[6] = 1
+        else:
+            ctr[4] += int((x.argmax(dim=1) == targets.detach()[:nv]).sum())
+        ctr[1] += nv
+        ctr[2] += 1
+        self.sums[0] += lv * loss_scale * nv
+        if beta is not None:
+            b = beta.detach().reshape(B, -1)[:nv].double()
+            self.sums[1] += float(b.sum())
+            self.sums[2] += b.numel()
+
+    # ---- result
+    def _integers_cpu(self, thr, n):
+        """tp / fp / fn [C, S, 3], 2U [C], n_pos / n_neg [C, 2] of the first n log entries, the kernels' definitions in numpy"""
+        pr, t = self.probs[:, :n].numpy(), self.truth[:, :n].numpy() != 0
+        pred = pr[:, None, :] >= thr[None, :, None]                                  # fp32 against fp32
+        tt = t[:, None, :]
+        counts = np.stack([(pred & tt).sum(2), (pred & ~tt).sum(2), (~pred & tt).sum(2)], axis=2).astype(np.int64)
+        two_u, npn = np.zeros(self.C, dtype=np.int64), np.zeros((self.C, 2), dtype=np.int64)
+        for c in range(self.C):
+            pos, neg = pr[c][t[c]], np.sort(pr[c][~t[c]])
+            below, upto = np.searchsorted(neg, pos, "left"), np.searchsorted(neg, pos, "right")
+            two_u[c] = int((2 * below + (upto - below)).sum())
+            npn[c] = (pos.size, neg.size)
+        return counts, two_u, npn
+
+    def result(self, thresholds=None):
+        sweep = np.asarray(SWEEP if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        if sweep.size + 1 > _MAX_THRESHOLDS:
+            raise ValueError(f"EpochStats.result: at most {_MAX_THRESHOLDS - 1} thresholds")
+        grid = np.concatenate([[0.5], sweep])                # entry 0: the reported F1s; the rest: the calibration sweep
+        thr = thresholds_up(grid)
+        S = thr.size
+        on_gpu = self.device.type == "cuda"
+        if on_gpu:
+            if self.multi:
+                from . import _lib, _ops
+                p = _ops._p
+                with torch.cuda.device(self.device):
+                    self._thr[:S].copy_(torch.from_numpy(thr), non_blocking=True)
+                    _lib.call("hriemo_stats_counts", p(self.probs), p(self.truth), self.capacity, self.C, p(self.counters), p(self._thr), S,
+                              p(self._counts), _ops._stream())
+                    _lib.call("hriemo_stats_auc", p(self.probs), p(self.truth), self.capacity, self.C, p(self.counters), p(self._partial),
+                              p(self._npn), _ops._stream())
+            ctr, sums, npn, counts, partial = self._views(self._small.cpu())          # the epoch's one read-back
+        else:
+            ctr, sums = self.counters, self.sums
+        ctr, sums = [int(v) for v in ctr.tolist()], [float(v) for v in sums.tolist()]
+        out = dict(zip(_CTR[1:5], ctr[1:5]))
+        n = out["n_samples"]
+        out["avg_loss"] = abs(sums[0] / max(1, n))
+        out["accuracy"] = out["n_correct"] / n if n > 0 else 0.0
+        out["mean_beta"] = sums[1] / sums[2] if sums[2] > 0 else 0.0
+        if not self.multi:
+            return out
+        if ctr[6]:
+            raise RuntimeError(f"EpochStats: the log of {self.capacity} samples overflowed ({n} samples were offered); size capacity for the epoch")
+        if ctr[5]:
+            raise ValueError(f"EpochStats: {ctr[5]} non-finite logits were logged; F1 / AUC of this epoch are undefined")
+        n_log = ctr[0]
+        if on_gpu:
+            counts = counts[:self.C * S * 3].view(self.C, S, 3).numpy().astype(np.int64)
+            two_u, npn = partial.numpy().sum(axis=1), npn.numpy().astype(np.int64)
+        else:
+            counts, two_u, npn = self._integers_cpu(thr, n_log)
+        tp, fp, fn = counts[:, 0, 0], counts[:, 0, 1], counts[:, 0, 2]
+        per_class = _f1(tp, fp, fn)
+        both = (npn[:, 0] > 0) & (npn[:, 1] > 0)
+        auc = two_u[both].astype(np.float64) / (2.0 * npn[both, 0].astype(np.float64) * npn[both, 1].astype(np.float64))
+        f1_sweep = _f1(counts[:, 1:, 0], counts[:, 1:, 1], counts[:, 1:, 2])          # [C, S - 1]
+        chosen, f1_cal = np.full(self.C, 0.5, dtype=np.float32), np.zeros(self.C)
+        for c in range(self.C):
+            best, best_t = -1.0, 0.5
+            for s in range(S - 1):
+                if f1_sweep[c, s] > best:
+                    best, best_t = float(f1_sweep[c, s]), sweep[s]
+            chosen[c] = best_t
+            f1_cal[c] = best if S > 1 else per_class[c]
+        out.update(n_logged=n_log, micro_f1=float(_f1(tp.sum(), fp.sum(), fn.sum())), macro_f1=float(per_class.mean()),
+                   per_class_f1=per_class, macro_auc=float(auc.mean()) if auc.size else 0.0, calibrated_thresholds=chosen,
+                   macro_f1_calibrated=float(f1_cal.mean()), tp=tp, fp=fp, fn=fn, sweep_counts=counts[:, 1:], auc_2u=two_u,
+                   n_pos=npn[:, 0], n_neg=npn[:, 1])
+        return out
+
+
+def evaluate_packed(model, batches, loss_fn, stats, pad_to=None):
+    """The reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
+    on ragged batches: model.eval() under torch.no_grad(); for every data.collate_seq_packed batch (rows_a, lengths_a, rows_t,
+    lengths_t, labels): forward_packed -> loss_fn(logits, beta, labels) -> stats.update.  Nothing is read back per batch --
+    ``stats.result()`` afterwards is the epoch's one read-back.  Eager launches (a captured eval forward is a different piece of
+    work); the module's training mode is restored.  Returns `stats`."""
+    was = model.training
+    dev = next(model.parameters()).device
+    model.eval()
+    try:
+        with torch.no_grad():
+            for rows_a, len_a, rows_t, len_t, y in batches:
+                y = y.to(dev, non_blocking=True)
+                logits, beta, _ = model.forward_packed(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), len_a, len_t,
+                                                       pad_to=pad_to)
+                stats.update(logits, beta, y, loss_fn(logits, beta, y))
+    finally:
+        model.train(was)
+    return stats

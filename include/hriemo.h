@@ -376,6 +376,38 @@ int hriemo_fusion_loss_n(const float* logits, const float* targets, const float*
 int hriemo_fusion_loss_ce_n(const float* logits, const long long* labels, const float* beta, int B, int C, int reg_mode,
                             float reg_coef, float scale, float* loss, float* dlogits, float* dbeta, const int* n_valid,
                             hriemo_stream_t stream);
+/* Epoch statistics in device memory (csrc/metrics.hip): what the reference's trainers report per epoch
+ * (scripts/fusion/train_fusion_seq_level_decoder.py:300-372: mean loss, accuracy, mean beta;
+ * train_mosei_fusion_seq_level_decoder.py:119-171,367-495: mean loss with non-finite batches skipped, micro / macro F1, macro AUC,
+ * the 19-threshold calibration sweep) without a read-back per step.  State of one epoch, owned by the caller, zeroed to reset:
+ *   probs   fp32  [C, capacity]   class-major log of p = 1 / (1 + expf(-logit))
+ *   truth   uint8 [C, capacity]   [target > 0]
+ *   counters int32[8]  {cursor, n_samples, n_batches, n_skipped, n_correct, n_nonfinite, overflow, spare}
+ *   sums    float64[4] {sum_loss, sum_beta, n_beta, spare}
+ * hriemo_stats_update: ONE block, meant to be recorded right behind the loss launch of a (captured) step -- every input is a device
+ * pointer; launches are stream-ordered, so the block owns the cursor and nothing is atomic.  Exactly one of targets (float [B, C],
+ * multi-label) and labels (int64 [B], single-label; nothing is logged, probs / truth may be NULL) is given.  loss: the scalar the
+ * loss kernel wrote; loss_scale by value (grad_accum, to undo the 1/k of hriemo_fusion_loss's scale: the reference logs the raw
+ * loss).  beta: NULL or B * beta_per_sample values.  n_valid: NULL or one aligned int32, nv = clamp(*n_valid, 1, B) as in
+ * hriemo_fusion_loss_n; rows b >= nv are never read.  skip_nonfinite != 0 and a NaN / Inf loss: n_skipped += 1 and nothing else.
+ * Otherwise, over the first nv samples: the log is appended at the cursor (multi-label), sum_loss += loss * loss_scale * nv,
+ * sum_beta / n_beta, n_correct (multi-label: every label of the sample has [p > 0.5] == [target > 0]; single-label: the first
+ * maximal logit's index equals the label, as torch.argmax), n_samples += nv, n_batches += 1, n_nonfinite += the non-finite logits
+ * that were logged.  cursor + nv > capacity: overflow = 1 and nothing is appended; the sums and counters are still updated.
+ * hriemo_stats_counts: out int32 [C, S, 3] = {tp, fp, fn} of the prediction p >= thresholds[s] (fp32 [S], S <= 64) over the first
+ * `cursor` log entries; the entry zeroes out first.  The reference compares fp32 p with float64 thresholds: hand in every
+ * threshold rounded UP to fp32 and the decisions are the same.
+ * hriemo_stats_auc: per class, 2U = sum over (positive i, negative j) of 2 [p_i > p_j] + [p_i == p_j], as partial sums
+ * partial uint64 [C, hriemo_stats_auc_tiles(capacity)] (256 rows i per tile; every tile is stored, tiles past the cursor as 0;
+ * the caller adds them), and npn int32 [C, 2] = {n_pos, n_neg}.  AUC = 2U / (2 n_pos n_neg), formed on the host. */
+int hriemo_stats_update(const float* logits, const float* targets, const long long* labels, const float* loss, float loss_scale,
+                        const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int skip_nonfinite,
+                        float* probs, unsigned char* truth, int capacity, int* counters, double* sums, hriemo_stream_t stream);
+int hriemo_stats_counts(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
+                        const float* thresholds, int S, int* out, hriemo_stream_t stream);
+int hriemo_stats_auc_tiles(int capacity);
+int hriemo_stats_auc(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
+                     unsigned long long* partial, int* npn, hriemo_stream_t stream);
 int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, int is_a, const float* dpool, const float* cnt,
                           const unsigned char* mask, void* dX, int B, int L, int d, hriemo_stream_t stream);
 /* Trainer step off the timed path, scripts/fusion/train_fusion_seq_level_decoder.py:332-334: clip_grad_norm_(5.0) +
