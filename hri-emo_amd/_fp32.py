@@ -165,10 +165,17 @@ def colsum(x32, mask=None):
 
 
 # ----------------------------------------------------------------------------- attention cores, LayerNorm
+def _no_mask_on_packed_rows(who, kpm, cu):
+    """the packed entries carry their lengths in cu_seqlens and have no mask argument: a mask handed in with them would be dropped"""
+    if cu is not None and kpm is not None:
+        raise RuntimeError(f"{who}: packed rows (cu_seqlens) take no key_padding_mask")
+
+
 def attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=False, drop=None, cu=None):
     """drop = (p, seed, site, b_offset): dropout on the attention weights (the keys of _ops.attn_fwd).
     cu = (cu_seqlens_q, cu_seqlens_k): q / k / v hold packed rows, Lq / Lk are the longest sequences, kpm is None (the masks the
     packed launch draws are those of the padded one: a mask log stays with the padded path)"""
+    _no_mask_on_packed_rows("_fp32.attn", kpm, cu)
     o = _new((q.shape[0], H * hd), q)
     lse = _new((B, H, Lq), q) if (want_lse or cu is not None) else None
     if cu is not None:
@@ -183,6 +190,7 @@ def attn(q, k, v, B, H, Lq, Lk, hd, kpm, want_lse=False, drop=None, cu=None):
 
 
 def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None, cu=None):
+    _no_mask_on_packed_rows("_fp32.attn_bwd", kpm, cu)
     delta = _new((B, H, Lq), q)
     if cu is not None:
         _lib.call("hriemo_attn_bwd_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(v), v.stride(0), _ops._p(o),
@@ -197,6 +205,7 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None, 
 
 def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None, cu=None, out_l=None):
     """cu / out_l as _ops.attn_probs: the padded map [B, out_l[0], out_l[1]] of packed rows"""
+    _no_mask_on_packed_rows("_fp32.probs", kpm, cu)
     if cu is not None:
         p = _new((B,) + tuple(out_l), q)
         _lib.call("hriemo_attn_probs_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(cu[0]), _ops._p(cu[1]),
