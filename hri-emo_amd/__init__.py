@@ -12,7 +12,8 @@ from .models.fusion_with_emotion_decoder import FusionWithEmotionDecoder  # noqa
 from .models.mosei_fusion_with_emotion_decoder import MoseiFusionWithEmotionDecoder  # noqa: F401
 from .models.fusion_classifier import FusionClassifier  # noqa: F401
 
+from .dp import EvalStep  # noqa: F401
 from ._ops import set_gemm_mode, gemm_mode, enable_fused_wgrad, set_precision, precision, set_varlen, varlen, set_varlen_maps, varlen_maps, set_mfma_maps, mfma_maps, set_ingest, ingest  # noqa: F401
 
-__all__ = ["set_gemm_mode", "gemm_mode", "enable_fused_wgrad", "set_precision", "precision", "set_varlen", "varlen", "set_varlen_maps", "varlen_maps", "set_mfma_maps", "mfma_maps", "set_ingest", "ingest", "CrossModalBlock", "CrossModalTransformer", "BetaGate", "EmotionDecoder", "ExplainableDecoderLayer",
+__all__ = ["EvalStep", "set_gemm_mode", "gemm_mode", "enable_fused_wgrad", "set_precision", "precision", "set_varlen", "varlen", "set_varlen_maps", "varlen_maps", "set_mfma_maps", "mfma_maps", "set_ingest", "ingest", "CrossModalBlock", "CrossModalTransformer", "BetaGate", "EmotionDecoder", "ExplainableDecoderLayer",
            "FusionWithEmotionDecoder", "MoseiFusionWithEmotionDecoder", "FusionClassifier"]

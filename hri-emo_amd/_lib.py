@@ -116,6 +116,7 @@ _SIGS = {
     "hriemo_fusion_loss_n": ("ppppiiiffppppp", "i"),
     "hriemo_fusion_loss_ce_n": ("pppiiiffppppp", "i"),
     "hriemo_stats_update": ("ppppfpipiiippippp", "i"),
+    "hriemo_predict_log": ("ppipiiipppipp", "i"),
     "hriemo_stats_counts": ("ppiippipp", "i"),
     "hriemo_stats_auc_tiles": ("i", "i"),
     "hriemo_stats_auc": ("ppiipppp", "i"),

@@ -6,6 +6,9 @@
 //                         samples to the epoch's log, adds to the sums and counters
 //   hriemo_stats_counts   tp / fp / fn per class and threshold over the log                     (once per epoch)
 //   hriemo_stats_auc      2 [p_i > p_j] + [p_i == p_j] over all (positive i, negative j) pairs   (once per epoch, the O(N^2) part)
+// and the products of the reference's inference driver (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy):
+//   hriemo_predict_log    one block behind the forward of a (captured) evaluation step: appends the batch's probabilities (sigmoid
+//                         or softmax), its per-sample mean beta and -- single-label -- its argmax to a log that needs no targets
 // The device hands back integers only; every ratio is formed on the host in float64 (train.EpochStats.result).
 // Plain C++, vector stores only.  Built with -fno-slp-vectorize like loss.hip: the scalar tails of the one-block kernel are where
 // hipcc produces the packed fp32 operand-select form `make check-isa` forbids.
@@ -108,6 +111,84 @@ __global__ __launch_bounds__(256) void stats_update_kernel(const float* __restri
     if (nb > 0) {
       sums[SS_BETA] += (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
       sums[SS_NBETA] += (double)nb;
+    }
+  }
+}
+
+// counters[4] (int32) of one prediction log: the layout include/hriemo.h documents
+enum { PL_CURSOR = 0, PL_SAMPLES, PL_OVERFLOW, PL_NONFINITE };
+
+// One block of 256, the only writer of its log and counters (stream order): no atomics.  Only the first nv = clamp(*n_valid, 1, B)
+// rows of x and beta are ever loaded.  KIND 0 (multi-label): one (sample, class) element per thread and trip, p = 1 / (1 + expf(-x))
+// -- stats_update_kernel's expression, so both logs hold the same bits for equal logits.  KIND 1 (single-label): one sample per
+// thread and trip; the first maximal logit's index (torch.argmax: a NaN counts as maximal) goes to pred, the fp32 softmax with that
+// maximum subtracted (exp_below_max; the sum over the classes in index order) to the log.  beta_mean: one sample per thread, its bps values summed in index order in float64.
+// exp(x - m) for x <= m with the difference carried exactly: d = fl(x - m) and its rounding error (TwoSum), exp(d + err) =
+// exp(d) (1 + err) up to err^2 < 2^-34.  Plain expf(x - m) loses |x - m| * 2^-24 relative -- 30 to 60 ulp for a logit 80 below the
+// row maximum.  x = -inf or an infinite difference: err is NaN and exp(d) (0, or NaN from NaN) stands.
+__device__ __forceinline__ float exp_below_max(float x, float m) {
+  const float d = x - m;
+  const float t = d - x;
+  const float err = (x - (d - t)) + (-m - t);
+  const float e = expf(d);
+  return err == err ? fmaf(e, err, e) : e;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void predict_log_kernel(const float* __restrict__ x, const float* __restrict__ beta, int bps,
+                                                          const int* __restrict__ n_valid, int B, int C, float* __restrict__ probs,
+                                                          float* __restrict__ beta_mean, int* __restrict__ pred, int capacity,
+                                                          int* __restrict__ counters) {
+  __shared__ int red_i[4];
+  const int nv = n_valid != nullptr ? min(max(n_valid[0], 1), B) : B;
+  const int cursor = counters[PL_CURSOR];           // every thread reads it here; thread 0 writes it behind the barrier
+  const bool fits = cursor >= 0 && (long)cursor + nv <= (long)capacity;
+  int nonfinite = 0;
+  if (fits) {
+    if (KIND == 0) {
+      const int n = nv * C;                         // B * C fits an int: the entry checks it
+      for (int i = threadIdx.x; i < n; i += 256) {
+        const int b = i / C, c = i - b * C;
+        const float xv = x[i];
+        probs[(long)c * capacity + cursor + b] = 1.f / (1.f + expf(-xv));
+        nonfinite += isfinite(xv) ? 0 : 1;
+      }
+    } else {
+      for (int b = threadIdx.x; b < nv; b += 256) {
+        const float* xr = x + (long)b * C;
+        int best = 0;
+        float bv = xr[0];
+        nonfinite += isfinite(bv) ? 0 : 1;
+        for (int c = 1; c < C; ++c) {
+          const float v = xr[c];
+          nonfinite += isfinite(v) ? 0 : 1;
+          if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
+        }
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s += exp_below_max(xr[c], bv);
+        for (int c = 0; c < C; ++c) probs[(long)c * capacity + cursor + b] = exp_below_max(xr[c], bv) / s;
+        if (pred != nullptr) pred[cursor + b] = best;
+      }
+    }
+    if (beta != nullptr && beta_mean != nullptr) {
+      for (int b = threadIdx.x; b < nv; b += 256) {
+        const float* br = beta + (long)b * bps;
+        double s = 0.0;
+        for (int k = 0; k < bps; ++k) s += (double)br[k];
+        beta_mean[cursor + b] = (float)(s / (double)bps);
+      }
+    }
+  }
+  nonfinite = wave_sum_i(nonfinite);
+  if ((threadIdx.x & 63) == 0) red_i[threadIdx.x >> 6] = nonfinite;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counters[PL_SAMPLES] += nv;
+    if (fits) {
+      counters[PL_CURSOR] = cursor + nv;
+      counters[PL_NONFINITE] += (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+    } else {
+      counters[PL_OVERFLOW] = 1;
     }
   }
 }
@@ -221,6 +302,26 @@ extern "C" int hriemo_stats_update(const float* logits, const float* targets, co
                        n_valid, B, C, skip_nonfinite, probs, truth, capacity, counters, sums);
   }
   HRIEMO_LAUNCH_CHECK("stats_update_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_predict_log(const float* logits, const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int kind,
+                                  float* probs, float* beta_mean, int* pred, int capacity, int* counters, hipStream_t st) {
+  HRIEMO_CHECK(B >= 1 && C >= 1 && capacity >= 1, "predict_log: B = %d, C = %d, capacity = %d (all >= 1)", B, C, capacity);
+  HRIEMO_CHECK((long)B * C <= 0x7fffffffL, "predict_log: B * C = %ld does not fit an int", (long)B * C);
+  HRIEMO_CHECK(kind == 0 || kind == 1, "predict_log: kind %d (0 multi-label, 1 single-label)", kind);
+  HRIEMO_CHECK(logits != nullptr && probs != nullptr && counters != nullptr, "predict_log: logits, probs and counters are required");
+  HRIEMO_CHECK(beta == nullptr || beta_per_sample >= 1, "predict_log: beta_per_sample %d", beta_per_sample);
+  HRIEMO_CHECK(n_valid == nullptr || ((uintptr_t)n_valid % 4) == 0, "predict_log: n_valid is one aligned int32 in device memory");
+  HRIEMO_CHECK(((uintptr_t)counters % 4) == 0 && ((uintptr_t)pred % 4) == 0, "predict_log: counters / pred are not aligned");
+  if (kind == 0) {
+    hipLaunchKernelGGL(predict_log_kernel<0>, dim3(1), dim3(256), 0, st, logits, beta, beta_per_sample, n_valid, B, C, probs, beta_mean, pred,
+                       capacity, counters);
+  } else {
+    hipLaunchKernelGGL(predict_log_kernel<1>, dim3(1), dim3(256), 0, st, logits, beta, beta_per_sample, n_valid, B, C, probs, beta_mean, pred,
+                       capacity, counters);
+  }
+  HRIEMO_LAUNCH_CHECK("predict_log_kernel");
   return 0;
 }
 

@@ -330,17 +330,18 @@ def _in_step_context(fn):
 
 class _GraphRecord:
     """One captured graph and what lives exactly as long as it: the loss tensor its replay writes, the buffers its kernels point
-    into (column-sum partials, queued weight-gradient operands), the packed plans of a bucket graph (None: the plain step).  A
-    record has ONE owner -- DataParallelStep._record or a _PackedState.graphs entry -- and dies through release()."""
-    __slots__ = ("graph", "loss", "keep", "seqs")
+    into (column-sum partials, queued weight-gradient operands), the packed plans of a bucket graph (None: the plain step), the
+    output tensors of a captured evaluation (EvalStep; None for a trainer step).  A record has ONE owner -- DataParallelStep._record
+    or a _PackedState.graphs entry -- and dies through release()."""
+    __slots__ = ("graph", "loss", "keep", "seqs", "out")
 
-    def __init__(self, graph, loss, keep, seqs=None):
-        self.graph, self.loss, self.keep, self.seqs = graph, loss, keep, seqs
+    def __init__(self, graph, loss, keep, seqs=None, out=None):
+        self.graph, self.loss, self.keep, self.seqs, self.out = graph, loss, keep, seqs, out
 
     def release(self):
-        """the one way down for _ops.GRAPHS_ALIVE (the way up: _capture_graph); the caller has synchronized the device"""
+        """the one way down for _ops.GRAPHS_ALIVE (the way up: _record_graph); the caller has synchronized the device"""
         from . import _ops
-        self.graph = self.loss = self.keep = self.seqs = None
+        self.graph = self.loss = self.keep = self.seqs = self.out = None
         _ops.GRAPHS_ALIVE -= 1
         if _ops.GRAPHS_ALIVE == 0:
             del _ops._ws_retired[:]   # no graph points into the outgrown workspaces any more
@@ -394,6 +395,77 @@ class _PackedState:
 
     def __getitem__(self, name):      # bench.py reads _pb["graphs"]
         return getattr(self, name)
+
+
+def _load_ragged(pb, static, rows_a, rows_t, la, lt, y, ctl=None):
+    """A checked ragged batch into the static state of a step captured from ragged batches (static = [src_a, src_t, -, -, y]) -> its
+    bucket key: the rows to the head of each source, zeros from there to the bucket's end (the MOSEI projections read every bucket
+    row), the lengths as one [2, B] block through the pinned twin, y (None: the step holds no targets).  A short batch is completed
+    with ghosts first (ghost_plan).  ctl = (first, last): the step-control block goes up with n_valid = the batch's own number of
+    utterances, by the protocol of the lengths block."""
+    front = pb.front
+    n_utt = len(la)
+    la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, pb.B, pb.La, pb.Lt)
+    for src, rows, n, n_rows in ((static[0], rows_a, rows_own_a, key[0]), (static[1], rows_t, rows_own_t, key[1])):
+        if rows.data_ptr() != src.data_ptr():
+            src[:n].copy_(rows, non_blocking=True)
+        src[n:n_rows].zero_()
+    front.lens.upload([la, lt])
+    if front.ctl is not None:
+        front.ctl.upload(ctl_words(n_utt, *(ctl if ctl is not None else (1, 1))))
+    if y is not None and y.data_ptr() != static[4].data_ptr():
+        static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
+    return key
+
+
+def _record_graph(dev, seqs, pool, warm, body, warmed=None, settle=0.0):
+    """The capture mechanics every captured step of the process shares: two eager warm-up passes (`warm()`) on the process's one
+    capture stream of `dev`, then `body()` recorded into a fresh graph on that stream (pool: the memory pool of a bucket graph, or
+    None) with CTX.capturing / capture_origin / seq_override in force.  -> the graph's _GraphRecord, whose `loss` is what body()
+    returned (the caller moves it where it belongs).  The one way up for _ops.GRAPHS_ALIVE.  warmed(): called behind the warm-up
+    passes, in front of the capture (drop what they left).  settle: seconds to wait between the
+    warm-up passes and the capture (eager collectives in the warm-up, DataParallelStep._capture_graph)."""
+    from . import _ops
+    # ONE capture stream per device for every capture of the process: workspaces are keyed by stream, a fresh stream per
+    # capture would allocate (and, with a graph alive, retire instead of free) a fresh 64 MB+ set each time
+    side = DataParallelStep._capture_streams.get(dev.index)
+    if side is None:
+        side = DataParallelStep._capture_streams[dev.index] = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream())
+    _ops.CTX.seq_override = seqs
+    try:
+        with torch.cuda.stream(side):                 # warm-up off the default stream, as graph capture wants
+            for _ in range(2):
+                warm()
+            if warmed is not None:
+                warmed()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if settle:
+            import time
+            time.sleep(settle)
+        graph = torch.cuda.CUDAGraph()
+        _ops.CTX.capturing = True
+        _ops.CTX.capture_origin = side        # every helper-stream fork of the step must start here (_ops.fork refuses nested forks)
+        _ops.begin_step()
+        try:
+            # capture on the stream the warm-up ran on: its workspaces (keyed by stream) exist already, so nothing the
+            # graph points into comes from the graph's private pool or is first sized during capture.
+            # thread_local: the RCCL watchdog thread may query events while we capture
+            kw = {"pool": pool} if pool is not None else {}
+            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local", **kw):
+                out = body()
+        finally:
+            _ops.CTX.capturing = False
+            _ops.CTX.capture_origin = None
+    finally:
+        _ops.CTX.seq_override = None
+    _ops.GRAPHS_ALIVE += 1            # from now on outgrown workspaces are retired, not freed (_ops.workspace)
+    # buffers the captured kernels point into (column-sum partials, queued weight-gradient operands) live exactly as long as
+    # this graph: they move from the process-wide lists to the graph's owner
+    keep = _ops._deferred.keep + _ops._small_dw.keep
+    _ops._deferred.keep, _ops._small_dw.keep = [], []
+    return _GraphRecord(graph, out, keep, seqs)
 
 
 class DataParallelStep:
@@ -682,24 +754,8 @@ class DataParallelStep:
         self._end_capture()
 
     def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
-        """a checked ragged batch into the static state -> its bucket key: the rows to the head of each source, zeros from there to
-        the bucket's end (the MOSEI projections read every bucket row), the lengths as one [2, B] block through the pinned twin, y.
-        A short batch (partial_batches) is completed with ghosts first (ghost_plan).  ctl = (first, last): the step-control block
-        goes up with n_valid = the batch's own number of utterances, by the protocol of the lengths block."""
-        pb = self._pb
-        front = pb.front
-        n_utt = len(la)
-        la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, pb.B, pb.La, pb.Lt)
-        for src, rows, n, n_rows in ((self._static[0], rows_a, rows_own_a, key[0]), (self._static[1], rows_t, rows_own_t, key[1])):
-            if rows.data_ptr() != src.data_ptr():
-                src[:n].copy_(rows, non_blocking=True)
-            src[n:n_rows].zero_()
-        front.lens.upload([la, lt])
-        if front.ctl is not None:
-            front.ctl.upload(ctl_words(n_utt, *(ctl if ctl is not None else (1, 1))))
-        if y.data_ptr() != self._static[4].data_ptr():
-            self._static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
-        return key
+        """a checked ragged batch into the static state -> its bucket key (_load_ragged)"""
+        return _load_ragged(self._pb, self._static, rows_a, rows_t, la, lt, y, ctl)
 
     @_in_step_context
     def step_packed(self, rows_a, rows_t, lengths_a, lengths_t, y):
@@ -831,63 +887,36 @@ class DataParallelStep:
         """warm-up + capture of one step on self._static; seqs = the packed plans of a bucket graph (or None) -> its _GraphRecord"""
         from . import _ops
         collectives = self._exchange_in_graph
-        # ONE capture stream per device for every capture of the process: workspaces are keyed by stream, a fresh stream per
-        # capture would allocate (and, with a graph alive, retire instead of free) a fresh 64 MB+ set each time
-        dev = self._static[0].device
-        side = DataParallelStep._capture_streams.get(dev.index)
-        if side is None:
-            side = DataParallelStep._capture_streams[dev.index] = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        _ops.CTX.seq_override = seqs
-        try:
-            with torch.cuda.stream(side):                 # warm-up off the default stream, as graph capture wants
-                for _ in range(2):
-                    self._fwd_bwd(*self._static)
-                    if collectives:
-                        self.buckets.finish()         # the warm-up steps exchange eagerly (every rank alike) and leave the buckets reset
-                self._outputs = None                  # warm-up passes never reach the statistics
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+
+        def warm():
+            self._fwd_bwd(*self._static)
             if collectives:
-                # The process group's watchdog thread polls the end event of every EAGER collective until it has seen it complete
-                # (every 100 ms).  The warm-up exchanges above are complete now, but not necessarily reaped -- and once the capture
-                # below pulls the group's communication stream into the capture, ROCm 7.2 answers a query of an event that was
-                # recorded on that stream with hipErrorCapturedEvent, which the watchdog turns into std::terminate (sporadic: 1 run
-                # in 8 aborted, gpurun_out/cap_8.log of round 4).  Two watchdog periods let it drain its list first.
-                import time
-                time.sleep(0.25)
-            graph = torch.cuda.CUDAGraph()
-            if seqs is not None and self._pb.pool is None:
-                self._pb.pool = torch.cuda.graph_pool_handle()
-            _ops.CTX.capturing = True
-            _ops.CTX.capture_origin = side        # every helper-stream fork of the step must start here (_ops.fork refuses nested forks)
-            _ops.begin_step()
-            try:
-                # capture on the stream the warm-up ran on: its workspaces (keyed by stream) exist already, so nothing the
-                # graph points into comes from the graph's private pool or is first sized during capture.
-                # thread_local: the RCCL watchdog thread may query events while we capture
-                kw = {"pool": self._pb.pool} if seqs is not None else {}
-                with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local", **kw):
-                    _ops.bump_seed_word(self._static[0].device)
-                    loss = self._fwd_bwd(*self._static)
-                    self._update_stats()              # recorded, not run: one block behind backward, in front of the optimizer
-                    if collectives:
-                        self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
-                    if self._optimizer is not None:
-                        front = self._pb.front if self._pb is not None else None
-                        ctl = front.ctl.dev if (front is not None and front.accum > 1) else None
-                        self._optimizer._enqueue(ctl=ctl)    # recorded, not run: norm, skip / hold / clip / bias corrections, update
-            finally:
-                _ops.CTX.capturing = False
-                _ops.CTX.capture_origin = None
-        finally:
-            _ops.CTX.seq_override = None
-        _ops.GRAPHS_ALIVE += 1            # from now on outgrown workspaces are retired, not freed (_ops.workspace)
-        # buffers the captured kernels point into (column-sum partials, queued weight-gradient operands) live exactly as long as
-        # this graph: they move from the process-wide lists to the graph's owner
-        keep = _ops._deferred.keep + _ops._small_dw.keep
-        _ops._deferred.keep, _ops._small_dw.keep = [], []
-        return _GraphRecord(graph, loss, keep, seqs)
+                self.buckets.finish()         # the warm-up steps exchange eagerly (every rank alike) and leave the buckets reset
+
+        def warmed():
+            self._outputs = None                  # warm-up passes never reach the statistics
+
+        def body():
+            _ops.bump_seed_word(self._static[0].device)
+            loss = self._fwd_bwd(*self._static)
+            self._update_stats()              # recorded, not run: one block behind backward, in front of the optimizer
+            if collectives:
+                self.buckets.finish()         # waits on the captured collectives + the average: part of the graph
+            if self._optimizer is not None:
+                front = self._pb.front if self._pb is not None else None
+                ctl = front.ctl.dev if (front is not None and front.accum > 1) else None
+                self._optimizer._enqueue(ctl=ctl)    # recorded, not run: norm, skip / hold / clip / bias corrections, update
+            return loss
+
+        if seqs is not None and self._pb.pool is None:
+            self._pb.pool = torch.cuda.graph_pool_handle()
+        # The process group's watchdog thread polls the end event of every EAGER collective until it has seen it complete
+        # (every 100 ms).  The warm-up exchanges are complete when the capture starts, but not necessarily reaped -- and once the
+        # capture pulls the group's communication stream into the capture, ROCm 7.2 answers a query of an event that was
+        # recorded on that stream with hipErrorCapturedEvent, which the watchdog turns into std::terminate (sporadic: 1 run
+        # in 8 aborted).  Two watchdog periods let it drain its list first.
+        return _record_graph(self._static[0].device, seqs, self._pb.pool if seqs is not None else None, warm, body, warmed,
+                             settle=0.25 if collectives else 0.0)
 
     def release_graph(self):
         """drop the captured step (before a re-capture, or to free its buffers): the graph(s), the buffers their kernels point into"""
@@ -950,3 +979,226 @@ class DataParallelStep:
         if self._optimizer is not None:
             self._optimizer.step()                        # use_graph(False): still the whole trainer step
         return loss
+
+
+# the switches a captured forward bakes in: name -> how it reads now (eval_packed refuses a replay under another setting)
+def _mode_switches():
+    from . import _ops
+    return (("precision", _ops.precision()), ("gemm_mode", _ops.gemm_mode()), ("PACKED_TAIL", bool(_ops.PACKED_TAIL)),
+            ("PACKED_TAIL_FP32", bool(_ops.PACKED_TAIL_FP32)), ("PACKED_TAIL_MX8", bool(_ops.PACKED_TAIL_MX8)), ("ingest", _ops.ingest()))
+
+
+class EvalStep:
+    """The evaluation half of an epoch as graph replays: capture_packed / step_packed of DataParallelStep for the FORWARD alone --
+    the reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
+    and the loop of scripts/infer/mosei_eval_infer.py.  An eager forward is ~150 launches issued from Python; one ``eval_packed``
+    is the copies of the batch into the static buffers and one replay.
+
+    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None): loss_fn(logits, beta, y, n_valid=...) as
+    hri_emo_amd.train's losses; stats a ``train.EpochStats``, log a ``train.PredictionLog`` -- both are fed INSIDE the graph, one
+    launch each, and never by a warm-up pass.  max_graphs: bucket graphs kept alive (default HRIEMO_VARLEN_MAX_GRAPHS), least
+    recently replayed one released first.  The step has its own ``_ops.StepContext`` and its own graph pool, creates no gradient
+    buffers and leaves the module's training flag, torch's CPU generator and the device seed word as it found them.
+
+    What a bucket graph holds, in this order: hriemo_seq_tables (lengths block -> cu_seqlens and masks), the model's
+    ``_forward_rows`` in eval mode under no_grad, the loss (when a loss_fn and targets were given at capture), stats.update,
+    log.update -- each with n_valid read from the control block, so a batch of 1 <= n <= B utterances is served by the graphs
+    captured for B (ghost utterances of length 1, ghost_plan).  No seed bump, no zero-grad, no backward, no optimizer.  The bf16 /
+    MX weight shadows are re-cast inside the graph: an evaluation that follows optimizer replays sees the new weights.
+    ``return_attention`` is not part of the captured step: attention maps stay with the eager forward_packed."""
+
+    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None):
+        from . import _ops
+        if max_graphs is not None and int(max_graphs) < 1:
+            raise ValueError("EvalStep: max_graphs is a positive integer (or None)")
+        self.model, self.loss_fn, self.stats, self.log = model, loss_fn, stats, log
+        self.max_graphs = None if max_graphs is None else int(max_graphs)
+        self.ctx = _ops.StepContext()      # this step's capture flag / packed plan: not shared with a trainer step's
+        self._pb = None                    # _PackedState: shapes, cu_seqlens buffers, the bucket graphs, the ragged front
+        self._static = None                # [src_a, src_t, None, None, y | None]: the layout _load_ragged fills
+        self._modes = None                 # _mode_switches() at capture
+        self._replay = True
+
+    @property
+    def captured(self):
+        """bucket graphs exist (use_graph decides whether eval_packed replays them)"""
+        return self._pb is not None and len(self._pb.graphs) > 0
+
+    @property
+    def _replaying(self):
+        return self._replay and self.captured
+
+    def use_graph(self, on):
+        """False: eval_packed is the eager forward_packed evaluation (same outputs, same updates of stats and log)"""
+        self._replay = bool(on) and self.captured
+
+    def release_graph(self):
+        """drop the captured step: the graphs, their outputs, the buffers their kernels point into, the static state"""
+        if self.captured:
+            torch.cuda.synchronize()
+            for rec in self._pb.graphs.values():
+                rec.release()
+        self._pb = self._static = self._modes = None
+
+    @_in_step_context
+    def capture_packed(self, rows_a, rows_t, lengths_a, lengths_t, y=None, pad_to=None):
+        """Capture the evaluation of ragged batches (data.collate_seq_packed): the arguments of DataParallelStep.capture_packed, y
+        optional.  pad_to = (L_a, L_t) and B = the number of utterances of this batch are fixed from here on; ``eval_packed`` then
+        serves every batch of 1 <= n <= B utterances.  With y (and a loss_fn) the graphs compute the loss and feed `stats`; with
+        y=None they are prediction-only: logits, beta, z and the log.  Static state as capture_packed builds it: zero-initialised
+        row sources of the largest bucket in the rows' dtype, the lengths as one int32 [2, B] block with a pinned twin, three
+        cu_seqlens and three mask buffers, y, and the control block whose n_valid word the loss, the statistics and the log read.
+        The switches in force now -- precision(), gemm_mode(), the three packed-tail flags, ingest() -- are recorded."""
+        from . import _ops
+        if not hasattr(self.model, "_forward_rows"):
+            raise TypeError("EvalStep.capture_packed: the model has no forward_packed entry")
+        if self.loss_fn is not None and y is not None and not _accepts_n_valid(self.loss_fn):
+            raise TypeError("EvalStep.capture_packed: loss_fn takes no n_valid= keyword -- the ghost utterances of a short batch must "
+                            "stay out of the loss (hri_emo_amd.train's losses accept it)")
+        if self.stats is not None and (self.loss_fn is None or y is None):
+            raise ValueError("EvalStep.capture_packed: statistics need a loss_fn and targets (prediction-only graphs feed the log)")
+        same_width = not hasattr(self.model, "audio_proj")
+        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
+        if pad_to is None:
+            raise ValueError("EvalStep.capture_packed: pad_to=(L_a, L_t) is required")
+        dev = next(self.model.parameters()).device
+        _ops._require_gpu(next(self.model.parameters()))
+        B = len(la)
+        if y is not None and y.shape[0] != B:
+            raise ValueError(f"EvalStep.capture_packed: targets of shape {tuple(y.shape)} for {B} utterances")
+        self.release_graph()              # a re-capture replaces the old graphs
+        cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
+        src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
+        src_t = torch.zeros(cap_t, rows_t.shape[1], dtype=rows_t.dtype, device=dev)
+        self._static = [src_a, src_t, None, None, None if y is None else y.to(dev, copy=True)]
+        masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
+        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, same_width, partial=True, accum=1,
+                             ctl=_HostBlock(ctl_words(B, 1, 1), dev))
+        self._pb = _PackedState(B, La, Lt, dev, front)
+        self._modes = _mode_switches()
+        self._replay = True
+        try:
+            self._packed_graph(_load_ragged(self._pb, self._static, rows_a, rows_t, la, lt, y))
+        except BaseException:
+            self.release_graph()
+            raise
+
+    def _pass(self, record):
+        """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
+        stats and log (the capture pass only) -> (logits, beta, z, loss | None)"""
+        from . import _ops
+        pb = self._pb
+        front = pb.front
+        seqs = _ops.CTX.seq_override
+        y = self._static[4]
+        with torch.no_grad():
+            _ops.seq_tables(front.lens.dev, pb.La, pb.Lt, rows=(seqs[0].N, seqs[1].N), cu=(pb.cu_a, pb.cu_t, pb.cu_f), masks=front.masks)
+            logits, beta, z = self.model._forward_rows(self._static[0], self._static[1], tuple(seqs), front.bool, (pb.La, pb.Lt))
+            n_valid = front.ctl.dev[:1]
+            loss = self.loss_fn(logits, beta, y, n_valid=n_valid) if (self.loss_fn is not None and y is not None) else None
+            if record and self.stats is not None:
+                self.stats.update(logits, beta, y, loss, n_valid=n_valid)
+            if record and self.log is not None:
+                self.log.update(logits, beta, n_valid=n_valid)
+        return logits, beta, z, loss
+
+    def _packed_graph(self, key):
+        """the record of bucket `key`: captured on the static state (already this batch) when the bucket is new"""
+        from . import _ops
+        pb = self._pb
+        rec = pb.graphs.get(key)
+        if rec is not None:
+            pb.graphs.move_to_end(key)
+            return rec
+        # nothing of an evaluation draws from torch's CPU generator; a bucket met inside eval_packed still hands it back as it was
+        rng = torch.get_rng_state() if self.captured else None
+        cap = self.max_graphs if self.max_graphs is not None else _VARLEN_MAX_GRAPHS
+        while len(pb.graphs) >= cap:
+            old_key, old = pb.graphs.popitem(last=False)
+            torch.cuda.synchronize()
+            old.release()
+            log.info("eval step: released the graph of bucket %s (cap %d)", old_key, cap)
+        seqs = (_ops.seq_bucket(pb.cu_a, pb.B, pb.La, key[0]), _ops.seq_bucket(pb.cu_t, pb.B, pb.Lt, key[1]),
+                _ops.seq_bucket_fused(pb.cu_f, pb.B, min(pb.La, pb.Lt), key[1]))
+        if pb.pool is None:
+            pb.pool = torch.cuda.graph_pool_handle()
+        was = self.model.training
+        self.model.eval()
+        try:
+            rec = _record_graph(self._static[0].device, seqs, pb.pool, lambda: self._pass(False), lambda: self._pass(True))
+        finally:
+            self.model.train(was)
+            if rng is not None:
+                torch.set_rng_state(rng)
+        rec.out, rec.loss = rec.loss[:3], rec.loss[3]
+        pb.graphs[key] = rec
+        log.info("eval step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb.graphs))
+        return rec
+
+    def _check_modes(self):
+        for (name, then), (_, now) in zip(self._modes, _mode_switches()):
+            if then != now:
+                raise RuntimeError(f"EvalStep.eval_packed: the step was captured with {name} = {then!r}; it is {now!r} now -- "
+                                   "capture_packed() again under the new setting, or switch back")
+
+    @_in_step_context
+    def eval_packed(self, rows_a, rows_t, lengths_a, lengths_t, y=None):
+        """One evaluation of a ragged batch of 1 <= n <= B utterances -> (logits [n, C], beta, z, loss | None).  The arguments are
+        checked on the host first -- a refusal (ValueError; RuntimeError for a mode switch that changed since the capture) leaves
+        every static buffer untouched -- then rows, lengths, n_valid and y are copied into the static state and the batch's bucket
+        graph is replayed (captured on the spot if the bucket is new).
+
+        The returned tensors are VIEWS of the replayed graph's own output tensors, cut to the first n samples: they are valid until
+        the graph of the same bucket is replayed again (clone what must outlive that).  loss is the 0-dim tensor the replay wrote:
+        the mean over the batch's n utterances.  After use_graph(False) this is the eager model.eval() + forward_packed evaluation
+        with the same outputs and the same updates of stats and log."""
+        from . import _ops
+        pb = self._pb
+        if pb is None:
+            raise RuntimeError("eval_packed needs capture_packed() first")
+        front = pb.front
+        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, (pb.La, pb.Lt), same_width=front.same_width)
+        n = len(la)
+        if not self._replaying:
+            return self._eval_eager(rows_a, rows_t, la, lt, y)
+        self._check_modes()
+        if n > pb.B:
+            raise ValueError(f"eval_packed: a batch of {n} utterances; the captured step holds at most B = {pb.B}")
+        for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
+            if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
+                raise ValueError(f"eval_packed: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
+        sy = self._static[4]
+        if sy is None and y is not None:
+            raise ValueError("eval_packed: targets given, but the step was captured without (prediction-only graphs)")
+        if sy is not None and y is None:
+            raise ValueError("eval_packed: the step was captured with targets; this batch has none")
+        if sy is not None:
+            want = (n,) + tuple(sy.shape[1:])
+            if tuple(y.shape) != want:
+                raise ValueError(f"eval_packed: targets of shape {tuple(y.shape)}; captured with {tuple(sy.shape)}"
+                                 + (f", this batch needs {want}" if n != pb.B else ""))
+        rec = self._packed_graph(_load_ragged(pb, self._static, rows_a, rows_t, la, lt, y))
+        rec.graph.replay()
+        logits, beta, z = rec.out
+        return logits[:n], beta[:n], z[:n], rec.loss
+
+    def _eval_eager(self, rows_a, rows_t, la, lt, y):
+        pb = self._pb
+        dev = self._static[0].device
+        was = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                logits, beta, z = self.model.forward_packed(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), la, lt,
+                                                            pad_to=(pb.La, pb.Lt))
+                loss = None
+                if self.loss_fn is not None and y is not None:
+                    y = y.to(dev, non_blocking=True)
+                    loss = self.loss_fn(logits, beta, y)
+                    if self.stats is not None:
+                        self.stats.update(logits, beta, y, loss)
+                if self.log is not None:
+                    self.log.update(logits, beta)
+        finally:
+            self.model.train(was)
+        return logits, beta, z, loss

@@ -290,12 +290,129 @@ class EpochStats:
         return out
 
 
-def evaluate_packed(model, batches, loss_fn, stats, pad_to=None):
+# ------------------------------------------------------------------------------------------------------------------ prediction log
+_PL = ("cursor", "n_samples", "overflow", "n_nonfinite")        # counters[4] of hriemo_predict_log
+
+
+class PredictionLog:
+    """The products of the reference's inference driver (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy),
+    accumulated where the forward runs: probabilities, per-sample mean beta and -- single-label -- the argmax of every sample, without
+    targets and without a read-back per batch.
+
+    PredictionLog(num_outputs, capacity, kind="multi_label" | "single_label", device=...): `capacity` is the number of samples the
+    log holds.  multi_label logs p = sigmoid(logits) (the bits EpochStats logs for the same logits), single_label the fp32 softmax
+    over the classes (row maximum subtracted) and the first maximal logit's index (torch.argmax's rule).
+
+    update(logits, beta=None, n_valid=None) enqueues ONE launch (hriemo_predict_log) on the current stream and reads nothing back; it
+    can be recorded into a captured step (dp.EvalStep(log=...)).  beta: None or B * k values, k per sample; the log keeps each
+    sample's mean (float64 sum in index order, stored as fp32).  n_valid: None or a 1-element int32 tensor on the device (a Python
+    int on the CPU path too): only the first clamp(n_valid, 1, B) samples are logged, whatever the rows behind them hold.
+
+    reset() starts over (the log needs no clearing: only entries in front of the cursor are ever read).
+
+    arrays(): ONE read-back -> dict(y_prob float32 [n, C], sample-major as the reference saves it; beta_mean float32 [n], or None
+    when no update carried beta; pred int32 [n], single_label only; n_nonfinite, the number of NaN / Inf logits logged; n_samples).
+    RuntimeError if the log overflowed.
+
+    CPU tensors take the same definitions in plain torch / numpy (sigmoid and softmax in float64, rounded to fp32)."""
+
+    def __init__(self, num_outputs, capacity, kind="multi_label", device="cuda"):
+        if kind not in ("multi_label", "single_label"):
+            raise ValueError("PredictionLog: kind is 'multi_label' or 'single_label'")
+        if int(num_outputs) < 1 or int(capacity) < 1:
+            raise ValueError("PredictionLog: num_outputs and capacity are positive")
+        self.C, self.capacity, self.kind = int(num_outputs), int(capacity), kind
+        self.device = torch.device(device)
+        self.multi = kind == "multi_label"
+        # everything arrays() reads back is ONE buffer: counters int32[4] | probs fp32 [C, capacity] | beta_mean fp32 [capacity] |
+        # pred int32 [capacity]
+        C, cap = self.C, self.capacity
+        self._parts = (16, 16 + 4 * C * cap, 16 + 4 * (C + 1) * cap)
+        self._buf = torch.zeros(16 + 4 * (C + 2) * cap, dtype=torch.uint8, device=self.device)
+        self.counters, self.probs, self.beta_mean, self.pred = self._views(self._buf)
+        self._has_beta = False
+
+    def _views(self, buf):
+        a, b, c = self._parts
+        return (buf[:a].view(torch.int32), buf[a:b].view(torch.float32).view(self.C, self.capacity), buf[b:c].view(torch.float32),
+                buf[c:].view(torch.int32))
+
+    def reset(self):
+        self.counters.zero_()
+
+    def update(self, logits, beta=None, n_valid=None):
+        if logits.dim() != 2 or logits.shape[1] != self.C:
+            raise ValueError(f"PredictionLog.update: logits of shape {tuple(logits.shape)}; expected [B, {self.C}]")
+        B = logits.shape[0]
+        if B < 1:
+            raise ValueError("PredictionLog.update: an empty batch")
+        if beta is not None and (beta.numel() == 0 or beta.numel() % B != 0):
+            raise ValueError(f"PredictionLog.update: beta of {beta.numel()} values for {B} samples")
+        if logits.device.type != self.device.type:
+            raise ValueError(f"PredictionLog.update: logits on {logits.device}; the log lives on {self.device}")
+        self._has_beta = self._has_beta or beta is not None
+        if not logits.is_cuda:
+            return self._update_cpu(logits, beta, n_valid, B)
+        from . import _lib, _ops
+        p = _ops._p
+        nv = _ops._n_valid_word((n_valid,), logits)
+        x = logits.detach().contiguous().float()
+        bt = beta.detach().contiguous().float() if beta is not None else None
+        _lib.call("hriemo_predict_log", p(x), p(bt), bt.numel() // B if bt is not None else 0, p(nv), B, self.C, 0 if self.multi else 1,
+                  p(self.probs), p(self.beta_mean), None if self.multi else p(self.pred), self.capacity, p(self.counters), _ops._stream())
+
+    def _update_cpu(self, logits, beta, n_valid, B):
+        nv = B if n_valid is None else min(max(int(n_valid), 1), B)
+        ctr = self.counters
+        ctr[1] += nv
+        cur = int(ctr[0])
+        if cur < 0 or cur + nv > self.capacity:
+            ctr[2] = 1
+            return
+        x = logits.detach()[:nv].float()
+        if self.multi:
+            pr = torch.sigmoid(x.double()).float()
+        else:
+            pr = torch.softmax(x.double(), dim=1).float()
+            self.pred[cur:cur + nv] = x.argmax(dim=1).to(torch.int32)
+        self.probs[:, cur:cur + nv] = pr.t()
+        if beta is not None:
+            self.beta_mean[cur:cur + nv] = beta.detach().reshape(B, -1)[:nv].double().mean(dim=1).float()
+        ctr[3] += int((~torch.isfinite(x)).sum())
+        ctr[0] = cur + nv
+
+    def arrays(self):
+        ctr, probs, beta_mean, pred = self._views(self._buf.cpu())                    # the one read-back
+        ctr = dict(zip(_PL, (int(v) for v in ctr.tolist())))
+        if ctr["overflow"]:
+            raise RuntimeError(f"PredictionLog: the log of {self.capacity} samples overflowed ({ctr['n_samples']} samples were offered); "
+                               "size capacity for the split")
+        n = ctr["cursor"]
+        out = {"y_prob": np.ascontiguousarray(probs[:, :n].numpy().T), "beta_mean": beta_mean[:n].numpy().copy() if self._has_beta else None,
+               "n_nonfinite": ctr["n_nonfinite"], "n_samples": ctr["n_samples"]}
+        if not self.multi:
+            out["pred"] = pred[:n].numpy().copy()
+        return out
+
+
+def evaluate_packed(model, batches, loss_fn, stats, pad_to=None, step=None):
     """The reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
     on ragged batches: model.eval() under torch.no_grad(); for every data.collate_seq_packed batch (rows_a, lengths_a, rows_t,
     lengths_t, labels): forward_packed -> loss_fn(logits, beta, labels) -> stats.update.  Nothing is read back per batch --
-    ``stats.result()`` afterwards is the epoch's one read-back.  Eager launches (a captured eval forward is a different piece of
-    work); the module's training mode is restored.  Returns `stats`."""
+    ``stats.result()`` afterwards is the epoch's one read-back.  Without `step` these are eager launches; the module's training
+    mode is restored.  step: a ``dp.EvalStep`` built on this model with this loss_fn and these stats -- every batch is then ONE
+    ``eval_packed`` (a graph replay that holds the forward, the loss and the statistics' update; short batches included).  A step
+    that holds no graph yet is captured on the spot from the first batch, which needs pad_to=(L_a, L_t).  Returns `stats`."""
+    if step is not None:
+        if step.model is not model or step.stats is not stats or step.loss_fn is not loss_fn:
+            raise ValueError("evaluate_packed(step=...): the EvalStep was built on another model, loss_fn or stats")
+        for rows_a, len_a, rows_t, len_t, y in batches:
+            if not step.captured:
+                if pad_to is None:
+                    raise ValueError("evaluate_packed(step=...): pad_to=(L_a, L_t) is required to capture the step from the first batch")
+                step.capture_packed(rows_a, rows_t, len_a, len_t, y, pad_to=pad_to)
+            step.eval_packed(rows_a, rows_t, len_a, len_t, y)
+        return stats
     was = model.training
     dev = next(model.parameters()).device
     model.eval()

@@ -408,6 +408,26 @@ int hriemo_stats_counts(const float* probs, const unsigned char* truth, int capa
 int hriemo_stats_auc_tiles(int capacity);
 int hriemo_stats_auc(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
                      unsigned long long* partial, int* npn, hriemo_stream_t stream);
+/* Prediction log in device memory (csrc/metrics.hip): the products of the reference's inference driver
+ * (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy) without targets and without a read-back per batch.
+ * State, owned by the caller, counters zeroed to reset:
+ *   probs     fp32  [C, capacity]  class-major, as the statistics' log
+ *   beta_mean fp32  [capacity]     (optional)
+ *   pred      int32 [capacity]     (optional, single-label only)
+ *   counters  int32 [4]            {cursor, n_samples, overflow, n_nonfinite}
+ * hriemo_predict_log: ONE block of 256, meant to be recorded behind the forward of a (captured) step -- every input is a device
+ * pointer; launches are stream-ordered, so the block owns the cursor and nothing is atomic.  nv = clamp(*n_valid, 1, B) (NULL: B)
+ * as in hriemo_fusion_loss_n; rows b >= nv of logits and beta are never read.  kind 0 (multi-label): probs[c, cursor + b] =
+ * 1 / (1 + expf(-logit)), the expression of hriemo_stats_update: equal logits give equal bits in both logs.  kind 1
+ * (single-label): the fp32 softmax over C with the row maximum subtracted (the difference carried with its rounding error, the
+ * sum over the classes in index order), and pred[cursor + b] = the first maximal logit's index (torch.argmax's rule; pred may
+ * be NULL).  beta: NULL or B * beta_per_sample values; beta_mean[cursor + b] = the mean of the
+ * sample's values, summed in index order in float64, stored as fp32 (beta_mean may be NULL).  cursor + nv > capacity: overflow = 1
+ * and nothing is appended; n_samples still counts.  Otherwise the cursor moves by nv and n_nonfinite gains the number of non-finite
+ * logits logged.  Refused (non-zero, nothing launched): B, C or capacity < 1, kind outside {0, 1}, NULL logits / probs / counters,
+ * beta with beta_per_sample < 1, n_valid / counters / pred not 4-byte aligned. */
+int hriemo_predict_log(const float* logits, const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int kind,
+                       float* probs, float* beta_mean, int* pred, int capacity, int* counters, hriemo_stream_t stream);
 int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, int is_a, const float* dpool, const float* cnt,
                           const unsigned char* mask, void* dX, int B, int L, int d, hriemo_stream_t stream);
 /* Trainer step off the timed path, scripts/fusion/train_fusion_seq_level_decoder.py:332-334: clip_grad_norm_(5.0) +
