@@ -203,9 +203,16 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk, hd, kpm, drop=None, 
               dv.stride(0), _ops._p(delta), B, H, Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
 
 
-def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None, cu=None, out_l=None):
-    """cu / out_l as _ops.attn_probs: the padded map [B, out_l[0], out_l[1]] of packed rows"""
+def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None, cu=None, out_l=None, log=None):
+    """cu / out_l as _ops.attn_probs: the padded map [B, out_l[0], out_l[1]] of packed rows; log (an _ops.LogSite): the maps go to the
+    site's log (hriemo_attn_probs_varlen_log_fp32, or the padded export and one append) and None comes back"""
     _no_mask_on_packed_rows("_fp32.probs", kpm, cu)
+    if cu is not None and log is not None:
+        n = log.take(B, out_l[0], out_l[1])
+        _lib.call("hriemo_attn_probs_varlen_log_fp32", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(cu[0]), _ops._p(cu[1]),
+                  _ops._p(lse), _ops._p(log.maps), n, H, Lq, Lk, out_l[0], out_l[1], hd, *_drop_args(drop, q.device), _ops._p(log.window),
+                  log.capacity, _ops._stream())
+        return None
     if cu is not None:
         p = _new((B,) + tuple(out_l), q)
         _lib.call("hriemo_attn_probs_f32_varlen", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(cu[0]), _ops._p(cu[1]),
@@ -214,6 +221,9 @@ def probs(q, k, B, H, Lq, Lk, hd, kpm, lse, drop=None, cu=None, out_l=None):
     p = _new((B, Lq, Lk), q)
     _lib.call("hriemo_attn_probs_f32", _ops._p(q), q.stride(0), _ops._p(k), k.stride(0), _ops._p(kpm), _ops._p(lse), _ops._p(p), B, H,
               Lq, Lk, hd, *_drop_args(drop, q.device), _ops._stream())
+    if log is not None:
+        _ops._log_append(p, log)
+        return None
     return p
 
 
@@ -307,7 +317,8 @@ def _attn_ln(ctx, head, q, k, v, xf, ar, H, hd, params, drops, need_w, out_l, sh
     o, lse = attn(q, k, v, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, want_lse=need_w or rec, drop=drops[0], cu=ar.cu)
     g = linear(o, sh, w_out, b_out)
     y16, y32 = add_ln(g, xf, gamma, beta, drop=drops[1], rows=ar.rows)
-    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=drops[0], cu=ar.cu, out_l=out_l) if need_w else None
+    pr = probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, drop=drops[0], cu=ar.cu, out_l=out_l,
+               log=need_w if isinstance(need_w, _ops.LogSite) else None) if need_w else None
     ctx.fp32 = True
     if rec:
         ctx.set_materialize_grads(False)

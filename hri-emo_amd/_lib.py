@@ -117,6 +117,11 @@ _SIGS = {
     "hriemo_fusion_loss_ce_n": ("pppiiiffppppp", "i"),
     "hriemo_stats_update": ("ppppfpipiiippippp", "i"),
     "hriemo_predict_log": ("ppipiiipppipp", "i"),
+    "hriemo_attn_log_plan": ("ppiipppp", "i"),
+    "hriemo_attn_log_close": ("pp", "i"),
+    "hriemo_attn_log_append": ("piippip", "i"),
+    "hriemo_attn_probs_varlen_log": ("plplppppiiiiiiifQpIipip", "i"),
+    "hriemo_attn_probs_varlen_log_fp32": ("plplppppiiiiiiifQpIipip", "i"),
     "hriemo_stats_counts": ("ppiippipp", "i"),
     "hriemo_stats_auc_tiles": ("i", "i"),
     "hriemo_stats_auc": ("ppiipppp", "i"),

@@ -924,10 +924,40 @@ def attn_bwd(q, k, v, o, do, dq, dk, dv, lse, B, H, Lq, Lk, hd, kpm, p, seed, si
     return fold
 
 
-def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off, cu=None, out_l=None):
+class LogSite:
+    """Where the maps of ONE attention site go when a train.AttentionLog takes them: the site's log tensor [capacity, Lq, Lk], the
+    log's window word {slot0, n_take, 0, 0} (device memory, written by hriemo_attn_log_plan at the top of the pass) and the capacity.
+    A site is handed this in the place of its need flag (it is truthy) and then returns no map: the samples inside the window are
+    in the log.  B: the number of samples of the pass -- a bucket plan's filler sequence has no sample to export."""
+    __slots__ = ("maps", "window", "capacity", "B")
+
+    def __init__(self, maps, window, capacity, B):
+        self.maps, self.window, self.capacity, self.B = maps, window, int(capacity), int(B)
+
+    def take(self, B, Lq, Lk):
+        """the number of samples to launch for, after checking that this site's maps are [., Lq, Lk]"""
+        if tuple(self.maps.shape[1:]) != (Lq, Lk):
+            raise ValueError(f"attention log: a site exports maps [{Lq}, {Lk}]; its log holds {tuple(self.maps.shape[1:])}")
+        return min(B, self.B)
+
+
+def _log_append(out, site):
+    """a map [B, Lq, Lk] that a padded export produced, into the site's log under the window (hriemo_attn_log_append)"""
+    n = site.take(out.shape[0], out.shape[1], out.shape[2])
+    _lib.call("hriemo_attn_log_append", _p(out), n, out.shape[1] * out.shape[2], _p(site.window), _p(site.maps), site.capacity, _stream())
+
+
+def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off, cu=None, out_l=None, log=None):
     """head-averaged probabilities [B, Lq, Lk].  cu = (cu_seqlens_q, cu_seqlens_k): q / k hold packed rows, Lq / Lk are the longest
     sequences and out_l = (L_q, L_k) the padded lengths of the two layouts: the padded map [B, L_q, L_k] comes back, zeros in the
-    PAD key columns and the PAD query rows (every element is written by the kernel)"""
+    PAD key columns and the PAD query rows (every element is written by the kernel).
+    log (a LogSite): the maps go to the site's log and None comes back -- straight from the packed export (hriemo_attn_probs_varlen_log),
+    or from the padded export through one append."""
+    if cu is not None and log is not None:
+        n = log.take(B, out_l[0], out_l[1])
+        _lib.call("hriemo_attn_probs_varlen_log", _p(q), q.stride(0), _p(k), k.stride(0), _p(cu[0]), _p(cu[1]), _p(lse), _p(log.maps), n, H,
+                  Lq, Lk, out_l[0], out_l[1], hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _p(log.window), log.capacity, _stream())
+        return None
     if cu is not None:
         out = torch.empty((B,) + tuple(out_l), dtype=torch.float32, device=q.device)
         _lib.call("hriemo_attn_probs_varlen", _p(q), q.stride(0), _p(k), k.stride(0), _p(cu[0]), _p(cu[1]), _p(lse), _p(out), B, H,
@@ -936,6 +966,9 @@ def attn_probs(q, k, B, H, Lq, Lk, hd, kpm, lse, p, seed, site, b_off, cu=None, 
     out = torch.empty((B, Lq, Lk), dtype=torch.float32, device=q.device)
     _lib.call("hriemo_attn_probs_mfma" if MFMA_MAPS else "hriemo_attn_probs", _p(q), q.stride(0), _p(k), k.stride(0), _p(kpm), _p(lse), _p(out), B, H, Lq, Lk,
               hd, float(p), seed, _p(seed_word(q.device)), site, b_off, _stream())
+    if log is not None:
+        _log_append(out, log)
+        return None
     return out
 
 
@@ -1405,10 +1438,16 @@ AttnRows = namedtuple("AttnRows", "B Lq Lk kpm cu stride rows kv_surplus")
 def attn_rows(seq_q, seq_k, need_w):
     """AttnRows of a sub-layer whose queries are laid out as seq_q and whose keys as seq_k (the same Seq for a self-attention).
     Packed: the attention sees Seq.B sequences of up to Seq.Lmax rows, the LayerNorm dropout stays keyed by the padded rows.
-    need_w on packed rows: only with the packed export switched on (set_varlen_maps) and a plan without a filler sequence."""
+    need_w on packed rows: only with the packed export switched on (set_varlen_maps) and a plan without a filler sequence -- or a
+    LogSite, whose launch covers the plan's real samples only (LogSite.B)."""
     if not (seq_q.packed or seq_k.packed):
         return AttnRows(seq_q.B, seq_q.L, seq_k.L, seq_k.kpm, None, seq_q.L, None, False)
-    if need_w and not (varlen_maps() and seq_q.B == seq_q.Breal and seq_k.B == seq_k.Breal):
+    if isinstance(need_w, LogSite):
+        if not varlen_maps():
+            raise ValueError("attention maps are exported by the padded path only")
+        if need_w.B > min(seq_q.Breal, seq_k.Breal):
+            raise ValueError(f"attention log: a pass of {need_w.B} samples, but the plan holds {min(seq_q.Breal, seq_k.Breal)}")
+    elif need_w and not (varlen_maps() and seq_q.B == seq_q.Breal and seq_k.B == seq_k.Breal):
         # (with the packed export on, a bucketed plan is still refused: its filler sequence has no sample to export)
         raise ValueError("attention maps are exported by the padded path only")
     if not (seq_q.packed and seq_k.packed) or seq_q.kpm is not None or seq_k.kpm is not None:
@@ -1815,7 +1854,8 @@ def _attn_ln_fwd(ctx, head, q, k, v, x2, x32v, ar, H, hd, sh, w_in16, w_out16, d
                               want_bits=attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq), cu=ar.cu)
     g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
                                          ar.rows)
-    probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, out_l) if need_w else None
+    probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, out_l,
+                       log=need_w if isinstance(need_w, LogSite) else None) if need_w else None
     ctx.save_for_backward(*head, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits[0] if mbits else None)
     ctx.rows = ar
     ctx.mark_non_differentiable(*([probs] if probs is not None else []))

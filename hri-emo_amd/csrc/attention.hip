@@ -1521,6 +1521,9 @@ struct ProbsArgs {
   int H, max_lq, max_lk, out_lq, out_lk;
   float scale;
   uint32_t thr16; float inv_keep; uint64_t seed; const unsigned long long* seed_dev; uint32_t site; int b_offset;
+  // hriemo_attn_probs_varlen_log: probs is a log [capacity, out_lq, out_lk] and window = {slot0, n_take, 0, 0} in device memory says
+  // which samples of this launch it takes (hriemo_attn_log_plan wrote it); NULL: sample b's map is probs[b], as ever
+  const int* window; int capacity;
 };
 template <int HD>
 __global__ __launch_bounds__(256) void attn_probs_mfma_kernel(const ProbsArgs a) {
@@ -1529,6 +1532,14 @@ __global__ __launch_bounds__(256) void attn_probs_mfma_kernel(const ProbsArgs a)
   __shared__ __attribute__((aligned(16))) char Kt[64 * STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
   const int b = blockIdx.z;
+  long slot = b;
+  if (a.window != nullptr) {
+    // block-uniform, in front of the first barrier and the first LDS access: a sample outside the window leaves no trace.  The
+    // capacity is a launch argument, so a stale window cannot send a store past the log either.
+    const int slot0 = a.window[0], n_take = a.window[1];
+    if (b >= n_take || slot0 < 0 || (long)slot0 + b >= (long)a.capacity) return;
+    slot = (long)slot0 + b;
+  }
   // the lengths are device data: clamped to what sized the buffers, so a stale cu cannot send a block out of bounds
   const int rq = a.cu_q[b], rk = a.cu_k[b];
   const int Lq = max(min(a.cu_q[b + 1] - rq, a.max_lq), 0), Lk = max(min(a.cu_k[b + 1] - rk, a.max_lk), 0);
@@ -1538,7 +1549,7 @@ __global__ __launch_bounds__(256) void attn_probs_mfma_kernel(const ProbsArgs a)
   const float sl2 = a.scale * LOG2E, invH = 1.f / (float)a.H;
   const uint64_t seed = a.thr16 != 0 ? eff_seed(a.seed, a.seed_dev) : 0ull;
   const bf16_t* Kb = a.K + (long)rk * a.ldk;
-  float* pb = a.probs + (long)b * a.out_lq * a.out_lk;
+  float* pb = a.probs + slot * a.out_lq * a.out_lk;
 
   TileRegs<HD, 64, 256> kr;
   if (kt0 < nlive) tile_fetch<HD, 64, 256>(kr, Kb, a.ldk, kt0 * 64, Lk, tid);
@@ -2075,21 +2086,23 @@ extern "C" int hriemo_attn_probs(const void* Q, long ldq, const void* K, long ld
   return 0;
 }
 
-// The export on packed rows (attn_probs_mfma_kernel): the padded map [B, out_lq, out_lk] of the varlen forward's operands and lse
-extern "C" int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q,
-                                        const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q,
-                                        int max_len_k, int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
-                                        const unsigned long long* seed_dev, unsigned site, int b_offset, hipStream_t st) {
-  HRIEMO_CHECK(Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr, "attn_probs_varlen: empty problem");
+// The export on packed rows (attn_probs_mfma_kernel): the padded map [B, out_lq, out_lk] of the varlen forward's operands and lse.
+// window NULL: probs is [B, out_lq, out_lk]; otherwise the log [capacity, out_lq, out_lk] of hriemo_attn_probs_varlen_log.
+static int attn_probs_varlen_launch(const char* who, const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q,
+                                    const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k,
+                                    int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
+                                    const unsigned long long* seed_dev, unsigned site, int b_offset, const int* window, int capacity,
+                                    hipStream_t st) {
+  HRIEMO_CHECK(Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr, "%s: empty problem", who);
   if (check_shape(B, H, max_len_q, max_len_k, head_dim)) return 1;
-  HRIEMO_CHECK(B <= 65535, "attn_probs_varlen: B=%d exceeds the grid", B);
-  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_probs_varlen: cu_seqlens_q and cu_seqlens_k must be given together");
-  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "attn_probs_varlen: the map [%d, %d] is smaller than the longest sequences [%d, %d]",
+  HRIEMO_CHECK(B <= 65535, "%s: B=%d exceeds the grid", who, B);
+  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "%s: cu_seqlens_q and cu_seqlens_k must be given together", who);
+  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "%s: the map [%d, %d] is smaller than the longest sequences [%d, %d]", who,
                out_lq, out_lk, max_len_q, max_len_k);
-  HRIEMO_CHECK(ldq % 8 == 0 && ldk % 8 == 0, "attn_probs_varlen: leading dims must be multiples of 8");
+  HRIEMO_CHECK(ldq % 8 == 0 && ldk % 8 == 0, "%s: leading dims must be multiples of 8", who);
   HRIEMO_CHECK(((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0 && ((uintptr_t)probs % 4) == 0 && ((uintptr_t)lse % 4) == 0,
-               "attn_probs_varlen: unaligned Q/K/lse/probs");
-  HRIEMO_CHECK(p_drop >= 0.f && p_drop < 1.f, "attn_probs_varlen: dropout p=%f", (double)p_drop);
+               "%s: unaligned Q/K/lse/probs", who);
+  HRIEMO_CHECK(p_drop >= 0.f && p_drop < 1.f, "%s: dropout p=%f", who, (double)p_drop);
   const DropCfg d = make_drop(p_drop, seed, site);
   ProbsArgs a = {};
   a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.ldq = ldq; a.ldk = ldk;
@@ -2097,10 +2110,31 @@ extern "C" int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, 
   a.H = H; a.max_lq = max_len_q; a.max_lk = max_len_k; a.out_lq = out_lq; a.out_lk = out_lk;
   a.scale = 1.0f / sqrtf((float)head_dim);
   a.thr16 = d.thr16; a.inv_keep = d.inv_keep; a.seed = seed; a.seed_dev = seed_dev; a.site = site; a.b_offset = b_offset;
+  a.window = window; a.capacity = capacity;
   const dim3 grid(tiles(out_lq, 64), tiles(out_lk, 64 * PROBS_KT), B);
   with_head_dim(head_dim, [&](auto hd) { hipLaunchKernelGGL((attn_probs_mfma_kernel<decltype(hd)::value>), grid, dim3(256), 0, st, a); });
   HRIEMO_LAUNCH_CHECK("attn_probs_mfma_kernel");
   return 0;
+}
+
+extern "C" int hriemo_attn_probs_varlen(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q,
+                                        const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q,
+                                        int max_len_k, int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
+                                        const unsigned long long* seed_dev, unsigned site, int b_offset, hipStream_t st) {
+  return attn_probs_varlen_launch("attn_probs_varlen", Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, B, H, max_len_q, max_len_k,
+                                  out_lq, out_lk, head_dim, p_drop, seed, seed_dev, site, b_offset, nullptr, 0, st);
+}
+
+// The same launch into an attention log (hriemo_attn_log_plan's window decides which samples land where)
+extern "C" int hriemo_attn_probs_varlen_log(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q,
+                                            const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q,
+                                            int max_len_k, int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
+                                            const unsigned long long* seed_dev, unsigned site, int b_offset, const int* window,
+                                            int capacity, hipStream_t st) {
+  HRIEMO_CHECK(window != nullptr && ((uintptr_t)window % 4) == 0, "attn_probs_varlen_log: window is int32[4] in device memory, 4-byte aligned");
+  HRIEMO_CHECK(capacity >= 1, "attn_probs_varlen_log: capacity %d", capacity);
+  return attn_probs_varlen_launch("attn_probs_varlen_log", Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, B, H, max_len_q,
+                                  max_len_k, out_lq, out_lk, head_dim, p_drop, seed, seed_dev, site, b_offset, window, capacity, st);
 }
 
 // The padded export on the matrix cores (attn_probs_mfma_pad_kernel): the arguments and the result of hriemo_attn_probs

@@ -565,12 +565,22 @@ template <int HD>
 __global__ __launch_bounds__(256) void attn_probs_f32_varlen_kernel(const float* __restrict__ Q, long ldq, const float* __restrict__ K, long ldk,
                                                                     const int* __restrict__ cu_q, const int* __restrict__ cu_k,
                                                                     const float* __restrict__ lse, float* __restrict__ probs, int H, int max_lq,
-                                                                    int max_lk, int out_lq, int out_lk, float scale, AttnDrop dr) {
+                                                                    int max_lk, int out_lq, int out_lk, float scale, AttnDrop dr,
+                                                                    const int* __restrict__ window, int capacity) {
   constexpr int LDR = HD + 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* Ks = (float*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
   const int b = blockIdx.y;
+  // window (hriemo_attn_probs_varlen_log_fp32): probs is a log [capacity, out_lq, out_lk], window = {slot0, n_take, 0, 0} in device
+  // memory; a sample outside it returns here -- block-uniform, in front of the first barrier and the first LDS access -- and the
+  // capacity is a launch argument, so a stale window cannot send a store past the log.  NULL: sample b's map is probs[b].
+  long slot = b;
+  if (window != nullptr) {
+    const int slot0 = window[0], n_take = window[1];
+    if (b >= n_take || slot0 < 0 || (long)slot0 + b >= (long)capacity) return;
+    slot = (long)slot0 + b;
+  }
   // the lengths are device data: clamped to what sized the buffers
   const int rq = cu_q[b], rk = cu_k[b];
   const int Lq = max(min(cu_q[b + 1] - rq, max_lq), 0), Lk = max(min(cu_k[b + 1] - rk, max_lk), 0);
@@ -613,7 +623,7 @@ __global__ __launch_bounds__(256) void attn_probs_f32_varlen_kernel(const float*
       }
     }
     if (q0 + i < out_lq) {
-      float* pp = probs + ((long)b * out_lq + q0 + i) * out_lk + k0;
+      float* pp = probs + (slot * out_lq + q0 + i) * out_lk + k0;
       const bool qv = q0 + i < Lq;
 #pragma unroll
       for (int n = 0; n < 4; ++n)
@@ -1333,31 +1343,52 @@ extern "C" int hriemo_attn_probs_f32(const float* Q, long ldq, const float* K, l
   return 0;
 }
 
-extern "C" int hriemo_attn_probs_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
-                                            const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
-                                            int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
-                                            int b_offset, hipStream_t st) {
+static int attn_probs_f32_varlen_launch(const char* who, const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q,
+                                        const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k,
+                                        int out_lq, int out_lk, int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev,
+                                        uint32_t site, int b_offset, const int* window, int capacity, hipStream_t st) {
   HRIEMO_CHECK(B > 0 && H > 0 && max_len_q > 0 && max_len_k > 0 && Q != nullptr && K != nullptr && lse != nullptr && probs != nullptr,
-               "attn_probs_f32_varlen: empty problem");
-  HRIEMO_CHECK(B <= 65535, "attn_probs_f32_varlen: B=%d exceeds the grid", B);
-  HRIEMO_CHECK(p >= 0.f && p < 1.f, "attn_probs_f32_varlen: dropout p=%f", (double)p);
-  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "attn_probs_f32_varlen: cu_seqlens_q and cu_seqlens_k must be given together");
-  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "attn_probs_f32_varlen: the map [%d, %d] is smaller than the longest sequences [%d, %d]",
+               "%s: empty problem", who);
+  HRIEMO_CHECK(B <= 65535, "%s: B=%d exceeds the grid", who, B);
+  HRIEMO_CHECK(p >= 0.f && p < 1.f, "%s: dropout p=%f", who, (double)p);
+  HRIEMO_CHECK(cu_seqlens_q != nullptr && cu_seqlens_k != nullptr, "%s: cu_seqlens_q and cu_seqlens_k must be given together", who);
+  HRIEMO_CHECK(out_lq >= max_len_q && out_lk >= max_len_k, "%s: the map [%d, %d] is smaller than the longest sequences [%d, %d]", who,
                out_lq, out_lk, max_len_q, max_len_k);
   const AttnDrop dr = make_attn_drop(p, seed, seed_dev, site, b_offset);
-  HRIEMO_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0, "attn_probs_f32_varlen: operands must be 16-byte aligned");
+  HRIEMO_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ((uintptr_t)Q % 16) == 0 && ((uintptr_t)K % 16) == 0, "%s: operands must be 16-byte aligned", who);
   const float scale = 1.0f / sqrtf((float)head_dim);
   const dim3 grid((out_lq + 63) / 64, B);
 #define CALL(HD)                                                                                                                           \
   {                                                                                                                                        \
     const int lds = 64 * (HD + 4) * 4;                                                                                                     \
     hipLaunchKernelGGL((attn_probs_f32_varlen_kernel<HD>), grid, dim3(256), lds, st, Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, H, \
-                       max_len_q, max_len_k, out_lq, out_lk, scale, dr);                                                                   \
+                       max_len_q, max_len_k, out_lq, out_lk, scale, dr, window, capacity);                                                 \
   }
   DISPATCH_HD_F32(head_dim, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("attn_probs_f32_varlen_kernel");
   return 0;
+}
+
+extern "C" int hriemo_attn_probs_f32_varlen(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                            const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
+                                            int head_dim, float p, uint64_t seed, const unsigned long long* seed_dev, uint32_t site,
+                                            int b_offset, hipStream_t st) {
+  return attn_probs_f32_varlen_launch("attn_probs_f32_varlen", Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, B, H, max_len_q,
+                                      max_len_k, out_lq, out_lk, head_dim, p, seed, seed_dev, site, b_offset, nullptr, 0, st);
+}
+
+// The same launch into an attention log (hriemo_attn_log_plan's window decides which samples land where)
+extern "C" int hriemo_attn_probs_varlen_log_fp32(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q,
+                                                const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q,
+                                                int max_len_k, int out_lq, int out_lk, int head_dim, float p, uint64_t seed,
+                                                const unsigned long long* seed_dev, uint32_t site, int b_offset, const int* window,
+                                                int capacity, hipStream_t st) {
+  HRIEMO_CHECK(window != nullptr && ((uintptr_t)window % 4) == 0, "attn_probs_varlen_log_fp32: window is int32[4] in device memory, 4-byte aligned");
+  HRIEMO_CHECK(capacity >= 1, "attn_probs_varlen_log_fp32: capacity %d", capacity);
+  HRIEMO_CHECK(((uintptr_t)probs % 4) == 0, "attn_probs_varlen_log_fp32: unaligned log");
+  return attn_probs_f32_varlen_launch("attn_probs_varlen_log_fp32", Q, ldq, K, ldk, cu_seqlens_q, cu_seqlens_k, lse, probs, B, H, max_len_q,
+                                      max_len_k, out_lq, out_lk, head_dim, p, seed, seed_dev, site, b_offset, window, capacity, st);
 }
 
 template <bool PACKED>

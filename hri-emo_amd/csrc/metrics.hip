@@ -9,6 +9,11 @@
 // and the products of the reference's inference driver (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy):
 //   hriemo_predict_log    one block behind the forward of a (captured) evaluation step: appends the batch's probabilities (sigmoid
 //                         or softmax), its per-sample mean beta and -- single-label -- its argmax to a log that needs no targets
+// and its --dump_attn --attn_max_samples K product, the attention maps of the split's first K samples:
+//   hriemo_attn_log_plan  one block at the top of a (captured) pass: moves the log's cursor and writes the window {slot0, n_take}
+//                         that the export launches of the pass read (hriemo_attn_probs_varlen_log, csrc/attention.hip; its fp32
+//                         twin, csrc/fp32mode.hip); hriemo_attn_log_close writes the closed window of a warm-up pass
+//   hriemo_attn_log_append  the window rule as a copy, for a map that a padded export produced
 // The device hands back integers only; every ratio is formed on the host in float64 (train.EpochStats.result).
 // Plain C++, vector stores only.  Built with -fno-slp-vectorize like loss.hip: the scalar tails of the one-block kernel are where
 // hipcc produces the packed fp32 operand-select form `make check-isa` forbids.
@@ -193,6 +198,53 @@ __global__ __launch_bounds__(256) void predict_log_kernel(const float* __restric
   }
 }
 
+// counters[4] (int32) of one attention log: the layout include/hriemo.h documents.  window[4] = {slot0, n_take, 0, 0}.
+enum { AL_CURSOR = 0, AL_OFFERED, AL_BATCHES, AL_SPARE };
+
+// One block of 256, recorded once per pass in front of every fork: the only writer of the cursor, the counters and the window
+// (stream order), no atomics.  It decides which samples of the pass the export launches behind it log -- slots slot0 ..
+// slot0 + n_take - 1 for samples 0 .. n_take - 1 -- and writes their lengths.  A full log takes nothing: the normal end state.
+__global__ __launch_bounds__(256) void attn_log_plan_kernel(const int* __restrict__ lens, const int* __restrict__ n_valid, int B,
+                                                            int capacity, int* __restrict__ counters, int* __restrict__ window,
+                                                            int* __restrict__ lengths) {
+  const int nv = n_valid != nullptr ? min(max(n_valid[0], 1), B) : B;
+  const int cursor = counters[AL_CURSOR];           // every thread reads it here; thread 0 writes it behind the barrier
+  const bool sane = cursor >= 0 && cursor <= capacity;          // anything else counts as full
+  const int n_take = sane ? min(capacity - cursor, nv) : 0;
+  if (lens != nullptr && lengths != nullptr)
+    for (int b = threadIdx.x; b < n_take; b += 256) {
+      lengths[(long)cursor + b] = lens[b];
+      lengths[(long)capacity + cursor + b] = lens[(long)B + b];
+    }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    window[0] = cursor;
+    window[1] = n_take;
+    window[2] = 0;
+    window[3] = 0;
+    if (n_take > 0) counters[AL_CURSOR] = cursor + n_take;
+    counters[AL_OFFERED] += nv;
+    counters[AL_BATCHES] += 1;
+  }
+}
+
+// the closed window of a pass that must leave no trace (warm-up): {0, 0, 0, 0}, nothing else touched
+__global__ __launch_bounds__(64) void attn_log_close_kernel(int* __restrict__ window) {
+  if (threadIdx.x < 4) window[threadIdx.x] = 0;
+}
+
+// The window rule as a plain copy: maps [B, map_elems] fp32 -> log[slot0 + b] for the samples inside the window.  Grid (chunks, B);
+// a block whose sample lies outside the window returns before it touches anything; the capacity is a launch argument.
+__global__ __launch_bounds__(256) void attn_log_append_kernel(const float* __restrict__ maps, int map_elems, const int* __restrict__ window,
+                                                              float* __restrict__ log, int capacity) {
+  const int b = blockIdx.y;
+  const int slot0 = window[0], n_take = window[1];
+  if (b >= n_take || slot0 < 0 || (long)slot0 + b >= (long)capacity) return;
+  const float* src = maps + (long)b * map_elems;
+  float* dst = log + ((long)slot0 + b) * map_elems;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < map_elems; e += gridDim.x * 256) dst[e] = src[e];
+}
+
 // tp / fp / fn of `p >= thr[s]` per class and threshold over the first n = clamp(cursor, 0, capacity) log entries.  Grid
 // (ceil(capacity / 256), C): one entry per thread, blocks past the cursor exit; a block adds its S * 3 integers to out[C, S, 3]
 // (zeroed by the entry in front of the launch) with integer atomics -- integer sums do not depend on the order.
@@ -322,6 +374,36 @@ extern "C" int hriemo_predict_log(const float* logits, const float* beta, int be
                        capacity, counters);
   }
   HRIEMO_LAUNCH_CHECK("predict_log_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_attn_log_plan(const int* lens, const int* n_valid, int B, int capacity, int* counters, int* window, int* lengths,
+                                    hipStream_t st) {
+  HRIEMO_CHECK(B >= 1 && capacity >= 1, "attn_log_plan: B = %d, capacity = %d (both >= 1)", B, capacity);
+  HRIEMO_CHECK(counters != nullptr && window != nullptr, "attn_log_plan: counters and window are required");
+  HRIEMO_CHECK((lens == nullptr) == (lengths == nullptr), "attn_log_plan: the lengths block [2, B] and the logged lengths [2, capacity] come together");
+  HRIEMO_CHECK(((uintptr_t)counters % 4) == 0 && ((uintptr_t)window % 4) == 0 && ((uintptr_t)lens % 4) == 0 && ((uintptr_t)lengths % 4) == 0 &&
+                   ((uintptr_t)n_valid % 4) == 0, "attn_log_plan: an int32 operand is not 4-byte aligned");
+  hipLaunchKernelGGL(attn_log_plan_kernel, dim3(1), dim3(256), 0, st, lens, n_valid, B, capacity, counters, window, lengths);
+  HRIEMO_LAUNCH_CHECK("attn_log_plan_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_attn_log_close(int* window, hipStream_t st) {
+  HRIEMO_CHECK(window != nullptr && ((uintptr_t)window % 4) == 0, "attn_log_close: window is int32[4] in device memory, 4-byte aligned");
+  hipLaunchKernelGGL(attn_log_close_kernel, dim3(1), dim3(64), 0, st, window);
+  HRIEMO_LAUNCH_CHECK("attn_log_close_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_attn_log_append(const float* maps, int B, int map_elems, const int* window, float* log, int capacity, hipStream_t st) {
+  HRIEMO_CHECK(B >= 1 && B <= 65535 && map_elems >= 1 && capacity >= 1, "attn_log_append: B = %d (1 .. 65535), map_elems = %d, capacity = %d (>= 1)",
+               B, map_elems, capacity);
+  HRIEMO_CHECK(maps != nullptr && window != nullptr && log != nullptr, "attn_log_append: maps, window and log are required");
+  HRIEMO_CHECK(((uintptr_t)maps % 4) == 0 && ((uintptr_t)log % 4) == 0 && ((uintptr_t)window % 4) == 0, "attn_log_append: an operand is not 4-byte aligned");
+  const int chunks = (map_elems + 255) / 256;
+  hipLaunchKernelGGL(attn_log_append_kernel, dim3(chunks < 64 ? chunks : 64, B), dim3(256), 0, st, maps, map_elems, window, log, capacity);
+  HRIEMO_LAUNCH_CHECK("attn_log_append_kernel");
   return 0;
 }
 

@@ -994,7 +994,7 @@ class EvalStep:
     and the loop of scripts/infer/mosei_eval_infer.py.  An eager forward is ~150 launches issued from Python; one ``eval_packed``
     is the copies of the batch into the static buffers and one replay.
 
-    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None): loss_fn(logits, beta, y, n_valid=...) as
+    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None): loss_fn(logits, beta, y, n_valid=...) as
     hri_emo_amd.train's losses; stats a ``train.EpochStats``, log a ``train.PredictionLog`` -- both are fed INSIDE the graph, one
     launch each, and never by a warm-up pass.  max_graphs: bucket graphs kept alive (default HRIEMO_VARLEN_MAX_GRAPHS), least
     recently replayed one released first.  The step has its own ``_ops.StepContext`` and its own graph pool, creates no gradient
@@ -1005,13 +1005,20 @@ class EvalStep:
     log.update -- each with n_valid read from the control block, so a batch of 1 <= n <= B utterances is served by the graphs
     captured for B (ghost utterances of length 1, ghost_plan).  No seed bump, no zero-grad, no backward, no optimizer.  The bf16 /
     MX weight shadows are re-cast inside the graph: an evaluation that follows optimizer replays sees the new weights.
-    ``return_attention`` is not part of the captured step: attention maps stay with the eager forward_packed."""
+    attn_log: a ``train.AttentionLog`` -- the attention maps of the split's first `capacity` samples from the same replays.  The
+    graph then holds, directly behind hriemo_seq_tables and so in front of every fork, the log's plan launch (hriemo_attn_log_plan
+    on the step's n_valid word and lengths block), and every attention site the log keeps exports under the window that launch
+    wrote: the varlen sites straight into their log slots (hriemo_attn_probs_varlen_log / _log_fp32), the decoder's padded
+    map -- packed tail off -- through one append.  Once the log is full those launches are blocks that read the window and exit, so
+    one family of bucket graphs serves the whole split.  Warm-up passes run with the closed window and leave the log bit-unchanged.
+    Needs set_varlen_maps(True); varlen_maps() and mfma_maps() then join the switches recorded at capture.  ``return_attention``
+    itself is not part of the captured step."""
 
-    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None):
+    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None):
         from . import _ops
         if max_graphs is not None and int(max_graphs) < 1:
             raise ValueError("EvalStep: max_graphs is a positive integer (or None)")
-        self.model, self.loss_fn, self.stats, self.log = model, loss_fn, stats, log
+        self.model, self.loss_fn, self.stats, self.log, self.attn_log = model, loss_fn, stats, log, attn_log
         self.max_graphs = None if max_graphs is None else int(max_graphs)
         self.ctx = _ops.StepContext()      # this step's capture flag / packed plan: not shared with a trainer step's
         self._pb = None                    # _PackedState: shapes, cu_seqlens buffers, the bucket graphs, the ragged front
@@ -1040,6 +1047,13 @@ class EvalStep:
                 rec.release()
         self._pb = self._static = self._modes = None
 
+    def _switches(self):
+        """the switches a replay depends on: with an attention log also the two that pick the export kernels"""
+        from . import _ops
+        if self.attn_log is None:
+            return _mode_switches()
+        return _mode_switches() + (("varlen_maps", _ops.varlen_maps()), ("mfma_maps", _ops.mfma_maps()))
+
     @_in_step_context
     def capture_packed(self, rows_a, rows_t, lengths_a, lengths_t, y=None, pad_to=None):
         """Capture the evaluation of ragged batches (data.collate_seq_packed): the arguments of DataParallelStep.capture_packed, y
@@ -1048,7 +1062,10 @@ class EvalStep:
         y=None they are prediction-only: logits, beta, z and the log.  Static state as capture_packed builds it: zero-initialised
         row sources of the largest bucket in the rows' dtype, the lengths as one int32 [2, B] block with a pinned twin, three
         cu_seqlens and three mask buffers, y, and the control block whose n_valid word the loss, the statistics and the log read.
-        The switches in force now -- precision(), gemm_mode(), the three packed-tail flags, ingest() -- are recorded."""
+        The switches in force now -- precision(), gemm_mode(), the three packed-tail flags, ingest(), with an attention log also
+        varlen_maps() and mfma_maps() -- are recorded.  With an attention log, a capture without set_varlen_maps(True) or with a
+        log whose pad_to, layer counts or num_emotions are not the model's and this call's is a ValueError that leaves the step
+        (and the log) as it was."""
         from . import _ops
         if not hasattr(self.model, "_forward_rows"):
             raise TypeError("EvalStep.capture_packed: the model has no forward_packed entry")
@@ -1066,6 +1083,12 @@ class EvalStep:
         B = len(la)
         if y is not None and y.shape[0] != B:
             raise ValueError(f"EvalStep.capture_packed: targets of shape {tuple(y.shape)} for {B} utterances")
+        if self.attn_log is not None:
+            if not _ops.varlen_maps():
+                raise ValueError("EvalStep.capture_packed: attention maps of packed rows need set_varlen_maps(True)")
+            why = self.attn_log.mismatch(self.model, (La, Lt))
+            if why is not None:
+                raise ValueError(f"EvalStep.capture_packed: the attention log does not fit: {why}")
         self.release_graph()              # a re-capture replaces the old graphs
         cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
         src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
@@ -1075,7 +1098,7 @@ class EvalStep:
         front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, same_width, partial=True, accum=1,
                              ctl=_HostBlock(ctl_words(B, 1, 1), dev))
         self._pb = _PackedState(B, La, Lt, dev, front)
-        self._modes = _mode_switches()
+        self._modes = self._switches()
         self._replay = True
         try:
             self._packed_graph(_load_ragged(self._pb, self._static, rows_a, rows_t, la, lt, y))
@@ -1085,7 +1108,8 @@ class EvalStep:
 
     def _pass(self, record):
         """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
-        stats and log (the capture pass only) -> (logits, beta, z, loss | None)"""
+        stats, log and attention log (the capture pass only; a warm-up pass runs the exports under the closed window)
+        -> (logits, beta, z, loss | None)"""
         from . import _ops
         pb = self._pb
         front = pb.front
@@ -1093,8 +1117,13 @@ class EvalStep:
         y = self._static[4]
         with torch.no_grad():
             _ops.seq_tables(front.lens.dev, pb.La, pb.Lt, rows=(seqs[0].N, seqs[1].N), cu=(pb.cu_a, pb.cu_t, pb.cu_f), masks=front.masks)
-            logits, beta, z = self.model._forward_rows(self._static[0], self._static[1], tuple(seqs), front.bool, (pb.La, pb.Lt))
             n_valid = front.ctl.dev[:1]
+            if self.attn_log is not None:
+                self.attn_log.plan(front.lens.dev, n_valid, pb.B, record=record)
+                logits, beta, z = self.model._forward_rows(self._static[0], self._static[1], tuple(seqs), front.bool, (pb.La, pb.Lt),
+                                                           attn_log=self.attn_log)
+            else:
+                logits, beta, z = self.model._forward_rows(self._static[0], self._static[1], tuple(seqs), front.bool, (pb.La, pb.Lt))
             loss = self.loss_fn(logits, beta, y, n_valid=n_valid) if (self.loss_fn is not None and y is not None) else None
             if record and self.stats is not None:
                 self.stats.update(logits, beta, y, loss, n_valid=n_valid)
@@ -1136,7 +1165,7 @@ class EvalStep:
         return rec
 
     def _check_modes(self):
-        for (name, then), (_, now) in zip(self._modes, _mode_switches()):
+        for (name, then), (_, now) in zip(self._modes, self._switches()):
             if then != now:
                 raise RuntimeError(f"EvalStep.eval_packed: the step was captured with {name} = {then!r}; it is {now!r} now -- "
                                    "capture_packed() again under the new setting, or switch back")
@@ -1189,8 +1218,9 @@ class EvalStep:
         self.model.eval()
         try:
             with torch.no_grad():
+                extra = {} if self.attn_log is None else {"attn_log": self.attn_log}
                 logits, beta, z = self.model.forward_packed(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), la, lt,
-                                                            pad_to=(pb.La, pb.Lt))
+                                                            pad_to=(pb.La, pb.Lt), **extra)
                 loss = None
                 if self.loss_fn is not None and y is not None:
                     y = y.to(dev, non_blocking=True)

@@ -67,7 +67,10 @@ class CrossModalBlock(nn.Module):
     def _fwd_pair(self, a, a32, t, t32, sa, st, need):
         """(bf16, fp32-twin) pairs in and out; returns (a, a32, t, t32, maps|None).
         sa / st: the _ops.Seq of a's and of t's rows -- padded [B, L, d] with the padding masks, or the packed valid rows
-        ([1, N, d], _ops.pack_pair), for which the attention kernels get cu_seqlens instead of padding masks."""
+        ([1, N, d], _ops.pack_pair), for which the attention kernels get cu_seqlens instead of padding masks.
+        need: a bool, or {site name: _ops.LogSite} -- the four maps then go to a train.AttentionLog and none is returned."""
+        logged = isinstance(need, dict)
+        nw = need if logged else dict.fromkeys(("audio_self", "text_self", "audio_queries_text", "text_queries_audio"), need)
         p = self.p if self.training else 0.0
         seed = _ops.next_seed(self.training and p > 0)
         s = self._site
@@ -100,12 +103,12 @@ class CrossModalBlock(nn.Module):
         # stage 1, nothing of the other branch needed yet: self-attention and, shared, ONE N = 3d GEMM that projects its output to
         # [Q of the branch's own cross-attention | K, V of the other one]
         q_a2t = q_t2a = kv_t2a = kv_a2t = slots_a = slots_t = None
-        a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], need)         # :74-81
+        a_s, a_s32, w_a = self._self(a, a32, self.self_attn_a, self.self_norm_a, sa, p, seed, s[0], nw["audio_self"])         # :74-81
         ja = join_for(a_s)
         if shared:
             q_a2t, kv_t2a, sga = self._shared_proj(a_s, self.attn_a2t, self.attn_t2a, ja)
         with tb.run():
-            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], need)     # :85-92
+            t_s, t_s32, w_t = self._self(t, t32, self.self_attn_t, self.self_norm_t, st, p, seed, s[1], nw["text_self"])     # :85-92
             jt = join_for(t_s)
             if shared:
                 q_t2a, kv_a2t, sgt = self._shared_proj(t_s, self.attn_t2a, self.attn_a2t, jt)
@@ -123,15 +126,15 @@ class CrossModalBlock(nn.Module):
                     kv_t2a = self._kv(a_s, self.attn_t2a, ja)
                 kv_a2t = self._kv(t_s, self.attn_a2t, jt)
         # stage 2: cross-attention + FFN
-        x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], need,
+        x, x32, w_a2t = self._cross(a_s, a_s32, kv(t_s, t_s32), self.attn_a2t, self.norm_a1, sa, st, p, seed, s[2], nw["audio_queries_text"],
                                     kv_a2t, ja, q_a2t, slots_a)                                                    # :98-105
         a_cm, a_cm32 = self._ffn(x, x32, self.ffn_a, self.norm_a2, p, seed, s[3], sa)                              # :106
         with tb.run():
-            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], need,
+            x, x32, w_t2a = self._cross(t_s, t_s32, kv(a_s, a_s32), self.attn_t2a, self.norm_t1, st, sa, p, seed, s[4], nw["text_queries_audio"],
                                         kv_t2a, jt, q_t2a, slots_t)                                                # :111-118
             t_cm, t_cm32 = self._ffn(x, x32, self.ffn_t, self.norm_t2, p, seed, s[5], st)                          # :119
         tb.join(t_cm, t_cm32, w_t, w_t2a)
-        maps = {"audio_self": w_a, "text_self": w_t, "audio_queries_text": w_a2t, "text_queries_audio": w_t2a} if need else None
+        maps = {"audio_self": w_a, "text_self": w_t, "audio_queries_text": w_a2t, "text_queries_audio": w_t2a} if (need and not logged) else None
         return a_cm, a_cm32, t_cm, t_cm32, maps
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
@@ -159,7 +162,8 @@ class CrossModalTransformer(nn.Module):
         outputs are unpacked as before and the layouts are the padded ones.
         raw (_ops.INGEST_ROWS): a / t are still the caller's tensors (a32 / t32 None); ONE launch each makes the pairs here, gathered
         straight into the packed rows where the encoder packs (_ops.ingest_pair).  plan: the caller's packed plan, a / t are already
-        its packed pairs (forward_packed): the encoder runs packed whatever set_varlen says."""
+        its packed pairs (forward_packed): the encoder runs packed whatever set_varlen says.
+        need: a bool, or a train.AttentionLog's encoder sites (per layer {name: _ops.LogSite}): the maps go to the log, `maps` is []."""
         all_layers_attn = []
         given = plan is not None
         B, La, Lt = (plan[0].Breal, plan[0].L, plan[1].L) if given else (a.shape[0], a.shape[1], t.shape[1])
@@ -178,11 +182,11 @@ class CrossModalTransformer(nn.Module):
                     (a, a32), (t, t32) = _ops.pack_pair(a, a32, plan[0]), _ops.pack_pair(t, t32, plan[1])
         if raw and plan is None:
             (a, a32), (t, t32) = _ops.ingest_pair(a, _ops.Seq.padded(B, La)), _ops.ingest_pair(t, _ops.Seq.padded(B, Lt))
-        for layer in self.layers:
+        for i, layer in enumerate(self.layers):
             # (padded: every layer converts the masks itself, as it always did -- a view for bool masks)
             sa, st = plan[:2] if plan is not None else (_ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))
-            a, a32, t, t32, maps = layer._fwd_pair(a, a32, t, t32, sa, st, need)
-            if need:
+            a, a32, t, t32, maps = layer._fwd_pair(a, a32, t, t32, sa, st, need[i] if isinstance(need, list) else need)
+            if maps is not None:
                 all_layers_attn.append(maps)
         if plan is not None:
             if tail and len(plan) == 3 and _ops.packed_tail():

@@ -112,7 +112,8 @@ class EmotionDecoder(nn.Module):
 
     def _fwd(self, memory16, sm, need, out_dtype):
         """sm: the _ops.Seq of the memory's rows -- a padded memory [B, L_f, d] with its [B, L_f] mask, or the fused plan of a packed
-        memory [1, N_f, d] (the K | V projections then run over the N_f packed rows)"""
+        memory [1, N_f, d] (the K | V projections then run over the N_f packed rows)
+        need: a bool, or a train.AttentionLog's decoder sites (per layer an _ops.LogSite): the maps go to the log, none is returned"""
         out, out32 = self._queries(sm.Breal)
         all_layers_attn = []
         if _ops.mx_of(memory16) is None and _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):
@@ -140,7 +141,7 @@ class EmotionDecoder(nn.Module):
             for kv in kvs:
                 _ops.share(kv, main)
         for i, layer in enumerate(self.layers):
-            out, out32, attn_map = layer._fwd_pair(out, out32, memory16, sm, need, kvs[i],
+            out, out32, attn_map = layer._fwd_pair(out, out32, memory16, sm, need[i] if isinstance(need, list) else need, kvs[i],
                                                    ready if i == 0 else None)
             if need and attn_map is not None:
                 all_layers_attn.append(attn_map)

@@ -9,7 +9,7 @@ try:
     from .. import _ops
 except ImportError:            # imported as top-level `models` (PYTHONPATH=<repo>/hri-emo_amd, the reference's import path)
     from hri_emo_amd import _ops
-from .fusion_with_emotion_decoder import FusionWithEmotionDecoder
+from .fusion_with_emotion_decoder import FusionWithEmotionDecoder, _check_attn_log
 
 
 class MoseiFusionWithEmotionDecoder(nn.Module):
@@ -33,21 +33,24 @@ class MoseiFusionWithEmotionDecoder(nn.Module):
         h_t_proj = _ops.LinearFn.apply(h_t, self.text_proj.weight, self.text_proj.bias, self._sh)     # :65
         return self.backbone(h_a_proj, h_t_proj, mask_a, mask_t, return_attention=return_attention)   # :68-79
 
-    def forward_packed(self, rows_a, rows_t, lengths_a, lengths_t, pad_to=None, return_attention=False):
+    def forward_packed(self, rows_a, rows_t, lengths_a, lengths_t, pad_to=None, return_attention=False, attn_log=None):
         """forward for ragged data (FusionWithEmotionDecoder.forward_packed): rows_a [sum(lengths_a), d_audio] and rows_t
-        [sum(lengths_t), d_text]; the two input projections run over the valid rows only"""
+        [sum(lengths_t), d_text]; the two input projections run over the valid rows only; attn_log as there"""
         la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=False)
-        if return_attention and not _ops.varlen_maps():
+        _check_attn_log(self.backbone, attn_log, return_attention, (La, Lt))
+        if (return_attention or attn_log is not None) and not _ops.varlen_maps():
             raise ValueError("forward_packed: attention maps of packed rows need set_varlen_maps(True)")
         _ops._require_gpu(rows_a)
         plan, masks = _ops.plans_from_lengths(la, lt, La, Lt, rows_a.device)
-        return self._forward_rows(rows_a, rows_t, plan, masks, (La, Lt), return_attention)
+        if attn_log is not None:
+            attn_log.plan(torch.tensor([la, lt], dtype=torch.int32).to(rows_a.device, non_blocking=True))
+        return self._forward_rows(rows_a, rows_t, plan, masks, (La, Lt), return_attention, attn_log)
 
-    def _forward_rows(self, rows_a, rows_t, plan, masks, pad, return_attention=False):
+    def _forward_rows(self, rows_a, rows_t, plan, masks, pad, return_attention=False, attn_log=None):
         """forward_packed behind its argument check (FusionWithEmotionDecoder._forward_rows): the projections run over the first
         plan.N rows of each source -- all of them for a batch's own plan; for a bucket plan the bucket's row count, a slice that is
         static per bucket graph (the caller keeps the rows between the batch's last row and plan.N finite: their gradient is zero,
         and zero times a NaN would not be)"""
         a = _ops.LinearFn.apply(rows_a[:plan[0].N], self.audio_proj.weight, self.audio_proj.bias, self._sh)
         t = _ops.LinearFn.apply(rows_t[:plan[1].N], self.text_proj.weight, self.text_proj.bias, self._sh)
-        return self.backbone._forward_rows(a, t, plan, masks, pad, return_attention)
+        return self.backbone._forward_rows(a, t, plan, masks, pad, return_attention, attn_log)

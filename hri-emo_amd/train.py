@@ -395,6 +395,221 @@ class PredictionLog:
         return out
 
 
+# ------------------------------------------------------------------------------------------------------------------- attention log
+_AL = ("cursor", "n_offered", "n_batches", "spare")             # counters[4] of hriemo_attn_log_plan
+ENCODER_SITES = ("audio_self", "text_self", "audio_queries_text", "text_queries_audio")      # the keys of a layer's map dict
+
+
+class AttentionLog:
+    """The third product of the reference's inference driver (scripts/infer/mosei_eval_infer.py --dump_attn --attn_max_samples K:
+    {split}_attentions.pt), accumulated where the forward runs: the head-averaged attention maps of the FIRST `capacity` samples of
+    a split, without an intermediate [B, Lq, Lk] tensor and without a read-back per batch.
+
+    AttentionLog(capacity, pad_to=(L_a, L_t), num_layers_fusion=2, num_layers_decoder=2, num_emotions=4, encoder=True,
+    decoder=True, device=...).  State: one fp32 [capacity, Lq, Lk] tensor per attention site -- ``encoder_maps``: per fusion layer
+    {audio_self [L_a, L_a], text_self [L_t, L_t], audio_queries_text [L_a, L_t], text_queries_audio [L_t, L_a]}; ``decoder_maps``:
+    per decoder layer [N_e, L_t] -- and ``counters`` int32 [4] {cursor, n_offered, n_batches, spare}, ``window`` int32 [4]
+    {slot0, n_take, 0, 0}, ``lengths`` int32 [2, capacity] (audio row, text row); ``nbytes`` is all of it.  encoder=False /
+    decoder=False: that half has no tensors and its exports are not launched at all.
+
+    The rule (hriemo_attn_log_plan; `plan` below is the same rule in plain torch for CPU tensors): a pass that offers nv samples
+    takes n_take = clamp(capacity - cursor, 0, nv) of them, samples 0 .. n_take-1 into slots cursor .. cursor+n_take-1, their
+    lengths beside them; cursor += n_take, n_offered += nv, n_batches += 1.  A full log takes nothing and is the normal end state.
+    A cursor outside [0, capacity] counts as full.
+
+    Fed by ``forward_packed(..., attn_log=log)`` (needs set_varlen_maps(True)) and, inside the graph, by
+    ``dp.EvalStep(..., attn_log=log)``: one plan launch at the top of the pass, then every attention site exports straight into
+    its slots.  ``append(maps, lengths, n_valid=None)`` feeds maps that exist already (the structure forward(return_attention=True)
+    returns, padded to pad_to) through the same rule.
+
+    reset(): counters to zero (the maps need no clearing: only slots in front of the cursor are ever read).
+    arrays(): reads back the first `cursor` slots only -> dict(encoder: per layer {name: float32 [n, Lq, Lk]}, decoder: per layer
+    float32 [n, N_e, L_t], lengths int32 [2, n], n_logged, n_offered).
+    as_reference(batch_size): the reference's ``collected_attns`` -- {"encoder": [per batch [per layer {name: array}]], "decoder":
+    [per batch [per layer array]]}, every batch of `batch_size` logged samples cropped to its own longest audio and text length (the
+    reference's pad-to-batch-max collate; the decoder's keys are the text length).  Two differences from the reference: the log
+    holds exactly the first `capacity` samples (the reference admits whole batches while seen < max, so it can run over), and PAD
+    query rows are zeros, as in the packed export everywhere else."""
+
+    def __init__(self, capacity, pad_to, num_layers_fusion=2, num_layers_decoder=2, num_emotions=4, encoder=True, decoder=True,
+                 device="cuda"):
+        if int(capacity) < 1:
+            raise ValueError("AttentionLog: capacity is positive")
+        try:
+            La, Lt = (int(v) for v in pad_to)
+        except (TypeError, ValueError):
+            raise ValueError("AttentionLog: pad_to = (L_a, L_t)") from None
+        if Lt < 1 or La < Lt:
+            raise ValueError(f"AttentionLog: pad_to = ({La}, {Lt}); 1 <= L_t <= L_a (the gate fuses over the text length)")
+        if not (encoder or decoder):
+            raise ValueError("AttentionLog: neither the encoder's nor the decoder's maps were asked for")
+        if int(num_layers_fusion) < 1 or int(num_layers_decoder) < 1 or int(num_emotions) < 1:
+            raise ValueError("AttentionLog: num_layers_fusion, num_layers_decoder and num_emotions are positive")
+        self.capacity, self.pad_to = int(capacity), (La, Lt)
+        self.num_layers_fusion, self.num_layers_decoder, self.num_emotions = int(num_layers_fusion), int(num_layers_decoder), int(num_emotions)
+        self.encoder, self.decoder = bool(encoder), bool(decoder)
+        self.device = torch.device(device)
+        cap, dev = self.capacity, self.device
+        # counters int32[4] | window int32[4] | lengths int32 [2, capacity]: ONE buffer, one read-back
+        self._small = torch.zeros(8 + 2 * cap, dtype=torch.int32, device=dev)
+        self.counters, self.window, self.lengths = self._views(self._small)
+        shapes = dict(zip(ENCODER_SITES, ((La, La), (Lt, Lt), (La, Lt), (Lt, La))))
+        self.encoder_maps = [{k: torch.zeros((cap,) + s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
+                             for _ in range(self.num_layers_fusion)] if self.encoder else []
+        self.decoder_maps = [torch.zeros(cap, self.num_emotions, Lt, dtype=torch.float32, device=dev)
+                             for _ in range(self.num_layers_decoder)] if self.decoder else []
+
+    @classmethod
+    def for_model(cls, model, capacity, pad_to, encoder=True, decoder=True, device=None):
+        """the log of `model` (a FusionWithEmotionDecoder, or the MOSEI wrapper around one): layer counts, num_emotions and the
+        device are the model's"""
+        core = getattr(model, "backbone", model)
+        if not (hasattr(core, "cross_modal") and hasattr(core, "emotion_decoder")):
+            raise TypeError("AttentionLog.for_model: the model has no fusion encoder / emotion decoder (FusionWithEmotionDecoder or its MOSEI wrapper)")
+        if device is None:
+            device = next(core.parameters()).device
+        return cls(capacity, pad_to, len(core.cross_modal.layers), len(core.emotion_decoder.layers), core.emotion_decoder.num_emotions,
+                   encoder=encoder, decoder=decoder, device=device)
+
+    def _views(self, buf):
+        return buf[:4], buf[4:8], buf[8:].view(2, self.capacity)
+
+    def _tensors(self):
+        return [t for layer in self.encoder_maps for t in layer.values()] + list(self.decoder_maps)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self._tensors()) + self._small.numel() * 4
+
+    def reset(self):
+        self._small[:8].zero_()
+
+    def mismatch(self, model, pad=None):
+        """None, or what keeps this log from taking `model`'s maps at the padded lengths `pad` -- as one sentence"""
+        core = getattr(model, "backbone", model)
+        if pad is not None and (int(pad[0]), int(pad[1])) != self.pad_to:
+            return f"the log's pad_to is {self.pad_to}, the forward's padded lengths are {(int(pad[0]), int(pad[1]))}"
+        have = (len(core.cross_modal.layers), len(core.emotion_decoder.layers), core.emotion_decoder.num_emotions)
+        for name, mine, its, on in (("num_layers_fusion", self.num_layers_fusion, have[0], self.encoder),
+                                    ("num_layers_decoder", self.num_layers_decoder, have[1], self.decoder),
+                                    ("num_emotions", self.num_emotions, have[2], self.decoder)):
+            if on and mine != its:
+                return f"the log's {name} is {mine}, the model's is {its}"
+        if self._small.device != next(core.parameters()).device:
+            return f"the log lives on {self._small.device}, the model on {next(core.parameters()).device}"
+        return None
+
+    # ---- the window rule
+    def plan(self, lens=None, n_valid=None, B=None, record=True):
+        """The top of one pass: lens int32 [2, B] on the log's device (None: no lengths are logged), n_valid None or a 1-element
+        int32 tensor on the device (a Python int on the CPU path too).  ONE launch (hriemo_attn_log_plan), nothing read back.
+        record=False: the closed window {0, 0} and nothing else (hriemo_attn_log_close) -- a warm-up pass."""
+        if lens is not None:
+            if lens.dim() != 2 or lens.shape[0] != 2 or lens.dtype != torch.int32 or not lens.is_contiguous():
+                raise ValueError(f"AttentionLog.plan: lengths of shape {tuple(lens.shape)} / {lens.dtype} (expected contiguous int32 [2, B])")
+            if lens.device.type != self.device.type:
+                raise ValueError(f"AttentionLog.plan: lengths on {lens.device}; the log lives on {self.device}")
+            B = lens.shape[1] if B is None else B
+            if lens.shape[1] != B:
+                raise ValueError(f"AttentionLog.plan: lengths of {lens.shape[1]} samples for B = {B}")
+        if B is None or int(B) < 1:
+            raise ValueError("AttentionLog.plan: B (or the lengths block) is required, B >= 1")
+        B = int(B)
+        if self.device.type != "cuda":
+            return self._plan_cpu(lens, n_valid, B, record)
+        from . import _lib, _ops
+        p = _ops._p
+        if not record:
+            _lib.call("hriemo_attn_log_close", p(self.window), _ops._stream())
+            return
+        nv = _ops._n_valid_word((n_valid,), self.counters)
+        _lib.call("hriemo_attn_log_plan", p(lens), p(nv), B, self.capacity, p(self.counters), p(self.window),
+                  p(self.lengths) if lens is not None else None, _ops._stream())
+
+    def _plan_cpu(self, lens, n_valid, B, record):
+        ctr, win = self.counters, self.window
+        win.zero_()
+        if not record:
+            return
+        nv = B if n_valid is None else min(max(int(n_valid), 1), B)
+        cur = int(ctr[0])
+        take = min(self.capacity - cur, nv) if 0 <= cur <= self.capacity else 0
+        if lens is not None and take > 0:
+            self.lengths[:, cur:cur + take] = lens[:, :take]
+        win[0], win[1] = cur, take
+        ctr[0] = cur + take if take > 0 else cur
+        ctr[1] += nv
+        ctr[2] += 1
+
+    def sites(self, B):
+        """(per fusion layer {name: _ops.LogSite} | None, per decoder layer _ops.LogSite | None) for a pass of B samples: what the
+        model's attention sites take in the place of their need flag"""
+        from ._ops import LogSite
+        enc = [{k: LogSite(t, self.window, self.capacity, B) for k, t in layer.items()} for layer in self.encoder_maps]
+        dec = [LogSite(t, self.window, self.capacity, B) for t in self.decoder_maps]
+        return enc or None, dec or None
+
+    def append(self, maps, lengths, n_valid=None):
+        """Maps that exist already through the window rule: maps = {"encoder": [per layer {name: [B, Lq, Lk]}], "decoder": [per
+        layer [B, N_e, L_t]]} at the log's padded lengths (the half the log does not keep is ignored), lengths int32 [2, B]."""
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(self.device).contiguous()
+        B = lengths.shape[1] if lengths.dim() == 2 else -1
+        pairs = []
+        if self.encoder:
+            if len(maps["encoder"]) != self.num_layers_fusion:
+                raise ValueError(f"AttentionLog.append: {len(maps['encoder'])} encoder layers; the log keeps {self.num_layers_fusion}")
+            pairs += [(layer[k], mine[k]) for layer, mine in zip(maps["encoder"], self.encoder_maps) for k in ENCODER_SITES]
+        if self.decoder:
+            if len(maps["decoder"]) != self.num_layers_decoder:
+                raise ValueError(f"AttentionLog.append: {len(maps['decoder'])} decoder layers; the log keeps {self.num_layers_decoder}")
+            pairs += list(zip(maps["decoder"], self.decoder_maps))
+        for src, dst in pairs:
+            if tuple(src.shape) != (B,) + tuple(dst.shape[1:]) or src.device.type != self.device.type:
+                raise ValueError(f"AttentionLog.append: a map of shape {tuple(src.shape)} on {src.device}; expected {(B,) + tuple(dst.shape[1:])} on {self.device}")
+        self.plan(lengths, n_valid, B)
+        for src, dst in pairs:
+            self._append_one(src, dst)
+
+    def _append_one(self, src, dst):
+        """one site's [B, Lq, Lk] maps into its log under the current window"""
+        src = src.detach().contiguous().float()
+        if self.device.type != "cuda":
+            slot0, take = int(self.window[0]), int(self.window[1])
+            take = min(take, src.shape[0], self.capacity - slot0) if slot0 >= 0 else 0
+            if take > 0:
+                dst[slot0:slot0 + take] = src[:take]
+            return
+        from . import _lib, _ops
+        p = _ops._p
+        _lib.call("hriemo_attn_log_append", p(src), src.shape[0], src[0].numel(), p(self.window), p(dst), self.capacity, _ops._stream())
+
+    # ---- read-back
+    def arrays(self):
+        ctr, _, lengths = self._views(self._small.cpu())
+        ctr = dict(zip(_AL, (int(v) for v in ctr.tolist())))
+        n = min(max(ctr["cursor"], 0), self.capacity)
+        host = lambda t: t[:n].cpu().numpy().copy()          # noqa: E731
+        return {"encoder": [{k: host(t) for k, t in layer.items()} for layer in self.encoder_maps],
+                "decoder": [host(t) for t in self.decoder_maps], "lengths": lengths[:, :n].numpy().copy(), "n_logged": n,
+                "n_offered": ctr["n_offered"]}
+
+    def as_reference(self, batch_size):
+        if int(batch_size) < 1:
+            raise ValueError("AttentionLog.as_reference: batch_size is positive")
+        arr = self.arrays()
+        out = {"encoder": [], "decoder": []}
+        for i in range(0, arr["n_logged"], int(batch_size)):
+            j = min(i + int(batch_size), arr["n_logged"])
+            ma, mt = int(arr["lengths"][0, i:j].max()), int(arr["lengths"][1, i:j].max())
+            crop = dict(zip(ENCODER_SITES, ((ma, ma), (mt, mt), (ma, mt), (mt, ma))))
+            if self.encoder:
+                out["encoder"].append([{k: np.ascontiguousarray(layer[k][i:j, :crop[k][0], :crop[k][1]]) for k in ENCODER_SITES}
+                                       for layer in arr["encoder"]])
+            if self.decoder:
+                out["decoder"].append([np.ascontiguousarray(t[i:j, :, :mt]) for t in arr["decoder"]])
+        return out
+
+
 def evaluate_packed(model, batches, loss_fn, stats, pad_to=None, step=None):
     """The reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
     on ragged batches: model.eval() under torch.no_grad(); for every data.collate_seq_packed batch (rows_a, lengths_a, rows_t,

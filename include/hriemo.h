@@ -428,6 +428,43 @@ int hriemo_stats_auc(const float* probs, const unsigned char* truth, int capacit
  * beta with beta_per_sample < 1, n_valid / counters / pred not 4-byte aligned. */
 int hriemo_predict_log(const float* logits, const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int kind,
                        float* probs, float* beta_mean, int* pred, int capacity, int* counters, hriemo_stream_t stream);
+/* Attention log in device memory (csrc/metrics.hip, csrc/attention.hip, csrc/fp32mode.hip): the --dump_attn --attn_max_samples K
+ * product of the same driver -- the attention maps of the FIRST `capacity` samples of a split -- from a captured evaluation whose
+ * launch list is fixed.  State, owned by the caller, counters zeroed to reset:
+ *   one fp32 [capacity, Lq, Lk] tensor per attention site (the log of that site)
+ *   lengths   int32 [2, capacity]  audio row, text row: the lengths of the logged samples (optional)
+ *   counters  int32 [4]            {cursor, n_offered, n_batches, spare}
+ *   window    int32 [4]            {slot0, n_take, 0, 0}: samples 0 .. n_take-1 of the current pass go to slots slot0 ..
+ * hriemo_attn_log_plan: ONE block, recorded once per pass in front of every export launch (in a captured step: directly behind
+ * hriemo_seq_tables, in front of every fork).  nv = clamp(*n_valid, 1, B) (NULL: B) as in hriemo_fusion_loss_n.  slot0 = cursor,
+ * n_take = clamp(capacity - cursor, 0, nv), lengths[:, slot0 + b] = lens[:, b] for b < n_take (lens: the pass's int32 [2, B]
+ * lengths block; lens and lengths are both given or both NULL), cursor += n_take, n_offered += nv, n_batches += 1.  A cursor
+ * outside [0, capacity] counts as full: n_take = 0 and only n_offered, n_batches and the window are written.  A full log is the
+ * normal end state, not an overflow.
+ * hriemo_attn_log_close: writes the window {0, 0, 0, 0} and touches nothing else -- the plan of a pass that must leave no trace
+ * (the warm-up passes of a capture): every export launch behind it exits.
+ * hriemo_attn_probs_varlen_log / hriemo_attn_probs_varlen_log_fp32: hriemo_attn_probs_varlen and hriemo_attn_probs_f32_varlen (same kernels, same
+ * arguments, same values) with probs = the site's log [capacity, out_lq, out_lk] and the window: the blocks of sample b return
+ * before their first barrier when b >= n_take, slot0 < 0 or slot0 + b >= capacity; otherwise the sample's map goes to slot
+ * slot0 + b, every element of the slot written.  capacity travels by value, so a stale window cannot send a store past the log.
+ * hriemo_attn_log_append: the same window rule as a copy of maps fp32 [B, map_elems] into log [capacity, map_elems], for a site
+ * whose map a padded export produced.
+ * Refused (non-zero, nothing launched): B or capacity < 1, map_elems < 1, a NULL or misaligned counters / window / log / maps
+ * pointer, lens without lengths or the reverse, and everything the two varlen exports refuse. */
+int hriemo_attn_log_plan(const int* lens, const int* n_valid, int B, int capacity, int* counters, int* window, int* lengths,
+                         hriemo_stream_t stream);
+int hriemo_attn_log_close(int* window, hriemo_stream_t stream);
+int hriemo_attn_log_append(const float* maps, int B, int map_elems, const int* window, float* log, int capacity,
+                           hriemo_stream_t stream);
+int hriemo_attn_probs_varlen_log(const void* Q, long ldq, const void* K, long ldk, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                 const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k, int out_lq, int out_lk,
+                                 int head_dim, float p_drop, unsigned long long seed, const unsigned long long* seed_dev, unsigned site,
+                                 int b_offset, const int* window, int capacity, hriemo_stream_t stream);
+int hriemo_attn_probs_varlen_log_fp32(const float* Q, long ldq, const float* K, long ldk, const int* cu_seqlens_q,
+                                     const int* cu_seqlens_k, const float* lse, float* probs, int B, int H, int max_len_q, int max_len_k,
+                                     int out_lq, int out_lk, int head_dim, float p_drop, unsigned long long seed,
+                                     const unsigned long long* seed_dev, unsigned site, int b_offset, const int* window, int capacity,
+                                     hriemo_stream_t stream);
 int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, int is_a, const float* dpool, const float* cnt,
                           const unsigned char* mask, void* dX, int B, int L, int d, hriemo_stream_t stream);
 /* Trainer step off the timed path, scripts/fusion/train_fusion_seq_level_decoder.py:332-334: clip_grad_norm_(5.0) +
