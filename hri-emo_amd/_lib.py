@@ -85,6 +85,7 @@ _SIGS = {
     "hriemo_unpack_rows": ("pppiiippp", "i"),
     "hriemo_ingest_rows": ("pilpiiiiipppplpp", "i"),
     "hriemo_seq_tables": ("ppiiiiippppppp", "i"),
+    "hriemo_gather_rows": ("plppiplp", "i"),
     "hriemo_dropout_bf16": ("pplifQpIlp", "i"),
     "hriemo_gemm_ln_supported": ("i", "i"),
     "hriemo_gemm_ln_fwd": ("iiiplplppppppppppffQpIlpp", "i"),

@@ -8,6 +8,9 @@ masks (True = PAD), plus what the reference leaves on the table (SURVEY.md 8f ra
 * ``length_bucketed_batches`` groups utterances of similar length so a batch's padding (= wasted rows in every
   GEMM / LayerNorm / attention of the path) stays small.
 """
+import itertools
+import weakref
+
 import torch
 
 
@@ -88,6 +91,214 @@ def length_bucketed_batches(lengths, batch_size, shuffle=True, generator=None, b
         perm = torch.randperm(len(batches), generator=generator).tolist()
         batches = [batches[i] for i in perm]
     return batches
+
+
+class DeviceFeatureStore:
+    """One split of a corpus resident on ONE device: every utterance's valid rows back to back, so that a batch is a list of utterance
+    ids and nothing but those ids and their lengths crosses to the device per step (the corpora of this model are a few GB; an
+    MI355X has 288 GB).  Built from whatever ``Dataset`` the user has (``from_samples``); ``DataParallelStep.capture_store`` /
+    ``step_store`` and ``EvalStep.capture_store`` / ``eval_store`` feed a captured step from it (one hriemo_gather_rows launch per
+    operand in front of the replay), ``fetch`` is the eager and test entry.
+
+    Device state: ``rows_a`` [N_a, d_a] and ``rows_t`` [N_t, d_t] in the store's dtype (fp32, bf16 or fp16), ``off_a`` / ``off_t``
+    int64 [N + 1] (utterance u owns the rows off[u] .. off[u + 1]), ``y`` [N, C] float or [N] int64 (single_label) and ``off_y`` =
+    0 .. N (the targets are a store in which every utterance owns one row).  Host state: ``lengths_a`` / ``lengths_t`` and
+    ``offsets_a`` / ``offsets_t`` as Python lists -- every bucket key, every plan and every check is computed from these; nothing is
+    ever read back from the device.
+
+    On a CPU ``device`` the store works with torch indexing in place of the kernel (host tests, gloo rehearsals), as
+    ``DevicePrefetcher`` passes batches through there; the captured front doors themselves need the GPU like every product path.
+    Under data parallelism every rank holds the whole store and passes its own slice of the global batch's ids."""
+
+    _DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+    def __init__(self, device, dtype=None, max_len=None, sanitize=True, loss_type="multi_label", chunk_bytes=64 << 20):
+        if dtype is not None and dtype not in self._DTYPES:
+            raise ValueError(f"DeviceFeatureStore: dtype {dtype} (float32, bfloat16 or float16)")
+        if max_len is not None and (len(max_len) != 2 or min(int(v) for v in max_len) < 1):
+            raise ValueError("DeviceFeatureStore: max_len=(L_a, L_t), both positive")
+        self.device, self.dtype, self.sanitize, self.loss_type = torch.device(device), dtype, bool(sanitize), loss_type
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())      # comparable with a module's device
+        self.max_len = None if max_len is None else (int(max_len[0]), int(max_len[1]))
+        self.chunk_bytes = int(chunk_bytes)
+        self.lengths_a, self.lengths_t, self.offsets_a, self.offsets_t = [], [], [0], [0]
+        self.rows_a = self.rows_t = self.off_a = self.off_t = self.off_y = self.y = None
+        self.widths = None                    # (d_a, d_t), fixed by the first sample
+        self.version = 0                     # bumped by every append: a step captured on an earlier version refuses the store
+        self._holders = weakref.WeakSet()     # the captured steps that read this store (capture_store .. release_graph)
+
+    @classmethod
+    def from_samples(cls, samples, device, dtype=None, max_len=None, sanitize=True, loss_type="multi_label", chunk_bytes=64 << 20):
+        """samples yields the reference datasets' items (h_a [L_a, d_a], m_a [L_a], h_t [L_t, d_t], m_t [L_t], y), the form
+        collate_seq_packed takes.  Per item, on the host: the rows with mask False are kept (the mask is honoured row by row, PAD rows
+        inside the stored length included); sanitize: nan_to_num(nan=0, posinf=0, neginf=0) as _load_feat of the MOSEI trainer;
+        max_len=(L_a, L_t): the trainers' crop_center on the kept rows -- rows (L - max_len) // 2 .. + max_len, only when L > max_len;
+        then the cast to `dtype` (default: the samples' own).  Rows are uploaded in chunks of about chunk_bytes, so host memory holds one
+        chunk beside the samples' source, never the whole split."""
+        store = cls(device, dtype, max_len, sanitize, loss_type, chunk_bytes)
+        store.append(samples)
+        return store
+
+    def __len__(self):
+        return len(self.lengths_a)
+
+    @property
+    def pad_to(self):
+        """(max L_a, max L_t) over the store: the padded lengths a step captured on it needs at least"""
+        return (max(self.lengths_a), max(self.lengths_t)) if len(self) else (0, 0)
+
+    @property
+    def nbytes(self):
+        """bytes of device memory the store holds"""
+        return sum(t.numel() * t.element_size() for t in (self.rows_a, self.rows_t, self.off_a, self.off_t, self.off_y, self.y) if t is not None)
+
+    def _item_rows(self, x, mask, limit):
+        x = x[~mask.bool()]
+        if self.sanitize:
+            x = torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)
+        if limit is not None and x.shape[0] > limit:
+            s = (x.shape[0] - limit) // 2
+            x = x[s:s + limit]
+        return x.to(self.dtype)
+
+    def append(self, samples):
+        """more utterances behind the ones held (ids continue).  Allowed only while no captured step reads the store (RuntimeError
+        otherwise: the graphs' front door has the store's addresses and sizes; release_graph() first)."""
+        if len(self._holders):
+            raise RuntimeError("DeviceFeatureStore.append: a captured step reads this store (release_graph() it first)")
+        la, lt, ys = [], [], []
+        dev_a, dev_t = ([] if self.rows_a is None else [self.rows_a]), ([] if self.rows_t is None else [self.rows_t])
+        host_a, host_t, held = [], [], 0
+
+        def flush():
+            nonlocal host_a, host_t, held
+            if host_a:
+                dev_a.append(torch.cat(host_a).to(self.device))
+                dev_t.append(torch.cat(host_t).to(self.device))
+            host_a, host_t, held = [], [], 0
+
+        for xa, ka, xt, kt, y in samples:
+            if self.dtype is None:
+                self.dtype = xa.dtype
+                if self.dtype not in self._DTYPES:
+                    raise ValueError(f"DeviceFeatureStore: samples of dtype {self.dtype} (float32, bfloat16 or float16)")
+            ra = self._item_rows(xa, ka, None if self.max_len is None else self.max_len[0])
+            rt = self._item_rows(xt, kt, None if self.max_len is None else self.max_len[1])
+            if ra.dim() != 2 or rt.dim() != 2:
+                raise ValueError("DeviceFeatureStore: a sample's features are [L, d] per modality")
+            if self.widths is None:
+                self.widths = (ra.shape[1], rt.shape[1])
+            if (ra.shape[1], rt.shape[1]) != self.widths:
+                raise ValueError(f"DeviceFeatureStore: rows of widths {(ra.shape[1], rt.shape[1])}; the store holds {self.widths}")
+            host_a.append(ra)
+            host_t.append(rt)
+            la.append(ra.shape[0])
+            lt.append(rt.shape[0])
+            ys.append(y)
+            held += ra.numel() * ra.element_size() + rt.numel() * rt.element_size()
+            if held >= self.chunk_bytes:
+                flush()
+        flush()
+        if not la:
+            return self
+        if self.loss_type == "single_label":
+            y = torch.tensor([int(v) for v in ys], dtype=torch.long)
+        else:
+            y = torch.stack(ys, dim=0)
+        y = y.to(self.device)
+        if self.y is not None and (y.dtype != self.y.dtype or y.shape[1:] != self.y.shape[1:]):
+            raise ValueError(f"DeviceFeatureStore: targets of shape {tuple(y.shape[1:])} / {y.dtype}; the store holds {tuple(self.y.shape[1:])} / {self.y.dtype}")
+        # one concatenation per append: the device briefly holds the old rows and the new ones twice
+        self.rows_a = dev_a[0] if len(dev_a) == 1 else torch.cat(dev_a)
+        self.rows_t = dev_t[0] if len(dev_t) == 1 else torch.cat(dev_t)
+        self.y = y if self.y is None else torch.cat([self.y, y])
+        for lens, offs, new in ((self.lengths_a, self.offsets_a, la), (self.lengths_t, self.offsets_t, lt)):
+            for v in new:
+                lens.append(v)
+                offs.append(offs[-1] + v)
+        self.off_a = torch.tensor(self.offsets_a, dtype=torch.int64).to(self.device)
+        self.off_t = torch.tensor(self.offsets_t, dtype=torch.int64).to(self.device)
+        self.off_y = torch.arange(len(self) + 1, dtype=torch.int64).to(self.device)
+        self.version += 1
+        return self
+
+    # ---- host arithmetic
+    def check_ids(self, ids):
+        """-> ids as a list of Python ints; ValueError for an empty list or an id outside [0, len(store)) -- checked here, on the host,
+        before anything is enqueued: the gather kernel cannot know how long the store is"""
+        ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+        if not ids:
+            raise ValueError("DeviceFeatureStore: an empty id list")
+        n = len(self)
+        bad = [v for v in ids if v < 0 or v >= n]
+        if bad:
+            raise ValueError(f"DeviceFeatureStore: utterance id {bad[0]} outside [0, {n})")
+        return ids
+
+    def plan_words(self, ids, stride):
+        """The plan block of a batch, as the host writes it from its own lengths: three plans {ids[n], dst_cu[n + 1]} -- audio rows,
+        text rows, targets (one row per utterance) -- `stride` >= 2 n + 1 int32 words apart, zero padded: what hriemo_gather_rows
+        reads for each of the three operands.  ids: checked (check_ids)."""
+        n = len(ids)
+        if stride < 2 * n + 1:
+            raise ValueError(f"DeviceFeatureStore.plan_words: {n} ids do not fit a plan of {stride} words")
+        words = []
+        for lens in ([self.lengths_a[i] for i in ids], [self.lengths_t[i] for i in ids], [1] * n):
+            words += ids + list(itertools.accumulate(lens, initial=0)) + [0] * (stride - 2 * n - 1)
+        return words
+
+    def gather_into(self, plan_dev, stride, n, dst_a, rows_a, dst_t, rows_t, dst_y):
+        """The batch of a plan block on the device (plan_words(ids, stride), n = len(ids)) into three destinations on the current
+        stream: rows 0 .. rows_a of dst_a and 0 .. rows_t of dst_t (the batch's rows, zeros behind them), the first n rows of dst_y
+        (None: no targets wanted).  One hriemo_gather_rows launch each; no allocation, no synchronisation."""
+        from . import _lib
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        base = plan_dev.data_ptr()
+        for p, (src, off, dst, rows) in enumerate(((self.rows_a, self.off_a, dst_a, rows_a), (self.rows_t, self.off_t, dst_t, rows_t),
+                                                   (self.y, self.off_y, dst_y, n))):
+            if dst is None:
+                continue
+            row_bytes = src[0].numel() * src.element_size()
+            if dst.dtype != src.dtype or dst[0].numel() * dst.element_size() != row_bytes or dst.shape[0] < rows or not dst.is_contiguous():
+                raise ValueError(f"DeviceFeatureStore.gather_into: destination {tuple(dst.shape)} / {dst.dtype} for {rows} rows of "
+                                 f"{tuple(src.shape[1:])} / {src.dtype}")
+            _lib.call("hriemo_gather_rows", src.data_ptr(), row_bytes, off.data_ptr(), base + 4 * p * stride, n, dst.data_ptr(), rows, stream)
+
+    # ---- batches
+    def fetch(self, ids):
+        """-> (rows_a, lengths_a, rows_t, lengths_t, y): exactly what collate_seq_packed gives for the samples `ids` (after the
+        store's mask / sanitise / crop / cast), as fresh tensors with rows and targets on the store's device.  The two lengths
+        tensors stay int64 HOST tensors, as the collate makes them: every consumer (forward_packed, step_packed, eval_packed) wants
+        them on the host and refuses device lengths.  On a GPU the rows come through hriemo_gather_rows, on a CPU device through
+        torch indexing."""
+        ids = self.check_ids(ids)
+        la, lt = [self.lengths_a[i] for i in ids], [self.lengths_t[i] for i in ids]
+        len_a, len_t = torch.tensor(la, dtype=torch.int64), torch.tensor(lt, dtype=torch.int64)
+        if self.device.type != "cuda":
+            rows_a = torch.cat([self.rows_a[self.offsets_a[i]:self.offsets_a[i + 1]] for i in ids], dim=0)
+            rows_t = torch.cat([self.rows_t[self.offsets_t[i]:self.offsets_t[i + 1]] for i in ids], dim=0)
+            return rows_a, len_a, rows_t, len_t, self.y[torch.tensor(ids, dtype=torch.int64)]
+        n, na, nt = len(ids), sum(la), sum(lt)
+        rows_a = torch.empty((max(na, 1),) + tuple(self.rows_a.shape[1:]), dtype=self.dtype, device=self.device)
+        rows_t = torch.empty((max(nt, 1),) + tuple(self.rows_t.shape[1:]), dtype=self.dtype, device=self.device)
+        y = torch.empty((n,) + tuple(self.y.shape[1:]), dtype=self.y.dtype, device=self.device)
+        stride = 2 * n + 1
+        plan = torch.tensor(self.plan_words(ids, stride), dtype=torch.int32).to(self.device)
+        self.gather_into(plan, stride, n, rows_a, rows_a.shape[0], rows_t, rows_t.shape[0], y)
+        return rows_a[:na], len_a, rows_t[:nt], len_t, y
+
+    def batches(self, batch_size, shuffle=True, generator=None, bucket_mult=50):
+        """The id lists of one epoch: every id exactly once, the short last batch kept.  Through length_bucketed_batches on the audio
+        lengths (batches of similar length; their row counts then repeat, and with them the bucket graphs of a captured step);
+        bucket_mult=0: plain consecutive (shuffle=False) or shuffled slices."""
+        if int(batch_size) < 1:
+            raise ValueError("DeviceFeatureStore.batches: batch_size is positive")
+        if bucket_mult:
+            return length_bucketed_batches(self.lengths_a, int(batch_size), shuffle, generator, bucket_mult)
+        n = len(self)
+        order = torch.randperm(n, generator=generator).tolist() if shuffle else list(range(n))
+        return [order[k:k + int(batch_size)] for k in range(0, n, int(batch_size))]
 
 
 class DevicePrefetcher:

@@ -72,7 +72,7 @@ def ghost_plan(la, lt, B, La, Lt):
     """A short batch of n = len(la) <= B utterances, as a captured step of B utterances sees it (capture_packed(partial_batches=True)):
     -> (audio lengths, text lengths, bucket key, (own audio rows, own text rows)).  The B - n missing utterances are ghosts of length
     1 in both modalities -- the shortest sequence every kernel of the step accepts; their rows lie directly behind the batch's own
-    rows, inside the region _load_packed zeroes up to the bucket's end, and the bucket key counts them.  n == B: the batch itself."""
+    rows, inside the region _load_ragged's fill zeroes up to the bucket's end, and the bucket key counts them.  n == B: the batch itself."""
     own = (sum(la), sum(lt))
     ghosts = [1] * (B - len(la))
     la, lt = list(la) + ghosts, list(lt) + ghosts
@@ -397,25 +397,103 @@ class _PackedState:
         return getattr(self, name)
 
 
-def _load_ragged(pb, static, rows_a, rows_t, la, lt, y, ctl=None):
+def _load_ragged(pb, static, fill, la, lt, ctl=None):
     """A checked ragged batch into the static state of a step captured from ragged batches (static = [src_a, src_t, -, -, y]) -> its
-    bucket key: the rows to the head of each source, zeros from there to the bucket's end (the MOSEI projections read every bucket
-    row), the lengths as one [2, B] block through the pinned twin, y (None: the step holds no targets).  A short batch is completed
-    with ghosts first (ghost_plan).  ctl = (first, last): the step-control block goes up with n_valid = the batch's own number of
-    utterances, by the protocol of the lengths block."""
+    bucket key.  What every front door shares lives here: a short batch is completed with ghosts first (ghost_plan); then
+    ``fill(static, n_utt, (own audio rows, own text rows), key)`` -- _caller_rows or _StoreFeed.fill -- puts the rows at the head of
+    each source with zeros from there to the bucket's end (the MOSEI projections read every bucket row) and the targets into the first
+    n_utt rows of y; then the lengths go up as one [2, B] block through the pinned twin.  ctl = (first, last): the step-control block
+    goes up with n_valid = the batch's own number of utterances, by the protocol of the lengths block."""
     front = pb.front
     n_utt = len(la)
-    la, lt, key, (rows_own_a, rows_own_t) = ghost_plan(la, lt, pb.B, pb.La, pb.Lt)
-    for src, rows, n, n_rows in ((static[0], rows_a, rows_own_a, key[0]), (static[1], rows_t, rows_own_t, key[1])):
-        if rows.data_ptr() != src.data_ptr():
-            src[:n].copy_(rows, non_blocking=True)
-        src[n:n_rows].zero_()
+    la, lt, key, own = ghost_plan(la, lt, pb.B, pb.La, pb.Lt)
+    fill(static, n_utt, own, key)
     front.lens.upload([la, lt])
     if front.ctl is not None:
         front.ctl.upload(ctl_words(n_utt, *(ctl if ctl is not None else (1, 1))))
-    if y is not None and y.data_ptr() != static[4].data_ptr():
-        static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
     return key
+
+
+def _caller_rows(rows_a, rows_t, y):
+    """the fill of a batch whose rows the caller holds (capture_packed / step_packed / eval_packed): copies, then the zero tail;
+    y None: the step holds no targets"""
+    def fill(static, n_utt, own, key):
+        for src, rows, n, n_rows in ((static[0], rows_a, own[0], key[0]), (static[1], rows_t, own[1], key[1])):
+            if rows.data_ptr() != src.data_ptr():
+                src[:n].copy_(rows, non_blocking=True)
+            src[n:n_rows].zero_()
+        if y is not None and y.data_ptr() != static[4].data_ptr():
+            static[4][:n_utt].copy_(y, non_blocking=True)      # a short batch: rows of an earlier batch stay behind it (ghosts)
+    return fill
+
+
+class _StoreFeed:
+    """what capture_store adds in front of the ragged front door: the data.DeviceFeatureStore the step reads and its version at
+    capture, and the plan block -- int32 [3, 2B + 1]: {ids[n], dst_cu[n + 1]} for the audio rows, the text rows and the targets, zero
+    padded -- with its pinned twin (_HostBlock), uploaded once per batch.  The gather itself is three eager launches on the step's
+    stream in front of the replay; the captured graphs do not know where their static rows came from.  While the feed is alive the
+    store refuses append()."""
+    __slots__ = ("store", "version", "B", "pad", "stride", "block", "__weakref__")
+
+    def __init__(self, store, B, pad, device):
+        self.store, self.version, self.B, self.pad = store, store.version, int(B), (int(pad[0]), int(pad[1]))
+        self.stride = 2 * self.B + 1
+        self.block = _HostBlock([0] * (3 * self.stride), device)
+        store._holders.add(self)
+
+    def close(self):
+        self.store._holders.discard(self)
+
+    def batch(self, ids, partial, who):
+        """every host check of a batch of ids -> (ids, audio lengths, text lengths) as lists.  RuntimeError: the store changed since
+        the capture.  ValueError: an id outside the store, more than B utterances (or another number than B without
+        partial_batches), a length outside [1, L].  Nothing has been enqueued when it raises."""
+        st = self.store
+        if st.version != self.version:
+            raise RuntimeError(f"{who}: the store changed since the capture (append): capture_store() again")
+        ids = st.check_ids(ids)
+        n = len(ids)
+        if n > self.B:
+            raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds at most B = {self.B}")
+        if n != self.B and not partial:
+            raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds B = {self.B} (drop the batch, run it with "
+                             "use_graph(False), or capture with partial_batches=True)")
+        return (ids,) + _store_batch(st, ids, self.pad, who)
+
+    def fill(self, ids, targets=True):
+        """the fill of a checked batch of ids (_load_ragged): one plan upload, one hriemo_gather_rows launch per operand -- the rows to
+        the head of each source and zeros up to the bucket's end in the same launch, the targets into the first n rows of y"""
+        def fill(static, n_utt, own, key):
+            self.block.upload(self.store.plan_words(ids, self.stride))
+            self.store.gather_into(self.block.dev, self.stride, n_utt, static[0], key[0], static[1], key[1], static[4] if targets else None)
+        return fill
+
+
+def _store_batch(store, ids, pad, who):
+    """checked ids -> (audio lengths, text lengths) of the batch from the store's host lists; ValueError for a length outside [1, L]"""
+    la, lt = [store.lengths_a[i] for i in ids], [store.lengths_t[i] for i in ids]
+    for name, ls, L in (("audio", la, pad[0]), ("text", lt, pad[1])):
+        bad = [v for v in ls if v < 1 or v > L]
+        if bad:
+            raise ValueError(f"{who}: {name} length {bad[0]} outside [1, {L}]")
+    return la, lt
+
+
+def _store_capture_facts(who, model, store, ids, pad_to):
+    """the host checks capture_store shares between the trainer and the evaluation step -> (ids, (La, Lt))"""
+    from .data import DeviceFeatureStore
+    if not isinstance(store, DeviceFeatureStore):
+        raise TypeError(f"{who}: store is a data.DeviceFeatureStore")
+    ids = store.check_ids(ids)
+    dev = next(model.parameters()).device
+    if store.device != dev:
+        raise ValueError(f"{who}: the store lives on {store.device}, the model on {dev}")
+    La, Lt = (int(v) for v in (pad_to if pad_to is not None else store.pad_to))
+    if Lt > La:
+        raise RuntimeError(f"{who}: L_t={Lt} > L_a={La}: the gate fuses over the text length and needs L_a >= L_t")
+    if not hasattr(model, "audio_proj") and store.widths[0] != store.widths[1]:
+        raise ValueError(f"{who}: the store's rows differ in width {store.widths}")
+    return ids, (La, Lt)
 
 
 def _record_graph(dev, seqs, pool, warm, body, warmed=None, settle=0.0):
@@ -502,6 +580,7 @@ class DataParallelStep:
         self._stats = None            # train.EpochStats fed by every executed (micro-)step (attach_stats)
         self._stats_scale = 1.0
         self._outputs = None          # with statistics attached: what the latest _fwd_bwd pass hands to _update_stats
+        self._feed = None             # _StoreFeed of a step captured on a data.DeviceFeatureStore (capture_store)
 
     @property
     def captured(self):
@@ -511,6 +590,11 @@ class DataParallelStep:
     @property
     def _replaying(self):
         return self._replay and self.captured
+
+    @property
+    def store(self):
+        """the data.DeviceFeatureStore this step was captured on (capture_store) and step_store's ids refer to; None otherwise"""
+        return None if self._feed is None else self._feed.store
 
     def set_global_batch(self, global_batch):
         lo, hi = shard_bounds(global_batch, self.rank, self.world)
@@ -726,36 +810,93 @@ class DataParallelStep:
         1/k loss scale stays the caller's, by value (``mosei_step_loss(grad_accum=k)``): it is constant per run.
         ``flush_accumulated()`` closes a group that the end of an epoch cut short."""
         from . import _ops
-        if not hasattr(self.model, "_forward_rows"):
-            raise TypeError("capture_packed: the model has no forward_packed entry")
-        if int(grad_accum) != grad_accum or grad_accum < 1:
-            raise ValueError(f"capture_packed: grad_accum = {grad_accum!r} (an integer >= 1)")
-        if partial_batches and not _accepts_n_valid(self.loss_fn):
-            raise TypeError("capture_packed(partial_batches=True): loss_fn takes no n_valid= keyword -- the ghost utterances of a short "
-                            "batch must stay out of the loss (hri_emo_amd.train's losses accept it)")
+        self._check_ragged_capture("capture_packed", partial_batches, grad_accum)
         same_width = not hasattr(self.model, "audio_proj")
-        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
+        la, lt, pad = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
         if pad_to is None:
             raise ValueError("capture_packed: pad_to=(L_a, L_t) is required")
         dev = next(self.model.parameters()).device
+        self._capture_ragged("capture_packed", (rows_a.shape[1], rows_t.shape[1]), rows_a.dtype, y.to(dev, copy=True), la, lt, pad,
+                             lambda: self._load_packed(rows_a, rows_t, la, lt, y), optimizer, collectives, partial_batches, grad_accum)
+
+    def _check_ragged_capture(self, entry, partial_batches, grad_accum):
+        if not hasattr(self.model, "_forward_rows"):
+            raise TypeError(f"{entry}: the model has no forward_packed entry")
+        if int(grad_accum) != grad_accum or grad_accum < 1:
+            raise ValueError(f"{entry}: grad_accum = {grad_accum!r} (an integer >= 1)")
+        if partial_batches and not _accepts_n_valid(self.loss_fn):
+            raise TypeError(f"{entry}(partial_batches=True): loss_fn takes no n_valid= keyword -- the ghost utterances of a short "
+                            "batch must stay out of the loss (hri_emo_amd.train's losses accept it)")
+
+    def _capture_ragged(self, entry, widths, dtype, y_static, la, lt, pad, load, optimizer, collectives, partial_batches, grad_accum,
+                        make_feed=None):
+        """what capture_packed and capture_store share behind their checks: the old step goes, the static state is built (row sources
+        of the largest bucket, zero-initialised; lengths block; masks; control block; y_static), the first batch is loaded by
+        load() -> bucket key and its bucket graph is captured.  make_feed(device) -> the _StoreFeed of a step that reads a store, made
+        after the old step (and its feed) has gone."""
+        from . import _ops
+        dev = next(self.model.parameters()).device
         _ops._require_gpu(next(self.model.parameters()))
-        self._begin_capture("capture_packed", optimizer, collectives, packed=True)
+        self._begin_capture(entry, optimizer, collectives, packed=True)
         self._micro = 0
-        B = len(la)
+        B, (La, Lt) = len(la), pad
         cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
-        src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
-        src_t = torch.zeros(cap_t, rows_t.shape[1], dtype=rows_t.dtype, device=dev)
-        self._static = [src_a, src_t, None, None, y.to(dev, copy=True)]
+        src_a = torch.zeros(cap_a, widths[0], dtype=dtype, device=dev)
+        src_t = torch.zeros(cap_t, widths[1], dtype=dtype, device=dev)
+        self._static = [src_a, src_t, None, None, y_static]
         masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
         ctl = _HostBlock(ctl_words(B, 1, 1), dev) if (partial_batches or grad_accum > 1) else None
-        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, same_width, partial_batches, grad_accum, ctl)
+        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, not hasattr(self.model, "audio_proj"), partial_batches, grad_accum, ctl)
         self._pb = _PackedState(B, La, Lt, dev, front)
-        self._packed_graph(self._load_packed(rows_a, rows_t, la, lt, y))
+        try:
+            if make_feed is not None:
+                self._feed = make_feed(dev)
+            self._packed_graph(load())
+        except BaseException:
+            self.release_graph()          # a failed capture leaves no graph behind -- and no feed that would keep the store from growing
+            raise
         self._end_capture()
 
-    def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
-        """a checked ragged batch into the static state -> its bucket key (_load_ragged)"""
-        return _load_ragged(self._pb, self._static, rows_a, rows_t, la, lt, y, ctl)
+    @_in_step_context
+    def capture_store(self, store, ids, pad_to=None, optimizer=None, collectives=False, partial_batches=False, grad_accum=1):
+        """capture_packed() for batches that are lists of utterance ids of a ``data.DeviceFeatureStore`` on this step's device: the
+        batch `ids` fixes B, pad_to = (L_a, L_t) defaults to ``store.pad_to`` (the store's longest utterances).  Everything behind the
+        static row sources is capture_packed unchanged -- bucket graphs and their LRU cap, ghosts and the control block
+        (partial_batches), grad_accum, optimizer=DeviceAdamW, attach_stats, fp32 and mx_fp8 modes -- and the captured graphs hold the
+        launches they hold after capture_packed, in the same order.  What changes is how a batch reaches the static state
+        (``step_store``): one upload of the plan block {ids, dst_cu} x 3 (written by the host from the store's host lengths, pinned
+        twin like the lengths block) and one hriemo_gather_rows launch per operand -- audio rows, text rows, targets -- on the
+        step's stream in front of the replay; the kernel writes the zero tail up to the bucket's end as well.  No row crosses
+        PCIe, nothing is read back, no device memory is allocated.
+        While the step is captured the store refuses ``append``.  Data parallel: every rank holds the whole store (a few GB) and
+        passes ITS slice of the global batch's ids (``shard_bounds``); ``set_batch_offset`` / ``set_global_batch`` are untouched."""
+        self._check_ragged_capture("capture_store", partial_batches, grad_accum)
+        ids, pad = _store_capture_facts("capture_store", self.model, store, ids, pad_to)
+        B = len(ids)
+        la, lt = _store_batch(store, ids, pad, "capture_store")        # before the old step is given up
+        dev = next(self.model.parameters()).device
+        y_static = torch.zeros((B,) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev)
+        self._capture_ragged("capture_store", store.widths, store.dtype, y_static, la, lt, pad, lambda: self._load_store(ids, la, lt), optimizer,
+                             collectives, partial_batches, grad_accum, make_feed=lambda d: _StoreFeed(store, B, pad, d))
+
+    @_in_step_context
+    def step_store(self, ids):
+        """One trainer step on the utterances `ids` of the captured store (capture_store): step_packed with "copy the caller's rows"
+        replaced by "gather by id".  The ids ALWAYS refer to the store given to capture_store -- ``self.store``; a caller that
+        keeps several stores (train / val / test) keeps one step per store or captures again, and checks ``step.store is store``
+        where the two could be confused (train.evaluate_store does).  Host checks first -- the store as it was at capture (RuntimeError after an append), every id
+        inside it, n <= B (n == B without partial_batches), lengths inside pad_to (ValueError) -- and nothing is enqueued when one
+        fails.  Then: plan block up, at most three hriemo_gather_rows launches, lengths (and control) block up, replay.  After
+        use_graph(False) this is the eager step_packed on ``store.fetch(ids)``.  Micro-steps, flush_accumulated() and the
+        optimizer in the graph behave as after capture_packed."""
+        feed = self._feed
+        if feed is None or self._pb is None or self._pb.front is None:
+            raise RuntimeError("step_store needs capture_store() first")
+        ids, la, lt = feed.batch(ids, self._pb.front.partial or not self._replaying, "step_store")
+        if self._replaying:
+            return self._replay_ragged(lambda ctl: self._load_store(ids, la, lt, ctl=ctl))
+        rows_a, _, rows_t, _, y = feed.store.fetch(ids)
+        return self._eager_ragged(rows_a, rows_t, la, lt, y)
 
     @_in_step_context
     def step_packed(self, rows_a, rows_t, lengths_a, lengths_t, y):
@@ -772,7 +913,6 @@ class DataParallelStep:
             raise RuntimeError("step_packed needs capture_packed() first")
         B, pad = pb.B, (pb.La, pb.Lt)
         la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front.same_width)
-        first, last = micro_flags(self._micro, front.accum)
         if self._replaying:
             n = len(la)
             if n != B and not front.partial:
@@ -787,24 +927,45 @@ class DataParallelStep:
             if tuple(y.shape) != want:
                 raise ValueError(f"step_packed: targets of shape {tuple(y.shape)}; captured with {tuple(self._static[4].shape)}"
                                  + (f", this batch needs {want}" if n != B else ""))
-            if self._optimizer is not None and last:
-                # the update of this group reads lr & co. as the scheduler left them after the previous update; a held micro-step
-                # reads none of them (the finalize returns in front of hyper[], the update kernel in front of everything)
-                self._optimizer._upload_hyper()
-            key = self._load_packed(rows_a, rows_t, la, lt, y, ctl=(first, last))
-            rec = self._packed_graph(key)                 # captures on the static state (already this batch) if the bucket is new
-            rec.graph.replay()
-            self._micro = 0 if last else self._micro + 1
-            if last:
-                self._after_replay()
-            return rec.loss
+            return self._replay_ragged(lambda ctl: self._load_packed(rows_a, rows_t, la, lt, y, ctl=ctl))
+        return self._eager_ragged(rows_a, rows_t, la, lt, y)
+
+    def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
+        """a checked ragged batch whose rows the caller holds into the static state -> its bucket key (_load_ragged)"""
+        return _load_ragged(self._pb, self._static, _caller_rows(rows_a, rows_t, y), la, lt, ctl)
+
+    def _load_store(self, ids, la, lt, ctl=None):
+        """a checked batch of ids of the captured store into the static state -> its bucket key (_load_ragged)"""
+        return _load_ragged(self._pb, self._static, self._feed.fill(ids), la, lt, ctl)
+
+    def _replay_ragged(self, load):
+        """a checked batch through the captured step, for every ragged front door: hyper-parameters up when this micro-step carries
+        the update, the batch into the static state (load(ctl) -> bucket key: _load_packed or _load_store), the bucket graph
+        picked -- or captured on the spot -- and replayed"""
+        first, last = micro_flags(self._micro, self._pb.front.accum)
+        if self._optimizer is not None and last:
+            # the update of this group reads lr & co. as the scheduler left them after the previous update; a held micro-step
+            # reads none of them (the finalize returns in front of hyper[], the update kernel in front of everything)
+            self._optimizer._upload_hyper()
+        key = load((first, last))
+        rec = self._packed_graph(key)                 # captures on the static state (already this batch) if the bucket is new
+        rec.graph.replay()
+        self._micro = 0 if last else self._micro + 1
+        if last:
+            self._after_replay()
+        return rec.loss
+
+    def _eager_ragged(self, rows_a, rows_t, la, lt, y):
+        """use_graph(False): the eager forward_packed step on a checked ragged batch"""
+        pb = self._pb
+        first, last = micro_flags(self._micro, pb.front.accum)
         dev = self._static[0].device
         was = self.buckets.suspended
         if not last:
             self.buckets.suspended = True                 # as step_accumulated: the exchange belongs to the group's last backward
         try:
             loss = self._fwd_bwd(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), None, None, y.to(dev, non_blocking=True),
-                                 zero=first, ragged=(la, lt, pad))
+                                 zero=first, ragged=(la, lt, (pb.La, pb.Lt)))
         finally:
             self.buckets.suspended = was
         self._update_stats()
@@ -925,6 +1086,9 @@ class DataParallelStep:
             for rec in ([self._record] if self._record is not None else self._pb.graphs.values()):
                 rec.release()
             self._record = self._pb = self._optimizer = None
+        if self._feed is not None:
+            self._feed.close()            # the store may grow again
+            self._feed = None
 
     def use_graph(self, on):
         """Switch between the captured replay (gradient exchange after it) and eager launches (exchange from the
@@ -1024,6 +1188,7 @@ class EvalStep:
         self._pb = None                    # _PackedState: shapes, cu_seqlens buffers, the bucket graphs, the ragged front
         self._static = None                # [src_a, src_t, None, None, y | None]: the layout _load_ragged fills
         self._modes = None                 # _mode_switches() at capture
+        self._feed = None                  # _StoreFeed of a step captured on a data.DeviceFeatureStore (capture_store)
         self._replay = True
 
     @property
@@ -1034,6 +1199,11 @@ class EvalStep:
     @property
     def _replaying(self):
         return self._replay and self.captured
+
+    @property
+    def store(self):
+        """the data.DeviceFeatureStore this step was captured on (capture_store) and eval_store's ids refer to; None otherwise"""
+        return None if self._feed is None else self._feed.store
 
     def use_graph(self, on):
         """False: eval_packed is the eager forward_packed evaluation (same outputs, same updates of stats and log)"""
@@ -1046,6 +1216,9 @@ class EvalStep:
             for rec in self._pb.graphs.values():
                 rec.release()
         self._pb = self._static = self._modes = None
+        if self._feed is not None:
+            self._feed.close()             # the store may grow again
+            self._feed = None
 
     def _switches(self):
         """the switches a replay depends on: with an attention log also the two that pick the export kernels"""
@@ -1075,7 +1248,7 @@ class EvalStep:
         if self.stats is not None and (self.loss_fn is None or y is None):
             raise ValueError("EvalStep.capture_packed: statistics need a loss_fn and targets (prediction-only graphs feed the log)")
         same_width = not hasattr(self.model, "audio_proj")
-        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
+        la, lt, pad = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
         if pad_to is None:
             raise ValueError("EvalStep.capture_packed: pad_to=(L_a, L_t) is required")
         dev = next(self.model.parameters()).device
@@ -1083,28 +1256,93 @@ class EvalStep:
         B = len(la)
         if y is not None and y.shape[0] != B:
             raise ValueError(f"EvalStep.capture_packed: targets of shape {tuple(y.shape)} for {B} utterances")
+        self._check_attn_log("capture_packed", pad)
+        self._capture_ragged((rows_a.shape[1], rows_t.shape[1]), rows_a.dtype, None if y is None else y.to(dev, copy=True), la, lt, pad,
+                             lambda: _caller_rows(rows_a, rows_t, y))
+
+    def _check_attn_log(self, entry, pad):
+        from . import _ops
         if self.attn_log is not None:
             if not _ops.varlen_maps():
-                raise ValueError("EvalStep.capture_packed: attention maps of packed rows need set_varlen_maps(True)")
-            why = self.attn_log.mismatch(self.model, (La, Lt))
+                raise ValueError(f"EvalStep.{entry}: attention maps of packed rows need set_varlen_maps(True)")
+            why = self.attn_log.mismatch(self.model, pad)
             if why is not None:
-                raise ValueError(f"EvalStep.capture_packed: the attention log does not fit: {why}")
+                raise ValueError(f"EvalStep.{entry}: the attention log does not fit: {why}")
+
+    def _capture_ragged(self, widths, dtype, y_static, la, lt, pad, make_fill, make_feed=None):
+        """what capture_packed and capture_store share behind their checks: the old graphs go, the static state is built, the first
+        batch is loaded by make_fill()'s fill (_load_ragged) and its bucket graph is captured.  make_feed(device) -> the _StoreFeed
+        of a step that reads a store."""
+        dev = next(self.model.parameters()).device
         self.release_graph()              # a re-capture replaces the old graphs
+        B, (La, Lt) = len(la), pad
         cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
-        src_a = torch.zeros(cap_a, rows_a.shape[1], dtype=rows_a.dtype, device=dev)
-        src_t = torch.zeros(cap_t, rows_t.shape[1], dtype=rows_t.dtype, device=dev)
-        self._static = [src_a, src_t, None, None, None if y is None else y.to(dev, copy=True)]
+        src_a = torch.zeros(cap_a, widths[0], dtype=dtype, device=dev)
+        src_t = torch.zeros(cap_t, widths[1], dtype=dtype, device=dev)
+        self._static = [src_a, src_t, None, None, y_static]
         masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
-        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, same_width, partial=True, accum=1,
+        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, not hasattr(self.model, "audio_proj"), partial=True, accum=1,
                              ctl=_HostBlock(ctl_words(B, 1, 1), dev))
         self._pb = _PackedState(B, La, Lt, dev, front)
         self._modes = self._switches()
         self._replay = True
         try:
-            self._packed_graph(_load_ragged(self._pb, self._static, rows_a, rows_t, la, lt, y))
+            if make_feed is not None:
+                self._feed = make_feed(dev)
+            self._packed_graph(_load_ragged(self._pb, self._static, make_fill(), la, lt))
         except BaseException:
             self.release_graph()
             raise
+
+    @_in_step_context
+    def capture_store(self, store, ids, pad_to=None):
+        """capture_packed() for batches that are lists of utterance ids of a ``data.DeviceFeatureStore`` on the model's device, built as
+        DataParallelStep.capture_store is: `ids` fixes B, pad_to defaults to ``store.pad_to``; the graphs are those of capture_packed
+        (with the store's targets when the step has a loss_fn, prediction-only without); ``eval_store(ids)`` uploads one plan block
+        and launches hriemo_gather_rows once per operand in front of the replay.  stats, log and attn_log work as before.  While the
+        step is captured the store refuses ``append``."""
+        from . import _ops
+        if not hasattr(self.model, "_forward_rows"):
+            raise TypeError("EvalStep.capture_store: the model has no forward_packed entry")
+        targets = self.loss_fn is not None
+        if targets and not _accepts_n_valid(self.loss_fn):
+            raise TypeError("EvalStep.capture_store: loss_fn takes no n_valid= keyword -- the ghost utterances of a short batch must "
+                            "stay out of the loss (hri_emo_amd.train's losses accept it)")
+        if self.stats is not None and not targets:
+            raise ValueError("EvalStep.capture_store: statistics need a loss_fn (prediction-only graphs feed the log)")
+        ids, pad = _store_capture_facts("EvalStep.capture_store", self.model, store, ids, pad_to)
+        B = len(ids)
+        la, lt = _store_batch(store, ids, pad, "EvalStep.capture_store")
+        dev = next(self.model.parameters()).device
+        _ops._require_gpu(next(self.model.parameters()))
+        self._check_attn_log("capture_store", pad)
+        y_static = torch.zeros((B,) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev) if targets else None
+        self._capture_ragged(store.widths, store.dtype, y_static, la, lt, pad, lambda: self._feed.fill(ids, targets),
+                             make_feed=lambda d: _StoreFeed(store, B, pad, d))
+
+    @_in_step_context
+    def eval_store(self, ids):
+        """One evaluation of the utterances `ids` (1 <= n <= B) of the captured store -> (logits [n, C], beta, z, loss | None):
+        eval_packed with "copy the caller's rows" replaced by "gather by id".  The ids ALWAYS refer to the store given to
+        capture_store -- ``self.store``: a step captured on the validation store evaluates the validation store whatever the ids
+        were meant for, so one step per store (or a new capture_store); train.evaluate_store refuses a step of another store.  Host checks first (the store as it was at capture:
+        RuntimeError after an append or a mode switch; ids, n and lengths: ValueError), nothing is enqueued when one fails.  The
+        returned tensors are views of the replayed graph's outputs, as eval_packed's.  After use_graph(False): the eager evaluation of
+        ``store.fetch(ids)``."""
+        pb, feed = self._pb, self._feed
+        if pb is None or feed is None:
+            raise RuntimeError("eval_store needs capture_store() first")
+        ids, la, lt = feed.batch(ids, True, "eval_store")
+        targets = self._static[4] is not None
+        if not self._replaying:
+            rows_a, _, rows_t, _, y = feed.store.fetch(ids)
+            return self._eval_eager(rows_a, rows_t, la, lt, y if targets else None)
+        self._check_modes("eval_store", "capture_store")
+        rec = self._packed_graph(_load_ragged(pb, self._static, feed.fill(ids, targets), la, lt))
+        rec.graph.replay()
+        logits, beta, z = rec.out
+        n = len(ids)
+        return logits[:n], beta[:n], z[:n], rec.loss
 
     def _pass(self, record):
         """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
@@ -1164,11 +1402,11 @@ class EvalStep:
         log.info("eval step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb.graphs))
         return rec
 
-    def _check_modes(self):
+    def _check_modes(self, entry="eval_packed", capture="capture_packed"):
         for (name, then), (_, now) in zip(self._modes, self._switches()):
             if then != now:
-                raise RuntimeError(f"EvalStep.eval_packed: the step was captured with {name} = {then!r}; it is {now!r} now -- "
-                                   "capture_packed() again under the new setting, or switch back")
+                raise RuntimeError(f"EvalStep.{entry}: the step was captured with {name} = {then!r}; it is {now!r} now -- "
+                                   f"{capture}() again under the new setting, or switch back")
 
     @_in_step_context
     def eval_packed(self, rows_a, rows_t, lengths_a, lengths_t, y=None):
@@ -1206,7 +1444,7 @@ class EvalStep:
             if tuple(y.shape) != want:
                 raise ValueError(f"eval_packed: targets of shape {tuple(y.shape)}; captured with {tuple(sy.shape)}"
                                  + (f", this batch needs {want}" if n != pb.B else ""))
-        rec = self._packed_graph(_load_ragged(pb, self._static, rows_a, rows_t, la, lt, y))
+        rec = self._packed_graph(_load_ragged(pb, self._static, _caller_rows(rows_a, rows_t, y), la, lt))
         rec.graph.replay()
         logits, beta, z = rec.out
         return logits[:n], beta[:n], z[:n], rec.loss

@@ -641,3 +641,37 @@ def evaluate_packed(model, batches, loss_fn, stats, pad_to=None, step=None):
     finally:
         model.train(was)
     return stats
+
+
+def evaluate_store(model, store, batches, loss_fn, stats, step=None):
+    """evaluate_packed() on a ``data.DeviceFeatureStore``: `batches` are lists of utterance ids (``store.batches(B, shuffle=False)``),
+    nothing but those ids and their lengths crosses to the device per batch.  Without `step`: model.eval() under torch.no_grad(),
+    ``store.fetch(ids)`` -> forward_packed (pad_to = store.pad_to) -> loss_fn -> stats.update, eager launches.  step: a
+    ``dp.EvalStep`` built on this model with this loss_fn and these stats -- every batch is then ONE ``eval_store`` (plan upload,
+    one gather launch per operand, one graph replay).  A step that holds no graph yet is captured on the spot from the first batch,
+    which therefore must be a full one (no later batch may be larger).  A step that IS captured must have been captured on this very
+    store (``step.store is store``): eval_store's ids refer to the captured store, so a step of the validation store handed in with
+    the test store would evaluate the wrong split without a sign -- ValueError before anything runs (one EvalStep per store, or
+    ``step.release_graph()`` first).  Returns `stats`."""
+    if step is not None:
+        if step.model is not model or step.stats is not stats or step.loss_fn is not loss_fn:
+            raise ValueError("evaluate_store(step=...): the EvalStep was built on another model, loss_fn or stats")
+        if step.captured and step.store is not store:
+            raise ValueError("evaluate_store(step=...): the EvalStep was captured " + ("by capture_packed" if step.store is None else
+                             "on another store") + "; its ids would not refer to this store (one step per store, or release_graph() first)")
+        for ids in batches:
+            if not step.captured:
+                step.capture_store(store, ids)
+            step.eval_store(ids)
+        return stats
+    was = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for ids in batches:
+                rows_a, len_a, rows_t, len_t, y = store.fetch(ids)
+                logits, beta, _ = model.forward_packed(rows_a, rows_t, len_a, len_t, pad_to=store.pad_to)
+                stats.update(logits, beta, y, loss_fn(logits, beta, y))
+    finally:
+        model.train(was)
+    return stats

@@ -292,6 +292,23 @@ int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const int* cu_seqle
 int hriemo_seq_tables(const int* lengths_a, const int* lengths_t, int B, int La, int Lt, int n_rows_a, int n_rows_t, int* cu_a,
                       int* cu_t, int* cu_f, unsigned char* mask_a, unsigned char* mask_t, unsigned char* mask_f,
                       hriemo_stream_t stream);
+/* A batch gathered from a device-resident feature store (data.DeviceFeatureStore) by utterance id, one launch per operand.
+ *  - store: rows of row_bytes bytes each, every utterance's rows back to back; offsets (int64 [N+1], device): utterance u owns the
+ *    rows offsets[u] .. offsets[u+1].  A store in which every utterance owns ONE row (the targets) has offsets = 0, 1, 2, ...
+ *  - plan (int32 [2n+1], device): {ids[n], dst_cu[n+1]}, written by the host from its own lengths.
+ *  - dst: dst_rows rows of row_bytes bytes.
+ * Rows offsets[ids[i]] .. offsets[ids[i]+1] of the store go to rows dst_cu[i] .. dst_cu[i+1] of dst (ids may repeat); the rows
+ * dst_cu[n] .. dst_rows of dst become zero (the tail a packed step's row sources carry); rows in front of dst_cu[0] are left as
+ * they are; nothing at or behind row dst_rows is written.  The values are copied bit for bit: the kernel sees bytes, any element
+ * type and any row_bytes >= 1 (10-byte rows included), any byte alignment of store and dst.  Destination chunks of 16 aligned
+ * bytes are written with 16-byte stores; their source is read 16 bytes wide where source and destination agree modulo 16 and in
+ * 8-, 4-, 2- or 1-byte pieces where they do not; chunks on a segment boundary go byte by byte.
+ * The caller guarantees 0 <= ids[i] < N: the kernel cannot know N.  For memory safety alone dst_cu is clamped to [0, dst_rows] and
+ * a segment longer than its utterance is completed with zeros instead of reading on.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): a null pointer; n < 1 or n > 2048; row_bytes < 1; dst_rows < 1; a
+ * plan that is not 4-byte or offsets that are not 8-byte aligned. */
+int hriemo_gather_rows(const void* store, long row_bytes, const long long* offsets, const int* plan, int n, void* dst, long dst_rows,
+                       hriemo_stream_t stream);
 long hriemo_add_ln_bwd_workspace_bytes(int M, int d);
 int hriemo_add_ln_bwd(const void* dY, const void* G, const void* X, const float* X32, const float* gamma, const float* mean,
                       const float* rstd, void* dX, void* dG, float* dgamma, float* dbeta, float* dbias, int accumulate,
