@@ -136,6 +136,13 @@ _SIGS = {
     "hriemo_ln_pool_bwd_pair": ("pip" + "ppppppppppip" * 2 + "iiip", "i"),
     "hriemo_ln_pool_bwd_workspace_bytes": ("iii", "l"),
     "hriemo_ln_pool_bwd": ("pipipppppppppp" + "iiiipp", "i"),
+    "hriemo_ln_pool2_fwd": ("p" * 9 + "iiiifp", "i"),
+    "hriemo_ln_pool2_fwd_pair": (("p" * 9 + "i") * 2 + "iiifp", "i"),
+    "hriemo_pooled_fuse_fwd": ("pipipipppiip", "i"),
+    "hriemo_pooled_fuse_bwd": ("ppppipppiip", "i"),
+    "hriemo_ln_pool_vec_bwd": ("pi" + "p" * 10 + "iiiipp", "i"),
+    "hriemo_ln_pool_vec_bwd_pair": ("i" + ("p" * 11 + "ip") * 2 + "iiip", "i"),
+    "hriemo_ingest_padded": ("pilpiiiippp", "i"),
     "hriemo_ln_pool_fwd_packed": ("pppiippppppipiiifp", "i"),
     "hriemo_ln_pool_fwd_packed_pair": ("pppiippppppi" * 2 + "piiifp", "i"),
     "hriemo_fuse_fwd_packed": ("pppppiiiip", "i"),

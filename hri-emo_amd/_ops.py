@@ -2340,6 +2340,52 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
         return (dx.view(B, L, d), None, r(dw1), r(db1), r(dw2), r(db2), r(dgamma), r(dbeta)) + (None,) * 7
 
 
+def _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh):
+    """the vector gate from the pooled partial sums of both modalities (beta_gate_tacfn.py:83-95): masked means, gate input
+    [a, t, |a-t|, a*t], the two-layer MLP, w = sigmoid, beta = mean(w) -> (gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16).
+    Shared by BetaGateFn and PooledGateFn."""
+    dev = pa.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    st_ = _stream()
+    gin = torch.empty((B, 4 * d), dtype=BF16, device=dev)
+    a_pool, t_pool = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
+    cnt = torch.empty((B, 2), **f32)
+    _lib.call("hriemo_gate_input", _p(pa), _p(pt), _p(sa.kpm), _p(st.kpm), B, La, Lt, d, _p(gin), _p(a_pool),
+              _p(t_pool), _p(cnt), st_)
+    w1_16, w2_16 = sh.get(w1), sh.get(w2)
+    hid = linear_fwd(gin, w1_16, b1, relu=True)
+    pre = linear_fwd(hid, w2_16, b2, out_f32=True)
+    w = torch.empty((B, d), **f32)
+    beta = torch.empty((B, 1), **f32)
+    _lib.call("hriemo_sigmoid_beta", _p(pre), _p(w), _p(beta), B, d, st_)
+    return gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16
+
+
+def _gate_weights_bwd(part, Lp, dbeta2, w, hid, gin, a_pool, t_pool, cnt, w1_16, w2_16, sink, params, B, d):
+    """backward of _gate_weights: part = the dw partial sums [B, hriemo_pool_chunks(Lp), d] -> (da, dt: the gradients of the masked
+    means, already divided by the valid counts; dw1, db1, dw2, db2 in the sink's buffers)"""
+    p_w1, p_b1, p_w2, p_b2 = params
+    dev = w.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    st_ = _stream()
+    acc = sink.fused
+    dpre = torch.empty((B, d), dtype=BF16, device=dev)
+    _lib.call("hriemo_gate_dpre", _p(part), Lp, _p(dbeta2), _p(w), _p(dpre), B, d, st_)
+    dw2 = sink.buf(p_w2)
+    linear_dw(dpre, hid, dw2, acc)
+    db2 = sink.buf(p_b2)
+    colsum(dpre, db2, acc)
+    dhid = linear_dx(dpre, w2_16, epi=2, aux=hid)
+    dw1 = sink.buf(p_w1)
+    linear_dw(dhid, gin, dw1, acc)
+    db1 = sink.buf(p_b1)
+    colsum(dhid, db1, acc)
+    dgin = linear_dx(dhid, w1_16)
+    da, dt = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
+    _lib.call("hriemo_gate_input_bwd", _p(dgin), _p(a_pool), _p(t_pool), _p(cnt), _p(da), _p(dt), B, d, st_)
+    return da, dt, dw1, db1, dw2, db2
+
+
 class BetaGateFn(_GradModeAware, torch.autograd.Function):
     """(h_fusion, beta) = BetaGate(h_a, h_t, masks)  -- models/beta_gate_tacfn.py:68-118
     sa / st / sf: the Seq of h_a's rows, of h_t's rows and of the fused memory's -- all padded ([B, L_a, d], [B, L_t, d], h_fusion
@@ -2394,17 +2440,7 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         else:
             ln_pool_fwd(*side_a, sf, d)
             ln_pool_fwd(*side_t, sf, d)
-        gin = torch.empty((B, 4 * d), dtype=BF16, device=dev)
-        a_pool, t_pool = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
-        cnt = torch.empty((B, 2), **f32)
-        _lib.call("hriemo_gate_input", _p(pa), _p(pt), _p(sa.kpm), _p(st.kpm), B, La, Lt, d, _p(gin), _p(a_pool),
-                  _p(t_pool), _p(cnt), st_)
-        w1_16, w2_16 = sh.get(w1), sh.get(w2)
-        hid = linear_fwd(gin, w1_16, b1, relu=True)
-        pre = linear_fwd(hid, w2_16, b2, out_f32=True)
-        w = torch.empty((B, d), **f32)
-        beta = torch.empty((B, 1), **f32)
-        _lib.call("hriemo_sigmoid_beta", _p(pre), _p(w), _p(beta), B, d, st_)
+        gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16 = _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh)
         H = torch.empty(sf.shape(d), dtype=BF16, device=dev)
         fuse_fwd(w, An, Tn, H, sf, d)
         ctx.save_for_backward(xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16,
@@ -2434,20 +2470,8 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
         part = torch.empty((B, L_.hriemo_pool_chunks(L), d), **f32)
         fuse_bwd_dw(dH2, An, Tn, part, sf, d)
-        dpre = torch.empty((B, d), dtype=BF16, device=dev)
-        _lib.call("hriemo_gate_dpre", _p(part), L, _p(dbeta2), _p(w), _p(dpre), B, d, st_)
-        dw2 = sink.buf(p_w2)
-        linear_dw(dpre, hid, dw2, acc)
-        db2 = sink.buf(p_b2)
-        colsum(dpre, db2, acc)
-        dhid = linear_dx(dpre, w2_16, epi=2, aux=hid)
-        dw1 = sink.buf(p_w1)
-        linear_dw(dhid, gin, dw1, acc)
-        db1 = sink.buf(p_b1)
-        colsum(dhid, db1, acc)
-        dgin = linear_dx(dhid, w1_16)
-        da, dt = torch.empty((B, d), **f32), torch.empty((B, d), **f32)
-        _lib.call("hriemo_gate_input_bwd", _p(dgin), _p(a_pool), _p(t_pool), _p(cnt), _p(da), _p(dt), B, d, st_)
+        da, dt, dw1, db1, dw2, db2 = _gate_weights_bwd(part, L, dbeta2, w, hid, gin, a_pool, t_pool, cnt, w1_16, w2_16, sink,
+                                                       (p_w1, p_b1, p_w2, p_b2), B, d)
         dxa = torch.empty(sa.shape(d), dtype=BF16, device=dev)
         dxt = torch.empty(st.shape(d), dtype=BF16, device=dev)
         dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
@@ -2581,6 +2605,203 @@ class LegacyBetaGateFn(torch.autograd.Function):
         _lib.call("hriemo_scalar_gate_dx", _p(dH2), L, _p(bflat), 1, _p(dpa), _p(cnt_a), _p(kpm_a), _p(dxa), B, La, d, st)
         _lib.call("hriemo_scalar_gate_dx", _p(dH2), L, _p(bflat), 0, _p(dpt), _p(cnt_t), _p(kpm_t), _p(dxt), B, Lt, d, st)
         return dxa, dxt, dw1, db1, dw2, db2, None, None, None
+
+
+# ----------------------------------------------------------------------------- pooled gate (FusionClassifier)
+# FusionClassifier.forward through PooledGateFn: opt-in, like the packed-tail switches (forward_packed always takes the pooled path)
+POOLED_GATE = False
+
+
+def pooled_gate():
+    return bool(POOLED_GATE)
+
+
+def _require_bf16_path(who):
+    if precision() != "bf16" or gemm_mode() != "bf16":
+        raise NotImplementedError(f"{who}: built for the bf16 path only (precision {precision()!r}, GEMM mode {gemm_mode()!r})")
+
+
+class IngestPaddedFn(torch.autograd.Function):
+    """packed rows x [n, d] (fp32 / bf16 / fp16) + the plan's cu_seqlens -> the PADDED (bf16 [Breal, L, d], fp32 twin | None) pair, PAD
+    rows zero: ONE launch (hriemo_ingest_padded), no source row behind cu[Breal] is read.  The twin is None where as_pair's is.
+    Backward: the pair's gradients gathered back to the packed rows (hriemo_pack_rows), cast to x's dtype and summed."""
+
+    @staticmethod
+    def forward(ctx, x, seq):
+        ctx.set_materialize_grads(False)
+        if x.dtype not in _XT:
+            raise TypeError(f"ingest: inputs of dtype {x.dtype} (expected float32, bfloat16 or float16)")
+        if not seq.packed or x.dim() != 2 or (seq.B == seq.Breal and x.shape[0] != seq.N):
+            raise ValueError(f"ingest: packed rows of shape {tuple(x.shape)} do not match the {seq.N} rows of their plan")
+        _require_gpu(x)
+        if not (x.is_contiguous() and x.data_ptr() % 16 == 0):
+            x = x.contiguous()
+        n, d = x.shape
+        B, L = seq.Breal, seq.L
+        y16 = torch.empty((B, L, d), dtype=BF16, device=x.device)
+        y32 = torch.empty((B, L, d), dtype=torch.float32, device=x.device) if (TWIN and x.dtype != BF16) else None
+        _lib.call("hriemo_ingest_padded", _p(x), _XT[x.dtype], d, _p(seq.cu), n, B, L, d, _p(y16), _p(y32), _stream())
+        ctx.seq, ctx.shape, ctx.dtype = seq, (n, d), x.dtype
+        return y16, y32
+
+    @staticmethod
+    def backward(ctx, d16, d32):
+        if not ctx.needs_input_grad[0] or (d16 is None and d32 is None):
+            return None, None
+        seq, (n, d) = ctx.seq, ctx.shape
+        g = None
+        for y, is32 in ((d16, False), (d32, True)):
+            if y is None:
+                continue
+            y = y.contiguous().float() if is32 else _contig_bf16(y)
+            out = torch.empty((n, d), dtype=y.dtype, device=y.device)
+            _lib.call("hriemo_pack_rows", None if is32 else _p(y), _p(y) if is32 else None, _p(seq.cu), seq.Breal, seq.L, d, n,
+                      None if is32 else _p(out), _p(out) if is32 else None, None, _stream())
+            out = out.to(ctx.dtype)
+            g = out if g is None else g + out
+        return g, None
+
+
+def ln_pool2_fwd(x, x32, sx, gamma, beta, mean, rstd, part, part_keep, Lkeep, d):
+    """row statistics, the masked-pooling partials of ln_pool_fwd and the partials over rows l < Lkeep; no Yn (padded rows)"""
+    _lib.call("hriemo_ln_pool2_fwd", _p(x), _p(x32), _p(sx.kpm), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(part), _p(part_keep),
+              sx.B, sx.L, Lkeep, d, _EPS, _stream())
+
+
+def ln_pool2_fwd_pair(a, t, Lkeep, d):
+    """ln_pool2_fwd of both modalities from one launch; a / t = (x, x32, sx, gamma, beta, mean, rstd, part, part_keep)"""
+    side = lambda x, x32, sx, *rest: (_p(x), _p(x32), _p(sx.kpm), *map(_p, rest), sx.L)          # noqa: E731
+    _lib.call("hriemo_ln_pool2_fwd_pair", *side(*a), *side(*t), a[2].B, Lkeep, d, _EPS, _stream())
+
+
+def ln_pool_vec_bwd(g, Lkeep, dpool, x, x32, sx, gamma, mean, rstd, dx, dgamma, dbeta, accumulate, ws, d):
+    """backward of ln_pool2_fwd for one modality; dgamma / dbeta None: the partial sums stay in ws (deferred reduce)"""
+    _lib.call("hriemo_ln_pool_vec_bwd", _p(g), Lkeep, _p(dpool), _p(sx.kpm), _p(x), _p(x32), _p(gamma), _p(mean), _p(rstd), _p(dx),
+              _p(dgamma), _p(dbeta), accumulate, sx.B, sx.L, d, _p(ws), _stream())
+
+
+def ln_pool_vec_bwd_pair(Lkeep, a, t, accumulate, d):
+    """ln_pool_vec_bwd of both modalities from one launch; a / t = (ws, g, dpool, x, x32, sx, gamma, mean, rstd, dx, dgamma, dbeta)"""
+    side = lambda ws, g, dpool, x, x32, sx, *rest: (_p(g), _p(dpool), _p(sx.kpm), _p(x), _p(x32), *map(_p, rest), sx.L, _p(ws))  # noqa: E731
+    _lib.call("hriemo_ln_pool_vec_bwd_pair", Lkeep, *side(*a), *side(*t), accumulate, a[5].B, d, _stream())
+
+
+class PooledGateFn(_GradModeAware, torch.autograd.Function):
+    """(pooled fp32 [B, d], beta [B, 1]) = mean over the L fused positions of BetaGate(h_a, h_t, masks)'s h_fusion
+    -- models/fusion_classifier.py:142-145 on the PADDED pairs (sa / st: padded Seq with the key-padding masks).
+    pooled = w * Abar + (1 - w) * Tbar with Abar / Tbar the unmasked means of the LayerNorm outputs over l < L (PAD rows included, as
+    the reference's h_fusion.mean(dim=1)); the gate weights come from _gate_weights, the code of the vector gate.  Neither the
+    LayerNorm outputs, h_fusion nor a [B, L, d] gradient of it is formed."""
+
+    @staticmethod
+    def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st):
+        if sa.packed or st.packed:
+            raise ValueError("PooledGate: the pooled mean includes PAD rows -- padded layouts only")
+        _require_bf16_path("PooledGate")
+        B, La, Lt, d = sa.Breal, sa.L, st.L, h_a.shape[-1]
+        sa.holds(h_a)
+        st.holds(h_t)
+        L = La if La == Lt else Lt                      # beta_gate_tacfn.py:98-104 (align to the text length)
+        if La < L:
+            raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
+        _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
+        _require_gpu(h_a)
+        h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
+        dev = h_a.device
+        xa, xt = _contig_bf16(h_a), _contig_bf16(h_t)
+        f32 = dict(dtype=torch.float32, device=dev)
+        L_ = _lib.lib()
+        nca, nct = L_.hriemo_pool_chunks(La), L_.hriemo_pool_chunks(Lt)
+        mean_a, rstd_a = torch.empty(B * La, **f32), torch.empty(B * La, **f32)
+        mean_t, rstd_t = torch.empty(B * Lt, **f32), torch.empty(B * Lt, **f32)
+        pa, pt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
+        ka, kt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
+        side_a = (xa, h_a32, sa, ga, ba, mean_a, rstd_a, pa, ka)
+        side_t = (xt, h_t32, st, gt, bt, mean_t, rstd_t, pt, kt)
+        if L_.hriemo_ln_pool_pair_supported(d):
+            ln_pool2_fwd_pair(side_a, side_t, L, d)
+        else:
+            ln_pool2_fwd(*side_a, L, d)
+            ln_pool2_fwd(*side_t, L, d)
+        gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16 = _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh)
+        abar, tbar, pooled = torch.empty((B, d), **f32), torch.empty((B, d), **f32), torch.empty((B, d), **f32)
+        _lib.call("hriemo_pooled_fuse_fwd", _p(ka), La, _p(kt), Lt, _p(w), L, _p(abar), _p(tbar), _p(pooled), B, d, _stream())
+        ctx.save_for_backward(xa, xt, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt,
+                              h_a32, h_t32, abar, tbar)
+        ctx.seqs = (sa, st)
+        ctx.params = (ga, ba, gt, bt, w1, b1, w2, b2)
+        return pooled, beta
+
+    @staticmethod
+    def backward(ctx, dpooled, dbeta):
+        (xa, xt, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt, h_a32, h_t32,
+         abar, tbar) = ctx.saved_tensors
+        sa, st = ctx.seqs
+        B, La, Lt, L, d = sa.Breal, sa.L, st.L, st.L, xa.shape[-1]
+        dev = xa.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        L_ = _lib.lib()
+        p_ga, p_ba, p_gt, p_bt, p_w1, p_b1, p_w2, p_b2 = ctx.params
+        sink = GradSink(ctx.params)
+        acc = sink.fused
+        dpooled2 = dpooled.contiguous().float() if dpooled is not None else None
+        dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
+        dwf, g_a, g_t = torch.empty((B, d), **f32), torch.empty((B, d), **f32), torch.empty((B, d), **f32)
+        _lib.call("hriemo_pooled_fuse_bwd", _p(dpooled2), _p(abar), _p(tbar), _p(w), L, _p(dwf), _p(g_a), _p(g_t), B, d, _stream())
+        # (dwf: ONE chunk of dw partials, [B, 1, d])
+        da, dt, dw1, db1, dw2, db2 = _gate_weights_bwd(dwf, 1, dbeta2, w, hid, gin, a_pool, t_pool, cnt, w1_16, w2_16, sink,
+                                                       (p_w1, p_b1, p_w2, p_b2), B, d)
+        dxa = torch.empty(sa.shape(d), dtype=BF16, device=dev)
+        dxt = torch.empty(st.shape(d), dtype=BF16, device=dev)
+        dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
+        defer = acc and DEFER_REDUCE and _in_backward()          # (as BetaGateFn: the LayerNorm-affine partials and who reduces them)
+        nba, nbt = L_.hriemo_ln_pool_bwd_workspace_bytes(B, La, d), L_.hriemo_ln_pool_bwd_workspace_bytes(B, Lt, d)
+        side_a = (g_a, da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa)
+        side_t = (g_t, dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt)
+        if defer:
+            wsa, wst = torch.empty(nba // 4 + 16, **f32), torch.empty(nbt // 4 + 16, **f32)
+            outs = (None,) * 4
+        else:
+            wsa = workspace(nba + nbt + 256, dev, slot=1)
+            wst = wsa[(nba // 4 + 63) // 64 * 64:]
+            outs = (dga, dba, dgt, dbt)
+        if L_.hriemo_ln_pool_pair_supported(d):
+            ln_pool_vec_bwd_pair(L, (wsa,) + side_a + outs[:2], (wst,) + side_t + outs[2:], int(acc), d)
+        else:
+            ln_pool_vec_bwd(*side_a, *outs[:2], int(acc), wsa, d)
+            ln_pool_vec_bwd(*side_t, *outs[2:], int(acc), wst, d)
+        if defer:
+            _deferred.add(wsa, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(La), d, 2, [dga, dba], True)
+            _deferred.add(wst, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lt), d, 2, [dgt, dbt], True)
+        sink.done()
+        r = sink.ret
+        return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None
+
+
+class DropoutF32Fn(torch.autograd.Function):
+    """y = drop(x) on fp32 [M, N] rows by the counter hash (hriemo_dropout_f32): the classifier head's Dropout as a hash site -- it
+    follows the device seed word inside a captured step, and tests/hashrng.py rebuilds its mask.  Backward: the same keep / (1 - p)."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, site, row_off):
+        _require_gpu(x)
+        x = x.contiguous()
+        M, N = x.shape
+        if DROP_LOG is not None and p > 0:
+            DROP_LOG.append(("rows", seed, site, M, N, float(p), row_off))
+        y = torch.empty_like(x)
+        _lib.call("hriemo_dropout_f32", _p(x), _p(y), M, N, 0, None, float(p), seed, _p(seed_word(x.device)), site, row_off, _stream())
+        ctx.drop = (float(p), seed, site, row_off)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, site, row_off = ctx.drop
+        dy = dy.contiguous().float()
+        M, N = dy.shape
+        dx = torch.empty_like(dy)
+        _lib.call("hriemo_dropout_f32", _p(dy), _p(dx), M, N, 0, None, p, seed, _p(seed_word(dy.device)), site, row_off, _stream())
+        return dx, None, None, None, None
 
 
 def _n_valid_word(n_valid, like):

@@ -1228,6 +1228,251 @@ __global__ __launch_bounds__(256) void ln_pool_bwd_packed_pair_kernel(const bf16
                               PAIR_PICK(rstd), PAIR_PICK(dX), PAIR_PICK(partials), PAIR_PICK(L), d, (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc), pk);
 }
 
+// ------------------------------------------------------------------ pooled gate (FusionClassifier: the fused sequence is only ever mean-pooled)
+// pooled[b] = w * Abar + (1 - w) * Tbar with Abar[b] = (1 / Lkeep) sum_{l < Lkeep} LN_a(h_a)[b, l] (PAD rows included, as the
+// reference's unmasked h_fusion.mean(dim=1)): no Yn, no H, no [B, L, d] gradient.
+// Forward: the walk of ln_pool_fwd_body (padded rows; block = 32-row chunk of one sample, a wave takes every fourth row, next-row
+// prefetch) with a second accumulator: `partials` are the masked sums of ln_pool_fwd_body bit for bit (same rows, same order, same
+// expression), `partials_keep` the sums over rows l < Lkeep whatever the mask says (chunks behind Lkeep: zeros).
+template <int NCH, bool PF>
+__device__ __forceinline__ void ln_pool2_fwd_body(const bf16_t* __restrict__ X, const float* __restrict__ X32, const uint8_t* __restrict__ mask,
+                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  float* __restrict__ mean_o, float* __restrict__ rstd_o, float* __restrict__ partials,
+                                                  float* __restrict__ partials_keep, int L, int Lkeep, int d, float eps, int chunk, int nchunks) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* red = (float*)smem_raw;   // [2][d]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, nchunk = d >> 3;
+  const long xbase = (long)b * L;
+  const float invd = 1.f / (float)d;
+  float acc[NCH][8], akeep[NCH][8];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { acc[c][j] = 0.f; akeep[c][j] = 0.f; }
+  constexpr bool HOIST = NCH <= 4;
+  float gm8[HOIST ? NCH : 1][8], bt8[HOIST ? NCH : 1][8];
+  if (HOIST) { load_cols<HOIST ? NCH : 1>(gamma, d >> 3, threadIdx.x & 63, gm8); load_cols<HOIST ? NCH : 1>(beta, d >> 3, threadIdx.x & 63, bt8); }
+  const int lend = min(L, chunk * 32 + 32);
+  float nx[NCH][8];
+  auto load_row = [&](int l, float (&dst)[NCH][8]) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) load_resid(X, X32, (xbase + l) * d + ch * 8, dst[c]);
+    }
+  };
+  if (PF && chunk * 32 + wave < lend) load_row(chunk * 32 + wave, nx);
+  for (int l = chunk * 32 + wave; l < lend; l += 4) {
+    const long row = xbase + l;
+    float s[NCH][8];
+    float sum = 0.f;
+    if (!PF) load_row(l, nx);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s[c][j] = nx[c][j]; sum += s[c][j]; }
+      }
+    }
+    if (PF && l + 4 < lend) load_row(l + 4, nx);
+    const float mu = wave_sum(sum) * invd;
+    float sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (lane + 64 * c < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float t = s[c][j] - mu; sq += t * t; }
+      }
+    const float rstd = rsqrtf(wave_sum(sq) * invd + eps);
+    const bool valid = mask == nullptr || mask[row] == 0;
+    const bool kept = l < Lkeep;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float o = (s[c][j] - mu) * rstd * (HOIST ? gm8[HOIST ? c : 0][j] : gamma[ch * 8 + j]) + (HOIST ? bt8[HOIST ? c : 0][j] : beta[ch * 8 + j]);
+          if (valid) acc[c][j] += o;
+          if (kept) akeep[c][j] += o;
+        }
+      }
+    }
+    if (lane == 0) { mean_o[row] = mu; rstd_o[row] = rstd; }
+  }
+  block_colsum<NCH>(red, acc, nchunk, lane, wave, 4);
+  block_colsum<NCH>(red + d, akeep, nchunk, lane, wave, 4);
+  float* out = partials + ((long)b * nchunks + chunk) * d;
+  float* outk = partials_keep + ((long)b * nchunks + chunk) * d;
+  for (int t = threadIdx.x; t < d; t += 256) { out[t] = red[t]; outk[t] = red[d + t]; }
+}
+template <int NCH, bool PF>
+__global__ __launch_bounds__(256) void ln_pool2_fwd_kernel(const bf16_t* __restrict__ X, const float* __restrict__ X32, const uint8_t* __restrict__ mask,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ mean_o, float* __restrict__ rstd_o, float* __restrict__ partials,
+                                                           float* __restrict__ partials_keep, int L, int Lkeep, int d, float eps) {
+  ln_pool2_fwd_body<NCH, PF>(X, X32, mask, gamma, beta, mean_o, rstd_o, partials, partials_keep, L, Lkeep, d, eps, blockIdx.x, gridDim.x);
+}
+struct Pool2FwdSide { const bf16_t* X; const float* X32; const uint8_t* mask; const float* gamma; const float* beta; float* mean; float* rstd; float* partials; float* partials_keep; int L, nc; };
+struct Pool2FwdPair { Pool2FwdSide s[2]; };
+// (d > 512: the second accumulator does not fit the 128 registers of four blocks per CU beside the prefetched row -- three then)
+template <int NCH, bool PF>
+__global__ __launch_bounds__(256, (NCH <= 1 ? 4 : 3)) void ln_pool2_fwd_pair_kernel(const Pool2FwdPair p, int Lkeep, int d, float eps) {
+  const bool second = (int)blockIdx.x >= p.s[0].nc;
+  ln_pool2_fwd_body<NCH, PF>(PAIR_PICK(X), PAIR_PICK(X32), PAIR_PICK(mask), PAIR_PICK(gamma), PAIR_PICK(beta), PAIR_PICK(mean), PAIR_PICK(rstd),
+                             PAIR_PICK(partials), PAIR_PICK(partials_keep), PAIR_PICK(L), Lkeep, d, eps,
+                             (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc));
+}
+
+// [B, d]: the prefix partials of both modalities -> Abar, Tbar (kept for backward) and pooled = w * Abar + (1 - w) * Tbar.  The
+// chunk sums are added in chunk order (chunks behind Lkeep hold zeros and are not read).
+__global__ __launch_bounds__(256) void pooled_fuse_fwd_kernel(const float* __restrict__ pa, int nca, const float* __restrict__ pt, int nct,
+                                                              const float* __restrict__ w, int Lkeep, float* __restrict__ abar,
+                                                              float* __restrict__ tbar, float* __restrict__ pooled, int d) {
+  const int b = blockIdx.x;
+  const int nk = (Lkeep + 31) / 32;
+  const float inv = 1.f / (float)Lkeep;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    float a = 0.f, t = 0.f;
+    for (int k = 0; k < nk; ++k) a += pa[((long)b * nca + k) * d + c];
+    for (int k = 0; k < nk; ++k) t += pt[((long)b * nct + k) * d + c];
+    a *= inv; t *= inv;
+    const float wv = w[(long)b * d + c];
+    abar[(long)b * d + c] = a; tbar[(long)b * d + c] = t;
+    pooled[(long)b * d + c] = wv * a + (1.f - wv) * t;
+  }
+}
+// [B, d] backward: dw = dpooled * (Abar - Tbar) (one chunk of dw partials for hriemo_gate_dpre) and the row gradients
+// g_a = w * dpooled / Lkeep, g_t = (1 - w) * dpooled / Lkeep that every row l < Lkeep of LN_a / LN_t receives
+__global__ __launch_bounds__(256) void pooled_fuse_bwd_kernel(const float* __restrict__ dpooled, const float* __restrict__ abar,
+                                                              const float* __restrict__ tbar, const float* __restrict__ w, int Lkeep,
+                                                              float* __restrict__ dw, float* __restrict__ ga, float* __restrict__ gt, int d) {
+  const int b = blockIdx.x;
+  const float inv = 1.f / (float)Lkeep;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const long i = (long)b * d + c;
+    const float g = dpooled != nullptr ? dpooled[i] : 0.f, wv = w[i];
+    dw[i] = g * (abar[i] - tbar[i]);
+    ga[i] = wv * g * inv;
+    gt[i] = (1.f - wv) * g * inv;
+  }
+}
+
+// backward of ln_pool2_fwd for one modality: ln_pool_bwd_body with the fp32 row vector g[b, :] standing in for coef * dH[b, l, :]
+//   dYn[l] = (l < Lkeep ? g[b] : 0) + (valid_l ? dpool[b] : 0),  dX = LN'(dYn)
+// the same blocks (POOL_BWD_ROWS rows of one sample), the same dgamma | dbeta partial layout; one operand stream (X) instead of two
+template <int NCH>
+__device__ __forceinline__ void ln_pool_vec_bwd_body(const float* __restrict__ g, int Lkeep, const float* __restrict__ dpool,
+                                                     const uint8_t* __restrict__ mask, const bf16_t* __restrict__ X, const float* __restrict__ X32,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
+                                                     bf16_t* __restrict__ dX, float* __restrict__ partials, int L, int d, int chunk, int nchunks) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* red = (float*)smem_raw;   // [2][d] column-sum scratch + [3][d] constants (dpool, g, gamma)
+  float* cst = red + 2 * d;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, nchunk = d >> 3;
+  const long xbase = (long)b * L;
+  const float invd = 1.f / (float)d;
+  float ag[NCH][8], ab[NCH][8];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ag[c][j] = 0.f; ab[c][j] = 0.f; }
+  for (int t = threadIdx.x; t < d; t += 256) {
+    cst[t] = dpool[(long)b * d + t];
+    cst[d + t] = g != nullptr ? g[(long)b * d + t] : 0.f;
+    cst[2 * d + t] = gamma[t];
+  }
+  __syncthreads();
+  const int lbeg = chunk * POOL_BWD_ROWS + wave, lend = min(L, chunk * POOL_BWD_ROWS + POOL_BWD_ROWS);
+  constexpr bool PF = NCH <= 2;   // wider rows (d > 1024) would spill with a second row in registers
+  float nxx[NCH][8];
+  auto load_row = [&](int l) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) load_resid(X, X32, (xbase + l) * d + ch * 8, nxx[c]);
+    }
+  };
+  if (PF) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) nxx[c][j] = 0.f;
+  }
+  if (PF && lbeg < lend) load_row(lbeg);
+  for (int l = lbeg; l < lend; l += 4) {
+    const long row = xbase + l;
+    const float mu = mean_i[row], rstd = rstd_i[row];
+    const bool valid = mask == nullptr || mask[row] == 0;
+    const bool kept = l < Lkeep;
+    float xh[NCH][8], dyg[NCH][8];
+    float c1 = 0.f, c2 = 0.f;
+    if (!PF) load_row(l);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) {
+        float dpc[8], gvc[8], gmc[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x4 a = *(const f32x4*)(cst + ch * 8 + h * 4), gq = *(const f32x4*)(cst + d + ch * 8 + h * 4), g4 = *(const f32x4*)(cst + 2 * d + ch * 8 + h * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { dpc[h * 4 + e] = a[e]; gvc[h * 4 + e] = gq[e]; gmc[h * 4 + e] = g4[e]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float dy = valid ? dpc[j] : 0.f;
+          if (kept) dy += gvc[j];
+          xh[c][j] = (nxx[c][j] - mu) * rstd;
+          dyg[c][j] = dy * gmc[j];
+          c1 += dyg[c][j];
+          asm volatile("" : "+v"(c1));      // no pairing of the steps of this serial sum (see ln_pool_bwd_body)
+          c2 += dyg[c][j] * xh[c][j];
+          ag[c][j] += dy * xh[c][j];
+          ab[c][j] += dy;
+        }
+      }
+    }
+    if (PF && l + 4 < lend) load_row(l + 4);
+    c1 = wave_sum(c1) * invd;
+    c2 = wave_sum(c2) * invd;
+    asm volatile("" : "+v"(c1));
+    asm volatile("" : "+v"(c2));
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int ch = lane + 64 * c;
+      if (ch < nchunk) {
+        float ds[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ds[j] = rstd * (dyg[c][j] - c1 - xh[c][j] * c2);
+        *(bf16x8*)(dX + row * d + ch * 8) = f32_to_bf8(ds);
+      }
+    }
+  }
+  block_colsum<NCH>(red, ag, nchunk, lane, wave, 4);
+  block_colsum<NCH>(red + d, ab, nchunk, lane, wave, 4);
+  float* out = partials + ((long)b * nchunks + chunk) * 2 * d;
+  for (int t = threadIdx.x; t < 2 * d; t += 256) out[t] = red[t];
+}
+template <int NCH>
+__global__ __launch_bounds__(256) void ln_pool_vec_bwd_kernel(const float* __restrict__ g, int Lkeep, const float* __restrict__ dpool,
+                                                              const uint8_t* __restrict__ mask, const bf16_t* __restrict__ X, const float* __restrict__ X32,
+                                                              const float* __restrict__ gamma, const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
+                                                              bf16_t* __restrict__ dX, float* __restrict__ partials, int L, int d) {
+  ln_pool_vec_bwd_body<NCH>(g, Lkeep, dpool, mask, X, X32, gamma, mean_i, rstd_i, dX, partials, L, d, blockIdx.x, gridDim.x);
+}
+struct PoolVecBwdSide { const float* g; const float* dpool; const uint8_t* mask; const bf16_t* X; const float* X32; const float* gamma; const float* mean; const float* rstd; bf16_t* dX; float* partials; int L, nc; };
+struct PoolVecBwdPair { PoolVecBwdSide s[2]; };
+template <int NCH>
+__global__ __launch_bounds__(256) void ln_pool_vec_bwd_pair_kernel(const PoolVecBwdPair p, int Lkeep, int d) {
+  const bool second = (int)blockIdx.x >= p.s[0].nc;
+  ln_pool_vec_bwd_body<NCH>(PAIR_PICK(g), Lkeep, PAIR_PICK(dpool), PAIR_PICK(mask), PAIR_PICK(X), PAIR_PICK(X32), PAIR_PICK(gamma), PAIR_PICK(mean),
+                            PAIR_PICK(rstd), PAIR_PICK(dX), PAIR_PICK(partials), PAIR_PICK(L), d, (int)blockIdx.x - (second ? p.s[0].nc : 0), PAIR_PICK(nc));
+}
+
 // ================================================================== host entry points
 #define DISPATCH_NCH(d, CALL)                         \
   {                                                   \
@@ -1745,6 +1990,72 @@ extern "C" int hriemo_ingest_rows(const void* X, int x_dtype, long ldx, const in
   return 0;
 }
 
+// ---- packed rows in, PADDED rows out (the FusionClassifier's front door: its unmasked mean pools PAD rows too, so its encoder runs
+// on the padded layout): X packed [>= cu[B], d] (fp32 / bf16 / fp16, row stride ldx) -> Y16 bf16 [B, L, d] and its fp32 twin Y32
+// (either may be NULL), row (b, l) = source row cu[b] + l for l < cu[b+1] - cu[b], zeros behind it.  One wave per DESTINATION row;
+// a source row is read only when it lies inside [cu[b], cu[b+1]) and in front of min(cu[B], n_rows): nothing behind cu[B] is read.
+// The conversions are ingest_rows_kernel's, so a valid row equals hriemo_ingest_rows + hriemo_unpack_rows bit for bit.
+template <int XT>
+__global__ __launch_bounds__(256) void ingest_padded_kernel(const void* __restrict__ X, long ldx, const int* __restrict__ cu, int n_rows, int B, int L, int d,
+                                                            bf16_t* __restrict__ Y16, float* __restrict__ Y32) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (row >= (long)B * L) return;
+  const int b = (int)(row / L), l = (int)(row - (long)b * L);
+  const int c0 = cu[b], c1 = min(min(cu[b + 1], cu[B]), n_rows);      // (lengths are device data: clamped to the source buffer)
+  const bool real = c0 >= 0 && l < c1 - c0;
+  constexpr int ESZ = XT == 0 ? 4 : 2;
+  const char* xrow = (const char*)X + ((long)c0 + l) * ldx * ESZ;
+  const int nchunk = d >> 3;
+  for (int ch = lane; ch < nchunk; ch += 64) {
+    float f[8];
+    bf16x8 h = bf16x8{};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = 0.f;
+    if (real) {
+      if (XT == 0) {
+        const f32x4 a = *(const f32x4*)(xrow + (long)ch * 32), b4 = *(const f32x4*)(xrow + (long)ch * 32 + 16);
+        f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b4[0]; f[5] = b4[1]; f[6] = b4[2]; f[7] = b4[3];
+        h = f32_to_bf8(f);
+      } else if (XT == 1) {
+        h = *(const bf16x8*)(xrow + (long)ch * 16);       // a bf16 source is copied, not converted
+        bf8_to_f32(h, f);
+      } else {
+        const f16x8 v = *(const f16x8*)(xrow + (long)ch * 16);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
+        h = f32_to_bf8(f);
+      }
+    }
+    const long off = row * d + ch * 8;
+    if (Y32 != nullptr) {
+      *(f32x4*)(Y32 + off) = (f32x4){f[0], f[1], f[2], f[3]};
+      *(f32x4*)(Y32 + off + 4) = (f32x4){f[4], f[5], f[6], f[7]};
+    }
+    if (Y16 != nullptr) *(bf16x8*)(Y16 + off) = h;
+  }
+}
+extern "C" int hriemo_ingest_padded(const void* X, int x_dtype, long ldx, const int* cu_seqlens, int n_rows, int B, int L, int d, void* Y16,
+                                    float* Y32, hipStream_t st) {
+  HRIEMO_CHECK(X != nullptr && cu_seqlens != nullptr && n_rows > 0 && B > 0 && L > 0 && d > 0, "ingest_padded: empty shape (n_rows=%d B=%d L=%d d=%d)", n_rows, B, L, d);
+  HRIEMO_CHECK(d % 8 == 0, "ingest_padded: d=%d must be a multiple of 8", d);
+  HRIEMO_CHECK(x_dtype >= 0 && x_dtype <= 2, "ingest_padded: unknown x_dtype %d (0 fp32, 1 bf16, 2 fp16)", x_dtype);
+  HRIEMO_CHECK(Y16 != nullptr || Y32 != nullptr, "ingest_padded: no output given");
+  HRIEMO_CHECK((long)B * L * d < (1L << 31), "ingest_padded: more than 2^31 elements");
+  const int esz = x_dtype == 0 ? 4 : 2;
+  HRIEMO_CHECK(ldx >= d && (ldx * esz) % 16 == 0, "ingest_padded: source row stride %ld (d=%d) must be >= d and a multiple of 16 bytes", ldx, d);
+  HRIEMO_CHECK(((uintptr_t)X % 16) == 0 && ((uintptr_t)Y16 % 16) == 0 && ((uintptr_t)Y32 % 16) == 0, "ingest_padded: unaligned operand");
+  const long rows = (long)B * L;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define PCALL(T) hipLaunchKernelGGL((ingest_padded_kernel<T>), grid, dim3(256), 0, st, X, ldx, cu_seqlens, n_rows, B, L, d, (bf16_t*)Y16, Y32)
+  if (x_dtype == 0) { PCALL(0); } else if (x_dtype == 1) { PCALL(1); } else { PCALL(2); }
+#undef PCALL
+  HRIEMO_LAUNCH_CHECK("ingest_padded_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)rows * d * (esz + (Y16 ? 2.0 : 0.0) + (Y32 ? 4.0 : 0.0)));
+  return 0;
+}
+
 // ---- the sequence tables of a ragged batch: ONE launch from the lengths to everything a packed step reads -----------------------
 // la / lt (int32 [B], device; clamped to [1, La] / [1, Lt] for memory safety) -> cu_a, cu_t, cu_f (int32 [B+2] = [0, inclusive
 // prefix sums ..., the bucket's row count]; fused length = min of the two) and the dense uint8 key-padding masks [B, La], [B, Lt],
@@ -2218,6 +2529,112 @@ extern "C" int hriemo_ln_pool_bwd_pair(const void* dH, int Lf, const float* w,
   else hipLaunchKernelGGL((ln_pool_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, Lf, w, p, d);
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * B * (La + Lt) + 2.0 * B * Lf) * d * 2);
+  if (dgamma_a == nullptr) return 0;
+  for (int side = 0; side < 2; ++side) {
+    float* ws = side ? workspace_t : workspace_a;
+    float* scratch = ws + (long)B * p.s[side].nc * 2 * d;
+    ReduceOut ro; ro.o[0] = side ? dgamma_t : dgamma_a; ro.o[1] = side ? dbeta_t : dbeta_a; ro.o[2] = nullptr;
+    launch_colreduce(ws, (long)2 * d, B * p.s[side].nc, ro, d, 2, accumulate, scratch, st);
+    HRIEMO_LAUNCH_CHECK("colreduce_kernel");
+  }
+  return 0;
+}
+
+// ---- the pooled gate (FusionClassifier): see ln_pool2_fwd_body.  d <= 2048 (two accumulators per column in registers).
+static int check_pool2(const char* who, int B, int L, int Lkeep, int d) {
+  if (check_rows(B * L, d)) return 1;
+  HRIEMO_CHECK(d <= 2048, "%s: d=%d (the pooled gate kernels are built for d <= 2048)", who, d);
+  HRIEMO_CHECK(Lkeep >= 1 && Lkeep <= L, "%s: Lkeep=%d out of range (L=%d)", who, Lkeep, L);
+  HRIEMO_CHECK((long)B * L * d < (1L << 31), "%s: more than 2^31 elements", who);
+  return 0;
+}
+extern "C" int hriemo_ln_pool2_fwd(const void* X, const float* X32, const unsigned char* mask, const float* gamma, const float* beta,
+                                   float* mean, float* rstd, float* partials, float* partials_keep, int B, int L, int Lkeep, int d,
+                                   float eps, hipStream_t st) {
+  if (check_pool2("ln_pool2_fwd", B, L, Lkeep, d)) return 1;
+  HRIEMO_CHECK(partials != nullptr && partials_keep != nullptr && partials != partials_keep, "ln_pool2_fwd: two distinct partial buffers are needed");
+  const int nc = (L + 31) / 32, nch = (d / 8 + 63) / 64;
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N, PF) hipLaunchKernelGGL((ln_pool2_fwd_kernel<N, PF>), dim3(nc, B), dim3(256), 2 * d * 4, st, (const bf16_t*)X, X32, mask, gamma, beta, mean, rstd, partials, partials_keep, L, Lkeep, d, eps)
+  if (nch <= 1) { CALL(1, true); } else if (nch <= 2) { CALL(2, true); } else { CALL(4, false); }
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("ln_pool2_fwd_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)B * L * d * 2);
+  return 0;
+}
+extern "C" int hriemo_ln_pool2_fwd_pair(const void* Xa, const float* Xa32, const unsigned char* mask_a, const float* gamma_a, const float* beta_a,
+                                        float* mean_a, float* rstd_a, float* partials_a, float* partials_keep_a, int La,
+                                        const void* Xt, const float* Xt32, const unsigned char* mask_t, const float* gamma_t, const float* beta_t,
+                                        float* mean_t, float* rstd_t, float* partials_t, float* partials_keep_t, int Lt,
+                                        int B, int Lkeep, int d, float eps, hipStream_t st) {
+  if (check_pool2("ln_pool2_fwd_pair", B, La, Lkeep, d) || check_pool2("ln_pool2_fwd_pair", B, Lt, Lkeep, d)) return 1;
+  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool2_fwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool2_fwd calls)", d);
+  HRIEMO_CHECK(partials_a != nullptr && partials_keep_a != nullptr && partials_t != nullptr && partials_keep_t != nullptr, "ln_pool2_fwd_pair: a partial buffer is missing");
+  Pool2FwdPair p;
+  p.s[0] = Pool2FwdSide{(const bf16_t*)Xa, Xa32, mask_a, gamma_a, beta_a, mean_a, rstd_a, partials_a, partials_keep_a, La, (La + 31) / 32};
+  p.s[1] = Pool2FwdSide{(const bf16_t*)Xt, Xt32, mask_t, gamma_t, beta_t, mean_t, rstd_t, partials_t, partials_keep_t, Lt, (Lt + 31) / 32};
+  const int nc = p.s[0].nc + p.s[1].nc;
+  hriemo_prof_begin(HP_ROWOPS, st);
+  if (d <= 512) hipLaunchKernelGGL((ln_pool2_fwd_pair_kernel<1, true>), dim3(nc, B), dim3(256), 2 * d * 4, st, p, Lkeep, d, eps);
+  else hipLaunchKernelGGL((ln_pool2_fwd_pair_kernel<2, true>), dim3(nc, B), dim3(256), 2 * d * 4, st, p, Lkeep, d, eps);
+  HRIEMO_LAUNCH_CHECK("ln_pool2_fwd_pair_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)B * (La + Lt) * d * 2);
+  return 0;
+}
+extern "C" int hriemo_pooled_fuse_fwd(const float* partials_keep_a, int La, const float* partials_keep_t, int Lt, const float* w, int Lkeep,
+                                      float* abar, float* tbar, float* pooled, int B, int d, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && d > 0 && Lkeep >= 1 && Lkeep <= La && Lkeep <= Lt, "pooled_fuse_fwd: bad shape (B=%d d=%d Lkeep=%d La=%d Lt=%d)", B, d, Lkeep, La, Lt);
+  hipLaunchKernelGGL(pooled_fuse_fwd_kernel, dim3(B), dim3(256), 0, st, partials_keep_a, (La + 31) / 32, partials_keep_t, (Lt + 31) / 32, w, Lkeep,
+                     abar, tbar, pooled, d);
+  HRIEMO_LAUNCH_CHECK("pooled_fuse_fwd_kernel");
+  return 0;
+}
+extern "C" int hriemo_pooled_fuse_bwd(const float* dpooled, const float* abar, const float* tbar, const float* w, int Lkeep, float* dw,
+                                      float* g_a, float* g_t, int B, int d, hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && d > 0 && Lkeep >= 1, "pooled_fuse_bwd: bad shape (B=%d d=%d Lkeep=%d)", B, d, Lkeep);
+  hipLaunchKernelGGL(pooled_fuse_bwd_kernel, dim3(B), dim3(256), 0, st, dpooled, abar, tbar, w, Lkeep, dw, g_a, g_t, d);
+  HRIEMO_LAUNCH_CHECK("pooled_fuse_bwd_kernel");
+  return 0;
+}
+extern "C" int hriemo_ln_pool_vec_bwd(const float* g, int Lkeep, const float* dpool, const unsigned char* mask, const void* X, const float* X32,
+                                      const float* gamma, const float* mean, const float* rstd, void* dX, float* dgamma, float* dbeta,
+                                      int accumulate, int B, int L, int d, float* workspace, hipStream_t st) {
+  if (check_pool2("ln_pool_vec_bwd", B, L, Lkeep, d)) return 1;
+  HRIEMO_CHECK(workspace != nullptr && dpool != nullptr && (dgamma == nullptr) == (dbeta == nullptr), "ln_pool_vec_bwd: bad arguments");
+  const int nc = hriemo_ln_pool_bwd_chunks(L), nch = (d / 8 + 63) / 64;
+  hriemo_prof_begin(HP_ROWOPS, st);
+#define CALL(N) hipLaunchKernelGGL((ln_pool_vec_bwd_kernel<N>), dim3(nc, B), dim3(256), 5 * d * 4, st, g, Lkeep, dpool, mask, (const bf16_t*)X, X32, gamma, mean, rstd, (bf16_t*)dX, workspace, L, d)
+  if (nch <= 1) { CALL(1); } else if (nch <= 2) { CALL(2); } else { CALL(4); }
+#undef CALL
+  HRIEMO_LAUNCH_CHECK("ln_pool_vec_bwd_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, 2.0 * B * L * d * 2);
+  if (dgamma == nullptr) return 0;          // partial sums stay in `workspace` for the launch-boundary reduce (as hriemo_ln_pool_bwd)
+  float* scratch = workspace + (long)B * nc * 2 * d;
+  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
+  launch_colreduce(workspace, (long)2 * d, B * nc, ro, d, 2, accumulate, scratch, st);
+  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
+  return 0;
+}
+extern "C" int hriemo_ln_pool_vec_bwd_pair(int Lkeep,
+                                           const float* g_a, const float* dpool_a, const unsigned char* mask_a, const void* Xa, const float* Xa32, const float* gamma_a,
+                                           const float* mean_a, const float* rstd_a, void* dXa, float* dgamma_a, float* dbeta_a, int La, float* workspace_a,
+                                           const float* g_t, const float* dpool_t, const unsigned char* mask_t, const void* Xt, const float* Xt32, const float* gamma_t,
+                                           const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t, float* dbeta_t, int Lt, float* workspace_t,
+                                           int accumulate, int B, int d, hipStream_t st) {
+  if (check_pool2("ln_pool_vec_bwd_pair", B, La, Lkeep, d) || check_pool2("ln_pool_vec_bwd_pair", B, Lt, Lkeep, d)) return 1;
+  HRIEMO_CHECK(workspace_a != nullptr && workspace_t != nullptr && workspace_a != workspace_t && dpool_a != nullptr && dpool_t != nullptr, "ln_pool_vec_bwd_pair: bad arguments");
+  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_vec_bwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_vec_bwd calls)", d);
+  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
+               "ln_pool_vec_bwd_pair: the four LayerNorm gradients come together or not at all");
+  PoolVecBwdPair p;
+  p.s[0] = PoolVecBwdSide{g_a, dpool_a, mask_a, (const bf16_t*)Xa, Xa32, gamma_a, mean_a, rstd_a, (bf16_t*)dXa, workspace_a, La, hriemo_ln_pool_bwd_chunks(La)};
+  p.s[1] = PoolVecBwdSide{g_t, dpool_t, mask_t, (const bf16_t*)Xt, Xt32, gamma_t, mean_t, rstd_t, (bf16_t*)dXt, workspace_t, Lt, hriemo_ln_pool_bwd_chunks(Lt)};
+  const int nc = p.s[0].nc + p.s[1].nc;
+  hriemo_prof_begin(HP_ROWOPS, st);
+  if (d <= 512) hipLaunchKernelGGL((ln_pool_vec_bwd_pair_kernel<1>), dim3(nc, B), dim3(256), 5 * d * 4, st, p, Lkeep, d);
+  else hipLaunchKernelGGL((ln_pool_vec_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, p, Lkeep, d);
+  HRIEMO_LAUNCH_CHECK("ln_pool_vec_bwd_pair_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, 2.0 * B * (La + Lt) * d * 2);
   if (dgamma_a == nullptr) return 0;
   for (int side = 0; side < 2; ++side) {
     float* ws = side ? workspace_t : workspace_a;

@@ -154,7 +154,7 @@ class CrossModalTransformer(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([CrossModalBlock(d_model, n_heads, dropout) for _ in range(num_layers)])
 
-    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=False, raw=False, plan=None):
+    def _fwd_pair(self, a, a32, t, t32, mask_a, mask_t, need, tail=False, raw=False, plan=None, padded=False):
         """-> (a, a32, t, t32, maps, (sa, st, sf)): the outputs, the _ops.Seq of their rows and the Seq of the fused memory the gate
         makes of them.  tail: the caller can take the packed tail (_ops.PACKED_TAIL).  When the encoder ran packed, its outputs then
         STAY packed ([1, N, d] pairs) and the layouts are the plan (Seq audio, Seq text, Seq fused) -- the gate and the decoder read
@@ -163,12 +163,14 @@ class CrossModalTransformer(nn.Module):
         raw (_ops.INGEST_ROWS): a / t are still the caller's tensors (a32 / t32 None); ONE launch each makes the pairs here, gathered
         straight into the packed rows where the encoder packs (_ops.ingest_pair).  plan: the caller's packed plan, a / t are already
         its packed pairs (forward_packed): the encoder runs packed whatever set_varlen says.
-        need: a bool, or a train.AttentionLog's encoder sites (per layer {name: _ops.LogSite}): the maps go to the log, `maps` is []."""
+        need: a bool, or a train.AttentionLog's encoder sites (per layer {name: _ops.LogSite}): the maps go to the log, `maps` is [].
+        padded: the encoder stays on the padded layout whatever set_varlen says (FusionClassifier's pooled path: its unmasked mean
+        reads the PAD rows of the output, which the unpack of a packed run writes as zeros)."""
         all_layers_attn = []
         given = plan is not None
         B, La, Lt = (plan[0].Breal, plan[0].L, plan[1].L) if given else (a.shape[0], a.shape[1], t.shape[1])
         _ops.FLUSH_SITES.add(self.layers[0]._site[1])        # layer-0 text self-attention: the last text-branch backward (_ops._DeferredWgrad)
-        if not given and _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None:
+        if not given and not padded and _ops.varlen() and (not need or _ops.varlen_maps()) and mask_a is not None and mask_t is not None:
             # SURVEY 8(f) rank 4: the encoder on the valid rows only (prefix masks, as the collate builds them); anything else
             # takes the padded path.  dp.DataParallelStep injects bucketed plans whose lengths are device data (_ops.CTX.seq_override).
             if _ops.CTX.seq_override is not None:

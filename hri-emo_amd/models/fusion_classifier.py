@@ -2,9 +2,16 @@
 transformer + vector beta-gate (both on the HIP kernels) + mean-pool + classifier head.
 
 The head works on [B, d] vectors (LayerNorm, Linear(d,d), ReLU, Dropout, Linear(d, num_classes)) and is NOT part
-of the north-star hot path (component 8); it stays plain torch.nn on the device."""
+of the north-star hot path (component 8); it stays plain torch.nn on the device.
+
+Two tails behind the encoder:
+  - forward() by default: the vector gate writes h_fusion [B, L, d], torch pools it (the path of record);
+  - the pooled gate (_ops.PooledGateFn): forward_packed / _forward_rows always, forward() with _ops.POOLED_GATE = True.  The
+    reference pools with an UNMASKED mean (:145), so PAD rows of the encoder output are part of the result: this path runs the
+    encoder on the PADDED layout with zero PAD input rows, whatever set_varlen says -- ragged in, padded inside."""
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 try:
     from .. import _ops
@@ -22,6 +29,15 @@ class FusionClassifier(nn.Module):
         self.beta_gate = BetaGate(d_model=d_model, hidden_dim=beta_hidden)
         self.classifier = nn.Sequential(nn.LayerNorm(d_model), nn.Linear(d_model, d_model), nn.ReLU(),
                                         nn.Dropout(dropout), nn.Linear(d_model, num_classes))
+        self._site = _ops.new_site_base()          # the head's Dropout as a counter-hash site (pooled path)
+        self.batch_offset = 0                      # global index of this shard's first utterance (data parallel)
+
+    def set_batch_offset(self, offset: int):
+        """Global index of this shard's first utterance: keeps dropout masks independent of how the
+        batch is sharded across GPUs (hri_emo_amd.dp)."""
+        for m in self.modules():
+            if hasattr(m, "batch_offset"):
+                m.batch_offset = int(offset)
 
     def _ensure_3d(self, x):
         if x.dim() == 2:
@@ -34,8 +50,61 @@ class FusionClassifier(nn.Module):
         h_a, h_t = self._ensure_3d(h_a), self._ensure_3d(h_t)
         a, a32 = _ops.as_pair(h_a)
         t, t32 = _ops.as_pair(h_t)
+        if _ops.pooled_gate():
+            return self._run_pooled(a, a32, t, t32, mask_a, mask_t, h_a.dtype)
         a, a32, t, t32, _, seqs = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, False)      # :139
         h_fusion, beta = self.beta_gate._fwd_pair(a, a32, t, t32, mask_a, mask_t, seqs)                 # :142
         h_fusion_pooled = h_fusion.float().mean(dim=1)                                            # :145
         logits = self.classifier(h_fusion_pooled)                                                 # :148
         return logits, beta, h_fusion_pooled.to(h_a.dtype if h_a.dtype != torch.bfloat16 else torch.float32)
+
+    def forward_packed(self, rows_a, rows_t, lengths_a, lengths_t, pad_to=None, return_attention=False, attn_log=None):
+        """forward for a batch that is already ragged: rows_a / rows_t [sum(lengths), d] (fp32, bf16 or fp16) hold the valid rows of
+        all utterances back to back, lengths_a / lengths_t are host sequences or CPU int tensors.  pad_to = (L_a, L_t), default the
+        batch maxima: the padded lengths the reference's collate would produce -- they key the dropout hash AND, for this model,
+        count in the result (the unmasked mean runs over L_t positions).  Utterance-level batches: lengths of all 1, pad_to=(1, 1).
+        One launch per modality makes the padded pairs with zero PAD rows (hriemo_ingest_padded); the encoder runs padded under the
+        masks of the lengths, the pooled gate follows.  Returns what forward returns for the zero-padded batch and its masks.
+        Attention maps are not exported on this path (ValueError)."""
+        la, lt, (La, Lt) = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to)
+        self._no_maps(return_attention, attn_log)
+        _ops._require_gpu(rows_a)
+        plan, masks = _ops.plans_from_lengths(la, lt, La, Lt, rows_a.device)
+        return self._forward_rows(rows_a, rows_t, plan, masks, (La, Lt))
+
+    @staticmethod
+    def _no_maps(return_attention, attn_log):
+        if return_attention or attn_log is not None:
+            raise ValueError("FusionClassifier.forward_packed: attention maps and attention logs are not exported by the classifier")
+
+    def _forward_rows(self, rows_a, rows_t, plan, masks, pad, return_attention=False, attn_log=None):
+        """forward_packed behind its argument check: the packed rows, their plan (Seq audio, Seq text, ...: only cu_seqlens, Breal
+        and L of the first two are read), the padded bool masks (mask_a [B, L_a], mask_t [B, L_t], ...) and pad = (L_a, L_t).
+        dp.DataParallelStep.step_packed calls it with a bucket plan and masks in device memory: rows_a / rows_t may then hold more
+        rows than the batch has (the ingest launch never reads past cu[B])."""
+        self._no_maps(return_attention, attn_log)
+        if (plan[0].L, plan[1].L) != tuple(pad):
+            raise ValueError(f"forward_packed: the plan pads to ({plan[0].L}, {plan[1].L}), not to {tuple(pad)}")
+        _ops._require_bf16_path("FusionClassifier.forward_packed")
+        a, a32 = _ops.IngestPaddedFn.apply(rows_a, plan[0])
+        t, t32 = _ops.IngestPaddedFn.apply(rows_t, plan[1])
+        return self._run_pooled(a, a32, t, t32, masks[0], masks[1], rows_a.dtype)
+
+    def _run_pooled(self, a, a32, t, t32, mask_a, mask_t, in_dtype):
+        """the model on padded pairs with the pooled gate: padded encoder, PooledGateFn, the fp32 head with a hash-site Dropout"""
+        _ops._require_bf16_path("FusionClassifier (pooled gate)")
+        _ops.begin_step()
+        B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
+        a, a32, t, t32, _, _ = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, False, padded=True)      # :139
+        g = self.beta_gate
+        pooled, beta = _ops.PooledGateFn.apply(a, a32, t, t32, g.norm_a.weight, g.norm_a.bias, g.norm_t.weight, g.norm_t.bias,
+                                               g.mlp[0].weight, g.mlp[0].bias, g.mlp[2].weight, g.mlp[2].bias, g._sh,
+                                               _ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))      # :142-145
+        head = self.classifier
+        p = float(head[3].p) if self.training else 0.0
+        seed = _ops.next_seed(self.training and p > 0)
+        h = F.relu(head[1](head[0](pooled)))
+        if p > 0:
+            h = _ops.DropoutF32Fn.apply(h, p, seed, self._site, self.batch_offset)
+        logits = head[4](h)                                                                                       # :148
+        return logits, beta, pooled.to(in_dtype if in_dtype != torch.bfloat16 else torch.float32)

@@ -559,6 +559,49 @@ int hriemo_ln_pool_bwd(const void* dH, int Lf, const float* w, int is_a, const f
 /* (dgamma / dbeta: overwritten, or added to when accumulate != 0; both NULL: the per-block partial sums stay in `workspace`, rows
  * [B * ceil(L/32)] of [dgamma | dbeta] (2d floats each), for hriemo_colreduce_batch at the end of backward) */
 
+/* ---- the pooled gate (models/fusion_classifier.py:142-145): the classifier reads the fused sequence only through its UNMASKED mean
+ * over the L fused positions, so   pooled[b] = w[b] * Abar[b] + (1 - w[b]) * Tbar[b],   Abar[b] = (1/Lkeep) sum_{l < Lkeep} LN_a(h_a)[b, l]
+ * (Tbar likewise; PAD rows l < Lkeep are part of the sum, as in the reference), and neither Yn, h_fusion nor a [B, L, d] gradient
+ * is ever formed.  Padded rows only; d % 8 == 0, d <= 2048 (pairs: d <= 1024); 1 <= Lkeep <= L.
+ *  - hriemo_ln_pool2_fwd: ONE pass over X (bf16, or its fp32 twin X32 when non-NULL; key-padding mask optional) with the blocks and
+ *    the wave walk of hriemo_ln_pool_fwd.  mean, rstd [B*L] and `partials` [B, hriemo_pool_chunks(L), d] (sums over the VALID rows
+ *    of every 32-row chunk) equal hriemo_ln_pool_fwd's bit for bit, so hriemo_gate_input runs unchanged; `partials_keep` (same
+ *    shape) holds the sums over rows l < Lkeep whatever the mask says, zeros in chunks behind Lkeep.  No Yn is written.
+ *  - hriemo_pooled_fuse_fwd: partials_keep of both sides + gate weights w [B, d] -> Abar, Tbar, pooled (fp32 [B, d]).
+ *  - hriemo_pooled_fuse_bwd: dpooled (NULL: zero) -> dw = dpooled * (Abar - Tbar) [B, d] (one chunk of dw partials: hriemo_gate_dpre
+ *    with L <= 32) and the row gradients g_a = w * dpooled / Lkeep, g_t = (1 - w) * dpooled / Lkeep [B, d].
+ *  - hriemo_ln_pool_vec_bwd: hriemo_ln_pool_bwd with the fp32 vector g[b, :] (NULL: zero) standing in for coef * dH[b, l, :] on
+ *    rows l < Lkeep:  dYn[b, l] = (l < Lkeep ? g[b] : 0) + (valid ? dpool[b] : 0),  dX = LayerNorm'(dYn).  Same workspace
+ *    (hriemo_ln_pool_bwd_workspace_bytes), same dgamma | dbeta partial layout and the same dgamma / dbeta / accumulate rules.
+ *  - *_pair: both modalities from one launch, the blocks -- and the results -- of the single calls. */
+int hriemo_ln_pool2_fwd(const void* X, const float* X32, const unsigned char* mask, const float* gamma, const float* beta,
+                        float* mean, float* rstd, float* partials, float* partials_keep, int B, int L, int Lkeep, int d, float eps,
+                        hriemo_stream_t stream);
+int hriemo_ln_pool2_fwd_pair(const void* Xa, const float* Xa32, const unsigned char* mask_a, const float* gamma_a, const float* beta_a,
+                             float* mean_a, float* rstd_a, float* partials_a, float* partials_keep_a, int La,
+                             const void* Xt, const float* Xt32, const unsigned char* mask_t, const float* gamma_t, const float* beta_t,
+                             float* mean_t, float* rstd_t, float* partials_t, float* partials_keep_t, int Lt,
+                             int B, int Lkeep, int d, float eps, hriemo_stream_t stream);
+int hriemo_pooled_fuse_fwd(const float* partials_keep_a, int La, const float* partials_keep_t, int Lt, const float* w, int Lkeep,
+                           float* abar, float* tbar, float* pooled, int B, int d, hriemo_stream_t stream);
+int hriemo_pooled_fuse_bwd(const float* dpooled, const float* abar, const float* tbar, const float* w, int Lkeep, float* dw,
+                           float* g_a, float* g_t, int B, int d, hriemo_stream_t stream);
+int hriemo_ln_pool_vec_bwd(const float* g, int Lkeep, const float* dpool, const unsigned char* mask, const void* X, const float* X32,
+                           const float* gamma, const float* mean, const float* rstd, void* dX, float* dgamma, float* dbeta,
+                           int accumulate, int B, int L, int d, float* workspace, hriemo_stream_t stream);
+int hriemo_ln_pool_vec_bwd_pair(int Lkeep,
+                                const float* g_a, const float* dpool_a, const unsigned char* mask_a, const void* Xa, const float* Xa32, const float* gamma_a,
+                                const float* mean_a, const float* rstd_a, void* dXa, float* dgamma_a, float* dbeta_a, int La, float* workspace_a,
+                                const float* g_t, const float* dpool_t, const unsigned char* mask_t, const void* Xt, const float* Xt32, const float* gamma_t,
+                                const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t, float* dbeta_t, int Lt, float* workspace_t,
+                                int accumulate, int B, int d, hriemo_stream_t stream);
+/* Packed rows in, PADDED rows out (the classifier's front door): X packed [n_rows, d] (x_dtype 0 fp32, 1 bf16, 2 fp16; row stride
+ * ldx elements) with cu_seqlens int32 [>= B + 1] in device memory -> Y16 bf16 [B, L, d] and the fp32 twin Y32 (either may be NULL).
+ * Row (b, l) is source row cu[b] + l for l < cu[b+1] - cu[b] and zeros behind it; no source row at or behind min(cu[B], n_rows) is
+ * read.  A valid row equals hriemo_ingest_rows followed by hriemo_unpack_rows bit for bit. */
+int hriemo_ingest_padded(const void* X, int x_dtype, long ldx, const int* cu_seqlens, int n_rows, int B, int L, int d, void* Y16,
+                         float* Y32, hriemo_stream_t stream);
+
 /* ---- the gate on packed (varlen) rows: the encoder's packed output feeds the gate and the gate's h_fusion stays packed for the
  * decoder, so no hriemo_unpack_rows / hriemo_pack_rows runs between the encoder and the loss.
  *  - A modality's X / X32 / mean / rstd / dX are packed [n_rows, d] buffers with cu_seqlens (int32 [nseq + 1], device memory):
