@@ -396,6 +396,39 @@ class _PackedState:
     def __getitem__(self, name):      # bench.py reads _pb["graphs"]
         return getattr(self, name)
 
+    def graph(self, key, cap, capture, label):
+        """The record of bucket `key`, the least recently used one last.  A bucket not seen yet is captured on the spot, on the static
+        state (already this batch): at most `cap` graphs stay alive, the three bucket plans are built, ``capture(seqs)`` -> the
+        bucket's _GraphRecord does whatever the step records (and sets aside whatever its warm-up passes would disturb), and the
+        record is kept only once capture() has returned.  label: the step, as the log names it."""
+        from . import _ops
+        rec = self.graphs.get(key)
+        if rec is not None:
+            self.graphs.move_to_end(key)
+            return rec
+        # a bucket met inside a step runs two eager warm-up passes + the capture pass; a trainer's draw dropout seeds from torch's
+        # CPU generator (an evaluation's draw nothing).  Ranks meet new buckets at different steps, so the generator is put back:
+        # its stream stays the one the caller (and every other rank) sees, as _ops.next_seed documents.  (The step's first capture
+        # keeps its draws.)
+        rng = torch.get_rng_state() if self.graphs else None
+        try:
+            while len(self.graphs) >= cap:
+                # bounded: a corpus with a wide length spread would otherwise accumulate a graph + its buffers per bucket pair
+                old_key, old = self.graphs.popitem(last=False)
+                torch.cuda.synchronize()
+                old.release()
+                log.info("%s: released the graph of bucket %s (cap %d)", label, old_key, cap)
+            seqs = (_ops.seq_bucket(self.cu_a, self.B, self.La, key[0]), _ops.seq_bucket(self.cu_t, self.B, self.Lt, key[1]),
+                    _ops.seq_bucket_fused(self.cu_f, self.B, min(self.La, self.Lt), key[1]))
+            if self.pool is None:
+                self.pool = torch.cuda.graph_pool_handle()
+            rec = self.graphs[key] = capture(seqs)
+        finally:
+            if rng is not None:
+                torch.set_rng_state(rng)
+        log.info("%s: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", label, key, len(self.graphs))
+        return rec
+
 
 def _load_ragged(pb, static, fill, la, lt, ctl=None):
     """A checked ragged batch into the static state of a step captured from ragged batches (static = [src_a, src_t, -, -, y]) -> its
@@ -427,6 +460,16 @@ def _caller_rows(rows_a, rows_t, y):
     return fill
 
 
+def _check_count(who, n, B, partial):
+    """ValueError for a batch of n utterances that a step captured for B cannot take: more than B, or another number than B
+    unless short batches are served (partial)"""
+    if n > B:
+        raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds at most B = {B}")
+    if n != B and not partial:
+        raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds B = {B} (drop the batch, run it with "
+                         "use_graph(False), or capture with partial_batches=True)")
+
+
 class _StoreFeed:
     """what capture_store adds in front of the ragged front door: the data.DeviceFeatureStore the step reads and its version at
     capture, and the plan block -- int32 [3, 2B + 1]: {ids[n], dst_cu[n + 1]} for the audio rows, the text rows and the targets, zero
@@ -452,12 +495,7 @@ class _StoreFeed:
         if st.version != self.version:
             raise RuntimeError(f"{who}: the store changed since the capture (append): capture_store() again")
         ids = st.check_ids(ids)
-        n = len(ids)
-        if n > self.B:
-            raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds at most B = {self.B}")
-        if n != self.B and not partial:
-            raise ValueError(f"{who}: a batch of {n} utterances; the captured step holds B = {self.B} (drop the batch, run it with "
-                             "use_graph(False), or capture with partial_batches=True)")
+        _check_count(who, len(ids), self.B, partial)
         return (ids,) + _store_batch(st, ids, self.pad, who)
 
     def fill(self, ids, targets=True):
@@ -479,36 +517,22 @@ def _store_batch(store, ids, pad, who):
     return la, lt
 
 
-def _store_capture_facts(who, model, store, ids, pad_to):
-    """the host checks capture_store shares between the trainer and the evaluation step -> (ids, (La, Lt))"""
-    from .data import DeviceFeatureStore
-    if not isinstance(store, DeviceFeatureStore):
-        raise TypeError(f"{who}: store is a data.DeviceFeatureStore")
-    ids = store.check_ids(ids)
-    dev = next(model.parameters()).device
-    if store.device != dev:
-        raise ValueError(f"{who}: the store lives on {store.device}, the model on {dev}")
-    La, Lt = (int(v) for v in (pad_to if pad_to is not None else store.pad_to))
-    if Lt > La:
-        raise RuntimeError(f"{who}: L_t={Lt} > L_a={La}: the gate fuses over the text length and needs L_a >= L_t")
-    if not hasattr(model, "audio_proj") and store.widths[0] != store.widths[1]:
-        raise ValueError(f"{who}: the store's rows differ in width {store.widths}")
-    return ids, (La, Lt)
+_capture_streams = {}         # device index -> the one stream every capture of this process records on
 
 
 def _record_graph(dev, seqs, pool, warm, body, warmed=None, settle=0.0):
     """The capture mechanics every captured step of the process shares: two eager warm-up passes (`warm()`) on the process's one
-    capture stream of `dev`, then `body()` recorded into a fresh graph on that stream (pool: the memory pool of a bucket graph, or
-    None) with CTX.capturing / capture_origin / seq_override in force.  -> the graph's _GraphRecord, whose `loss` is what body()
-    returned (the caller moves it where it belongs).  The one way up for _ops.GRAPHS_ALIVE.  warmed(): called behind the warm-up
+    capture stream of `dev`, then `body()` -> (loss, out) recorded into a fresh graph on that stream (pool: the memory pool of a
+    bucket graph, or None) with CTX.capturing / capture_origin / seq_override in force.  -> the graph's _GraphRecord with that loss
+    and those outputs (None: a trainer step has none).  The one way up for _ops.GRAPHS_ALIVE.  warmed(): called behind the warm-up
     passes, in front of the capture (drop what they left).  settle: seconds to wait between the
     warm-up passes and the capture (eager collectives in the warm-up, DataParallelStep._capture_graph)."""
     from . import _ops
     # ONE capture stream per device for every capture of the process: workspaces are keyed by stream, a fresh stream per
     # capture would allocate (and, with a graph alive, retire instead of free) a fresh 64 MB+ set each time
-    side = DataParallelStep._capture_streams.get(dev.index)
+    side = _capture_streams.get(dev.index)
     if side is None:
-        side = DataParallelStep._capture_streams[dev.index] = torch.cuda.Stream(device=dev)
+        side = _capture_streams[dev.index] = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream())
     _ops.CTX.seq_override = seqs
     try:
@@ -532,7 +556,7 @@ def _record_graph(dev, seqs, pool, warm, body, warmed=None, settle=0.0):
             # thread_local: the RCCL watchdog thread may query events while we capture
             kw = {"pool": pool} if pool is not None else {}
             with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local", **kw):
-                out = body()
+                loss, out = body()
         finally:
             _ops.CTX.capturing = False
             _ops.CTX.capture_origin = None
@@ -543,10 +567,139 @@ def _record_graph(dev, seqs, pool, warm, body, warmed=None, settle=0.0):
     # this graph: they move from the process-wide lists to the graph's owner
     keep = _ops._deferred.keep + _ops._small_dw.keep
     _ops._deferred.keep, _ops._small_dw.keep = [], []
-    return _GraphRecord(graph, out, keep, seqs)
+    return _GraphRecord(graph, loss, keep, seqs, out)
 
 
-class DataParallelStep:
+def _ragged_state(model, B, pad, widths, dtype, y_static, partial, accum, ctl):
+    """The static state of a step captured from ragged batches -> (its _PackedState, the static list [src_a, src_t, None, None, y]):
+    one zero-initialised row source per modality, `widths` wide, in `dtype` and as long as the LARGEST bucket (a full batch of B*L
+    rows still gets its surplus sequence, bucket_rows); the lengths as one int32 [2, B] block; the three masks; y_static (or None:
+    a prediction-only evaluation); the _RaggedFront with the step-control block when `ctl` says there is one."""
+    dev = next(model.parameters()).device
+    La, Lt = pad
+    src_a = torch.zeros(bucket_rows(B * La, B, La), widths[0], dtype=dtype, device=dev)
+    src_t = torch.zeros(bucket_rows(B * Lt, B, Lt), widths[1], dtype=dtype, device=dev)
+    masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
+    front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, not hasattr(model, "audio_proj"), partial, accum,
+                         _HostBlock(ctl_words(B, 1, 1), dev) if ctl else None)
+    return _PackedState(B, La, Lt, dev, front), [src_a, src_t, None, None, y_static]
+
+
+class _RaggedStep:
+    """What a captured trainer step (DataParallelStep) and a captured evaluation (EvalStep) are alike: a model whose static state
+    (_static, _pb) ragged batches are loaded into -- rows the caller holds, or ids of a data.DeviceFeatureStore behind a feed
+    (_feed) -- and one graph per bucket, picked or captured on the spot and replayed.  A subclass adds what its graphs record
+    (_capture_bucket; _label names it in the log), how its old step goes, and its entry points with their own refusals."""
+
+    max_graphs = None             # bucket graphs kept alive; None: _VARLEN_MAX_GRAPHS (EvalStep takes its own)
+
+    def __init__(self, model, loss_fn):
+        from . import _ops
+        self.model, self.loss_fn = model, loss_fn
+        self.ctx = _ops.StepContext()      # this step's capture flag / packed plan / join scope: not shared with another step's
+        self._pb = None               # _PackedState of a step captured in packed (varlen) mode: shapes, cu_seqlens, bucket graphs, front
+        self._static = None           # the static batch the captured step reads: [h_a | src_a, h_t | src_t, m_a, m_t, y | None]
+        self._feed = None             # _StoreFeed of a step captured on a data.DeviceFeatureStore (capture_store)
+        self._replay = True           # use_graph(False) runs a captured step eagerly
+
+    @property
+    def captured(self):
+        """bucket graphs exist (use_graph decides whether they are replayed)"""
+        return self._pb is not None and len(self._pb.graphs) > 0
+
+    @property
+    def _replaying(self):
+        return self._replay and self.captured
+
+    @property
+    def store(self):
+        """the data.DeviceFeatureStore this step was captured on (capture_store) and the ids of step_store / eval_store refer to;
+        None otherwise"""
+        return None if self._feed is None else self._feed.store
+
+    def _packed_graph(self, key):
+        """the record of bucket `key`: captured on the static state (already this batch) when the bucket is new"""
+        return self._pb.graph(key, self.max_graphs if self.max_graphs is not None else _VARLEN_MAX_GRAPHS, self._capture_bucket, self._label)
+
+    def _release_buckets(self):
+        """every bucket graph goes, with the buffers its kernels point into, and the feed closes: the store may grow again"""
+        if self._pb is not None and self._pb.graphs:
+            torch.cuda.synchronize()
+            for rec in self._pb.graphs.values():
+                rec.release()
+        if self._feed is not None:
+            self._feed.close()
+            self._feed = None
+
+    def _need_forward_packed(self, who):
+        if not hasattr(self.model, "_forward_rows"):
+            raise TypeError(f"{who}: the model has no forward_packed entry")
+
+    def _need_n_valid(self, who):
+        if not _accepts_n_valid(self.loss_fn):
+            raise TypeError(f"{who}: loss_fn takes no n_valid= keyword -- the ghost utterances of a short batch must stay out of "
+                            "the loss (hri_emo_amd.train's losses accept it)")
+
+    def _store_capture(self, who, store, ids, pad_to, targets=True):
+        """the host checks of capture_store, before the old step is given up -> (ids, audio lengths, text lengths, (La, Lt), the
+        static targets: zeros in the store's form, or None without `targets`)"""
+        from .data import DeviceFeatureStore
+        if not isinstance(store, DeviceFeatureStore):
+            raise TypeError(f"{who}: store is a data.DeviceFeatureStore")
+        ids = store.check_ids(ids)
+        dev = next(self.model.parameters()).device
+        if store.device != dev:
+            raise ValueError(f"{who}: the store lives on {store.device}, the model on {dev}")
+        La, Lt = (int(v) for v in (pad_to if pad_to is not None else store.pad_to))
+        if Lt > La:
+            raise RuntimeError(f"{who}: L_t={Lt} > L_a={La}: the gate fuses over the text length and needs L_a >= L_t")
+        if not hasattr(self.model, "audio_proj") and store.widths[0] != store.widths[1]:
+            raise ValueError(f"{who}: the store's rows differ in width {store.widths}")
+        la, lt = _store_batch(store, ids, (La, Lt), who)
+        y_static = torch.zeros((len(ids),) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev) if targets else None
+        return ids, la, lt, (La, Lt), y_static
+
+    def _capture_ragged(self, begin, widths, dtype, y_static, la, lt, pad, load, store=None, partial=True, accum=1, ctl=True):
+        """What every capture from ragged batches does behind its entry's checks: begin() -- the old step goes (behind the refusals
+        that need it untouched) and the subclass's facts of the new one are set --, the static state is built (_ragged_state), a
+        step that reads `store` gets its _StoreFeed (made after the old step and its feed have gone), the first batch is loaded by
+        load() -> bucket key and its bucket graph is captured."""
+        from . import _ops
+        _ops._require_gpu(next(self.model.parameters()))
+        begin()
+        self._pb, self._static = _ragged_state(self.model, len(la), pad, widths, dtype, y_static, partial, accum, ctl)
+        try:
+            if store is not None:
+                self._feed = _StoreFeed(store, len(la), pad, self._static[0].device)
+            self._packed_graph(load())
+        except BaseException:
+            self.release_graph()          # a failed capture leaves no graph behind -- and no feed that would keep the store from growing
+            raise
+
+    def _check_batch(self, who, rows_a, rows_t, n, y):
+        """the refusals of a ragged batch whose rows the caller holds, before anything is enqueued: the number of utterances, row
+        width / dtype against the static sources, the targets' shape against the static targets (when the step holds any)"""
+        B, sy = self._pb.B, self._static[4]
+        _check_count(who, n, B, self._pb.front.partial)
+        for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
+            if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
+                raise ValueError(f"{who}: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
+        if sy is not None:
+            want = (n,) + tuple(sy.shape[1:])
+            if tuple(y.shape) != want:
+                raise ValueError(f"{who}: targets of shape {tuple(y.shape)}; captured with {tuple(sy.shape)}"
+                                 + (f", this batch needs {want}" if n != B else ""))
+
+    def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
+        """a checked ragged batch whose rows the caller holds into the static state -> its bucket key (_load_ragged)"""
+        return _load_ragged(self._pb, self._static, _caller_rows(rows_a, rows_t, y), la, lt, ctl)
+
+    def _load_store(self, ids, la, lt, ctl=None):
+        """a checked batch of ids of the captured store into the static state -> its bucket key (_load_ragged)"""
+        return _load_ragged(self._pb, self._static, self._feed.fill(ids, self._static[4] is not None), la, lt, ctl)
+
+
+class DataParallelStep(_RaggedStep):
     """fwd -> loss -> bwd -> gradient all-reduce for one shard; mirrors the order of operations of
     train_one_epoch (scripts/fusion/train_fusion_seq_level_decoder.py:310-334) minus the optimizer.
 
@@ -557,44 +710,29 @@ class DataParallelStep:
     all-reduce runs after the replay on the flat buffer.  ``capture(..., optimizer=opt)`` with an ``optim.DeviceAdamW``
     records the optimizer's three launches at the end of the graph as well: one ``step()`` is then the whole trainer step."""
 
-    _capture_streams = {}         # device index -> the one stream every capture of this process records on
+    _label = "packed step"
 
     def __init__(self, model, loss_fn, group=None, bucket_bytes=32 << 20, overlap=True, comm_dtype=torch.float32, force_exchange=False,
                  launch_from="notify", force_queue=None):
-        self.model, self.loss_fn = model, loss_fn
+        super().__init__(model, loss_fn)
         self.force_queue = force_queue    # None: the loader / consumer GEMMs draw from the work queue when collectives run beside backward; True / False: always / never
         self._exchange_in_graph = False   # capture(collectives=True): the bucket all-reduces are part of the captured step
-        self._replay = True               # use_graph(False) runs a captured step eagerly
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.buckets = GradBuckets(model.parameters(), bucket_bytes, group, overlap, comm_dtype, force_exchange, launch_from)
-        from . import _ops
-        self.ctx = _ops.StepContext()      # this step's capture flag / packed plan / join scope: not shared with another model's
         # a captured graph has one owner: _record (the plain step) or _pb.graphs (the packed modes, one record per bucket)
         self._record = None
-        self._pb = None               # _PackedState of a step captured in packed (varlen) mode, see capture()
-        self._static = None           # the static batch the captured step reads: [h_a, h_t, m_a, m_t, y]
         self._mask_seen = None        # mask-fed packed step: (mask identity, bucket key, cu_seqlens clones, the masks) of the last step
         self._optimizer = None        # optim.DeviceAdamW whose update closes the captured step (capture(optimizer=...))
         self._micro = 0               # micro-steps of the open accumulation group (capture_packed(grad_accum=k)): 0 .. k-1
         self._stats = None            # train.EpochStats fed by every executed (micro-)step (attach_stats)
         self._stats_scale = 1.0
         self._outputs = None          # with statistics attached: what the latest _fwd_bwd pass hands to _update_stats
-        self._feed = None             # _StoreFeed of a step captured on a data.DeviceFeatureStore (capture_store)
 
     @property
     def captured(self):
         """a captured step exists (use_graph decides whether step() replays it)"""
         return self._record is not None or (self._pb is not None and len(self._pb.graphs) > 0)
-
-    @property
-    def _replaying(self):
-        return self._replay and self.captured
-
-    @property
-    def store(self):
-        """the data.DeviceFeatureStore this step was captured on (capture_store) and step_store's ids refer to; None otherwise"""
-        return None if self._feed is None else self._feed.store
 
     def set_global_batch(self, global_batch):
         lo, hi = shard_bounds(global_batch, self.rank, self.world)
@@ -816,46 +954,22 @@ class DataParallelStep:
         if pad_to is None:
             raise ValueError("capture_packed: pad_to=(L_a, L_t) is required")
         dev = next(self.model.parameters()).device
-        self._capture_ragged("capture_packed", (rows_a.shape[1], rows_t.shape[1]), rows_a.dtype, y.to(dev, copy=True), la, lt, pad,
-                             lambda: self._load_packed(rows_a, rows_t, la, lt, y), optimizer, collectives, partial_batches, grad_accum)
+        self._capture_ragged(lambda: self._begin_ragged("capture_packed", optimizer, collectives), (rows_a.shape[1], rows_t.shape[1]),
+                             rows_a.dtype, y.to(dev, copy=True), la, lt, pad, lambda: self._load_packed(rows_a, rows_t, la, lt, y),
+                             partial=partial_batches, accum=grad_accum, ctl=partial_batches or grad_accum > 1)
+        self._end_capture()
 
     def _check_ragged_capture(self, entry, partial_batches, grad_accum):
-        if not hasattr(self.model, "_forward_rows"):
-            raise TypeError(f"{entry}: the model has no forward_packed entry")
+        self._need_forward_packed(entry)
         if int(grad_accum) != grad_accum or grad_accum < 1:
             raise ValueError(f"{entry}: grad_accum = {grad_accum!r} (an integer >= 1)")
-        if partial_batches and not _accepts_n_valid(self.loss_fn):
-            raise TypeError(f"{entry}(partial_batches=True): loss_fn takes no n_valid= keyword -- the ghost utterances of a short "
-                            "batch must stay out of the loss (hri_emo_amd.train's losses accept it)")
+        if partial_batches:
+            self._need_n_valid(f"{entry}(partial_batches=True)")
 
-    def _capture_ragged(self, entry, widths, dtype, y_static, la, lt, pad, load, optimizer, collectives, partial_batches, grad_accum,
-                        make_feed=None):
-        """what capture_packed and capture_store share behind their checks: the old step goes, the static state is built (row sources
-        of the largest bucket, zero-initialised; lengths block; masks; control block; y_static), the first batch is loaded by
-        load() -> bucket key and its bucket graph is captured.  make_feed(device) -> the _StoreFeed of a step that reads a store, made
-        after the old step (and its feed) has gone."""
-        from . import _ops
-        dev = next(self.model.parameters()).device
-        _ops._require_gpu(next(self.model.parameters()))
+    def _begin_ragged(self, entry, optimizer, collectives):
+        """_capture_ragged's begin(): the refusals capture() shares, the old step goes, a new accumulation group opens"""
         self._begin_capture(entry, optimizer, collectives, packed=True)
         self._micro = 0
-        B, (La, Lt) = len(la), pad
-        cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
-        src_a = torch.zeros(cap_a, widths[0], dtype=dtype, device=dev)
-        src_t = torch.zeros(cap_t, widths[1], dtype=dtype, device=dev)
-        self._static = [src_a, src_t, None, None, y_static]
-        masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
-        ctl = _HostBlock(ctl_words(B, 1, 1), dev) if (partial_batches or grad_accum > 1) else None
-        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, not hasattr(self.model, "audio_proj"), partial_batches, grad_accum, ctl)
-        self._pb = _PackedState(B, La, Lt, dev, front)
-        try:
-            if make_feed is not None:
-                self._feed = make_feed(dev)
-            self._packed_graph(load())
-        except BaseException:
-            self.release_graph()          # a failed capture leaves no graph behind -- and no feed that would keep the store from growing
-            raise
-        self._end_capture()
 
     @_in_step_context
     def capture_store(self, store, ids, pad_to=None, optimizer=None, collectives=False, partial_batches=False, grad_accum=1):
@@ -871,13 +985,11 @@ class DataParallelStep:
         While the step is captured the store refuses ``append``.  Data parallel: every rank holds the whole store (a few GB) and
         passes ITS slice of the global batch's ids (``shard_bounds``); ``set_batch_offset`` / ``set_global_batch`` are untouched."""
         self._check_ragged_capture("capture_store", partial_batches, grad_accum)
-        ids, pad = _store_capture_facts("capture_store", self.model, store, ids, pad_to)
-        B = len(ids)
-        la, lt = _store_batch(store, ids, pad, "capture_store")        # before the old step is given up
-        dev = next(self.model.parameters()).device
-        y_static = torch.zeros((B,) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev)
-        self._capture_ragged("capture_store", store.widths, store.dtype, y_static, la, lt, pad, lambda: self._load_store(ids, la, lt), optimizer,
-                             collectives, partial_batches, grad_accum, make_feed=lambda d: _StoreFeed(store, B, pad, d))
+        ids, la, lt, pad, y_static = self._store_capture("capture_store", store, ids, pad_to)
+        self._capture_ragged(lambda: self._begin_ragged("capture_store", optimizer, collectives), store.widths, store.dtype, y_static, la, lt,
+                             pad, lambda: self._load_store(ids, la, lt), store, partial=partial_batches, accum=grad_accum,
+                             ctl=partial_batches or grad_accum > 1)
+        self._end_capture()
 
     @_in_step_context
     def step_store(self, ids):
@@ -911,32 +1023,11 @@ class DataParallelStep:
         front = pb.front if pb is not None else None
         if front is None:
             raise RuntimeError("step_packed needs capture_packed() first")
-        B, pad = pb.B, (pb.La, pb.Lt)
-        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad, same_width=front.same_width)
+        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, (pb.La, pb.Lt), same_width=front.same_width)
         if self._replaying:
-            n = len(la)
-            if n != B and not front.partial:
-                raise ValueError(f"step_packed: a batch of {n} utterances; the captured step holds B = {B} (drop the batch, run it "
-                                 "with use_graph(False), or capture with partial_batches=True)")
-            if n > B:
-                raise ValueError(f"step_packed: a batch of {n} utterances; the captured step holds at most B = {B}")
-            for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
-                if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
-                    raise ValueError(f"step_packed: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
-            want = (n,) + tuple(self._static[4].shape[1:])
-            if tuple(y.shape) != want:
-                raise ValueError(f"step_packed: targets of shape {tuple(y.shape)}; captured with {tuple(self._static[4].shape)}"
-                                 + (f", this batch needs {want}" if n != B else ""))
+            self._check_batch("step_packed", rows_a, rows_t, len(la), y)
             return self._replay_ragged(lambda ctl: self._load_packed(rows_a, rows_t, la, lt, y, ctl=ctl))
         return self._eager_ragged(rows_a, rows_t, la, lt, y)
-
-    def _load_packed(self, rows_a, rows_t, la, lt, y, ctl=None):
-        """a checked ragged batch whose rows the caller holds into the static state -> its bucket key (_load_ragged)"""
-        return _load_ragged(self._pb, self._static, _caller_rows(rows_a, rows_t, y), la, lt, ctl)
-
-    def _load_store(self, ids, la, lt, ctl=None):
-        """a checked batch of ids of the captured store into the static state -> its bucket key (_load_ragged)"""
-        return _load_ragged(self._pb, self._static, self._feed.fill(ids), la, lt, ctl)
 
     def _replay_ragged(self, load):
         """a checked batch through the captured step, for every ragged front door: hyper-parameters up when this micro-step carries
@@ -1011,38 +1102,17 @@ class DataParallelStep:
             buf.copy_(torch.tensor(cu, dtype=torch.int32))
         return key
 
-    def _packed_graph(self, key):
-        from . import _ops
-        pb = self._pb
-        rec = pb.graphs.get(key)
-        if rec is None:
-            # a bucket met inside step() runs two eager warm-up passes + the capture pass; each draws dropout seeds from torch's
-            # CPU generator.  Ranks meet new buckets at different steps, so the generator is put back: its stream stays the one
-            # the caller (and every other rank) sees, as _ops.next_seed documents.  (The step's first capture keeps its draws.)
-            rng = torch.get_rng_state() if self.captured else None
-            while len(pb.graphs) >= _VARLEN_MAX_GRAPHS:
-                # bounded: a corpus with a wide length spread would otherwise accumulate a graph + its buffers per bucket pair
-                old_key, old = pb.graphs.popitem(last=False)
-                torch.cuda.synchronize()
-                old.release()
-                log.info("packed step: released the graph of bucket %s (cap %d)", old_key, _VARLEN_MAX_GRAPHS)
-            seqs = (_ops.seq_bucket(pb.cu_a, pb.B, pb.La, key[0]), _ops.seq_bucket(pb.cu_t, pb.B, pb.Lt, key[1]),
-                    _ops.seq_bucket_fused(pb.cu_f, pb.B, min(pb.La, pb.Lt), key[1]))
-            # inside an accumulation group the warm-up passes run with ctl.first = 0 and would add to the running gradient sum:
-            # it is set aside and put back (a copy of the flat buffer, paid only when a bucket is met for the first time)
-            front = pb.front
-            held = self.buckets.flat.clone() if (front is not None and front.accum > 1 and self._micro > 0) else None
-            try:
-                rec = pb.graphs[key] = self._capture_graph(seqs)
-            finally:
-                if rng is not None:
-                    torch.set_rng_state(rng)
-                if held is not None:
-                    self.buckets.flat.copy_(held)
-            log.info("packed step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb.graphs))
-        else:
-            pb.graphs.move_to_end(key)
-        return rec
+    def _capture_bucket(self, seqs):
+        """the bucket graph of the plans `seqs` (_PackedState.graph)"""
+        # inside an accumulation group the warm-up passes run with ctl.first = 0 and would add to the running gradient sum:
+        # it is set aside and put back (a copy of the flat buffer, paid only when a bucket is met for the first time)
+        front = self._pb.front
+        held = self.buckets.flat.clone() if (front is not None and front.accum > 1 and self._micro > 0) else None
+        try:
+            return self._capture_graph(seqs)
+        finally:
+            if held is not None:
+                self.buckets.flat.copy_(held)
 
     def _capture_graph(self, seqs):
         """warm-up + capture of one step on self._static; seqs = the packed plans of a bucket graph (or None) -> its _GraphRecord"""
@@ -1067,10 +1137,8 @@ class DataParallelStep:
                 front = self._pb.front if self._pb is not None else None
                 ctl = front.ctl.dev if (front is not None and front.accum > 1) else None
                 self._optimizer._enqueue(ctl=ctl)    # recorded, not run: norm, skip / hold / clip / bias corrections, update
-            return loss
+            return loss, None
 
-        if seqs is not None and self._pb.pool is None:
-            self._pb.pool = torch.cuda.graph_pool_handle()
         # The process group's watchdog thread polls the end event of every EAGER collective until it has seen it complete
         # (every 100 ms).  The warm-up exchanges are complete when the capture starts, but not necessarily reaped -- and once the
         # capture pulls the group's communication stream into the capture, ROCm 7.2 answers a query of an event that was
@@ -1081,14 +1149,13 @@ class DataParallelStep:
 
     def release_graph(self):
         """drop the captured step (before a re-capture, or to free its buffers): the graph(s), the buffers their kernels point into"""
-        if self.captured:
+        was = self.captured
+        if self._record is not None:
             torch.cuda.synchronize()
-            for rec in ([self._record] if self._record is not None else self._pb.graphs.values()):
-                rec.release()
+            self._record.release()
+        self._release_buckets()
+        if was:
             self._record = self._pb = self._optimizer = None
-        if self._feed is not None:
-            self._feed.close()            # the store may grow again
-            self._feed = None
 
     def use_graph(self, on):
         """Switch between the captured replay (gradient exchange after it) and eager launches (exchange from the
@@ -1152,7 +1219,7 @@ def _mode_switches():
             ("PACKED_TAIL_FP32", bool(_ops.PACKED_TAIL_FP32)), ("PACKED_TAIL_MX8", bool(_ops.PACKED_TAIL_MX8)), ("ingest", _ops.ingest()))
 
 
-class EvalStep:
+class EvalStep(_RaggedStep):
     """The evaluation half of an epoch as graph replays: capture_packed / step_packed of DataParallelStep for the FORWARD alone --
     the reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
     and the loop of scripts/infer/mosei_eval_infer.py.  An eager forward is ~150 launches issued from Python; one ``eval_packed``
@@ -1178,32 +1245,15 @@ class EvalStep:
     Needs set_varlen_maps(True); varlen_maps() and mfma_maps() then join the switches recorded at capture.  ``return_attention``
     itself is not part of the captured step."""
 
+    _label = "eval step"
+
     def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None):
-        from . import _ops
         if max_graphs is not None and int(max_graphs) < 1:
             raise ValueError("EvalStep: max_graphs is a positive integer (or None)")
-        self.model, self.loss_fn, self.stats, self.log, self.attn_log = model, loss_fn, stats, log, attn_log
+        super().__init__(model, loss_fn)
+        self.stats, self.log, self.attn_log = stats, log, attn_log
         self.max_graphs = None if max_graphs is None else int(max_graphs)
-        self.ctx = _ops.StepContext()      # this step's capture flag / packed plan: not shared with a trainer step's
-        self._pb = None                    # _PackedState: shapes, cu_seqlens buffers, the bucket graphs, the ragged front
-        self._static = None                # [src_a, src_t, None, None, y | None]: the layout _load_ragged fills
         self._modes = None                 # _mode_switches() at capture
-        self._feed = None                  # _StoreFeed of a step captured on a data.DeviceFeatureStore (capture_store)
-        self._replay = True
-
-    @property
-    def captured(self):
-        """bucket graphs exist (use_graph decides whether eval_packed replays them)"""
-        return self._pb is not None and len(self._pb.graphs) > 0
-
-    @property
-    def _replaying(self):
-        return self._replay and self.captured
-
-    @property
-    def store(self):
-        """the data.DeviceFeatureStore this step was captured on (capture_store) and eval_store's ids refer to; None otherwise"""
-        return None if self._feed is None else self._feed.store
 
     def use_graph(self, on):
         """False: eval_packed is the eager forward_packed evaluation (same outputs, same updates of stats and log)"""
@@ -1211,14 +1261,8 @@ class EvalStep:
 
     def release_graph(self):
         """drop the captured step: the graphs, their outputs, the buffers their kernels point into, the static state"""
-        if self.captured:
-            torch.cuda.synchronize()
-            for rec in self._pb.graphs.values():
-                rec.release()
+        self._release_buckets()
         self._pb = self._static = self._modes = None
-        if self._feed is not None:
-            self._feed.close()             # the store may grow again
-            self._feed = None
 
     def _switches(self):
         """the switches a replay depends on: with an attention log also the two that pick the export kernels"""
@@ -1240,27 +1284,23 @@ class EvalStep:
         log whose pad_to, layer counts or num_emotions are not the model's and this call's is a ValueError that leaves the step
         (and the log) as it was."""
         from . import _ops
-        if not hasattr(self.model, "_forward_rows"):
-            raise TypeError("EvalStep.capture_packed: the model has no forward_packed entry")
-        if self.loss_fn is not None and y is not None and not _accepts_n_valid(self.loss_fn):
-            raise TypeError("EvalStep.capture_packed: loss_fn takes no n_valid= keyword -- the ghost utterances of a short batch must "
-                            "stay out of the loss (hri_emo_amd.train's losses accept it)")
+        self._need_forward_packed("EvalStep.capture_packed")
+        if self.loss_fn is not None and y is not None:
+            self._need_n_valid("EvalStep.capture_packed")
         if self.stats is not None and (self.loss_fn is None or y is None):
             raise ValueError("EvalStep.capture_packed: statistics need a loss_fn and targets (prediction-only graphs feed the log)")
         same_width = not hasattr(self.model, "audio_proj")
         la, lt, pad = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, pad_to, same_width=same_width)
         if pad_to is None:
             raise ValueError("EvalStep.capture_packed: pad_to=(L_a, L_t) is required")
+        if y is not None and y.shape[0] != len(la):
+            raise ValueError(f"EvalStep.capture_packed: targets of shape {tuple(y.shape)} for {len(la)} utterances")
         dev = next(self.model.parameters()).device
-        _ops._require_gpu(next(self.model.parameters()))
-        B = len(la)
-        if y is not None and y.shape[0] != B:
-            raise ValueError(f"EvalStep.capture_packed: targets of shape {tuple(y.shape)} for {B} utterances")
-        self._check_attn_log("capture_packed", pad)
-        self._capture_ragged((rows_a.shape[1], rows_t.shape[1]), rows_a.dtype, None if y is None else y.to(dev, copy=True), la, lt, pad,
-                             lambda: _caller_rows(rows_a, rows_t, y))
+        self._capture_ragged(lambda: self._begin_ragged("capture_packed", pad), (rows_a.shape[1], rows_t.shape[1]), rows_a.dtype,
+                             None if y is None else y.to(dev, copy=True), la, lt, pad, lambda: self._load_packed(rows_a, rows_t, la, lt, y))
 
-    def _check_attn_log(self, entry, pad):
+    def _begin_ragged(self, entry, pad):
+        """_capture_ragged's begin(): the attention log's refusals, then the old graphs go and the switches in force are recorded"""
         from . import _ops
         if self.attn_log is not None:
             if not _ops.varlen_maps():
@@ -1268,31 +1308,9 @@ class EvalStep:
             why = self.attn_log.mismatch(self.model, pad)
             if why is not None:
                 raise ValueError(f"EvalStep.{entry}: the attention log does not fit: {why}")
-
-    def _capture_ragged(self, widths, dtype, y_static, la, lt, pad, make_fill, make_feed=None):
-        """what capture_packed and capture_store share behind their checks: the old graphs go, the static state is built, the first
-        batch is loaded by make_fill()'s fill (_load_ragged) and its bucket graph is captured.  make_feed(device) -> the _StoreFeed
-        of a step that reads a store."""
-        dev = next(self.model.parameters()).device
         self.release_graph()              # a re-capture replaces the old graphs
-        B, (La, Lt) = len(la), pad
-        cap_a, cap_t = bucket_rows(B * La, B, La), bucket_rows(B * Lt, B, Lt)
-        src_a = torch.zeros(cap_a, widths[0], dtype=dtype, device=dev)
-        src_t = torch.zeros(cap_t, widths[1], dtype=dtype, device=dev)
-        self._static = [src_a, src_t, None, None, y_static]
-        masks = tuple(torch.ones(B, L, dtype=torch.uint8, device=dev) for L in (La, Lt, Lt))
-        front = _RaggedFront(_HostBlock([[1] * B] * 2, dev), masks, not hasattr(self.model, "audio_proj"), partial=True, accum=1,
-                             ctl=_HostBlock(ctl_words(B, 1, 1), dev))
-        self._pb = _PackedState(B, La, Lt, dev, front)
         self._modes = self._switches()
         self._replay = True
-        try:
-            if make_feed is not None:
-                self._feed = make_feed(dev)
-            self._packed_graph(_load_ragged(self._pb, self._static, make_fill(), la, lt))
-        except BaseException:
-            self.release_graph()
-            raise
 
     @_in_step_context
     def capture_store(self, store, ids, pad_to=None):
@@ -1301,24 +1319,15 @@ class EvalStep:
         (with the store's targets when the step has a loss_fn, prediction-only without); ``eval_store(ids)`` uploads one plan block
         and launches hriemo_gather_rows once per operand in front of the replay.  stats, log and attn_log work as before.  While the
         step is captured the store refuses ``append``."""
-        from . import _ops
-        if not hasattr(self.model, "_forward_rows"):
-            raise TypeError("EvalStep.capture_store: the model has no forward_packed entry")
+        self._need_forward_packed("EvalStep.capture_store")
         targets = self.loss_fn is not None
-        if targets and not _accepts_n_valid(self.loss_fn):
-            raise TypeError("EvalStep.capture_store: loss_fn takes no n_valid= keyword -- the ghost utterances of a short batch must "
-                            "stay out of the loss (hri_emo_amd.train's losses accept it)")
+        if targets:
+            self._need_n_valid("EvalStep.capture_store")
         if self.stats is not None and not targets:
             raise ValueError("EvalStep.capture_store: statistics need a loss_fn (prediction-only graphs feed the log)")
-        ids, pad = _store_capture_facts("EvalStep.capture_store", self.model, store, ids, pad_to)
-        B = len(ids)
-        la, lt = _store_batch(store, ids, pad, "EvalStep.capture_store")
-        dev = next(self.model.parameters()).device
-        _ops._require_gpu(next(self.model.parameters()))
-        self._check_attn_log("capture_store", pad)
-        y_static = torch.zeros((B,) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev) if targets else None
-        self._capture_ragged(store.widths, store.dtype, y_static, la, lt, pad, lambda: self._feed.fill(ids, targets),
-                             make_feed=lambda d: _StoreFeed(store, B, pad, d))
+        ids, la, lt, pad, y_static = self._store_capture("EvalStep.capture_store", store, ids, pad_to, targets)
+        self._capture_ragged(lambda: self._begin_ragged("capture_store", pad), store.widths, store.dtype, y_static, la, lt, pad,
+                             lambda: self._load_store(ids, la, lt), store)
 
     @_in_step_context
     def eval_store(self, ids):
@@ -1338,16 +1347,12 @@ class EvalStep:
             rows_a, _, rows_t, _, y = feed.store.fetch(ids)
             return self._eval_eager(rows_a, rows_t, la, lt, y if targets else None)
         self._check_modes("eval_store", "capture_store")
-        rec = self._packed_graph(_load_ragged(pb, self._static, feed.fill(ids, targets), la, lt))
-        rec.graph.replay()
-        logits, beta, z = rec.out
-        n = len(ids)
-        return logits[:n], beta[:n], z[:n], rec.loss
+        return self._replay_bucket(self._load_store(ids, la, lt), len(ids))
 
     def _pass(self, record):
         """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
         stats, log and attention log (the capture pass only; a warm-up pass runs the exports under the closed window)
-        -> (logits, beta, z, loss | None)"""
+        -> (loss | None, (logits, beta, z)), the form _record_graph takes"""
         from . import _ops
         pb = self._pb
         front = pb.front
@@ -1367,40 +1372,23 @@ class EvalStep:
                 self.stats.update(logits, beta, y, loss, n_valid=n_valid)
             if record and self.log is not None:
                 self.log.update(logits, beta, n_valid=n_valid)
-        return logits, beta, z, loss
+        return loss, (logits, beta, z)
 
-    def _packed_graph(self, key):
-        """the record of bucket `key`: captured on the static state (already this batch) when the bucket is new"""
-        from . import _ops
-        pb = self._pb
-        rec = pb.graphs.get(key)
-        if rec is not None:
-            pb.graphs.move_to_end(key)
-            return rec
-        # nothing of an evaluation draws from torch's CPU generator; a bucket met inside eval_packed still hands it back as it was
-        rng = torch.get_rng_state() if self.captured else None
-        cap = self.max_graphs if self.max_graphs is not None else _VARLEN_MAX_GRAPHS
-        while len(pb.graphs) >= cap:
-            old_key, old = pb.graphs.popitem(last=False)
-            torch.cuda.synchronize()
-            old.release()
-            log.info("eval step: released the graph of bucket %s (cap %d)", old_key, cap)
-        seqs = (_ops.seq_bucket(pb.cu_a, pb.B, pb.La, key[0]), _ops.seq_bucket(pb.cu_t, pb.B, pb.Lt, key[1]),
-                _ops.seq_bucket_fused(pb.cu_f, pb.B, min(pb.La, pb.Lt), key[1]))
-        if pb.pool is None:
-            pb.pool = torch.cuda.graph_pool_handle()
+    def _capture_bucket(self, seqs):
+        """the bucket graph of the plans `seqs` (_PackedState.graph): the module in eval mode while it is warmed up and recorded"""
         was = self.model.training
         self.model.eval()
         try:
-            rec = _record_graph(self._static[0].device, seqs, pb.pool, lambda: self._pass(False), lambda: self._pass(True))
+            return _record_graph(self._static[0].device, seqs, self._pb.pool, lambda: self._pass(False), lambda: self._pass(True))
         finally:
             self.model.train(was)
-            if rng is not None:
-                torch.set_rng_state(rng)
-        rec.out, rec.loss = rec.loss[:3], rec.loss[3]
-        pb.graphs[key] = rec
-        log.info("eval step: captured the graph of bucket (audio rows, text rows) = %s (%d alive)", key, len(pb.graphs))
-        return rec
+
+    def _replay_bucket(self, key, n):
+        """the graph of bucket `key` (captured now if it is new) replayed on the static state -> the outputs of its first n samples"""
+        rec = self._packed_graph(key)
+        rec.graph.replay()
+        logits, beta, z = rec.out
+        return logits[:n], beta[:n], z[:n], rec.loss
 
     def _check_modes(self, entry="eval_packed", capture="capture_packed"):
         for (name, then), (_, now) in zip(self._modes, self._switches()):
@@ -1423,31 +1411,18 @@ class EvalStep:
         pb = self._pb
         if pb is None:
             raise RuntimeError("eval_packed needs capture_packed() first")
-        front = pb.front
-        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, (pb.La, pb.Lt), same_width=front.same_width)
+        la, lt, _ = _ops.packed_lengths(rows_a, rows_t, lengths_a, lengths_t, (pb.La, pb.Lt), same_width=pb.front.same_width)
         n = len(la)
         if not self._replaying:
             return self._eval_eager(rows_a, rows_t, la, lt, y)
         self._check_modes()
-        if n > pb.B:
-            raise ValueError(f"eval_packed: a batch of {n} utterances; the captured step holds at most B = {pb.B}")
-        for name, rows, src in (("rows_a", rows_a, self._static[0]), ("rows_t", rows_t, self._static[1])):
-            if rows.shape[1] != src.shape[1] or rows.dtype != src.dtype:
-                raise ValueError(f"eval_packed: {name} of width {rows.shape[1]} / {rows.dtype}; captured with width {src.shape[1]} / {src.dtype}")
         sy = self._static[4]
         if sy is None and y is not None:
             raise ValueError("eval_packed: targets given, but the step was captured without (prediction-only graphs)")
         if sy is not None and y is None:
             raise ValueError("eval_packed: the step was captured with targets; this batch has none")
-        if sy is not None:
-            want = (n,) + tuple(sy.shape[1:])
-            if tuple(y.shape) != want:
-                raise ValueError(f"eval_packed: targets of shape {tuple(y.shape)}; captured with {tuple(sy.shape)}"
-                                 + (f", this batch needs {want}" if n != pb.B else ""))
-        rec = self._packed_graph(_load_ragged(pb, self._static, _caller_rows(rows_a, rows_t, y), la, lt))
-        rec.graph.replay()
-        logits, beta, z = rec.out
-        return logits[:n], beta[:n], z[:n], rec.loss
+        self._check_batch("eval_packed", rows_a, rows_t, n, y)
+        return self._replay_bucket(self._load_packed(rows_a, rows_t, la, lt, y), n)
 
     def _eval_eager(self, rows_a, rows_t, la, lt, y):
         pb = self._pb
