@@ -2340,6 +2340,76 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
         return (dx.view(B, L, d), None, r(dw1), r(db1), r(dw2), r(db2), r(dgamma), r(dbeta)) + (None,) * 7
 
 
+def _gate_align(La, Lt):
+    """the fused length: both streams aligned to the text length (beta_gate_tacfn.py:98-104, beta_gate.py:97-101)"""
+    L = La if La == Lt else Lt
+    if La < L:
+        raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
+    return L
+
+
+def _gate_prologue(h_a, h_a32, h_t, h_t32, params, sa, st):
+    """what both gate forwards do before their first launch -> (L, xa, h_a32, xt, h_t32, (mean, rstd, masked-pool partials) of the
+    audio side, the same of the text side)"""
+    L = _gate_align(sa.L, st.L)
+    _require_fp32_masters(*params)
+    _require_gpu(h_a)
+    d = h_a.shape[-1]
+    f32 = dict(dtype=torch.float32, device=h_a.device)
+    chunks = _lib.lib().hriemo_pool_chunks
+    bufs = lambda s: (torch.empty(s.N, **f32), torch.empty(s.N, **f32), torch.empty((s.Breal, chunks(s.L), d), **f32))  # noqa: E731
+    return L, _contig_bf16(h_a), _c32(h_a32), _contig_bf16(h_t), _c32(h_t32), bufs(sa), bufs(st)
+
+
+def _both_sides(d, dev, pair, single, side_a, side_t, two_streams=False, shared=()):
+    """One step of the gate for both modalities.  pair(side_a, side_t): both from ONE launch, no fork / join around the step (two graph
+    edges and 10-27 us of idle device each) -- where the library has it (d <= 1024) and the caller offers it (pair not None).  Else
+    single(*side) per modality; the two are independent: with two_streams the (small) text one runs on the side stream beside the audio
+    one -- `shared`: what the side stream touched of this stream's tensors -- else behind it."""
+    main = torch.cuda.current_stream(dev)
+    side = side_stream(dev) if two_streams else None
+    if pair is not None and _lib.lib().hriemo_ln_pool_pair_supported(d):
+        pair(side_a, side_t)
+    elif side is not None and side != main:
+        fork(side, main)
+        with torch.cuda.stream(side):
+            single(*side_t)
+        single(*side_a)
+        main.wait_stream(side)
+        if not CTX.capturing:
+            for t_ in shared:
+                share(t_, side)
+    else:
+        single(*side_a)
+        single(*side_t)
+
+
+class _LnAffine:
+    """The LayerNorm-affine gradients grads = (dga, dba, dgt, dbt) of a gate backward.  They are finished by the launch-boundary reduce
+    when they accumulate into .grad inside backward (defer: the kernels' partial sums then live in buffers of their own and outs is all
+    None), else by the launch's own reduce, out of the shared workspace slot."""
+
+    def __init__(self, sink, grads, B, La, Lt, d, dev):
+        L_ = _lib.lib()
+        self.defer = sink.fused and DEFER_REDUCE and _in_backward()
+        self.grads, self.outs, self.acc = grads, (None,) * 4 if self.defer else grads, int(sink.fused)
+        self.nbytes = tuple(L_.hriemo_ln_pool_bwd_workspace_bytes(B, L, d) for L in (La, Lt))
+        self.rows = tuple(B * L_.hriemo_ln_pool_bwd_chunks(L) for L in (La, Lt))
+        self.d, self.dev = d, dev
+
+    def workspaces(self):
+        """(audio, text) for launches on ONE stream: own buffers when deferring, else one slot split at a 64-float boundary"""
+        if self.defer:
+            return tuple(torch.empty(n // 4 + 16, dtype=torch.float32, device=self.dev) for n in self.nbytes)
+        wsa = workspace(sum(self.nbytes) + 256, self.dev, slot=1)
+        return wsa, wsa[(self.nbytes[0] // 4 + 63) // 64 * 64:]
+
+    def queue(self, ws, text):
+        """behind the launch that left the partial sums of one side (text = 0 | 1) in ws"""
+        if self.defer:
+            _deferred.add(ws, 2 * self.d, self.rows[text], self.d, 2, list(self.grads[2 * text:2 * text + 2]), True)
+
+
 def _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh):
     """the vector gate from the pooled partial sums of both modalities (beta_gate_tacfn.py:83-95): masked means, gate input
     [a, t, |a-t|, a*t], the two-layer MLP, w = sigmoid, beta = mean(w) -> (gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16).
@@ -2401,45 +2471,17 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         Ra, Rt = h_a.shape[0] * h_a.shape[1], h_t.shape[0] * h_t.shape[1]
         if Ra != sa.N or Rt != st.N:
             raise ValueError(f"BetaGate: packed rows {Ra} / {Rt} do not match the plan ({sa.N} / {st.N})")
-        L = La if La == Lt else Lt                      # :98-104 (align to the text length)
-        if La < L:
-            raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
-        if precision() == "fp32":            # -> (h_fusion as the fp32 tensor itself, beta)
+        _gate_align(La, Lt)                  # the refusal comes before the fp32 dispatch; the prologue aligns again for its L
+        if precision() == "fp32":           # -> (h_fusion as the fp32 tensor itself, beta)
             return _fp32().beta_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st, sf)
-        _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
-        _require_gpu(h_a)
-        h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
+        _, xa, h_a32, xt, h_t32, (mean_a, rstd_a, pa), (mean_t, rstd_t, pt) = _gate_prologue(h_a, h_a32, h_t, h_t32,
+                                                                                              (ga, ba, gt, bt, w1, b1, w2, b2), sa, st)
         dev = h_a.device
-        xa, xt = _contig_bf16(h_a), _contig_bf16(h_t)
-        f32 = dict(dtype=torch.float32, device=dev)
-        L_ = _lib.lib()
-        nca, nct = L_.hriemo_pool_chunks(La), L_.hriemo_pool_chunks(Lt)
         An = torch.empty(sf.shape(d), dtype=BF16, device=dev)
         Tn = torch.empty(sf.shape(d), dtype=BF16, device=dev)
-        mean_a, rstd_a = torch.empty(Ra, **f32), torch.empty(Ra, **f32)
-        mean_t, rstd_t = torch.empty(Rt, **f32), torch.empty(Rt, **f32)
-        pa, pt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
-        st_ = _stream()
-        side_a = (xa, h_a32, sa, ga, ba, An, mean_a, rstd_a, pa)
-        side_t = (xt, h_t32, st, gt, bt, Tn, mean_t, rstd_t, pt)
-        # the two modalities' LayerNorm + pooling are independent: the (small) text one runs on the side stream beside the audio one
-        main = torch.cuda.current_stream(dev)
-        side = side_stream(dev) if GATE_TWO_STREAMS else None
-        if GATE_PAIR and L_.hriemo_ln_pool_pair_supported(d):
-            # both modalities from one launch: no fork / join around the step (two graph edges and 10-27 us of idle device each)
-            ln_pool_fwd_pair(side_a, side_t, sf, d)
-        elif side is not None and side != main:
-            fork(side, main)
-            with torch.cuda.stream(side):
-                ln_pool_fwd(*side_t, sf, d)
-            ln_pool_fwd(*side_a, sf, d)
-            main.wait_stream(side)
-            if not CTX.capturing:
-                for t_ in (xt, h_t32, st.kpm, Tn, mean_t, rstd_t, pt):
-                    share(t_, side)
-        else:
-            ln_pool_fwd(*side_a, sf, d)
-            ln_pool_fwd(*side_t, sf, d)
+        _both_sides(d, dev, (lambda a, t: ln_pool_fwd_pair(a, t, sf, d)) if GATE_PAIR else None, lambda *s: ln_pool_fwd(*s, sf, d),
+                    (xa, h_a32, sa, ga, ba, An, mean_a, rstd_a, pa), (xt, h_t32, st, gt, bt, Tn, mean_t, rstd_t, pt),
+                    GATE_TWO_STREAMS, (xt, h_t32, st.kpm, Tn, mean_t, rstd_t, pt))
         gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16 = _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh)
         H = torch.empty(sf.shape(d), dtype=BF16, device=dev)
         fuse_fwd(w, An, Tn, H, sf, d)
@@ -2459,63 +2501,36 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         B, La, Lt, L, d = sa.Breal, sa.L, st.L, st.L, xa.shape[-1]
         dev = xa.device
         f32 = dict(dtype=torch.float32, device=dev)
-        st_ = _stream()
-        L_ = _lib.lib()
         p_ga, p_ba, p_gt, p_bt, p_w1, p_b1, p_w2, p_b2 = ctx.params
         # parameter gradients go straight into .grad when the parameters were opted in (dp.GradBuckets): no autograd accumulate
         # launches on the serial chain between the decoder's and the encoder's backward
         sink = GradSink(ctx.params)
-        acc = sink.fused
         dH2 = _contig_bf16(dH) if dH is not None else torch.zeros(An.shape, dtype=BF16, device=dev)
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
-        part = torch.empty((B, L_.hriemo_pool_chunks(L), d), **f32)
+        part = torch.empty((B, _lib.lib().hriemo_pool_chunks(L), d), **f32)
         fuse_bwd_dw(dH2, An, Tn, part, sf, d)
         da, dt, dw1, db1, dw2, db2 = _gate_weights_bwd(part, L, dbeta2, w, hid, gin, a_pool, t_pool, cnt, w1_16, w2_16, sink,
                                                        (p_w1, p_b1, p_w2, p_b2), B, d)
         dxa = torch.empty(sa.shape(d), dtype=BF16, device=dev)
         dxt = torch.empty(st.shape(d), dtype=BF16, device=dev)
         dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
-        # LayerNorm-affine gradients: finished by the launch-boundary reduce when they accumulate into .grad inside backward (the
-        # kernel's partial sums then live in a buffer of their own instead of the shared workspace), else by the call's own reduce
-        defer = acc and DEFER_REDUCE and _in_backward()
-        nba, nbt = L_.hriemo_ln_pool_bwd_workspace_bytes(B, La, d), L_.hriemo_ln_pool_bwd_workspace_bytes(B, Lt, d)
+        aff = _LnAffine(sink, (dga, dba, dgt, dbt), B, La, Lt, d, dev)
 
-        def one_side(is_a, dpool, x, x32, sx, gamma, mean, rstd, dx, dgam, dbet, nbytes):
-            wsx = torch.empty(nbytes // 4 + 16, **f32) if defer else workspace(nbytes, dev, slot=1)
-            outs_ = (None, None, 1) if defer else (dgam, dbet, int(acc))
-            ln_pool_bwd(dH2, sf, w, is_a, dpool, x, x32, sx, gamma, mean, rstd, dx, *outs_, wsx, d)
-            if defer:
-                _deferred.add(wsx, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(sx.L), d, 2, [dgam, dbet], True)
+        def pair(a, t):
+            wsa, wst = aff.workspaces()
+            ln_pool_bwd_pair(dH2, sf, w, (wsa,) + a[1:] + aff.outs[:2], (wst,) + t[1:] + aff.outs[2:], aff.acc, d)
+            aff.queue(wsa, 0)
+            aff.queue(wst, 1)
 
-        side_a = (da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa)
-        side_t = (dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt)
-        main = torch.cuda.current_stream(dev)
-        side = side_stream(dev) if GATE_TWO_STREAMS else None
-        if GATE_PAIR and L_.hriemo_ln_pool_pair_supported(d):
-            if defer:
-                wsa, wst = torch.empty(nba // 4 + 16, **f32), torch.empty(nbt // 4 + 16, **f32)
-                outs = (None,) * 4
-            else:
-                wsa = workspace(nba + nbt + 256, dev, slot=1)
-                wst = wsa[(nba // 4 + 63) // 64 * 64:]
-                outs = (dga, dba, dgt, dbt)
-            ln_pool_bwd_pair(dH2, sf, w, (wsa,) + side_a + outs[:2], (wst,) + side_t + outs[2:], int(acc), d)
-            if defer:
-                _deferred.add(wsa, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(La), d, 2, [dga, dba], True)
-                _deferred.add(wst, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lt), d, 2, [dgt, dbt], True)
-        elif side is not None and side != main:
-            # text on the side stream (its own workspace there), audio on this one; joined before the gradients are handed back
-            fork(side, main)
-            with torch.cuda.stream(side):
-                one_side(0, *side_t, dgt, dbt, nbt)
-            one_side(1, *side_a, dga, dba, nba)
-            main.wait_stream(side)
-            if not CTX.capturing:
-                for t_ in (dH2, w, dt, dxt, dgt, dbt):
-                    share(t_, side)
-        else:
-            one_side(1, *side_a, dga, dba, nba)
-            one_side(0, *side_t, dgt, dbt, nbt)
+        def one_side(text, *rest):
+            # a workspace per side, taken on the stream the side runs on (the text side's may be the side stream)
+            wsx = torch.empty(aff.nbytes[text] // 4 + 16, **f32) if aff.defer else workspace(aff.nbytes[text], dev, slot=1)
+            ln_pool_bwd(dH2, sf, w, 1 - text, *rest, *aff.outs[2 * text:2 * text + 2], aff.acc, wsx, d)
+            aff.queue(wsx, text)
+
+        # (two streams: joined before the gradients are handed back)
+        _both_sides(d, dev, pair if GATE_PAIR else None, one_side, (0, da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa),
+                    (1, dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt), GATE_TWO_STREAMS, (dH2, w, dt, dxt, dgt, dbt))
         sink.done()
         r = sink.ret
         return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None, None
@@ -2536,9 +2551,7 @@ class LegacyBetaGateFn(torch.autograd.Function):
         _require_gpu(h_a)
         B, La, d = h_a.shape
         Lt = h_t.shape[1]
-        L = La if La == Lt else Lt                      # beta_gate.py:97-101
-        if La < L:
-            raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
+        L = _gate_align(La, Lt)
         dev = h_a.device
         xa, xt = _contig_bf16(h_a), _contig_bf16(h_t)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -2701,28 +2714,13 @@ class PooledGateFn(_GradModeAware, torch.autograd.Function):
         B, La, Lt, d = sa.Breal, sa.L, st.L, h_a.shape[-1]
         sa.holds(h_a)
         st.holds(h_t)
-        L = La if La == Lt else Lt                      # beta_gate_tacfn.py:98-104 (align to the text length)
-        if La < L:
-            raise RuntimeError(f"BetaGate: audio length {La} < text length {Lt}; the reference cannot fuse this either")
-        _require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
-        _require_gpu(h_a)
-        h_a32, h_t32 = _c32(h_a32), _c32(h_t32)
+        L, xa, h_a32, xt, h_t32, (mean_a, rstd_a, pa), (mean_t, rstd_t, pt) = _gate_prologue(h_a, h_a32, h_t, h_t32,
+                                                                                              (ga, ba, gt, bt, w1, b1, w2, b2), sa, st)
         dev = h_a.device
-        xa, xt = _contig_bf16(h_a), _contig_bf16(h_t)
         f32 = dict(dtype=torch.float32, device=dev)
-        L_ = _lib.lib()
-        nca, nct = L_.hriemo_pool_chunks(La), L_.hriemo_pool_chunks(Lt)
-        mean_a, rstd_a = torch.empty(B * La, **f32), torch.empty(B * La, **f32)
-        mean_t, rstd_t = torch.empty(B * Lt, **f32), torch.empty(B * Lt, **f32)
-        pa, pt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
-        ka, kt = torch.empty((B, nca, d), **f32), torch.empty((B, nct, d), **f32)
-        side_a = (xa, h_a32, sa, ga, ba, mean_a, rstd_a, pa, ka)
-        side_t = (xt, h_t32, st, gt, bt, mean_t, rstd_t, pt, kt)
-        if L_.hriemo_ln_pool_pair_supported(d):
-            ln_pool2_fwd_pair(side_a, side_t, L, d)
-        else:
-            ln_pool2_fwd(*side_a, L, d)
-            ln_pool2_fwd(*side_t, L, d)
+        ka, kt = torch.empty_like(pa), torch.empty_like(pt)
+        _both_sides(d, dev, lambda a, t: ln_pool2_fwd_pair(a, t, L, d), lambda *s: ln_pool2_fwd(*s, L, d),
+                    (xa, h_a32, sa, ga, ba, mean_a, rstd_a, pa, ka), (xt, h_t32, st, gt, bt, mean_t, rstd_t, pt, kt))
         gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16 = _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh)
         abar, tbar, pooled = torch.empty((B, d), **f32), torch.empty((B, d), **f32), torch.empty((B, d), **f32)
         _lib.call("hriemo_pooled_fuse_fwd", _p(ka), La, _p(kt), Lt, _p(w), L, _p(abar), _p(tbar), _p(pooled), B, d, _stream())
@@ -2740,10 +2738,8 @@ class PooledGateFn(_GradModeAware, torch.autograd.Function):
         B, La, Lt, L, d = sa.Breal, sa.L, st.L, st.L, xa.shape[-1]
         dev = xa.device
         f32 = dict(dtype=torch.float32, device=dev)
-        L_ = _lib.lib()
         p_ga, p_ba, p_gt, p_bt, p_w1, p_b1, p_w2, p_b2 = ctx.params
         sink = GradSink(ctx.params)
-        acc = sink.fused
         dpooled2 = dpooled.contiguous().float() if dpooled is not None else None
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
         dwf, g_a, g_t = torch.empty((B, d), **f32), torch.empty((B, d), **f32), torch.empty((B, d), **f32)
@@ -2754,25 +2750,14 @@ class PooledGateFn(_GradModeAware, torch.autograd.Function):
         dxa = torch.empty(sa.shape(d), dtype=BF16, device=dev)
         dxt = torch.empty(st.shape(d), dtype=BF16, device=dev)
         dga, dba, dgt, dbt = sink.buf(p_ga), sink.buf(p_ba), sink.buf(p_gt), sink.buf(p_bt)
-        defer = acc and DEFER_REDUCE and _in_backward()          # (as BetaGateFn: the LayerNorm-affine partials and who reduces them)
-        nba, nbt = L_.hriemo_ln_pool_bwd_workspace_bytes(B, La, d), L_.hriemo_ln_pool_bwd_workspace_bytes(B, Lt, d)
-        side_a = (g_a, da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa)
-        side_t = (g_t, dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt)
-        if defer:
-            wsa, wst = torch.empty(nba // 4 + 16, **f32), torch.empty(nbt // 4 + 16, **f32)
-            outs = (None,) * 4
-        else:
-            wsa = workspace(nba + nbt + 256, dev, slot=1)
-            wst = wsa[(nba // 4 + 63) // 64 * 64:]
-            outs = (dga, dba, dgt, dbt)
-        if L_.hriemo_ln_pool_pair_supported(d):
-            ln_pool_vec_bwd_pair(L, (wsa,) + side_a + outs[:2], (wst,) + side_t + outs[2:], int(acc), d)
-        else:
-            ln_pool_vec_bwd(*side_a, *outs[:2], int(acc), wsa, d)
-            ln_pool_vec_bwd(*side_t, *outs[2:], int(acc), wst, d)
-        if defer:
-            _deferred.add(wsa, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(La), d, 2, [dga, dba], True)
-            _deferred.add(wst, 2 * d, B * L_.hriemo_ln_pool_bwd_chunks(Lt), d, 2, [dgt, dbt], True)
+        aff = _LnAffine(sink, (dga, dba, dgt, dbt), B, La, Lt, d, dev)
+        ws = aff.workspaces()
+        _both_sides(d, dev,
+                    lambda a, t: ln_pool_vec_bwd_pair(L, (ws[0],) + a[1:] + aff.outs[:2], (ws[1],) + t[1:] + aff.outs[2:], aff.acc, d),
+                    lambda text, g, *rest: ln_pool_vec_bwd(g, L, *rest, *aff.outs[2 * text:2 * text + 2], aff.acc, ws[text], d),
+                    (0, g_a, da, xa, h_a32, sa, ga, mean_a, rstd_a, dxa), (1, g_t, dt, xt, h_t32, st, gt, mean_t, rstd_t, dxt))
+        aff.queue(ws[0], 0)
+        aff.queue(ws[1], 1)
         sink.done()
         r = sink.ret
         return dxa, None, dxt, None, r(dga), r(dba), r(dgt), r(dbt), r(dw1), r(db1), r(dw2), r(db2), None, None, None

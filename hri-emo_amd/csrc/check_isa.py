@@ -16,9 +16,6 @@ import re, sys
 # kernels that are known to spill inside a loop (a speed problem, never a correctness one: scratch traffic is counted by vmcnt
 # like any other memory operation); none of them is on the default path of BASELINE configs[1]
 LOOP_SPILL_OK = (
-    "attn_bwd_dkv_kernelILi96ELi4ELi2ELi32ELb1ELb1ELb1E",   # HRIEMO_ATTN_PAIR=1 (512-thread pairing, opt-in, measured slower)
-    "attn_bwd_dkv_kernelILi96ELi4ELi2ELi32ELb0ELb1ELb1E",
-    "gemm_mx8_kernel",                                       # HRIEMO_GEMM=mx_fp8 (opt-in)
     "ln_pool_bwd_kernelILi8E",                               # d_model > 2048 (no BASELINE config)
 )
 PK = re.compile(r"^\s*(v_pk_(?:add|mul|fma)_f32)\b.*?\bop_sel:\[([01](?:,[01])+)\]")

@@ -2324,6 +2324,63 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
   }
 }
 
+extern "C" int hriemo_sumsq_f32(const float* x, long n, float* partial, int nblocks, hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0 && nblocks > 0 && nblocks <= 4096, "sumsq_f32: n=%ld must be a positive multiple of 4, 0 < nblocks <= 4096", n);
+  HRIEMO_CHECK(((uintptr_t)x % 16) == 0, "sumsq_f32: unaligned buffer");
+  hipLaunchKernelGGL(sumsq_f32_kernel, dim3(nblocks), dim3(256), 0, st, x, n, partial);
+  HRIEMO_LAUNCH_CHECK("sumsq_f32_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_adamw_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int step, float max_norm, const float* norm2, hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0 && step >= 1, "adamw_flat: n=%ld must be a positive multiple of 4 and step >= 1", n);
+  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0, "adamw_flat: unaligned buffer");
+  HRIEMO_CHECK(max_norm <= 0.f || norm2 != nullptr, "adamw_flat: clipping needs the squared gradient norm");
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  hipLaunchKernelGGL(adamw_flat_kernel, dim3((int)gsz), dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                     max_norm, norm2);
+  HRIEMO_LAUNCH_CHECK("adamw_flat_kernel");
+  return 0;
+}
+
+// ---- what the launchers share
+// single forward launches: next-row prefetch for d <= 1024 (N <= 2), where it fits the registers
+#define LAUNCH_PF(KERNEL, N, ...)                                         \
+  if ((N) <= 2) hipLaunchKernelGGL((KERNEL<N, ((N) <= 2)>), __VA_ARGS__); \
+  else hipLaunchKernelGGL((KERNEL<N, false>), __VA_ARGS__)
+// pair launches (d <= 1024): one or two 8-column chunks per lane
+#define LAUNCH_PAIR(D, K1, K2, ...) \
+  if ((D) <= 512) hipLaunchKernelGGL(K1, __VA_ARGS__); else hipLaunchKernelGGL(K2, __VA_ARGS__)
+
+extern "C" int hriemo_ln_pool_pair_supported(int d) { return d % 8 == 0 && d <= 1024 ? 1 : 0; }
+// who must end in "_pair": the message names the single launcher by cutting those five characters off (every caller passes
+// a literal of that form)
+static int check_pair_width(const char* who, int d) {
+  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "%s: d=%d (pairs are built for d <= 1024; use two hriemo_%.*s calls)", who, d, (int)strlen(who) - 5, who);
+  return 0;
+}
+// the refusals of the backward pair launchers
+static int check_pair_bwd(const char* who, int d, const float* ws_a, const float* ws_t, const float* dgamma_a, const float* dbeta_a,
+                          const float* dgamma_t, const float* dbeta_t) {
+  HRIEMO_CHECK(ws_a != nullptr && ws_t != nullptr && ws_a != ws_t, "%s: bad arguments", who);
+  if (check_pair_width(who, d)) return 1;
+  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
+               "%s: the four LayerNorm gradients come together or not at all", who);
+  return 0;
+}
+// dgamma / dbeta of one side from the backward's partial sums ws [B * nc][2d] (scratch of the reduce behind them); no destination:
+// they stay in ws for the launch-boundary reduce
+static int reduce_affine(float* ws, int B, int nc, int d, float* dgamma, float* dbeta, int accumulate, hipStream_t st) {
+  if (dgamma == nullptr) return 0;
+  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
+  launch_colreduce(ws, (long)2 * d, B * nc, ro, d, 2, accumulate, ws + (long)B * nc * 2 * d, st);
+  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
+  return 0;
+}
+
 // ---- beta gate ----
 extern "C" int hriemo_pool_chunks(int L) { return (L + 31) / 32; }
 
@@ -2334,12 +2391,7 @@ extern "C" int hriemo_ln_pool_fwd(const void* X, const float* X32, const unsigne
   HRIEMO_CHECK(Lkeep >= 0 && Lkeep <= L, "ln_pool_fwd: Lkeep=%d out of range (L=%d)", Lkeep, L);
   const int nc = (L + 31) / 32;
   hriemo_prof_begin(HP_ROWOPS, st);
-  // (next-row prefetch for d <= 1024, where it fits the registers)
-#define CALL(N)                                                                                                                  \
-  if ((N) <= 2)                                                                                                                  \
-    hipLaunchKernelGGL((ln_pool_fwd_kernel<N, ((N) <= 2)>), dim3(nc, B), dim3(256), d * 4, st, (const bf16_t*)X, X32, mask, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, Lkeep, d, eps); \
-  else                                                                                                                           \
-    hipLaunchKernelGGL((ln_pool_fwd_kernel<N, false>), dim3(nc, B), dim3(256), d * 4, st, (const bf16_t*)X, X32, mask, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, Lkeep, d, eps)
+#define CALL(N) LAUNCH_PF(ln_pool_fwd_kernel, N, dim3(nc, B), dim3(256), d * 4, st, (const bf16_t*)X, X32, mask, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, Lkeep, d, eps)
   DISPATCH_NCH(d, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("ln_pool_fwd_kernel");
@@ -2348,7 +2400,6 @@ extern "C" int hriemo_ln_pool_fwd(const void* X, const float* X32, const unsigne
 }
 
 // the gate's two LayerNorm + pool steps from one launch (side 0 = audio, side 1 = text; same d, B, eps): see ln_pool_fwd_pair_kernel
-extern "C" int hriemo_ln_pool_pair_supported(int d) { return d % 8 == 0 && d <= 1024 ? 1 : 0; }
 extern "C" int hriemo_ln_pool_fwd_pair(const void* Xa, const float* Xa32, const unsigned char* mask_a, const float* gamma_a, const float* beta_a,
                                        void* Yna, float* mean_a, float* rstd_a, float* partials_a, int La,
                                        const void* Xt, const float* Xt32, const unsigned char* mask_t, const float* gamma_t, const float* beta_t,
@@ -2356,14 +2407,13 @@ extern "C" int hriemo_ln_pool_fwd_pair(const void* Xa, const float* Xa32, const 
                                        int B, int Lkeep, int d, float eps, hipStream_t st) {
   if (check_rows(B * La, d) || check_rows(B * Lt, d)) return 1;
   HRIEMO_CHECK(Lkeep >= 0 && Lkeep <= La && Lkeep <= Lt, "ln_pool_fwd_pair: Lkeep=%d out of range (La=%d, Lt=%d)", Lkeep, La, Lt);
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_fwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_fwd calls)", d);
+  if (check_pair_width("ln_pool_fwd_pair", d)) return 1;
   PoolFwdPair p;
   p.s[0] = PoolFwdSide{(const bf16_t*)Xa, Xa32, mask_a, gamma_a, beta_a, (bf16_t*)Yna, mean_a, rstd_a, partials_a, La, Lkeep, (La + 31) / 32};
   p.s[1] = PoolFwdSide{(const bf16_t*)Xt, Xt32, mask_t, gamma_t, beta_t, (bf16_t*)Ynt, mean_t, rstd_t, partials_t, Lt, Lkeep, (Lt + 31) / 32};
   const int nc = p.s[0].nc + p.s[1].nc;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool_fwd_pair_kernel<1, true>), dim3(nc, B), dim3(256), d * 4, st, p, d, eps);
-  else hipLaunchKernelGGL((ln_pool_fwd_pair_kernel<2, true>), dim3(nc, B), dim3(256), d * 4, st, p, d, eps);
+  LAUNCH_PAIR(d, (ln_pool_fwd_pair_kernel<1, true>), (ln_pool_fwd_pair_kernel<2, true>), dim3(nc, B), dim3(256), d * 4, st, p, d, eps);
   HRIEMO_LAUNCH_CHECK("ln_pool_fwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, ((double)B * (La + Lt) + 2.0 * B * Lkeep) * d * 2);
   return 0;
@@ -2424,28 +2474,6 @@ extern "C" int hriemo_scalar_gate_dx(const void* dH, int Lf, const float* beta, 
   return 0;
 }
 
-extern "C" int hriemo_sumsq_f32(const float* x, long n, float* partial, int nblocks, hipStream_t st) {
-  HRIEMO_CHECK(n > 0 && n % 4 == 0 && nblocks > 0 && nblocks <= 4096, "sumsq_f32: n=%ld must be a positive multiple of 4, 0 < nblocks <= 4096", n);
-  HRIEMO_CHECK(((uintptr_t)x % 16) == 0, "sumsq_f32: unaligned buffer");
-  hipLaunchKernelGGL(sumsq_f32_kernel, dim3(nblocks), dim3(256), 0, st, x, n, partial);
-  HRIEMO_LAUNCH_CHECK("sumsq_f32_kernel");
-  return 0;
-}
-
-extern "C" int hriemo_adamw_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, int step, float max_norm, const float* norm2, hipStream_t st) {
-  HRIEMO_CHECK(n > 0 && n % 4 == 0 && step >= 1, "adamw_flat: n=%ld must be a positive multiple of 4 and step >= 1", n);
-  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0, "adamw_flat: unaligned buffer");
-  HRIEMO_CHECK(max_norm <= 0.f || norm2 != nullptr, "adamw_flat: clipping needs the squared gradient norm");
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  long gsz = (n / 4 + 255) / 256;
-  if (gsz > 4096) gsz = 4096;
-  hipLaunchKernelGGL(adamw_flat_kernel, dim3((int)gsz), dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
-                     max_norm, norm2);
-  HRIEMO_LAUNCH_CHECK("adamw_flat_kernel");
-  return 0;
-}
-
 extern "C" int hriemo_fuse_fwd(const float* w, const void* A, const void* T, void* H, int B, int L, int d, hipStream_t st) {
   if (check_rows(B * L, d)) return 1;
   long g = ((long)B * L * (d / 8) + 255) / 256;
@@ -2499,12 +2527,7 @@ extern "C" int hriemo_ln_pool_bwd(const void* dH, int Lf, const float* w, int is
 #undef CALL
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * B * L + (double)B * Lf) * d * 2);
-  if (dgamma == nullptr) return 0;          // partial sums stay in `workspace` ([B * hriemo_ln_pool_bwd_chunks(L)][2d]) for the launch-boundary reduce
-  float* scratch = workspace + (long)B * nc * 2 * d;
-  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
-  launch_colreduce(workspace, (long)2 * d, B * nc, ro, d, 2, accumulate, scratch, st);
-  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  return 0;
+  return reduce_affine(workspace, B, nc, d, dgamma, dbeta, accumulate, st);
 }
 
 // both modalities' gate backward from one launch (side 0 = audio: coefficient w, side 1 = text: 1 - w).  dgamma / dbeta as in the
@@ -2516,28 +2539,18 @@ extern "C" int hriemo_ln_pool_bwd_pair(const void* dH, int Lf, const float* w,
                                        const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t, float* dbeta_t, int Lt, float* workspace_t,
                                        int accumulate, int B, int d, hipStream_t st) {
   if (check_rows(B * La, d) || check_rows(B * Lt, d)) return 1;
-  HRIEMO_CHECK(workspace_a != nullptr && workspace_t != nullptr && workspace_a != workspace_t && Lf <= La && Lf <= Lt, "ln_pool_bwd_pair: bad arguments");
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_bwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_bwd calls)", d);
-  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
-               "ln_pool_bwd_pair: the four LayerNorm gradients come together or not at all");
+  HRIEMO_CHECK(Lf <= La && Lf <= Lt, "ln_pool_bwd_pair: bad arguments");
+  if (check_pair_bwd("ln_pool_bwd_pair", d, workspace_a, workspace_t, dgamma_a, dbeta_a, dgamma_t, dbeta_t)) return 1;
   PoolBwdPair p;
   p.s[0] = PoolBwdSide{dpool_a, mask_a, (const bf16_t*)Xa, Xa32, gamma_a, mean_a, rstd_a, (bf16_t*)dXa, workspace_a, La, hriemo_ln_pool_bwd_chunks(La)};
   p.s[1] = PoolBwdSide{dpool_t, mask_t, (const bf16_t*)Xt, Xt32, gamma_t, mean_t, rstd_t, (bf16_t*)dXt, workspace_t, Lt, hriemo_ln_pool_bwd_chunks(Lt)};
   const int nc = p.s[0].nc + p.s[1].nc;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool_bwd_pair_kernel<1>), dim3(nc, B), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, Lf, w, p, d);
-  else hipLaunchKernelGGL((ln_pool_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, Lf, w, p, d);
+  LAUNCH_PAIR(d, (ln_pool_bwd_pair_kernel<1>), (ln_pool_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, Lf, w, p, d);
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * B * (La + Lt) + 2.0 * B * Lf) * d * 2);
-  if (dgamma_a == nullptr) return 0;
-  for (int side = 0; side < 2; ++side) {
-    float* ws = side ? workspace_t : workspace_a;
-    float* scratch = ws + (long)B * p.s[side].nc * 2 * d;
-    ReduceOut ro; ro.o[0] = side ? dgamma_t : dgamma_a; ro.o[1] = side ? dbeta_t : dbeta_a; ro.o[2] = nullptr;
-    launch_colreduce(ws, (long)2 * d, B * p.s[side].nc, ro, d, 2, accumulate, scratch, st);
-    HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  }
-  return 0;
+  if (int e = reduce_affine(workspace_a, B, p.s[0].nc, d, dgamma_a, dbeta_a, accumulate, st)) return e;
+  return reduce_affine(workspace_t, B, p.s[1].nc, d, dgamma_t, dbeta_t, accumulate, st);
 }
 
 // ---- the pooled gate (FusionClassifier): see ln_pool2_fwd_body.  d <= 2048 (two accumulators per column in registers).
@@ -2568,15 +2581,14 @@ extern "C" int hriemo_ln_pool2_fwd_pair(const void* Xa, const float* Xa32, const
                                         float* mean_t, float* rstd_t, float* partials_t, float* partials_keep_t, int Lt,
                                         int B, int Lkeep, int d, float eps, hipStream_t st) {
   if (check_pool2("ln_pool2_fwd_pair", B, La, Lkeep, d) || check_pool2("ln_pool2_fwd_pair", B, Lt, Lkeep, d)) return 1;
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool2_fwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool2_fwd calls)", d);
+  if (check_pair_width("ln_pool2_fwd_pair", d)) return 1;
   HRIEMO_CHECK(partials_a != nullptr && partials_keep_a != nullptr && partials_t != nullptr && partials_keep_t != nullptr, "ln_pool2_fwd_pair: a partial buffer is missing");
   Pool2FwdPair p;
   p.s[0] = Pool2FwdSide{(const bf16_t*)Xa, Xa32, mask_a, gamma_a, beta_a, mean_a, rstd_a, partials_a, partials_keep_a, La, (La + 31) / 32};
   p.s[1] = Pool2FwdSide{(const bf16_t*)Xt, Xt32, mask_t, gamma_t, beta_t, mean_t, rstd_t, partials_t, partials_keep_t, Lt, (Lt + 31) / 32};
   const int nc = p.s[0].nc + p.s[1].nc;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool2_fwd_pair_kernel<1, true>), dim3(nc, B), dim3(256), 2 * d * 4, st, p, Lkeep, d, eps);
-  else hipLaunchKernelGGL((ln_pool2_fwd_pair_kernel<2, true>), dim3(nc, B), dim3(256), 2 * d * 4, st, p, Lkeep, d, eps);
+  LAUNCH_PAIR(d, (ln_pool2_fwd_pair_kernel<1, true>), (ln_pool2_fwd_pair_kernel<2, true>), dim3(nc, B), dim3(256), 2 * d * 4, st, p, Lkeep, d, eps);
   HRIEMO_LAUNCH_CHECK("ln_pool2_fwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (double)B * (La + Lt) * d * 2);
   return 0;
@@ -2608,12 +2620,7 @@ extern "C" int hriemo_ln_pool_vec_bwd(const float* g, int Lkeep, const float* dp
 #undef CALL
   HRIEMO_LAUNCH_CHECK("ln_pool_vec_bwd_kernel");
   hriemo_prof_end(HP_ROWOPS, st, 2.0 * B * L * d * 2);
-  if (dgamma == nullptr) return 0;          // partial sums stay in `workspace` for the launch-boundary reduce (as hriemo_ln_pool_bwd)
-  float* scratch = workspace + (long)B * nc * 2 * d;
-  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
-  launch_colreduce(workspace, (long)2 * d, B * nc, ro, d, 2, accumulate, scratch, st);
-  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  return 0;
+  return reduce_affine(workspace, B, nc, d, dgamma, dbeta, accumulate, st);
 }
 extern "C" int hriemo_ln_pool_vec_bwd_pair(int Lkeep,
                                            const float* g_a, const float* dpool_a, const unsigned char* mask_a, const void* Xa, const float* Xa32, const float* gamma_a,
@@ -2622,28 +2629,18 @@ extern "C" int hriemo_ln_pool_vec_bwd_pair(int Lkeep,
                                            const float* mean_t, const float* rstd_t, void* dXt, float* dgamma_t, float* dbeta_t, int Lt, float* workspace_t,
                                            int accumulate, int B, int d, hipStream_t st) {
   if (check_pool2("ln_pool_vec_bwd_pair", B, La, Lkeep, d) || check_pool2("ln_pool_vec_bwd_pair", B, Lt, Lkeep, d)) return 1;
-  HRIEMO_CHECK(workspace_a != nullptr && workspace_t != nullptr && workspace_a != workspace_t && dpool_a != nullptr && dpool_t != nullptr, "ln_pool_vec_bwd_pair: bad arguments");
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_vec_bwd_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_vec_bwd calls)", d);
-  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
-               "ln_pool_vec_bwd_pair: the four LayerNorm gradients come together or not at all");
+  HRIEMO_CHECK(dpool_a != nullptr && dpool_t != nullptr, "ln_pool_vec_bwd_pair: bad arguments");
+  if (check_pair_bwd("ln_pool_vec_bwd_pair", d, workspace_a, workspace_t, dgamma_a, dbeta_a, dgamma_t, dbeta_t)) return 1;
   PoolVecBwdPair p;
   p.s[0] = PoolVecBwdSide{g_a, dpool_a, mask_a, (const bf16_t*)Xa, Xa32, gamma_a, mean_a, rstd_a, (bf16_t*)dXa, workspace_a, La, hriemo_ln_pool_bwd_chunks(La)};
   p.s[1] = PoolVecBwdSide{g_t, dpool_t, mask_t, (const bf16_t*)Xt, Xt32, gamma_t, mean_t, rstd_t, (bf16_t*)dXt, workspace_t, Lt, hriemo_ln_pool_bwd_chunks(Lt)};
   const int nc = p.s[0].nc + p.s[1].nc;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool_vec_bwd_pair_kernel<1>), dim3(nc, B), dim3(256), 5 * d * 4, st, p, Lkeep, d);
-  else hipLaunchKernelGGL((ln_pool_vec_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, p, Lkeep, d);
+  LAUNCH_PAIR(d, (ln_pool_vec_bwd_pair_kernel<1>), (ln_pool_vec_bwd_pair_kernel<2>), dim3(nc, B), dim3(256), 5 * d * 4, st, p, Lkeep, d);
   HRIEMO_LAUNCH_CHECK("ln_pool_vec_bwd_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, 2.0 * B * (La + Lt) * d * 2);
-  if (dgamma_a == nullptr) return 0;
-  for (int side = 0; side < 2; ++side) {
-    float* ws = side ? workspace_t : workspace_a;
-    float* scratch = ws + (long)B * p.s[side].nc * 2 * d;
-    ReduceOut ro; ro.o[0] = side ? dgamma_t : dgamma_a; ro.o[1] = side ? dbeta_t : dbeta_a; ro.o[2] = nullptr;
-    launch_colreduce(ws, (long)2 * d, B * p.s[side].nc, ro, d, 2, accumulate, scratch, st);
-    HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  }
-  return 0;
+  if (int e = reduce_affine(workspace_a, B, p.s[0].nc, d, dgamma_a, dbeta_a, accumulate, st)) return e;
+  return reduce_affine(workspace_t, B, p.s[1].nc, d, dgamma_t, dbeta_t, accumulate, st);
 }
 
 // ---- the gate on packed (varlen) rows: the encoder's packed output goes straight into the gate and the gate's h_fusion stays
@@ -2664,11 +2661,7 @@ extern "C" int hriemo_ln_pool_fwd_packed(const void* X, const float* X32, const 
   const int nc = (L + 31) / 32;
   const PackedArgs pk{cu_seqlens, nseq, n_rows, cu_fused, n_fused, B};
   hriemo_prof_begin(HP_ROWOPS, st);
-#define CALL(N)                                                                                                                  \
-  if ((N) <= 2)                                                                                                                  \
-    hipLaunchKernelGGL((ln_pool_fwd_packed_kernel<N, ((N) <= 2)>), dim3(nc, nseq + 1), dim3(256), d * 4, st, (const bf16_t*)X, X32, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, d, eps, pk); \
-  else                                                                                                                           \
-    hipLaunchKernelGGL((ln_pool_fwd_packed_kernel<N, false>), dim3(nc, nseq + 1), dim3(256), d * 4, st, (const bf16_t*)X, X32, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, d, eps, pk)
+#define CALL(N) LAUNCH_PF(ln_pool_fwd_packed_kernel, N, dim3(nc, nseq + 1), dim3(256), d * 4, st, (const bf16_t*)X, X32, gamma, beta, (bf16_t*)Yn, mean, rstd, partials, L, d, eps, pk)
   DISPATCH_NCH(d, CALL)
 #undef CALL
   HRIEMO_LAUNCH_CHECK("ln_pool_fwd_packed_kernel");
@@ -2684,14 +2677,13 @@ extern "C" int hriemo_ln_pool_fwd_packed_pair(const void* Xa, const float* Xa32,
   if (check_packed("ln_pool_fwd_packed_pair", cu_a, nseq_a, n_rows_a, cu_fused, n_fused, B, La, d) ||
       check_packed("ln_pool_fwd_packed_pair", cu_t, nseq_t, n_rows_t, cu_fused, n_fused, B, Lt, d)) return 1;
   HRIEMO_CHECK(cu_a != nullptr && cu_t != nullptr && Xa != nullptr && Xt != nullptr && Yna != nullptr && Ynt != nullptr, "ln_pool_fwd_packed_pair: NULL operand");
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_fwd_packed_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_fwd_packed calls)", d);
+  if (check_pair_width("ln_pool_fwd_packed_pair", d)) return 1;
   PoolFwdPairPk p;
   p.s[0] = PoolFwdSidePk{(const bf16_t*)Xa, Xa32, cu_a, gamma_a, beta_a, (bf16_t*)Yna, mean_a, rstd_a, partials_a, La, (La + 31) / 32, nseq_a, n_rows_a};
   p.s[1] = PoolFwdSidePk{(const bf16_t*)Xt, Xt32, cu_t, gamma_t, beta_t, (bf16_t*)Ynt, mean_t, rstd_t, partials_t, Lt, (Lt + 31) / 32, nseq_t, n_rows_t};
   const int nc = p.s[0].nc + p.s[1].nc, ny = (nseq_a > nseq_t ? nseq_a : nseq_t) + 1;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool_fwd_packed_pair_kernel<1, true>), dim3(nc, ny), dim3(256), d * 4, st, p, cu_fused, n_fused, B, d, eps);
-  else hipLaunchKernelGGL((ln_pool_fwd_packed_pair_kernel<2, true>), dim3(nc, ny), dim3(256), d * 4, st, p, cu_fused, n_fused, B, d, eps);
+  LAUNCH_PAIR(d, (ln_pool_fwd_packed_pair_kernel<1, true>), (ln_pool_fwd_packed_pair_kernel<2, true>), dim3(nc, ny), dim3(256), d * 4, st, p, cu_fused, n_fused, B, d, eps);
   HRIEMO_LAUNCH_CHECK("ln_pool_fwd_packed_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, ((double)n_rows_a + n_rows_t + 2.0 * n_fused) * d * 2);
   return 0;
@@ -2753,12 +2745,7 @@ extern "C" int hriemo_ln_pool_bwd_packed(const void* dH, const int* cu_fused, in
 #undef CALL
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_packed_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * n_rows + (double)n_fused) * d * 2);
-  if (dgamma == nullptr) return 0;          // partial sums stay in `workspace` ([B * hriemo_ln_pool_bwd_chunks(L)][2d]) for the launch-boundary reduce
-  float* scratch = workspace + (long)B * nc * 2 * d;
-  ReduceOut ro; ro.o[0] = dgamma; ro.o[1] = dbeta; ro.o[2] = nullptr;
-  launch_colreduce(workspace, (long)2 * d, B * nc, ro, d, 2, accumulate, scratch, st);
-  HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  return 0;
+  return reduce_affine(workspace, B, nc, d, dgamma, dbeta, accumulate, st);
 }
 
 extern "C" int hriemo_ln_pool_bwd_packed_pair(const void* dH, const int* cu_fused, int n_fused, const float* w,
@@ -2770,27 +2757,16 @@ extern "C" int hriemo_ln_pool_bwd_packed_pair(const void* dH, const int* cu_fuse
                                               int Lt, float* workspace_t, int accumulate, int B, int d, hipStream_t st) {
   if (check_packed("ln_pool_bwd_packed_pair", cu_a, nseq_a, n_rows_a, cu_fused, n_fused, B, La, d) ||
       check_packed("ln_pool_bwd_packed_pair", cu_t, nseq_t, n_rows_t, cu_fused, n_fused, B, Lt, d)) return 1;
-  HRIEMO_CHECK(cu_a != nullptr && cu_t != nullptr && workspace_a != nullptr && workspace_t != nullptr && workspace_a != workspace_t && dXa != nullptr && dXt != nullptr,
-               "ln_pool_bwd_packed_pair: bad arguments");
-  HRIEMO_CHECK(hriemo_ln_pool_pair_supported(d), "ln_pool_bwd_packed_pair: d=%d (pairs are built for d <= 1024; use two hriemo_ln_pool_bwd_packed calls)", d);
-  HRIEMO_CHECK((dgamma_a == nullptr) == (dbeta_a == nullptr) && (dgamma_t == nullptr) == (dbeta_t == nullptr) && (dgamma_a == nullptr) == (dgamma_t == nullptr),
-               "ln_pool_bwd_packed_pair: the four LayerNorm gradients come together or not at all");
+  HRIEMO_CHECK(cu_a != nullptr && cu_t != nullptr && dXa != nullptr && dXt != nullptr, "ln_pool_bwd_packed_pair: bad arguments");
+  if (check_pair_bwd("ln_pool_bwd_packed_pair", d, workspace_a, workspace_t, dgamma_a, dbeta_a, dgamma_t, dbeta_t)) return 1;
   PoolBwdPairPk p;
   p.s[0] = PoolBwdSidePk{dpool_a, cu_a, (const bf16_t*)Xa, Xa32, gamma_a, mean_a, rstd_a, (bf16_t*)dXa, workspace_a, La, hriemo_ln_pool_bwd_chunks(La), nseq_a, n_rows_a};
   p.s[1] = PoolBwdSidePk{dpool_t, cu_t, (const bf16_t*)Xt, Xt32, gamma_t, mean_t, rstd_t, (bf16_t*)dXt, workspace_t, Lt, hriemo_ln_pool_bwd_chunks(Lt), nseq_t, n_rows_t};
   const int nc = p.s[0].nc + p.s[1].nc, ny = nseq_a > nseq_t ? nseq_a : nseq_t;
   hriemo_prof_begin(HP_ROWOPS, st);
-  if (d <= 512) hipLaunchKernelGGL((ln_pool_bwd_packed_pair_kernel<1>), dim3(nc, ny), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, w, p, cu_fused, n_fused, B, d);
-  else hipLaunchKernelGGL((ln_pool_bwd_packed_pair_kernel<2>), dim3(nc, ny), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, w, p, cu_fused, n_fused, B, d);
+  LAUNCH_PAIR(d, (ln_pool_bwd_packed_pair_kernel<1>), (ln_pool_bwd_packed_pair_kernel<2>), dim3(nc, ny), dim3(256), 5 * d * 4, st, (const bf16_t*)dH, w, p, cu_fused, n_fused, B, d);
   HRIEMO_LAUNCH_CHECK("ln_pool_bwd_packed_pair_kernel");
   hriemo_prof_end(HP_ROWOPS, st, (2.0 * (n_rows_a + n_rows_t) + 2.0 * n_fused) * d * 2);
-  if (dgamma_a == nullptr) return 0;
-  for (int side = 0; side < 2; ++side) {
-    float* ws = side ? workspace_t : workspace_a;
-    float* scratch = ws + (long)B * p.s[side].nc * 2 * d;
-    ReduceOut ro; ro.o[0] = side ? dgamma_t : dgamma_a; ro.o[1] = side ? dbeta_t : dbeta_a; ro.o[2] = nullptr;
-    launch_colreduce(ws, (long)2 * d, B * p.s[side].nc, ro, d, 2, accumulate, scratch, st);
-    HRIEMO_LAUNCH_CHECK("colreduce_kernel");
-  }
-  return 0;
+  if (int e = reduce_affine(workspace_a, B, p.s[0].nc, d, dgamma_a, dbeta_a, accumulate, st)) return e;
+  return reduce_affine(workspace_t, B, p.s[1].nc, d, dgamma_t, dbeta_t, accumulate, st);
 }
