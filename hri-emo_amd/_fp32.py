@@ -95,10 +95,11 @@ def _weight_split(sh, w, form, rows=None, kp=None):
     """split copy of an fp32 master weight (form 5: [N,6K] for the forward, form 7: [6N,K] for dX), cached next to the bf16 shadows
     and refreshed like them; rows = (r0, r1): of that row block only (the Q or K|V rows of a packed in-projection)"""
     key = ("x3", id(w), form, rows, kp)
+    _ops._note_form(("weight_split", id(sh), key), _weight_split, sh, w, form, rows, kp)
     ent = sh._d.get(key)
     ver = (w._version, w.data_ptr(), _ops.WEIGHTS_EPOCH)
     # inside a capture every step splits again (a replay must honour optimizer updates, as Shadows.get re-casts), once per step
-    if (_ops.CTX.capturing and (ent is None or ent[2] != _ops.STEP_ID)) or ent is None or ent[0] != ver or ent[1].device != w.device:
+    if _ops.form_stale(ent, ver, w.device):
         _ops._require_gpu(w)
         _ops._require_fp32_master(w)
         src = _c(w.detach())

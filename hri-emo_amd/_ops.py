@@ -103,11 +103,17 @@ class StepContext:
       capture_origin the stream the capture runs on (every helper-stream fork must start there: fork())
       seq_override   (Seq audio, Seq text, Seq fused) injected for the bucketed packed graphs (models/cross_modal_block_tacfn.py)
       join_scope     > 0 inside a forward whose outputs ALL depend on both encoder branches (grad_join)
-      half_reports   id(parameter) -> SharedProjFn nodes that have written their half of its gradient in this step"""
-    __slots__ = ("capturing", "capture_origin", "seq_override", "join_scope", "half_reports")
+      half_reports   id(parameter) -> SharedProjFn nodes that have written their half of its gradient in this step
+      stationary     set by dp.EvalStep(stationary=True) around the passes of a bucket graph: a capture derives no weight form
+                     (form_stale), the step's weights pass keeps them fresh
+      forms          a FormLog while such a step looks for the forms its forward asks for; None otherwise
+      prologue       such a step's hand-over of the decoder's query prologue: prologue(decoder, B) -> the static (tgt, tgt32) layer 0
+                     starts its cross-attention on (models/emotion_decoder.py); None otherwise"""
+    __slots__ = ("capturing", "capture_origin", "seq_override", "join_scope", "half_reports", "stationary", "forms", "prologue")
 
     def __init__(self):
         self.capturing, self.capture_origin, self.seq_override, self.join_scope, self.half_reports = False, None, None, 0, {}
+        self.stationary, self.forms, self.prologue = False, None, None
 
 
 CTX = StepContext()        # the context in force
@@ -262,6 +268,45 @@ def next_seed(training):
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def form_stale(ent, ver, device=None, once_per_step=True):
+    """THE staleness rule of every cached weight form (bf16 shadows, concatenations, padded and MX-fp8 copies, the fp32 mode's
+    splits): must the form be derived from its fp32 master(s) now?  ent: the cache entry (version key, form[, STEP_ID of its
+    derivation]) or None; ver: the masters' version key now; device: where the form has to live (None: the site does not ask).
+    Outside a capture: when there is no entry, the version key differs or the device does.  Inside a capture additionally whenever
+    the form was not derived in this step yet -- the replayed graph must honour optimizer updates -- or, for a site that keeps no
+    step id (once_per_step=False), always.  Inside a capture of a stationary step (CTX.stationary) nothing is derived: the step's
+    weights pass has refreshed every form, so a stale one is an error, not a cast to record."""
+    fresh = ent is not None and ent[0] == ver and (device is None or ent[1].device == device)
+    if not CTX.capturing:
+        return not fresh
+    if CTX.stationary:
+        if not fresh:
+            raise RuntimeError("hri_emo_amd: a weight form is stale inside the capture of a stationary step (internal error: the "
+                               "weights pass should have refreshed it) -- no cast is recorded")
+        return False
+    return not once_per_step or not fresh or len(ent) < 3 or ent[2] != STEP_ID
+
+
+class FormLog:
+    """The weight forms a forward asked for, in call order, as (key, getter, arguments): what a stationary dp.EvalStep replays as its
+    weights pass.  A request whose key was known before the pass in flight is not kept again; within one pass every request is."""
+
+    def __init__(self):
+        self.known, self.new = set(), []
+
+    def take(self):
+        """the requests of the pass just run whose keys were not known before it"""
+        new, self.new = self.new, []
+        self.known.update(k for k, _, _ in new)
+        return new
+
+
+def _note_form(key, fn, *args):
+    log = CTX.forms
+    if log is not None and key not in log.known:
+        log.new.append((key, fn, args))
+
+
 class Shadows:
     """bf16 copies of fp32 master weights, refreshed when the master changes (optimizer step,
     load_state_dict, .to())."""
@@ -271,11 +316,12 @@ class Shadows:
 
     def get(self, p):
         key = id(p)
+        _note_form(("get", id(self), key), self.get, p)
         ent = self._d.get(key)
         ver = (p._version, p.data_ptr(), WEIGHTS_EPOCH)
         # inside a capture every step re-casts (the replayed graph must honour optimizer updates), but only once per step:
         # a shadow prefetched at the top of the step (prefetch()) is not cast again on the decoder's serial chain
-        if (CTX.capturing and (ent is None or len(ent) < 3 or ent[2] != STEP_ID)) or ent is None or ent[0] != ver or ent[1].device != p.device:
+        if form_stale(ent, ver, p.device):
             s = ent[1] if ent is not None and ent[1].device == p.device and ent[1].shape == p.shape else \
                 torch.empty(p.shape, dtype=BF16, device=p.device)
             _require_gpu(p)
@@ -296,7 +342,7 @@ class Shadows:
         """would get(p) cast now?  -> (needs a cast, destination tensor, version key)"""
         ent = self._d.get(id(p))
         ver = (p._version, p.data_ptr(), WEIGHTS_EPOCH)
-        need = (CTX.capturing and (ent is None or len(ent) < 3 or ent[2] != STEP_ID)) or ent is None or ent[0] != ver or ent[1].device != p.device
+        need = form_stale(ent, ver, p.device)
         dst = ent[1] if ent is not None and ent[1].device == p.device and ent[1].shape == p.shape else None
         return need, dst, ver
 
@@ -304,10 +350,11 @@ class Shadows:
         """bf16 shadow of the row-wise concatenation of master slices: parts = ((param, r0, r1), ...) -> [sum(r1 - r0), K].
         One GEMM per shared input (SharedProjFn) reads it; refreshed when any of the masters changes, like get()."""
         key = ("cat",) + tuple((id(p), r0, r1) for p, r0, r1 in parts)
+        _note_form(("get_cat", id(self), key), self.get_cat, parts)
         ent = self._d.get(key)
         ver = tuple((p._version, p.data_ptr()) for p, _, _ in parts) + (WEIGHTS_EPOCH,)
         dev = parts[0][0].device
-        if (CTX.capturing and (ent is None or ent[2] != STEP_ID)) or ent is None or ent[0] != ver or ent[1].device != dev:
+        if form_stale(ent, ver, dev):
             rows = sum(r1 - r0 for _, r0, r1 in parts)
             K = parts[0][0].shape[1]
             s = ent[1] if ent is not None and ent[1].device == dev else torch.empty((rows, K), dtype=BF16, device=dev)
@@ -329,12 +376,12 @@ class Shadows:
         projection's [3d, d] bf16 weight shadow and [3d] fp32 bias; before: two casts, a torch.cat and a copy per refresh."""
         kw = ("cat",) + tuple((id(p), r0, r1) for p, r0, r1 in wparts)
         kb = ("catv",) + tuple((id(p), r0, r1) for p, r0, r1 in bparts)
+        _note_form(("get_cat_wb", id(self), kw, kb), self.get_cat_wb, wparts, bparts)
         ew, eb = self._d.get(kw), self._d.get(kb)
         vw = tuple((p._version, p.data_ptr()) for p, _, _ in wparts) + (WEIGHTS_EPOCH,)
         vb = tuple((p._version, p.data_ptr()) for p, _, _ in bparts) + (WEIGHTS_EPOCH,)
         dev = wparts[0][0].device
-        stale_w = (CTX.capturing and (ew is None or ew[2] != STEP_ID)) or ew is None or ew[0] != vw or ew[1].device != dev
-        stale_b = (CTX.capturing and (eb is None or eb[2] != STEP_ID)) or eb is None or eb[0] != vb or eb[1].device != dev
+        stale_w, stale_b = form_stale(ew, vw, dev), form_stale(eb, vb, dev)
         if not (stale_w or stale_b):
             return ew[1], eb[1]
         if not all(p.is_contiguous() for p, _, _ in wparts + bparts):
@@ -368,9 +415,10 @@ class Shadows:
         mx8_shadow: every slice is quantised from its fp32 master straight into its rows of ONE buffer (the scale matrix is
         k-block major with one column per row, so a slice owns a column range of it)"""
         key = ("catmx",) + tuple((id(p), r0, r1) for p, r0, r1 in parts)
+        _note_form(("get_cat_mx8", id(self), key), self.get_cat_mx8, parts)
         ent = self._d.get(key)
         ver = tuple((p._version, p.data_ptr()) for p, _, _ in parts) + (WEIGHTS_EPOCH,)
-        if CTX.capturing or ent is None or ent[0] != ver:
+        if form_stale(ent, ver, once_per_step=False):
             rows = sum(r1 - r0 for _, r0, r1 in parts)
             K = parts[0][0].shape[1]
             dev = parts[0][0].device
@@ -399,9 +447,10 @@ class Shadows:
     def get_cat_vec(self, parts):
         """fp32 concatenation of bias slices ((param, r0, r1), ...), cached like the weight shadows"""
         key = ("catv",) + tuple((id(p), r0, r1) for p, r0, r1 in parts)
+        _note_form(("get_cat_vec", id(self), key), self.get_cat_vec, parts)
         ent = self._d.get(key)
         ver = tuple((p._version, p.data_ptr()) for p, _, _ in parts) + (WEIGHTS_EPOCH,)
-        if (CTX.capturing and (ent is None or ent[2] != STEP_ID)) or ent is None or ent[0] != ver:
+        if form_stale(ent, ver):
             v = torch.cat([p.detach()[r0:r1] for p, r0, r1 in parts])
             if ent is not None and ent[1].shape == v.shape and ent[1].device == v.device:
                 ent[1].copy_(v)           # same storage: a captured graph keeps pointing at it
@@ -470,6 +519,7 @@ def prefetch_batch(pairs):
     """bf16 shadows of many masters in ONE launch per 64 matrices (hriemo_cast_f32_to_bf16_batch): pairs = ((Shadows, param), ...).
     The gate's and the decoder's fourteen matrices at the top of a step: one ~25 us launch instead of a chain of fourteen
     dependent ~5 us ones in front of whatever runs next on that stream."""
+    _note_form(("prefetch_batch",) + tuple((id(sh), id(p)) for sh, p in pairs), prefetch_batch, pairs)
     jobs, upd = [], []
     for sh, p in pairs:
         need, dst, ver = sh.stale(p)
@@ -494,9 +544,10 @@ def prefetch_batch(pairs):
 def padded_shadow(sh, p, kp):
     """bf16 shadow of a [N,K] weight zero-padded to [N,kp] (kp = K rounded up to 8: 16-byte rows)"""
     key = (id(p), "pad")
+    _note_form(("padded_shadow", id(sh), key), padded_shadow, sh, p, kp)
     ent = sh._d.get(key)
     ver = (p._version, p.data_ptr(), WEIGHTS_EPOCH)
-    if CTX.capturing or ent is None or ent[0] != ver or ent[1].device != p.device:
+    if form_stale(ent, ver, p.device, once_per_step=False):
         _require_gpu(p)
         _require_fp32_master(p)
         s_ = ent[1] if ent is not None and ent[1].device == p.device else \
@@ -658,13 +709,17 @@ def want_mx_copy(M, d):
     return gemm_mode() == "mx_fp8" and d % 128 == 0 and M >= MX_MIN_ROWS
 
 
-def quant_mx8(x):
-    """x [M,K] bf16 or fp32 (row stride free) -> (e4m3 bytes [M,K], E8M0 scales [K/32, ld])"""
+def quant_mx8(x, out=None):
+    """x [M,K] bf16 or fp32 (row stride free) -> (e4m3 bytes [M,K], E8M0 scales [K/32, ld]); out: a pair of that form and device to
+    write into (anything else: fresh buffers)"""
     M, K = x.shape
     L_ = _lib.lib()
     ld = L_.hriemo_mx8_scale_ld(M)
-    q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
-    sc = torch.empty((K // 32, ld), dtype=torch.uint8, device=x.device)
+    if out is not None and out[0].shape == (M, K) and out[1].shape == (K // 32, ld) and out[0].device == out[1].device == x.device:
+        q, sc = out
+    else:
+        q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
+        sc = torch.empty((K // 32, ld), dtype=torch.uint8, device=x.device)
     _lib.call("hriemo_quant_mx8", _p(x), x.stride(0), int(x.dtype == torch.float32), M, K, _p(q), K, _p(sc), ld, _stream())
     return q, sc
 
@@ -690,9 +745,10 @@ def linear_fwd_mx8(xq, xs, wq, ws, bias, relu=False, out_f32=False, want_q=False
 def mx8_shadow(sh, p, rows=None):
     """MX-fp8 copy (bytes, scales) of an fp32 master weight [N,K] (or of its row slice `rows`), refreshed like the bf16 shadow"""
     key = (id(p), "mx8", rows)
+    _note_form(("mx8_shadow", id(sh), key), mx8_shadow, sh, p, rows)
     ent = sh._d.get(key)
     ver = (p._version, p.data_ptr(), WEIGHTS_EPOCH)
-    if CTX.capturing or ent is None or ent[0] != ver:
+    if form_stale(ent, ver, once_per_step=False):
         _require_gpu(p)
         _require_fp32_master(p)
         src = p.detach()
@@ -700,7 +756,9 @@ def mx8_shadow(sh, p, rows=None):
             src = src[rows[0]:rows[1]]
         if not src.is_contiguous():
             src = src.contiguous()
-        ent = (ver, quant_mx8(src))
+        # a refresh writes into the buffers the form already has: a captured graph (and a stationary evaluation, whose bucket
+        # graphs never derive it themselves) keeps pointing at them
+        ent = (ver, quant_mx8(src, out=ent[1] if ent is not None else None))
         sh._d[key] = ent
     return ent[1]
 

@@ -1219,13 +1219,107 @@ def _mode_switches():
             ("PACKED_TAIL_FP32", bool(_ops.PACKED_TAIL_FP32)), ("PACKED_TAIL_MX8", bool(_ops.PACKED_TAIL_MX8)), ("ingest", _ops.ingest()))
 
 
+class _WeightsPass:
+    """What a stationary EvalStep keeps beside its bucket graphs: everything that depends on the parameters alone.
+      log      the _ops.FormLog of the weight forms the step's forwards asked for
+      records  _GraphRecords replayed in order.  The first holds the forms of the first bucket's forward and the decoder's query
+               prologue (its `out`: the static (tgt, tgt32) layer 0 reads, None for a model without a decoder); a later one the
+               forms a later bucket asked for first.  Each is recorded by the default capture rule with the step's context not
+               stationary: every form once per pass, in the order the forward asked.
+      seen     (_ops.WEIGHTS_EPOCH, every parameter's _version) when the pass last ran; ptrs: every parameter's data_ptr() at the
+               capture; forms: (Shadows, key) -> the data_ptr()s of that cached form at the capture"""
+
+    def __init__(self, model, B):
+        from . import _ops
+        from .models.emotion_decoder import EmotionDecoder
+        self.model, self.params = model, list(model.parameters())
+        self.shadows = [m._sh for m in model.modules() if hasattr(m, "_sh")]
+        decoders = [m for m in model.modules() if isinstance(m, EmotionDecoder)]
+        self.decoder, self.B = (decoders[0] if decoders else None), B
+        self.log, self.records, self.entries = _ops.FormLog(), [], []
+        self.seen, self.ptrs, self.forms = None, tuple(p.data_ptr() for p in self.params), {}
+
+    def _body(self, entries, prologue):
+        with torch.no_grad():
+            for _, fn, args in entries:
+                fn(*args)
+            out = self.decoder.prologue(self.B) if prologue else None
+        return None, out
+
+    def eager(self):
+        """the whole pass as plain launches, by the eager rule: every form whose masters moved, then the prologue (tests, and the
+        measurement of what an evaluation behind an update pays)"""
+        from . import _ops
+        was = self.model.training
+        self.model.eval()
+        try:
+            _ops.begin_step()
+            return self._body(self.entries, self.decoder is not None)[1]
+        finally:
+            self.model.train(was)
+
+    def record(self, dev, new):
+        """one more graph: the derivation of the forms `new`, and, in the first, the prologue"""
+        prologue = not self.records and self.decoder is not None
+        self.records.append(_record_graph(dev, None, None, lambda: self._body(new, prologue), lambda: self._body(new, prologue)))
+        self.entries += new
+        self.replay()
+
+    def handed(self, decoder, B):
+        """_ops.StepContext.prologue of the step's bucket passes"""
+        if decoder is not self.decoder or B != self.B or not self.records:
+            raise RuntimeError("EvalStep (stationary): the decoder asks for a prologue the weights pass did not record")
+        return self.records[0].out
+
+    def state(self):
+        from . import _ops
+        return (_ops.WEIGHTS_EPOCH, tuple(p._version for p in self.params))
+
+    def moved(self):
+        return self.seen != self.state()
+
+    def replay(self):
+        for rec in self.records:
+            rec.graph.replay()
+        self.seen = self.state()
+
+    def _form_ptrs(self):
+        out = {}
+        for sh in self.shadows:
+            for key, ent in sh._d.items():
+                form = ent[1]
+                out[(id(sh), key)] = tuple(t.data_ptr() for t in (form if isinstance(form, tuple) else (form,)))
+        return out
+
+    def note(self):
+        """the forms as they lie in memory now, behind a capture: what the bucket graphs point at"""
+        self.forms = self._form_ptrs()
+
+    def rehomed(self, forms):
+        """None, or what lives elsewhere than at the capture: a parameter, or (looked at with `forms` only: a form's storage
+        changes in a refresh, and a refresh needs moved weights) a weight form"""
+        if tuple(p.data_ptr() for p in self.params) != self.ptrs:
+            return "a parameter"
+        if forms:
+            now = self._form_ptrs()
+            for key, ptrs in self.forms.items():
+                if now.get(key) != ptrs:
+                    return "a weight form"
+        return None
+
+    def release(self):
+        for rec in self.records:
+            rec.release()
+        self.records, self.entries = [], []
+
+
 class EvalStep(_RaggedStep):
     """The evaluation half of an epoch as graph replays: capture_packed / step_packed of DataParallelStep for the FORWARD alone --
     the reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
     and the loop of scripts/infer/mosei_eval_infer.py.  An eager forward is ~150 launches issued from Python; one ``eval_packed``
     is the copies of the batch into the static buffers and one replay.
 
-    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None): loss_fn(logits, beta, y, n_valid=...) as
+    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False): loss_fn(logits, beta, y, n_valid=...) as
     hri_emo_amd.train's losses; stats a ``train.EpochStats``, log a ``train.PredictionLog`` -- both are fed INSIDE the graph, one
     launch each, and never by a warm-up pass.  max_graphs: bucket graphs kept alive (default HRIEMO_VARLEN_MAX_GRAPHS), least
     recently replayed one released first.  The step has its own ``_ops.StepContext`` and its own graph pool, creates no gradient
@@ -1243,26 +1337,45 @@ class EvalStep(_RaggedStep):
     map -- packed tail off -- through one append.  Once the log is full those launches are blocks that read the window and exit, so
     one family of bucket graphs serves the whole split.  Warm-up passes run with the closed window and leave the log bit-unchanged.
     Needs set_varlen_maps(True); varlen_maps() and mfma_maps() then join the switches recorded at capture.  ``return_attention``
-    itself is not part of the captured step."""
+    itself is not part of the captured step.
+
+    stationary=True: a bucket graph holds only what depends on the batch.  What depends on the parameters alone -- every weight
+    form the forward asks for (bf16 shadows, concatenations, padded and MX-fp8 copies, the fp32 mode's splits) and the decoder's
+    query prologue (EmotionDecoder.prologue: the broadcast queries and layer 0's self-attention sub-layer) -- lives in the step's
+    WEIGHTS PASS: one more captured graph (a further one for forms a later bucket asks for first), recorded in front of the first
+    bucket graph by the default capture rule, so its launches and the bucket graph's are together those of a default bucket
+    graph, and the values are the same bits.  eval_packed / eval_store replay it in front of the bucket graph only when the
+    weights moved since it last ran: _ops.WEIGHTS_EPOCH changed (captured optimizer replays, DeviceAdamW.step,
+    FusedClipAdamW.step) or the _version of a parameter did (torch.optim, load_state_dict, in-place edits) -- host arithmetic,
+    nothing is read back.  Every form is refreshed in the storage the bucket graphs point at; when a parameter or a form has
+    moved to other memory since the capture (a DeviceAdamW built afterwards, .to()) the call raises RuntimeError("... capture
+    again") before anything is enqueued.  The default, False, is launch for launch the step without the option; use_graph(False)
+    ignores it."""
 
     _label = "eval step"
 
-    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None):
+    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False):
         if max_graphs is not None and int(max_graphs) < 1:
             raise ValueError("EvalStep: max_graphs is a positive integer (or None)")
         super().__init__(model, loss_fn)
         self.stats, self.log, self.attn_log = stats, log, attn_log
         self.max_graphs = None if max_graphs is None else int(max_graphs)
+        self.stationary = bool(stationary)
         self._modes = None                 # _mode_switches() at capture
+        self._weights = None               # _WeightsPass of a stationary step, from its first bucket capture to release_graph()
 
     def use_graph(self, on):
         """False: eval_packed is the eager forward_packed evaluation (same outputs, same updates of stats and log)"""
         self._replay = bool(on) and self.captured
 
     def release_graph(self):
-        """drop the captured step: the graphs, their outputs, the buffers their kernels point into, the static state"""
+        """drop the captured step: the graphs (a stationary step's weights pass included), their outputs, the buffers their kernels
+        point into, the static state"""
         self._release_buckets()
-        self._pb = self._static = self._modes = None
+        if self._weights is not None:
+            torch.cuda.synchronize()
+            self._weights.release()
+        self._pb = self._static = self._modes = self._weights = None
 
     def _switches(self):
         """the switches a replay depends on: with an attention log also the two that pick the export kernels"""
@@ -1347,7 +1460,8 @@ class EvalStep(_RaggedStep):
             rows_a, _, rows_t, _, y = feed.store.fetch(ids)
             return self._eval_eager(rows_a, rows_t, la, lt, y if targets else None)
         self._check_modes("eval_store", "capture_store")
-        return self._replay_bucket(self._load_store(ids, la, lt), len(ids))
+        moved = self.stationary and self._weights_moved("eval_store")
+        return self._replay_bucket(self._load_store(ids, la, lt), len(ids), moved)
 
     def _pass(self, record):
         """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
@@ -1376,15 +1490,67 @@ class EvalStep(_RaggedStep):
 
     def _capture_bucket(self, seqs):
         """the bucket graph of the plans `seqs` (_PackedState.graph): the module in eval mode while it is warmed up and recorded"""
+        from . import _ops
         was = self.model.training
         self.model.eval()
         try:
-            return _record_graph(self._static[0].device, seqs, self._pb.pool, lambda: self._pass(False), lambda: self._pass(True))
+            if not self.stationary:
+                return _record_graph(self._static[0].device, seqs, self._pb.pool, lambda: self._pass(False), lambda: self._pass(True))
+            # stationary: the weights pass first (the forms this bucket's forward asks for, the prologue), then the bucket's passes
+            # with the rule switched -- the warm-up passes find every form fresh, the capture pass must (_ops.form_stale raises)
+            self._prepare_weights(seqs)
+            ctx = _ops.CTX
+            ctx.stationary, ctx.prologue = True, self._weights.handed
+            try:
+                return _record_graph(self._static[0].device, seqs, self._pb.pool, lambda: self._pass(False), lambda: self._pass(True))
+            finally:
+                ctx.stationary, ctx.prologue = False, None
         finally:
             self.model.train(was)
 
-    def _replay_bucket(self, key, n):
-        """the graph of bucket `key` (captured now if it is new) replayed on the static state -> the outputs of its first n samples"""
+    def _prepare_weights(self, seqs):
+        """in front of a stationary bucket capture, module in eval mode: one eager default pass on the bucket's plans under a FormLog
+        finds the weight forms this forward asks for; the ones not known yet are recorded, with the prologue the first time, as a
+        further graph of the weights pass, which is then replayed once: its outputs are what the bucket graphs read"""
+        from . import _ops
+        dev = self._static[0].device
+        if self._weights is None:
+            self._weights = _WeightsPass(self.model, self._pb.B)
+        wp, ctx = self._weights, _ops.CTX
+        side = _capture_streams.get(dev.index)
+        if side is None:
+            side = _capture_streams[dev.index] = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        ctx.seq_override, ctx.forms = seqs, wp.log
+        try:
+            with torch.cuda.stream(side):
+                self._pass(False)
+        finally:
+            ctx.seq_override, ctx.forms = None, None
+        torch.cuda.current_stream().wait_stream(side)
+        new = wp.log.take()
+        if new or (not wp.records and wp.decoder is not None):
+            wp.record(dev, new)
+        wp.note()
+
+    def _weights_moved(self, who):
+        """host arithmetic in front of a stationary replay -> did the weights move since the weights pass last ran?  RuntimeError,
+        before anything is enqueued, when a parameter or a weight form lives in other memory than at the capture"""
+        wp = self._weights
+        if wp is None:
+            return False
+        moved = wp.moved()
+        why = wp.rehomed(forms=moved)
+        if why is not None:
+            raise RuntimeError(f"EvalStep.{who}: {why} moved to other memory since the capture (an optimizer built afterwards, .to()): "
+                               "the stationary bucket graphs still point at the old one -- capture again")
+        return moved
+
+    def _replay_bucket(self, key, n, moved=False):
+        """the graph of bucket `key` (captured now if it is new) replayed on the static state -> the outputs of its first n samples;
+        moved: a stationary step whose weights moved (_weights_moved) -- its weights pass goes first"""
+        if moved:
+            self._weights.replay()                # the weights moved: every form and the prologue again, into the same storage
         rec = self._packed_graph(key)
         rec.graph.replay()
         logits, beta, z = rec.out
@@ -1422,7 +1588,8 @@ class EvalStep(_RaggedStep):
         if sy is not None and y is None:
             raise ValueError("eval_packed: the step was captured with targets; this batch has none")
         self._check_batch("eval_packed", rows_a, rows_t, n, y)
-        return self._replay_bucket(self._load_packed(rows_a, rows_t, la, lt, y), n)
+        moved = self.stationary and self._weights_moved("eval_packed")
+        return self._replay_bucket(self._load_packed(rows_a, rows_t, la, lt, y), n, moved)
 
     def _eval_eager(self, rows_a, rows_t, la, lt, y):
         pb = self._pb

@@ -50,16 +50,21 @@ class ExplainableDecoderLayer(nn.Module):
                                               self.nhead, sp, p, seed, self._site[0], self.batch_offset, False)       # :42-43
         return tgt, tgt32, seed
 
-    def _fwd_pair(self, tgt, tgt32, memory, sm, need, kv_pre=None, kv_ready=None):
+    def _fwd_pair(self, tgt, tgt32, memory, sm, need, kv_pre=None, kv_ready=None, self_done=False):
         """sm: the _ops.Seq of the memory's rows -- padded [B, L_f, d] with its mask, or the fused plan: memory is then the packed
-        fused memory [1, N_f, d] and the cross-attention runs on cu_seqlens (N_e query rows per sample, the fused lengths as keys)."""
+        fused memory [1, N_f, d] and the cross-attention runs on cu_seqlens (N_e query rows per sample, the fused lengths as keys).
+        self_done: (tgt, tgt32) are what _self_block returned already (EmotionDecoder.prologue) -- the layer starts at its
+        cross-attention."""
         packed = sm.packed
         Bq, Nq, dq = tgt.shape
         sp = _ops.Seq.padded(Bq, Nq)                                        # the queries' own layout (no mask) ...
         sq = _ops.query_seq(Bq, Nq, tgt.device) if packed else sp           # ... and as the cross-attention on `memory` sees it
         p = self.p if self.training else 0.0
         ca, s = self.cross_attn, self._site
-        tgt, tgt32, seed = self._self_block(tgt, tgt32, sp)
+        if self_done:
+            seed = _ops.next_seed(self.training and p > 0)
+        else:
+            tgt, tgt32, seed = self._self_block(tgt, tgt32, sp)
         if kv_ready is not None:          # K | V of the memory were projected on the side stream (EmotionDecoder._fwd)
             torch.cuda.current_stream(memory.device).wait_event(kv_ready)
         if packed:
@@ -110,11 +115,22 @@ class EmotionDecoder(nn.Module):
         out32 = self.emotion_queries.detach().float().unsqueeze(0).expand(B, -1, -1).contiguous() if _ops.TWIN else None
         return out, out32
 
+    def prologue(self, B):
+        """What the decoder computes from parameters alone once dropout is off: the broadcast queries and layer 0's query
+        self-attention sub-layer, [B, N_e, d] -> (tgt, tgt32) as layer 0's cross-attention takes them.  A stationary dp.EvalStep
+        runs this in its weights pass and hands the result to _fwd through its step context."""
+        if self.training:
+            raise RuntimeError("EmotionDecoder.prologue: the query prologue depends on parameters alone in eval mode only")
+        out, out32 = self._queries(B)
+        tgt, tgt32, _ = self.layers[0]._self_block(out, out32, _ops.Seq.padded(B, out.shape[1]))
+        return tgt, tgt32
+
     def _fwd(self, memory16, sm, need, out_dtype):
         """sm: the _ops.Seq of the memory's rows -- a padded memory [B, L_f, d] with its [B, L_f] mask, or the fused plan of a packed
         memory [1, N_f, d] (the K | V projections then run over the N_f packed rows)
         need: a bool, or a train.AttentionLog's decoder sites (per layer an _ops.LogSite): the maps go to the log, none is returned"""
-        out, out32 = self._queries(sm.Breal)
+        handed = _ops.CTX.prologue          # a stationary dp.EvalStep inside a bucket pass; None everywhere else
+        out, out32 = handed(self, sm.Breal) if handed is not None else self._queries(sm.Breal)
         all_layers_attn = []
         if _ops.mx_of(memory16) is None and _ops.want_mx_copy(memory16.shape[0] * memory16.shape[1], memory16.shape[2]):
             # fp8 GEMM mode: every layer projects the same memory to K | V -- quantise it once (a packed memory arrives with the
@@ -142,7 +158,7 @@ class EmotionDecoder(nn.Module):
                 _ops.share(kv, main)
         for i, layer in enumerate(self.layers):
             out, out32, attn_map = layer._fwd_pair(out, out32, memory16, sm, need[i] if isinstance(need, list) else need, kvs[i],
-                                                   ready if i == 0 else None)
+                                                   ready if i == 0 else None, self_done=(i == 0 and handed is not None))
             if need and attn_map is not None:
                 all_layers_attn.append(attn_map)
         logits = None
