@@ -13,7 +13,7 @@ from .models.mosei_fusion_with_emotion_decoder import MoseiFusionWithEmotionDeco
 from .models.fusion_classifier import FusionClassifier  # noqa: F401
 
 from .dp import EvalStep  # noqa: F401
-from ._ops import set_gemm_mode, gemm_mode, enable_fused_wgrad, set_precision, precision, set_varlen, varlen, set_varlen_maps, varlen_maps, set_mfma_maps, mfma_maps, set_ingest, ingest  # noqa: F401
+from ._ops import set_gemm_mode, gemm_mode, enable_fused_wgrad, set_precision, precision, set_varlen, varlen, set_varlen_maps, varlen_maps, set_mfma_maps, mfma_maps, set_ingest, ingest, set_pooled_gate_fp32, pooled_gate_fp32  # noqa: F401
 
-__all__ = ["EvalStep", "set_gemm_mode", "gemm_mode", "enable_fused_wgrad", "set_precision", "precision", "set_varlen", "varlen", "set_varlen_maps", "varlen_maps", "set_mfma_maps", "mfma_maps", "set_ingest", "ingest", "CrossModalBlock", "CrossModalTransformer", "BetaGate", "EmotionDecoder", "ExplainableDecoderLayer",
+__all__ = ["EvalStep", "set_gemm_mode", "gemm_mode", "enable_fused_wgrad", "set_precision", "precision", "set_varlen", "varlen", "set_varlen_maps", "varlen_maps", "set_mfma_maps", "mfma_maps", "set_ingest", "ingest", "set_pooled_gate_fp32", "pooled_gate_fp32", "CrossModalBlock", "CrossModalTransformer", "BetaGate", "EmotionDecoder", "ExplainableDecoderLayer",
            "FusionWithEmotionDecoder", "MoseiFusionWithEmotionDecoder", "FusionClassifier"]

@@ -572,6 +572,90 @@ def beta_gate_bwd(ctx, dH, dbeta):
     return ga16, ga32, gt16, gt32, dga, dba, dgt, dbt, dw1, db1, dw2, db2, None, None, None, None
 
 
+def pooled_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st):
+    """models/fusion_classifier.py:142-145 in fp32 -> (pooled fp32 [B, d], beta [B, 1]): the mean over the L fused positions of
+    beta_gate's h_fusion, PAD rows included, without the LayerNorm outputs, h_fusion or a [B, L, d] gradient of it
+    (hriemo_pool32_*; the [B, d]-sized pieces are the kernels of the bf16 pooled gate and of beta_gate).  sa / st: the padded Seq of
+    _ops.PooledGateFn, which has checked them."""
+    _ops._require_fp32_masters(ga, ba, gt, bt, w1, b1, w2, b2)
+    _ops._require_gpu(h_a)
+    B, La, Lt, d = sa.Breal, sa.L, st.L, h_a.shape[-1]
+    L = _ops._gate_align(La, Lt)
+    dev = h_a.device
+    st_ = _ops._stream()
+    chunks = _lib.lib().hriemo_pool_chunks
+    a32 = _twin(h_a, h_a32).view(B, La, d)
+    t32 = _twin(h_t, h_t32).view(B, Lt, d)
+    parts = []
+    for x32, sx, gamma, beta_ in ((a32, sa, ga, ba), (t32, st, gt, bt)):
+        pv = torch.empty((B, chunks(sx.L), d), dtype=F32, device=dev)
+        pk = torch.empty_like(pv)
+        _lib.call("hriemo_pool32_ln_fwd", _ops._p(x32), _ops._p(sx.kpm), _ops._p(gamma.detach()), _ops._p(beta_.detach()), _ops._p(pv),
+                  _ops._p(pk), B, sx.L, L, d, _ops._EPS, st_)
+        parts.append((pv, pk))
+    (pa, ka), (pt, kt) = parts
+    a_pool, t_pool = _new((B, d), a32), _new((B, d), a32)
+    gin = _new((B, 4 * d), a32)
+    _lib.call("hriemo_pool32_gate_input", _ops._p(pa), _ops._p(sa.kpm), La, _ops._p(pt), _ops._p(st.kpm), Lt, _ops._p(a_pool),
+              _ops._p(t_pool), _ops._p(gin), B, d, st_)
+    hid = linear(gin, sh, w1, b1)
+    pre = linear(hid, sh, w2, b2, relu_in=True)
+    w, beta = _new((B, d), a32), _new((B, 1), a32)
+    _lib.call("hriemo_sigmoid_beta_f32", _ops._p(pre), _ops._p(w), _ops._p(beta), B, d, st_)
+    abar, tbar, pooled = _new((B, d), a32), _new((B, d), a32), _new((B, d), a32)
+    _lib.call("hriemo_pooled_fuse_fwd", _ops._p(ka), La, _ops._p(kt), Lt, _ops._p(w), L, _ops._p(abar), _ops._p(tbar), _ops._p(pooled),
+              B, d, st_)
+    ctx.fp32 = True
+    if recording(ctx):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(a32, t32, a_pool, t_pool, gin, hid, w, abar, tbar)
+        ctx.seqs = (sa, st)
+        ctx.f32_params = (ga, ba, gt, bt, w1, b1, w2, b2, sh)
+        ctx.f32_twins = (h_a32 is not None, h_t32 is not None, h_a.dtype, h_t.dtype)
+    return pooled, beta
+
+
+def pooled_gate_bwd(ctx, dpooled, dbeta):
+    a32, t32, a_pool, t_pool, gin, hid, w, abar, tbar = ctx.saved_tensors
+    sa, st = ctx.seqs
+    B, La, Lt, L, d = sa.Breal, sa.L, st.L, st.L, a32.shape[-1]
+    ga, ba, gt, bt, w1, b1, w2, b2, sh = ctx.f32_params
+    dev = a32.device
+    st_ = _ops._stream()
+    dp = _c(dpooled.float()).view(B, d) if dpooled is not None else torch.zeros((B, d), dtype=F32, device=dev)
+    db = _c(dbeta.float()).view(B) if dbeta is not None else None
+    # row gradients g_a = w dpooled / L, g_t = (1 - w) dpooled / L of every row l < L (dw: the bf16 path's partial, unused here)
+    dwf, g_a, g_t = _new((B, d), a32), _new((B, d), a32), _new((B, d), a32)
+    _lib.call("hriemo_pooled_fuse_bwd", _ops._p(dp), _ops._p(abar), _ops._p(tbar), _ops._p(w), L, _ops._p(dwf), _ops._p(g_a), _ops._p(g_t),
+              B, d, st_)
+    # pooled = w Abar + (1 - w) Tbar is beta_gate's fusion over ONE position: dpre from its kernel with L = 1
+    dpre = _new((B, d), a32)
+    _lib.call("hriemo_gate_dpre_f32", _ops._p(dp), _ops._p(abar), 1, _ops._p(tbar), 1, _ops._p(w), _ops._p(db), _ops._p(dpre), B, 1, d, st_)
+    dw2 = linear_dw(dpre, hid, relu_x=True)
+    db2 = colsum(dpre)
+    dhid = linear_dx(dpre, sh, w2)
+    dw1 = linear_dw(dhid, gin, mask=hid)
+    db1 = colsum(dhid, mask=hid)
+    dgin = linear_dx(dhid, sh, w1, mask=hid)
+    da, dt = _new((B, d), a32), _new((B, d), a32)
+    _lib.call("hriemo_gate_input_bwd_f32", _ops._p(dgin), _ops._p(a_pool), _ops._p(t_pool), _ops._p(da), _ops._p(dt), B, d, st_)
+    outs = []
+    for g, dpool, sx, x32, gamma in ((g_a, da, sa, a32, ga), (g_t, dt, st, t32, gt)):
+        dx = _new((B, sx.L, d), a32)
+        stats = _new((2, d), a32)
+        ws = _ws(_lib.lib().hriemo_pool32_ln_bwd_workspace_bytes(B, sx.L, d), dev)
+        _lib.call("hriemo_pool32_ln_bwd", _ops._p(g), L, _ops._p(dpool), _ops._p(sx.kpm), _ops._p(x32), _ops._p(gamma.detach()), _ops._p(dx),
+                  _ops._p(stats[0]), _ops._p(stats[1]), 0, B, sx.L, d, _ops._EPS, _ops._p(ws), st_)
+        outs.append((dx, stats[0], stats[1]))
+    (dxa, dga, dba), (dxt, dgt, dbt) = outs
+    twin_a, twin_t, dt_a, dt_t = ctx.f32_twins
+    ga16 = None if twin_a else (dxa.to(dt_a) if ctx.needs_input_grad[0] else None)
+    ga32 = dxa if (twin_a and ctx.needs_input_grad[1]) else None
+    gt16 = None if twin_t else (dxt.to(dt_t) if ctx.needs_input_grad[2] else None)
+    gt32 = dxt if (twin_t and ctx.needs_input_grad[3]) else None
+    return ga16, ga32, gt16, gt32, dga, dba, dgt, dbt, dw1, db1, dw2, db2, None, None, None
+
+
 def linear_any_k(ctx, x, w, b, sh):
     """LinearFn (MOSEI projections, K = 74 / 300): contraction padded to a multiple of 8"""
     _ops._require_fp32_masters(w, b)

@@ -142,6 +142,10 @@ _SIGS = {
     "hriemo_pooled_fuse_bwd": ("ppppipppiip", "i"),
     "hriemo_ln_pool_vec_bwd": ("pi" + "p" * 10 + "iiiipp", "i"),
     "hriemo_ln_pool_vec_bwd_pair": ("i" + ("p" * 11 + "ip") * 2 + "iiip", "i"),
+    "hriemo_pool32_ln_fwd": ("pppppp" + "iiiifp", "i"),
+    "hriemo_pool32_gate_input": ("ppippipppiip", "i"),
+    "hriemo_pool32_ln_bwd_workspace_bytes": ("iii", "l"),
+    "hriemo_pool32_ln_bwd": ("pippppppp" + "iiiifpp", "i"),
     "hriemo_ingest_padded": ("pilpiiiippp", "i"),
     "hriemo_ln_pool_fwd_packed": ("pppiippppppipiiifp", "i"),
     "hriemo_ln_pool_fwd_packed_pair": ("pppiippppppi" * 2 + "piiifp", "i"),

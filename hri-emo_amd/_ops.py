@@ -2687,9 +2687,29 @@ def pooled_gate():
     return bool(POOLED_GATE)
 
 
-def _require_bf16_path(who):
-    if precision() != "bf16" or gemm_mode() != "bf16":
-        raise NotImplementedError(f"{who}: built for the bf16 path only (precision {precision()!r}, GEMM mode {gemm_mode()!r})")
+# The pooled gate in the fp32 precision mode (_fp32.pooled_gate, hriemo_pool32_*): with it FusionClassifier's ragged path --
+# forward_packed, the captured steps, EvalStep, forward() under POOLED_GATE -- runs in fp32.  A switch of its own, for the reason
+# PACKED_TAIL_FP32 has one: an arm becomes a default only after it has been measured as a step (DESIGN 3.5,
+# scripts_dev/bench_classifier_fp32.py).  False: the pooled path refuses the fp32 precision, as it did before the fp32 gate existed.
+POOLED_GATE_FP32 = False
+
+
+def set_pooled_gate_fp32(on):
+    global POOLED_GATE_FP32
+    POOLED_GATE_FP32 = bool(on)
+
+
+def pooled_gate_fp32():
+    return bool(POOLED_GATE_FP32)
+
+
+def _require_pooled_path(who):
+    """the pooled gate serves bf16 GEMM operands in bf16 precision, and in fp32 precision once POOLED_GATE_FP32 is set"""
+    if gemm_mode() != "bf16":
+        raise NotImplementedError(f"{who}: built for the bf16 GEMM mode only (precision {precision()!r}, GEMM mode {gemm_mode()!r})")
+    if precision() == "fp32" and not POOLED_GATE_FP32:
+        raise NotImplementedError(f"{who}: the fp32 precision takes the pooled gate only with _ops.POOLED_GATE_FP32 set "
+                                  f"(hri_emo_amd.set_pooled_gate_fp32(True)); precision {precision()!r}, GEMM mode {gemm_mode()!r}")
 
 
 class IngestPaddedFn(torch.autograd.Function):
@@ -2768,10 +2788,13 @@ class PooledGateFn(_GradModeAware, torch.autograd.Function):
     def forward(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st):
         if sa.packed or st.packed:
             raise ValueError("PooledGate: the pooled mean includes PAD rows -- padded layouts only")
-        _require_bf16_path("PooledGate")
+        _require_pooled_path("PooledGate")
         B, La, Lt, d = sa.Breal, sa.L, st.L, h_a.shape[-1]
         sa.holds(h_a)
         st.holds(h_t)
+        _gate_align(La, Lt)                  # the refusal comes before the fp32 dispatch, as in BetaGateFn
+        if precision() == "fp32":           # -> (pooled fp32, beta)
+            return _fp32().pooled_gate(ctx, h_a, h_a32, h_t, h_t32, ga, ba, gt, bt, w1, b1, w2, b2, sh, sa, st)
         L, xa, h_a32, xt, h_t32, (mean_a, rstd_a, pa), (mean_t, rstd_t, pt) = _gate_prologue(h_a, h_a32, h_t, h_t32,
                                                                                               (ga, ba, gt, bt, w1, b1, w2, b2), sa, st)
         dev = h_a.device
@@ -2790,6 +2813,8 @@ class PooledGateFn(_GradModeAware, torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled, dbeta):
+        if getattr(ctx, "fp32", False):
+            return _fp32().pooled_gate_bwd(ctx, dpooled, dbeta)
         (xa, xt, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16, w2_16, ga, gt, h_a32, h_t32,
          abar, tbar) = ctx.saved_tensors
         sa, st = ctx.seqs

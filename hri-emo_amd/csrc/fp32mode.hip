@@ -1267,6 +1267,266 @@ extern "C" int hriemo_rowdot_bwd_f32(const float* dl, const float* Z, const floa
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------- pooled gate in fp32 (FusionClassifier)
+// The classifier reads the fused sequence only through its UNMASKED mean (models/fusion_classifier.py:142-145), so
+// pooled = w * Abar + (1 - w) * Tbar with Abar = mean_{l < Lkeep} LN_a(h_a)[:, l] (PAD rows included): the bf16 pooled gate of
+// rowops.hip (hriemo_ln_pool2_fwd / hriemo_ln_pool_vec_bwd) in this file's arithmetic.  Padded rows only, d <= 1024 (the limit of
+// this mode's LayerNorm backward: the row, its gradient and two column accumulators in registers).  The [B, d]-sized pieces
+// (hriemo_pooled_fuse_fwd / _bwd, the sigmoid, the gate input's backward) are the existing kernels.
+//
+// Forward: block = one 32-row chunk of one sample, wave w takes rows 32 chunk + w, + 4, ...; the LayerNorm of add_ln_f32_kernel per
+// row, never stored; two column accumulators per wave (valid rows / rows l < Lkeep), folded wave 0..3 in LDS.
+#define POOL32_NV4 4
+static int pool32_chunks(int L) { return (L + 31) / 32; }          // = hriemo_pool_chunks (rowops.hip)
+// fold the four waves' column accumulators in wave order into dst [d] (LDS); ends behind a barrier
+__device__ __forceinline__ void pool32_fold(const f32x4 (&a)[POOL32_NV4], float* dst, int nq, int lane, int wave) {
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int c = 0; c < POOL32_NV4; ++c) {
+        const int q = lane + 64 * c;
+        if (q < nq) {
+          f32x4 v = a[c];
+          if (w != 0) v += *(const f32x4*)(dst + q * 4);
+          *(f32x4*)(dst + q * 4) = v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(256) void pool32_ln_fwd_kernel(const float* __restrict__ X, const uint8_t* __restrict__ mask,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ part_valid, float* __restrict__ part_keep, int L, int Lkeep,
+                                                            int d, float eps) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* red = (float*)smem_raw;            // [2][d]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int chunk = blockIdx.x, b = blockIdx.y, nq = d >> 2;
+  const int lend = min(L, chunk * 32 + 32);
+  f32x4 av[POOL32_NV4], ak[POOL32_NV4];
+#pragma unroll
+  for (int c = 0; c < POOL32_NV4; ++c) av[c] = ak[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int l = chunk * 32 + wave; l < lend; l += 4) {
+    const long row = (long)b * L + l;
+    f32x4 s[POOL32_NV4];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < POOL32_NV4; ++c) {
+      const int q = lane + 64 * c;
+      s[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (q < nq) {
+        s[c] = *(const f32x4*)(X + row * d + q * 4);
+        sum += s[c][0] + s[c][1] + s[c][2] + s[c][3];
+      }
+    }
+    const float mu = wave_sum(sum) / (float)d;
+    float sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < POOL32_NV4; ++c)
+      if (lane + 64 * c < nq) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float t = s[c][j] - mu; sq += t * t; }
+      }
+    const float rstd = 1.f / sqrtf(wave_sum(sq) / (float)d + eps);
+    const bool valid = mask == nullptr || mask[row] == 0;
+    const bool kept = l < Lkeep;
+#pragma unroll
+    for (int c = 0; c < POOL32_NV4; ++c) {
+      const int q = lane + 64 * c;
+      if (q < nq) {
+        const f32x4 gm = *(const f32x4*)(gamma + q * 4), bt = *(const f32x4*)(beta + q * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float o = (s[c][j] - mu) * rstd * gm[j] + bt[j];
+          if (valid) av[c][j] += o;
+          if (kept) ak[c][j] += o;
+        }
+      }
+    }
+  }
+  pool32_fold(av, red, nq, lane, wave);
+  pool32_fold(ak, red + d, nq, lane, wave);
+  const long o = ((long)b * gridDim.x + chunk) * d;
+  for (int t = threadIdx.x; t < d; t += 256) { part_valid[o + t] = red[t]; part_keep[o + t] = red[d + t]; }
+}
+// number of valid rows of sample b, formed by one wave as gate_dy_f32_kernel forms it (exact: a sum of ones)
+__device__ __forceinline__ float pool32_count(const uint8_t* __restrict__ mask, int b, int L, int lane) {
+  float n = 0.f;
+  for (int k = lane; k < L; k += 64) n += (mask == nullptr || mask[(long)b * L + k] == 0) ? 1.f : 0.f;
+  return fmaxf(wave_sum(n), 1.f);
+}
+// masked means from the chunk sums (chunk order) and the gate input [a, t, |a - t|, a * t]: the expressions of
+// masked_mean_f32_kernel's division and of gate_in_f32_kernel
+__global__ __launch_bounds__(256) void pool32_gate_in_kernel(const float* __restrict__ pa, const uint8_t* __restrict__ mask_a, int La,
+                                                             const float* __restrict__ pt, const uint8_t* __restrict__ mask_t, int Lt,
+                                                             float* __restrict__ a_pool, float* __restrict__ t_pool, float* __restrict__ gin,
+                                                             int d) {
+  __shared__ float cnt_s[2];
+  const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave < 2) {
+    const float n = wave == 0 ? pool32_count(mask_a, b, La, lane) : pool32_count(mask_t, b, Lt, lane);
+    if (lane == 0) cnt_s[wave] = n;
+  }
+  __syncthreads();
+  if (c >= d) return;
+  const int nca = (La + 31) / 32, nct = (Lt + 31) / 32;
+  float sa = 0.f, st = 0.f;
+  for (int k = 0; k < nca; ++k) sa += pa[((long)b * nca + k) * d + c];
+  for (int k = 0; k < nct; ++k) st += pt[((long)b * nct + k) * d + c];
+  const float av = sa / cnt_s[0], tv = st / cnt_s[1];
+  a_pool[(long)b * d + c] = av;
+  t_pool[(long)b * d + c] = tv;
+  float* g = gin + (long)b * 4 * d;
+  g[c] = av; g[d + c] = tv; g[2 * d + c] = fabsf(av - tv); g[3 * d + c] = av * tv;
+}
+// Backward of pool32_ln_fwd for one modality: dYn[b, l] = (l < Lkeep ? g[b] : 0) + (valid ? dpool[b] / max(#valid_b, 1) : 0),
+// dX = LayerNorm'(dYn) with the statistics recomputed from X (add_ln_bwd_f32_kernel's row arithmetic).  A block walks the
+// (sample, chunk) pairs blockIdx.x, + gridDim.x, ...; its column partials [dgamma | dbeta] go to part (NULL: not wanted).
+__global__ __launch_bounds__(256) void pool32_ln_bwd_kernel(const float* __restrict__ g, int Lkeep, const float* __restrict__ dpool,
+                                                            const uint8_t* __restrict__ mask, const float* __restrict__ X,
+                                                            const float* __restrict__ gamma, float* __restrict__ dX, float* __restrict__ part,
+                                                            int B, int L, int d, float eps) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* red = (float*)smem_raw;            // [2][d]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nq = d >> 2, nc = (L + 31) / 32;
+  const float invd = 1.f / (float)d;
+  f32x4 ag[POOL32_NV4], ab[POOL32_NV4];
+#pragma unroll
+  for (int c = 0; c < POOL32_NV4; ++c) ag[c] = ab[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int item = blockIdx.x; item < B * nc; item += gridDim.x) {
+    const int b = item / nc, chunk = item - b * nc;
+    const int lend = min(L, chunk * 32 + 32);
+    const float cnt = pool32_count(mask, b, L, lane);
+    for (int l = chunk * 32 + wave; l < lend; l += 4) {
+      const long row = (long)b * L + l;
+      const bool valid = mask == nullptr || mask[row] == 0;
+      const bool kept = g != nullptr && l < Lkeep;
+      f32x4 s[POOL32_NV4], dy[POOL32_NV4];
+      float sum = 0.f;
+#pragma unroll
+      for (int c = 0; c < POOL32_NV4; ++c) {
+        const int q = lane + 64 * c;
+        s[c] = dy[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (q < nq) {
+          s[c] = *(const f32x4*)(X + row * d + q * 4);
+          sum += (s[c][0] + s[c][1]) + (s[c][2] + s[c][3]);
+          if (kept) dy[c] = *(const f32x4*)(g + (long)b * d + q * 4);
+          if (valid) {
+            const f32x4 dp = *(const f32x4*)(dpool + (long)b * d + q * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dy[c][j] += dp[j] / cnt;
+          }
+        }
+      }
+      const float mu = wave_sum(sum) * invd;
+      float sq = 0.f;
+#pragma unroll
+      for (int c = 0; c < POOL32_NV4; ++c)
+        if (lane + 64 * c < nq) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { const float t = s[c][j] - mu; sq += t * t; }
+        }
+      const float rstd = 1.f / sqrtf(wave_sum(sq) * invd + eps);
+      float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+      for (int c = 0; c < POOL32_NV4; ++c) {
+        const int q = lane + 64 * c;
+        if (q < nq) {
+          const f32x4 gm = *(const f32x4*)(gamma + q * 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float xh = (s[c][j] - mu) * rstd;
+            const float dyg = dy[c][j] * gm[j];
+            c1 += dyg;
+            c2 += dyg * xh;
+            ag[c][j] += dy[c][j] * xh;
+            ab[c][j] += dy[c][j];
+            s[c][j] = xh;                 // xhat from here on
+            dy[c][j] = dyg;               // dy * gamma from here on
+          }
+        }
+      }
+      c1 = wave_sum(c1) * invd;
+      c2 = wave_sum(c2) * invd;
+#pragma unroll
+      for (int c = 0; c < POOL32_NV4; ++c) {
+        const int q = lane + 64 * c;
+        if (q < nq) {
+          f32x4 ds;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) ds[j] = rstd * (dy[c][j] - c1 - s[c][j] * c2);
+          *(f32x4*)(dX + row * d + q * 4) = ds;
+        }
+      }
+    }
+  }
+  if (part == nullptr) return;              // (uniform: a launch argument)
+  pool32_fold(ag, red, nq, lane, wave);
+  pool32_fold(ab, red + d, nq, lane, wave);
+  float* out = part + (long)blockIdx.x * 2 * d;
+  for (int t = threadIdx.x; t < 2 * d; t += 256) out[t] = red[t];
+}
+
+static int check_pool32(const char* who, int B, int L, int Lkeep, int d) {
+  HRIEMO_CHECK(B > 0 && L > 0 && d > 0 && d % 4 == 0 && d <= 1024, "%s: d=%d must be a multiple of 4, at most 1024 (B=%d L=%d)", who, d, B, L);
+  HRIEMO_CHECK(Lkeep >= 1 && Lkeep <= L, "%s: Lkeep=%d outside 1 .. L=%d", who, Lkeep, L);
+  HRIEMO_CHECK(pool32_chunks(L) <= 65535 && B <= 65535, "%s: B=%d / L=%d exceed the grid", who, B, L);
+  return 0;
+}
+extern "C" int hriemo_pool32_ln_fwd(const float* X, const unsigned char* mask, const float* gamma, const float* beta, float* part_valid,
+                                    float* part_keep, int B, int L, int Lkeep, int d, float eps, hipStream_t st) {
+  if (check_pool32("pool32_ln_fwd", B, L, Lkeep, d)) return 1;
+  HRIEMO_CHECK(X != nullptr && gamma != nullptr && beta != nullptr && part_valid != nullptr && part_keep != nullptr && part_valid != part_keep,
+               "pool32_ln_fwd: missing operand (two distinct partial buffers are needed)");
+  HRIEMO_CHECK(((uintptr_t)X % 16) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, "pool32_ln_fwd: operands must be 16-byte aligned");
+  hriemo_prof_begin(HP_ROWOPS, st);
+  hipLaunchKernelGGL(pool32_ln_fwd_kernel, dim3(pool32_chunks(L), B), dim3(256), 2 * d * 4, st, X, mask, gamma, beta, part_valid, part_keep, L,
+                     Lkeep, d, eps);
+  HRIEMO_LAUNCH_CHECK("pool32_ln_fwd_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)B * L * d * 4.0);
+  return 0;
+}
+extern "C" int hriemo_pool32_gate_input(const float* part_valid_a, const unsigned char* mask_a, int La, const float* part_valid_t,
+                                        const unsigned char* mask_t, int Lt, float* a_pool, float* t_pool, float* gate_in, int B, int d,
+                                        hipStream_t st) {
+  HRIEMO_CHECK(B > 0 && B <= 65535 && La > 0 && Lt > 0 && d > 0, "pool32_gate_input: bad shape (B=%d La=%d Lt=%d d=%d)", B, La, Lt, d);
+  HRIEMO_CHECK(part_valid_a != nullptr && part_valid_t != nullptr && a_pool != nullptr && t_pool != nullptr && gate_in != nullptr,
+               "pool32_gate_input: missing operand");
+  hipLaunchKernelGGL(pool32_gate_in_kernel, dim3((d + 255) / 256, B), dim3(256), 0, st, part_valid_a, mask_a, La, part_valid_t, mask_t, Lt, a_pool,
+                     t_pool, gate_in, d);
+  HRIEMO_LAUNCH_CHECK("pool32_gate_in_kernel");
+  return 0;
+}
+static int pool32_ln_bwd_blocks(int B, int L) { const long n = (long)B * pool32_chunks(L); return n > 512 ? 512 : (int)n; }
+extern "C" long hriemo_pool32_ln_bwd_workspace_bytes(int B, int L, int d) {
+  if (B <= 0 || L <= 0 || d <= 0) return 0;
+  return (long)pool32_ln_bwd_blocks(B, L) * 2 * d * 4;
+}
+extern "C" int hriemo_pool32_ln_bwd(const float* g, int Lkeep, const float* dpool, const unsigned char* mask, const float* X,
+                                    const float* gamma, float* dX, float* dgamma, float* dbeta, int accumulate, int B, int L, int d,
+                                    float eps, float* workspace, hipStream_t st) {
+  if (check_pool32("pool32_ln_bwd", B, L, Lkeep, d)) return 1;
+  HRIEMO_CHECK((dgamma == nullptr) == (dbeta == nullptr), "pool32_ln_bwd: dgamma and dbeta come together (both NULL, or neither)");
+  HRIEMO_CHECK(dpool != nullptr && X != nullptr && gamma != nullptr && dX != nullptr && (dgamma == nullptr || workspace != nullptr),
+               "pool32_ln_bwd: missing operand");
+  HRIEMO_CHECK(((uintptr_t)X % 16) == 0 && ((uintptr_t)dX % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)dpool % 16) == 0 &&
+               ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)workspace % 16) == 0, "pool32_ln_bwd: operands must be 16-byte aligned");
+  const int nb = pool32_ln_bwd_blocks(B, L);
+  hriemo_prof_begin(HP_ROWOPS, st);
+  hipLaunchKernelGGL(pool32_ln_bwd_kernel, dim3(nb), dim3(256), 2 * d * 4, st, g, Lkeep, dpool, mask, X, gamma, dX,
+                     dgamma != nullptr ? workspace : nullptr, B, L, d, eps);
+  HRIEMO_LAUNCH_CHECK("pool32_ln_bwd_kernel");
+  hriemo_prof_end(HP_ROWOPS, st, (double)B * L * d * 8.0);
+  if (dgamma != nullptr) {
+    SegOut so; so.o[0] = dgamma; so.o[1] = dbeta; so.o[2] = nullptr;
+    hipLaunchKernelGGL(colreduce_f32_kernel, dim3((d + 255) / 256, 2), dim3(256), 0, st, workspace, nb, d, 2, so, accumulate);
+    HRIEMO_LAUNCH_CHECK("colreduce_f32_kernel");
+  }
+  return 0;
+}
+
 #define DISPATCH_HD_F32(hd, CALL)     \
   switch (hd) {                       \
     case 16: { CALL(16); } break;     \

@@ -1213,10 +1213,15 @@ class DataParallelStep(_RaggedStep):
 
 
 # the switches a captured forward bakes in: name -> how it reads now (eval_packed refuses a replay under another setting)
+# POOLED_GATE_FP32 is read by the fp32 precision alone and is recorded only there: in bf16 precision the recorded switches stay the six
+# of before (a replay under another precision is refused by the first entry, whatever follows)
 def _mode_switches():
     from . import _ops
-    return (("precision", _ops.precision()), ("gemm_mode", _ops.gemm_mode()), ("PACKED_TAIL", bool(_ops.PACKED_TAIL)),
-            ("PACKED_TAIL_FP32", bool(_ops.PACKED_TAIL_FP32)), ("PACKED_TAIL_MX8", bool(_ops.PACKED_TAIL_MX8)), ("ingest", _ops.ingest()))
+    six = (("precision", _ops.precision()), ("gemm_mode", _ops.gemm_mode()), ("PACKED_TAIL", bool(_ops.PACKED_TAIL)),
+           ("PACKED_TAIL_FP32", bool(_ops.PACKED_TAIL_FP32)), ("PACKED_TAIL_MX8", bool(_ops.PACKED_TAIL_MX8)), ("ingest", _ops.ingest()))
+    if _ops.precision() != "fp32":
+        return six
+    return six + (("POOLED_GATE_FP32", bool(_ops.POOLED_GATE_FP32)),)
 
 
 class _WeightsPass:

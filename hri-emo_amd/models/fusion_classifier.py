@@ -8,7 +8,8 @@ Two tails behind the encoder:
   - forward() by default: the vector gate writes h_fusion [B, L, d], torch pools it (the path of record);
   - the pooled gate (_ops.PooledGateFn): forward_packed / _forward_rows always, forward() with _ops.POOLED_GATE = True.  The
     reference pools with an UNMASKED mean (:145), so PAD rows of the encoder output are part of the result: this path runs the
-    encoder on the PADDED layout with zero PAD input rows, whatever set_varlen says -- ragged in, padded inside."""
+    encoder on the PADDED layout with zero PAD input rows, whatever set_varlen says -- ragged in, padded inside.  In the fp32
+    precision mode it is served by _fp32.pooled_gate once _ops.POOLED_GATE_FP32 is set (set_pooled_gate_fp32), and refused otherwise."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -85,14 +86,14 @@ class FusionClassifier(nn.Module):
         self._no_maps(return_attention, attn_log)
         if (plan[0].L, plan[1].L) != tuple(pad):
             raise ValueError(f"forward_packed: the plan pads to ({plan[0].L}, {plan[1].L}), not to {tuple(pad)}")
-        _ops._require_bf16_path("FusionClassifier.forward_packed")
+        _ops._require_pooled_path("FusionClassifier.forward_packed")
         a, a32 = _ops.IngestPaddedFn.apply(rows_a, plan[0])
         t, t32 = _ops.IngestPaddedFn.apply(rows_t, plan[1])
         return self._run_pooled(a, a32, t, t32, masks[0], masks[1], rows_a.dtype)
 
     def _run_pooled(self, a, a32, t, t32, mask_a, mask_t, in_dtype):
         """the model on padded pairs with the pooled gate: padded encoder, PooledGateFn, the fp32 head with a hash-site Dropout"""
-        _ops._require_bf16_path("FusionClassifier (pooled gate)")
+        _ops._require_pooled_path("FusionClassifier (pooled gate)")
         _ops.begin_step()
         B, La, Lt = a.shape[0], a.shape[1], t.shape[1]
         a, a32, t, t32, _, _ = self.cross_modal._fwd_pair(a, a32, t, t32, mask_a, mask_t, False, padded=True)      # :139

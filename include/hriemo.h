@@ -736,6 +736,34 @@ int hriemo_gate_dy_f32(const float* dH, const float* w, int is_a, const float* d
 int hriemo_rowdot_bwd_f32(const float* dl, const float* Z, const float* w, float* dZ, float* dw, float* db, int accumulate, int M, int d,
                           hriemo_stream_t stream);
 
+/* ---- the pooled gate in the fp32-tolerance mode (FusionClassifier; "the pooled gate" above is its bf16 form): fp32 in and out,
+ * padded rows only, d % 4 == 0 and d <= 1024 (the limit of the mode's LayerNorm backward), 1 <= Lkeep <= L; anything else is
+ * refused with a message.  Every sum has a fixed order (no float atomics): two launches on the same inputs agree bit for bit.
+ *  - hriemo_pool32_ln_fwd: ONE pass over X fp32 [B, L, d] (mask uint8 [B, L], 1 = PAD, or NULL).  Per row the LayerNorm of
+ *    hriemo_add_ln_f32 (two-pass variance, 1 / sqrt(var + eps)), kept in registers and never stored.  part_valid / part_keep are
+ *    fp32 [B, hriemo_pool_chunks(L), d]: per 32-row chunk the sums of the LayerNorm outputs over the VALID rows, and over the rows
+ *    l < Lkeep whatever the mask says (chunks behind Lkeep: zeros).  Within a chunk wave w of four adds rows w, w + 4, ... in that
+ *    order, then the four waves are added in wave order.  No Yn, mean or rstd is written.
+ *  - hriemo_pool32_gate_input: the chunk sums of both modalities added in chunk order and divided by max(#valid, 1) -> a_pool,
+ *    t_pool [B, d] and gate_in [B, 4d] = [a, t, |a - t|, a * t], bit-equal to hriemo_gate_input_f32 of those pools.  One launch in
+ *    place of two masked means and the gate-input kernel.
+ *  - hriemo_pool32_ln_bwd: dYn[b, l] = (l < Lkeep ? g[b] : 0) + (valid ? dpool[b] / max(#valid_b, 1) : 0) with g, dpool fp32 [B, d]
+ *    (g NULL: zero; the count is formed in the kernel), dX fp32 [B, L, d] = LayerNorm'(dYn) with the row statistics recomputed
+ *    from X.  dgamma / dbeta [d]: column sums over all B * L rows (per-block partials in `workspace`,
+ *    hriemo_pool32_ln_bwd_workspace_bytes(B, L, d), then one fixed-order reduce); overwritten, or added to when accumulate != 0;
+ *    both NULL (no affine gradients, workspace unused), or neither.  No [B, L, d] gradient other than dX is formed.
+ *  The [B, d]-sized pieces are the existing exports: hriemo_pooled_fuse_fwd / _bwd (fp32 arithmetic), hriemo_sigmoid_beta_f32,
+ *  hriemo_gate_dpre_f32 with L = 1 (dH = dpooled, A = Abar, T = Tbar) and hriemo_gate_input_bwd_f32. */
+int hriemo_pool32_ln_fwd(const float* X, const unsigned char* mask, const float* gamma, const float* beta, float* part_valid,
+                         float* part_keep, int B, int L, int Lkeep, int d, float eps, hriemo_stream_t stream);
+int hriemo_pool32_gate_input(const float* part_valid_a, const unsigned char* mask_a, int La, const float* part_valid_t,
+                             const unsigned char* mask_t, int Lt, float* a_pool, float* t_pool, float* gate_in, int B, int d,
+                             hriemo_stream_t stream);
+long hriemo_pool32_ln_bwd_workspace_bytes(int B, int L, int d);
+int hriemo_pool32_ln_bwd(const float* g, int Lkeep, const float* dpool, const unsigned char* mask, const float* X, const float* gamma,
+                         float* dX, float* dgamma, float* dbeta, int accumulate, int B, int L, int d, float eps, float* workspace,
+                         hriemo_stream_t stream);
+
 /* ---- fp32-tolerance mode on packed (varlen) sequences: the encoder on the valid rows only (hriemo_attn_*_varlen's contract).
  *  - hriemo_attn_fwd_f32_varlen / hriemo_attn_bwd_f32_varlen: hriemo_attn_fwd_f32 / _bwd_f32 with cu_seqlens_q / cu_seqlens_k
  *    (int32 [B+1], device memory, every length >= 1) in place of the key padding mask: sample b = rows cu[b] .. cu[b+1]-1 of
