@@ -109,6 +109,8 @@ _SIGS = {
     "hriemo_adamw_flat_dev": ("pppplppp", "i"),
     "hriemo_grad_begin": ("plpp", "i"),
     "hriemo_optim_finalize_ctl": ("pipppppp", "i"),
+    "hriemo_optim_finalize_groups": ("pipippppp", "i"),
+    "hriemo_adamw_flat_groups": ("pppplppippip", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),

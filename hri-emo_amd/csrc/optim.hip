@@ -9,11 +9,17 @@
 //   ctl[4]    written by the host (int32): n_valid (read by the masked losses, loss.hip), first, last, one spare word
 // hriemo_grad_begin zeroes the flat gradient buffer when ctl.first is set and leaves every bit of it in place otherwise;
 // hriemo_optim_finalize_ctl holds the update (state.skip = 1, nothing else) on every micro-step but the one with ctl.last set.
+// Parameter groups (DeviceAdamW(param_groups=...)): hyper[G][8] and state[G][8], one row per group, and a segment table over the
+// flat buffer that says which group owns which elements.  Row 0 of state keeps the meaning above word for word (one norm, one clip
+// coefficient, one skip decision, one step count for all groups); rows g >= 1 carry step_size, 1 / sqrt(bc2) and decay of their
+// group (words 3, 4, 5) and nothing else.  max_norm is read from row 0 of hyper.  A step is hriemo_sumsq_f32 ->
+// hriemo_optim_finalize_groups (one block) -> hriemo_adamw_flat_groups (streaming): three launches, as with one group.
 #include "common.h"
 
 enum { HY_LR = 0, HY_BETA1, HY_BETA2, HY_EPS, HY_WD, HY_MAX_NORM };
 enum { ST_STEP = 0, ST_SKIP, ST_COEF, ST_STEP_SIZE, ST_ISB2, ST_DECAY, ST_GRAD_NORM, ST_SKIPPED };
 enum { CTL_N_VALID = 0, CTL_FIRST, CTL_LAST };
+enum { AG_MAX_GROUPS = 16, AG_MAX_SEGS = 2048 };
 
 // One block.  Sums the sumsq_f32 partials in a fixed order (deterministic), forms the unscaled gradient norm, decides whether
 // the step is skipped (GradScaler found an inf / the norm is not finite: torch's GradScaler.step and the reference trainer's
@@ -61,26 +67,136 @@ __global__ __launch_bounds__(256) void optim_finalize_kernel(const float* __rest
   state[ST_DECAY] = 1.f - lr * wd;
 }
 
-// adamw_flat_kernel (rowops.hip) with its scalars read from hyper[] / state[]: torch.optim.AdamW's arithmetic on the clipped,
-// unscaled gradient coef * g.  A skipped step returns before it touches p, m or v.
+// One 16-byte vector of the update: torch.optim.AdamW's arithmetic on the clipped, unscaled gradient coef * g.  The ONE place the
+// per-element arithmetic of the device-state optimizer lives: adamw_flat_dev_kernel and adamw_flat_groups_kernel both call it, so
+// a group's elements get, bit for bit, what the single-group kernel gives them under that group's scalars.
+struct AdamScalars { float b1, b2, eps, coef, step, isb2, decay; };
+
+__device__ __forceinline__ void adamw_vec4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                           long i, const AdamScalars& s) {
+  const float b1 = s.b1, b2 = s.b2, eps = s.eps, coef = s.coef, step = s.step, isb2 = s.isb2, decay = s.decay;
+  f32x4 pp = *(const f32x4*)(p + i * 4), mm = *(const f32x4*)(m + i * 4), vv = *(const f32x4*)(v + i * 4);
+  const f32x4 gg = *(const f32x4*)(g + i * 4) * coef;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    pp[e] *= decay;
+    mm[e] += (gg[e] - mm[e]) * (1.f - b1);
+    vv[e] = vv[e] * b2 + gg[e] * gg[e] * (1.f - b2);
+    pp[e] -= step * mm[e] / (sqrtf(vv[e]) * isb2 + eps);
+  }
+  *(f32x4*)(p + i * 4) = pp; *(f32x4*)(m + i * 4) = mm; *(f32x4*)(v + i * 4) = vv;
+}
+
+// adamw_flat_kernel (rowops.hip) with its scalars read from hyper[] / state[].  A skipped step returns before it touches p, m or v.
 __global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                              float* __restrict__ v, long n, const float* __restrict__ hyper,
                                                              const float* __restrict__ state) {
   if (state[ST_SKIP] != 0.f) return;
-  const float b1 = hyper[HY_BETA1], b2 = hyper[HY_BETA2], eps = hyper[HY_EPS];
-  const float coef = state[ST_COEF], step = state[ST_STEP_SIZE], isb2 = state[ST_ISB2], decay = state[ST_DECAY];
+  const AdamScalars s = {hyper[HY_BETA1], hyper[HY_BETA2], hyper[HY_EPS], state[ST_COEF], state[ST_STEP_SIZE], state[ST_ISB2], state[ST_DECAY]};
+  const long nv = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) adamw_vec4(p, g, m, v, i, s);
+}
+
+// optim_finalize_kernel for G parameter groups.  One norm over the whole flat buffer, one clip coefficient, one skip decision, one
+// step count and one `skipped` counter, all in row 0 of state exactly as optim_finalize_kernel leaves them (G = 1: the same bits
+// in all 8 words); thread g < G then writes its group's step_size = lr_g / bc1_g, 1 / sqrt(bc2_g) and decay_g = 1 - lr_g * wd_g
+// into row g, each from that group's own lr, betas and weight decay.  Rows g >= 1: words 3, 4, 5 and nothing else.
+// ctl == nullptr: the plain finalize; otherwise the HOLD of optim_finalize_kernel<true> (ctl.last == 0: state[0][ST_SKIP] = 1, nothing else).
+__global__ __launch_bounds__(256) void optim_finalize_groups_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
+                                                                    int G, const float* __restrict__ grad_scale,
+                                                                    const float* __restrict__ found_inf, float* __restrict__ state,
+                                                                    const int* __restrict__ ctl) {
+  __shared__ float red[4];
+  if (ctl != nullptr && ctl[CTL_LAST] == 0) {      // block-uniform: nobody reaches the barrier below
+    if (threadIdx.x == 0) state[ST_SKIP] = 1.f;
+    return;
+  }
+  const float step = state[ST_STEP] + 1.f;         // read by every thread in front of the barrier, written by thread 0 behind it
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblocks; i += 256) s += partial[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const int grp = threadIdx.x;
+  if (grp >= G) return;
+  const float sum = red[0] + red[1] + red[2] + red[3];
+  const float gs = grad_scale != nullptr ? grad_scale[0] : 1.f;
+  const float norm = sqrtf(sum) / gs;
+  const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+  const bool skip = !finite || (found_inf != nullptr && !(found_inf[0] == 0.f));
+  if (grp == 0) state[ST_GRAD_NORM] = norm;
+  if (skip) {
+    if (grp == 0) {
+      state[ST_SKIP] = 1.f;
+      state[ST_SKIPPED] += 1.f;
+    }
+    return;
+  }
+  const float* hy = hyper + grp * 8;
+  float* stg = state + grp * 8;
+  const float lr = hy[HY_LR], b1 = hy[HY_BETA1], b2 = hy[HY_BETA2], wd = hy[HY_WD], max_norm = hyper[HY_MAX_NORM];
+  const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
+  if (grp == 0) {
+    float coef = 1.f;
+    if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
+    state[ST_STEP] = step;
+    state[ST_SKIP] = 0.f;
+    state[ST_COEF] = coef / gs;
+  }
+  stg[ST_STEP_SIZE] = lr / bc1;
+  stg[ST_ISB2] = 1.f / sqrtf(bc2);
+  stg[ST_DECAY] = 1.f - lr * wd;
+}
+
+// adamw_flat_dev_kernel with per-segment scalars: ONE launch over the whole flat buffer.  seg[S + 1] (ascending element offsets,
+// seg[0] = 0, seg[S] = n, multiples of 4) and seg_group[S] say which group owns which elements; a group may own several segments.
+// How a vector finds its group: the table is copied into LDS once per block ((S + 1) int64 + the 7 scalars of every group + S group
+// bytes: at most 19 KiB) and every thread keeps its CURRENT segment -- bounds and scalars -- in registers, as gather_rows_kernel
+// (store.hip) does.  A vector inside the current segment costs two compares; one outside it a binary search in LDS (<= 11 probes)
+// and 7 LDS reads, once per sweep of the capped grid at worst.  The table only ever selects scalars, it addresses nothing: the
+// search result is clamped to [0, S) and the group to [0, G), so a table that breaks its contract changes which hyper-parameters
+// an element gets and cannot make hyper, state, p, g, m or v be read or written out of range.  Nothing at or beyond n is written.
+__global__ __launch_bounds__(256) void adamw_flat_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, long n, const long long* __restrict__ seg,
+                                                                const int* __restrict__ seg_group, int S, const float* __restrict__ hyper,
+                                                                const float* __restrict__ state, int G) {
+  if (state[ST_SKIP] != 0.f) return;               // block-uniform: nobody reaches the barrier below
+  extern __shared__ __attribute__((aligned(16))) long long ag_lds[];
+  long long* segb = ag_lds;                        // [S + 1]
+  float* sc = (float*)(segb + (S + 1));            // [G][8]: b1, b2, eps, coef, step_size, isb2, decay, spare
+  unsigned char* sg = (unsigned char*)(sc + G * 8);   // [S] group of segment s, clamped to [0, G)
+  for (int i = threadIdx.x; i <= S; i += 256) {
+    segb[i] = seg[i];
+    if (i < S) {
+      const int q = seg_group[i];
+      sg[i] = (unsigned char)(q < 0 ? 0 : (q >= G ? G - 1 : q));
+    }
+  }
+  if (threadIdx.x < G) {
+    const float* hy = hyper + threadIdx.x * 8;
+    const float* stg = state + threadIdx.x * 8;
+    float* o = sc + threadIdx.x * 8;
+    o[0] = hy[HY_BETA1]; o[1] = hy[HY_BETA2]; o[2] = hy[HY_EPS]; o[3] = state[ST_COEF];
+    o[4] = stg[ST_STEP_SIZE]; o[5] = stg[ST_ISB2]; o[6] = stg[ST_DECAY]; o[7] = 0.f;
+  }
+  __syncthreads();
+  AdamScalars s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  long long cur_lo = 0, cur_hi = 0;                // empty: the first vector searches
   const long nv = n >> 2;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
-    f32x4 pp = *(const f32x4*)(p + i * 4), mm = *(const f32x4*)(m + i * 4), vv = *(const f32x4*)(v + i * 4);
-    const f32x4 gg = *(const f32x4*)(g + i * 4) * coef;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      pp[e] *= decay;
-      mm[e] += (gg[e] - mm[e]) * (1.f - b1);
-      vv[e] = vv[e] * b2 + gg[e] * gg[e] * (1.f - b2);
-      pp[e] -= step * mm[e] / (sqrtf(vv[e]) * isb2 + eps);
+    const long long x = (long long)i * 4;
+    if (x < cur_lo || x >= cur_hi) {
+      // upper bound: the first k in [1, S] with segb[k] > x (S if there is none); the owner is k - 1, in [0, S)
+      int lo = 1, hi = S;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (segb[mid] > x) hi = mid; else lo = mid + 1;
+      }
+      cur_lo = segb[lo - 1]; cur_hi = segb[lo];
+      const float* o = sc + (int)sg[lo - 1] * 8;
+      s.b1 = o[0]; s.b2 = o[1]; s.eps = o[2]; s.coef = o[3]; s.step = o[4]; s.isb2 = o[5]; s.decay = o[6];
     }
-    *(f32x4*)(p + i * 4) = pp; *(f32x4*)(m + i * 4) = mm; *(f32x4*)(v + i * 4) = vv;
+    adamw_vec4(p, g, m, v, i, s);
   }
 }
 
@@ -134,5 +250,36 @@ extern "C" int hriemo_adamw_flat_dev(float* p, const float* g, float* m, float* 
   if (gsz > 4096) gsz = 4096;
   hipLaunchKernelGGL(adamw_flat_dev_kernel, dim3((int)gsz), dim3(256), 0, st, p, g, m, v, n, hyper, state);
   HRIEMO_LAUNCH_CHECK("adamw_flat_dev_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_optim_finalize_groups(const float* partial, int nblocks, const float* hyper, int G, const float* grad_scale,
+                                            const float* found_inf, float* state, const int* ctl, hipStream_t st) {
+  HRIEMO_CHECK(partial != nullptr && hyper != nullptr && state != nullptr, "optim_finalize_groups: partial, hyper and state are required");
+  HRIEMO_CHECK(nblocks > 0 && nblocks <= 4096, "optim_finalize_groups: nblocks=%d out of range (1..4096)", nblocks);
+  HRIEMO_CHECK(G >= 1 && G <= AG_MAX_GROUPS, "optim_finalize_groups: G=%d groups (1 .. %d)", G, (int)AG_MAX_GROUPS);
+  HRIEMO_CHECK(((uintptr_t)ctl % 4) == 0, "optim_finalize_groups: ctl is the int32 step-control block in device memory (or NULL)");
+  hipLaunchKernelGGL(optim_finalize_groups_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, G, grad_scale, found_inf, state, ctl);
+  HRIEMO_LAUNCH_CHECK("optim_finalize_groups_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_adamw_flat_groups(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group,
+                                        int S, const float* hyper, const float* state, int G, hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0, "adamw_flat_groups: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(p != nullptr && g != nullptr && m != nullptr && v != nullptr, "adamw_flat_groups: p, g, m and v are required");
+  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+               "adamw_flat_groups: unaligned buffer");
+  HRIEMO_CHECK(hyper != nullptr && state != nullptr, "adamw_flat_groups: hyper and state are required");
+  HRIEMO_CHECK(G >= 1 && G <= AG_MAX_GROUPS, "adamw_flat_groups: G=%d groups (1 .. %d)", G, (int)AG_MAX_GROUPS);
+  HRIEMO_CHECK(S >= 1 && S <= AG_MAX_SEGS, "adamw_flat_groups: S=%d segments (1 .. %d)", S, (int)AG_MAX_SEGS);
+  HRIEMO_CHECK(seg != nullptr && seg_group != nullptr, "adamw_flat_groups: seg (int64 [S + 1]) and seg_group (int32 [S]) are required");
+  HRIEMO_CHECK(((uintptr_t)seg % 8) == 0, "adamw_flat_groups: seg (int64 [S + 1]) is not 8-byte aligned");
+  HRIEMO_CHECK(((uintptr_t)seg_group % 4) == 0, "adamw_flat_groups: seg_group (int32 [S]) is not 4-byte aligned");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  const size_t lds = (size_t)(S + 1) * sizeof(long long) + (size_t)G * 8 * sizeof(float) + (size_t)S;
+  hipLaunchKernelGGL(adamw_flat_groups_kernel, dim3((int)gsz), dim3(256), lds, st, p, g, m, v, n, seg, seg_group, S, hyper, state, G);
+  HRIEMO_LAUNCH_CHECK("adamw_flat_groups_kernel");
   return 0;
 }

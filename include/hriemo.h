@@ -518,6 +518,37 @@ int hriemo_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, 
 int hriemo_grad_begin(float* flat, long n, const int* ctl, hriemo_stream_t stream);
 int hriemo_optim_finalize_ctl(const float* partial, int nblocks, const float* hyper, const float* grad_scale, const float* found_inf,
                               float* state, const int* ctl, hriemo_stream_t stream);
+/* Parameter groups (DeviceAdamW(param_groups=...)): the same step with per-group lr, betas, eps and weight decay, still three
+ * launches (hriemo_sumsq_f32 -> hriemo_optim_finalize_groups -> hriemo_adamw_flat_groups).  Layout, 1 <= G <= 16 groups:
+ *   hyper[G][8] (host-written fp32):   row g = {lr, beta1, beta2, eps, weight_decay, max_norm, 2 spare words} of group g;
+ *                                      max_norm is GLOBAL and read from row 0 only (one clip over the whole flat buffer, as
+ *                                      clip_grad_norm_(model.parameters()) gives);
+ *   state[G][8] (device-written fp32): row 0 = the state[8] above, word for word: step, skip, coef, step_size, 1/sqrt(bc2), decay
+ *                                      (those three of group 0), grad_norm, skipped -- one norm, one skip decision, one step count
+ *                                      and one `skipped` counter serve all groups;
+ *                                      row g >= 1: words 3, 4, 5 = step_size = lr_g/bc1_g, 1/sqrt(bc2_g), decay_g = 1 - lr_g*wd_g
+ *                                      from group g's own lr, betas and weight decay; its other five words are never written;
+ *   seg   int64 [S+1] (device):        ascending element offsets into the flat buffer, seg[0] = 0, seg[S] = n, every entry a
+ *                                      multiple of 4; 1 <= S <= 2048;
+ *   seg_group int32 [S] (device):      the group in [0, G) that owns elements seg[s] .. seg[s+1]-1; a group may own several
+ *                                      segments, adjacent or not.
+ * hriemo_optim_finalize_groups is hriemo_optim_finalize for G groups; with G = 1 all 8 words of state are those of
+ * hriemo_optim_finalize bit for bit.  ctl may be NULL; otherwise it is the step-control block and the launch HOLDS the update as
+ * hriemo_optim_finalize_ctl does (ctl[2] == 0: state[0][1] (skip) = 1 and no other word of any row changes).
+ * hriemo_adamw_flat_groups is hriemo_adamw_flat_dev with the scalars of the group that owns each 16-byte vector, in ONE launch over
+ * the flat buffer: the per-element arithmetic is the same inline function, so on a group's elements the result equals
+ * hriemo_adamw_flat_dev run with that group's hyper row, bit for bit.  Each block copies the tables into LDS ((S+1)*8 + G*32 + S
+ * bytes) and every thread keeps its current segment in registers.  The tables only select scalars and address nothing: a lookup
+ * that falls outside them is clamped to the last segment, a group outside [0, G) to the nearest valid one, so hyper and state are
+ * never indexed out of range, and nothing at or beyond element n is written whatever seg holds.  A skipped or held step
+ * (state[0][1] != 0) leaves p, m, v untouched.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): G outside 1..16, S outside 1..2048, n <= 0 or n % 4 != 0, a NULL
+ * p / g / m / v / hyper / state / seg / seg_group, buffers that are not 16-byte aligned, seg not 8-byte or seg_group / ctl not
+ * 4-byte aligned. */
+int hriemo_optim_finalize_groups(const float* partial, int nblocks, const float* hyper, int G, const float* grad_scale,
+                                 const float* found_inf, float* state, const int* ctl, hriemo_stream_t stream);
+int hriemo_adamw_flat_groups(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group, int S,
+                             const float* hyper, const float* state, int G, hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
