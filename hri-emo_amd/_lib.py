@@ -111,6 +111,10 @@ _SIGS = {
     "hriemo_optim_finalize_ctl": ("pipppppp", "i"),
     "hriemo_optim_finalize_groups": ("pipippppp", "i"),
     "hriemo_adamw_flat_groups": ("pppplppippip", "i"),
+    "hriemo_optim_finalize_avg": ("pipippppppp", "i"),
+    "hriemo_adamw_flat_dev_avg": ("pppplppppp", "i"),
+    "hriemo_adamw_flat_groups_avg": ("pppplppippippp", "i"),
+    "hriemo_swap_fp32": ("pplp", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),

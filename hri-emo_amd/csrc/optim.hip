@@ -14,12 +14,30 @@
 // coefficient, one skip decision, one step count for all groups); rows g >= 1 carry step_size, 1 / sqrt(bc2) and decay of their
 // group (words 3, 4, 5) and nothing else.  max_norm is read from row 0 of hyper.  A step is hriemo_sumsq_f32 ->
 // hriemo_optim_finalize_groups (one block) -> hriemo_adamw_flat_groups (streaming): three launches, as with one group.
+// Weight averaging (DeviceAdamW(averaging="ema" | "swa")): torch.optim.swa_utils.AveragedModel's average as one more streaming
+// operand of the update, `avg`, a flat fp32 buffer laid out like p.  Two more blocks, outside hyper[] / state[]:
+//   avg_hyper[4]  written by the host:   mode (0 off, 1 ema, 2 swa), decay, start, every
+//   avg_state[4]  written by the device: n_averaged, w (this update's weight), flag (0 none, 1 averaging update, 2 first
+//                                        averaging update: avg = p), stamp (the step count the flag belongs to)
+// A step is hriemo_sumsq_f32 -> hriemo_optim_finalize_avg (one block; G groups, ctl or none: the one finalize of all three forms)
+// -> hriemo_adamw_flat_dev_avg or hriemo_adamw_flat_groups_avg: three launches.  With t the step count of a real update (neither
+// skipped nor held), the update averages iff t > start and (t - start) % every == 0; the finalize then writes
+// w = 1 - decay (ema) or 1 / (n + 1) (swa), n += 1, flag and stamp = t, once, in fp32; a real update that does not average writes
+// flag = 0 and stamp = t and leaves n and w alone; a skipped or held step writes NO word of avg_state.
+// How the update kernel tells "this step averages" from a stale flag: (1) a skipped or held step returns on state.skip before it
+// reads avg_state at all, and every real update rewrites flag; (2) the flag only counts when stamp == state.step, so a flag left by
+// an earlier step -- the state block advanced by a finalize that knows nothing of averaging, a loaded checkpoint -- is not an
+// update.  On a step that does not average, avg is neither loaded nor stored.
+// hriemo_swap_fp32 exchanges two flat fp32 buffers bit for bit (DeviceAdamW.averaged_weights(): evaluation on the average).
 #include "common.h"
 
 enum { HY_LR = 0, HY_BETA1, HY_BETA2, HY_EPS, HY_WD, HY_MAX_NORM };
 enum { ST_STEP = 0, ST_SKIP, ST_COEF, ST_STEP_SIZE, ST_ISB2, ST_DECAY, ST_GRAD_NORM, ST_SKIPPED };
 enum { CTL_N_VALID = 0, CTL_FIRST, CTL_LAST };
 enum { AG_MAX_GROUPS = 16, AG_MAX_SEGS = 2048 };
+enum { AH_MODE = 0, AH_DECAY, AH_START, AH_EVERY };
+enum { AS_N = 0, AS_W, AS_FLAG, AS_STAMP };
+enum { AV_NONE = 0, AV_UPDATE = 1, AV_FIRST = 2, AV_EMA = 1, AV_SWA = 2 };
 
 // One block.  Sums the sumsq_f32 partials in a fixed order (deterministic), forms the unscaled gradient norm, decides whether
 // the step is skipped (GradScaler found an inf / the norm is not finite: torch's GradScaler.step and the reference trainer's
@@ -69,10 +87,11 @@ __global__ __launch_bounds__(256) void optim_finalize_kernel(const float* __rest
 
 // One 16-byte vector of the update: torch.optim.AdamW's arithmetic on the clipped, unscaled gradient coef * g.  The ONE place the
 // per-element arithmetic of the device-state optimizer lives: adamw_flat_dev_kernel and adamw_flat_groups_kernel both call it, so
-// a group's elements get, bit for bit, what the single-group kernel gives them under that group's scalars.
+// a group's elements get, bit for bit, what the single-group kernel gives them under that group's scalars.  Returns the new p
+// vector (the averaging forms fold it into avg without reading it back).
 struct AdamScalars { float b1, b2, eps, coef, step, isb2, decay; };
 
-__device__ __forceinline__ void adamw_vec4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+__device__ __forceinline__ f32x4 adamw_vec4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                            long i, const AdamScalars& s) {
   const float b1 = s.b1, b2 = s.b2, eps = s.eps, coef = s.coef, step = s.step, isb2 = s.isb2, decay = s.decay;
   f32x4 pp = *(const f32x4*)(p + i * 4), mm = *(const f32x4*)(m + i * 4), vv = *(const f32x4*)(v + i * 4);
@@ -85,16 +104,68 @@ __device__ __forceinline__ void adamw_vec4(float* __restrict__ p, const float* _
     pp[e] -= step * mm[e] / (sqrtf(vv[e]) * isb2 + eps);
   }
   *(f32x4*)(p + i * 4) = pp; *(f32x4*)(m + i * 4) = mm; *(f32x4*)(v + i * 4) = vv;
+  return pp;
+}
+
+// What this step does to avg, read once per block behind the skip test: AV_NONE unless the finalize of THIS step (stamp ==
+// state.step) flagged an averaging update.  Block-uniform (scalar loads), so the branches on it in the sweep are uniform too.
+struct AvgStep { int kind; float w; };
+
+__device__ __forceinline__ AvgStep avg_step(const float* __restrict__ state, const float* __restrict__ avg_state) {
+  const float flag = avg_state[AS_FLAG];
+  AvgStep a = {AV_NONE, 0.f};
+  if (avg_state[AS_STAMP] == state[ST_STEP] && (flag == (float)AV_UPDATE || flag == (float)AV_FIRST)) {
+    a.kind = flag == (float)AV_FIRST ? AV_FIRST : AV_UPDATE;
+    a.w = avg_state[AS_W];
+  }
+  return a;
+}
+
+// One 16-byte vector of the average from the freshly updated p vector: the first averaging update copies the bits of p (torch's
+// first AveragedModel.update_parameters), a later one is avg += w * (p - avg) with one rounding of the difference and one of the fma.
+__device__ __forceinline__ void avg_vec4(float* __restrict__ avg, long i, const f32x4 pp, const AvgStep a) {
+  if (a.kind == AV_FIRST) {
+    *(f32x4*)(avg + i * 4) = pp;
+    return;
+  }
+  f32x4 aa = *(const f32x4*)(avg + i * 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) aa[e] = __builtin_fmaf(a.w, pp[e] - aa[e], aa[e]);
+  *(f32x4*)(avg + i * 4) = aa;
 }
 
 // adamw_flat_kernel (rowops.hip) with its scalars read from hyper[] / state[].  A skipped step returns before it touches p, m or v.
-__global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                             float* __restrict__ v, long n, const float* __restrict__ hyper,
-                                                             const float* __restrict__ state) {
+// AVG: the averaging form (hriemo_adamw_flat_dev_avg) -- the same sweep, avg_vec4 behind adamw_vec4 on an averaging update and
+// neither a load nor a store of avg on any other step; AVG = false is the kernel of before, avg and avg_state unused.
+template <bool AVG>
+__device__ __forceinline__ void adamw_flat_dev_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, long n, const float* __restrict__ hyper,
+                                                    const float* __restrict__ state, float* __restrict__ avg,
+                                                    const float* __restrict__ avg_state) {
   if (state[ST_SKIP] != 0.f) return;
   const AdamScalars s = {hyper[HY_BETA1], hyper[HY_BETA2], hyper[HY_EPS], state[ST_COEF], state[ST_STEP_SIZE], state[ST_ISB2], state[ST_DECAY]};
   const long nv = n >> 2;
+  if (AVG) {
+    const AvgStep a = avg_step(state, avg_state);
+    if (a.kind != AV_NONE) {
+      for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) avg_vec4(avg, i, adamw_vec4(p, g, m, v, i, s), a);
+      return;
+    }
+  }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) adamw_vec4(p, g, m, v, i, s);
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, long n, const float* __restrict__ hyper,
+                                                             const float* __restrict__ state) {
+  adamw_flat_dev_body<false>(p, g, m, v, n, hyper, state, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_dev_avg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                 float* __restrict__ v, long n, const float* __restrict__ hyper,
+                                                                 const float* __restrict__ state, float* __restrict__ avg,
+                                                                 const float* __restrict__ avg_state) {
+  adamw_flat_dev_body<true>(p, g, m, v, n, hyper, state, avg, avg_state);
 }
 
 // optim_finalize_kernel for G parameter groups.  One norm over the whole flat buffer, one clip coefficient, one skip decision, one
@@ -102,10 +173,15 @@ __global__ __launch_bounds__(256) void adamw_flat_dev_kernel(float* __restrict__
 // in all 8 words); thread g < G then writes its group's step_size = lr_g / bc1_g, 1 / sqrt(bc2_g) and decay_g = 1 - lr_g * wd_g
 // into row g, each from that group's own lr, betas and weight decay.  Rows g >= 1: words 3, 4, 5 and nothing else.
 // ctl == nullptr: the plain finalize; otherwise the HOLD of optim_finalize_kernel<true> (ctl.last == 0: state[0][ST_SKIP] = 1, nothing else).
-__global__ __launch_bounds__(256) void optim_finalize_groups_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
-                                                                    int G, const float* __restrict__ grad_scale,
-                                                                    const float* __restrict__ found_inf, float* __restrict__ state,
-                                                                    const int* __restrict__ ctl) {
+// AVG: the averaging finalize (hriemo_optim_finalize_avg): thread 0 of a REAL update also writes avg_state -- the decision of the
+// header comment, w once per step in fp32 -- behind the words of state; a held or skipped step returns in front of it and writes
+// no word of avg_state.  AVG = false is the kernel of before, avg_hyper and avg_state unused.
+template <bool AVG>
+__device__ __forceinline__ void optim_finalize_groups_body(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
+                                                           int G, const float* __restrict__ grad_scale,
+                                                           const float* __restrict__ found_inf, float* __restrict__ state,
+                                                           const int* __restrict__ ctl, const float* __restrict__ avg_hyper,
+                                                           float* __restrict__ avg_state) {
   __shared__ float red[4];
   if (ctl != nullptr && ctl[CTL_LAST] == 0) {      // block-uniform: nobody reaches the barrier below
     if (threadIdx.x == 0) state[ST_SKIP] = 1.f;
@@ -146,6 +222,35 @@ __global__ __launch_bounds__(256) void optim_finalize_groups_kernel(const float*
   stg[ST_STEP_SIZE] = lr / bc1;
   stg[ST_ISB2] = 1.f / sqrtf(bc2);
   stg[ST_DECAY] = 1.f - lr * wd;
+  if (AVG && grp == 0) {
+    // step counts and the schedule are whole numbers below 2^24 held in fp32: the difference and fmodf are exact.  every = 0 or a
+    // NaN word gives NaN != 0: no averaging, never a fault.
+    const float mode = avg_hyper[AH_MODE], since = step - avg_hyper[AH_START];
+    float flag = (float)AV_NONE;
+    if ((mode == (float)AV_EMA || mode == (float)AV_SWA) && since > 0.f && fmodf(since, avg_hyper[AH_EVERY]) == 0.f) {
+      const float n_avg = avg_state[AS_N];
+      flag = n_avg == 0.f ? (float)AV_FIRST : (float)AV_UPDATE;
+      avg_state[AS_W] = mode == (float)AV_EMA ? 1.f - avg_hyper[AH_DECAY] : 1.f / (n_avg + 1.f);
+      avg_state[AS_N] = n_avg + 1.f;
+    }
+    avg_state[AS_FLAG] = flag;
+    avg_state[AS_STAMP] = step;
+  }
+}
+
+__global__ __launch_bounds__(256) void optim_finalize_groups_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
+                                                                    int G, const float* __restrict__ grad_scale,
+                                                                    const float* __restrict__ found_inf, float* __restrict__ state,
+                                                                    const int* __restrict__ ctl) {
+  optim_finalize_groups_body<false>(partial, nblocks, hyper, G, grad_scale, found_inf, state, ctl, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void optim_finalize_avg_kernel(const float* __restrict__ partial, int nblocks, const float* __restrict__ hyper,
+                                                                 int G, const float* __restrict__ grad_scale,
+                                                                 const float* __restrict__ found_inf, float* __restrict__ state,
+                                                                 const int* __restrict__ ctl, const float* __restrict__ avg_hyper,
+                                                                 float* __restrict__ avg_state) {
+  optim_finalize_groups_body<true>(partial, nblocks, hyper, G, grad_scale, found_inf, state, ctl, avg_hyper, avg_state);
 }
 
 // adamw_flat_dev_kernel with per-segment scalars: ONE launch over the whole flat buffer.  seg[S + 1] (ascending element offsets,
@@ -156,11 +261,17 @@ __global__ __launch_bounds__(256) void optim_finalize_groups_kernel(const float*
 // and 7 LDS reads, once per sweep of the capped grid at worst.  The table only ever selects scalars, it addresses nothing: the
 // search result is clamped to [0, S) and the group to [0, G), so a table that breaks its contract changes which hyper-parameters
 // an element gets and cannot make hyper, state, p, g, m or v be read or written out of range.  Nothing at or beyond n is written.
-__global__ __launch_bounds__(256) void adamw_flat_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, long n, const long long* __restrict__ seg,
-                                                                const int* __restrict__ seg_group, int S, const float* __restrict__ hyper,
-                                                                const float* __restrict__ state, int G) {
+// AVG: the averaging form (hriemo_adamw_flat_groups_avg): avg_vec4 behind adamw_vec4 on an averaging update (avg is indexed by the
+// vector index alone, like p), nothing of avg touched on any other step; AVG = false is the kernel of before.
+template <bool AVG>
+__device__ __forceinline__ void adamw_flat_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, long n, const long long* __restrict__ seg,
+                                                       const int* __restrict__ seg_group, int S, const float* __restrict__ hyper,
+                                                       const float* __restrict__ state, int G, float* __restrict__ avg,
+                                                       const float* __restrict__ avg_state) {
   if (state[ST_SKIP] != 0.f) return;               // block-uniform: nobody reaches the barrier below
+  AvgStep a = {AV_NONE, 0.f};
+  if (AVG) a = avg_step(state, avg_state);
   extern __shared__ __attribute__((aligned(16))) long long ag_lds[];
   long long* segb = ag_lds;                        // [S + 1]
   float* sc = (float*)(segb + (S + 1));            // [G][8]: b1, b2, eps, coef, step_size, isb2, decay, spare
@@ -196,7 +307,35 @@ __global__ __launch_bounds__(256) void adamw_flat_groups_kernel(float* __restric
       const float* o = sc + (int)sg[lo - 1] * 8;
       s.b1 = o[0]; s.b2 = o[1]; s.eps = o[2]; s.coef = o[3]; s.step = o[4]; s.isb2 = o[5]; s.decay = o[6];
     }
-    adamw_vec4(p, g, m, v, i, s);
+    const f32x4 pp = adamw_vec4(p, g, m, v, i, s);
+    if (AVG && a.kind != AV_NONE) avg_vec4(avg, i, pp, a);   // block-uniform branch
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, long n, const long long* __restrict__ seg,
+                                                                const int* __restrict__ seg_group, int S, const float* __restrict__ hyper,
+                                                                const float* __restrict__ state, int G) {
+  adamw_flat_groups_body<false>(p, g, m, v, n, seg, seg_group, S, hyper, state, G, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_groups_avg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                    float* __restrict__ v, long n, const long long* __restrict__ seg,
+                                                                    const int* __restrict__ seg_group, int S, const float* __restrict__ hyper,
+                                                                    const float* __restrict__ state, int G, float* __restrict__ avg,
+                                                                    const float* __restrict__ avg_state) {
+  adamw_flat_groups_body<true>(p, g, m, v, n, seg, seg_group, S, hyper, state, G, avg, avg_state);
+}
+
+// Exact exchange of two fp32 buffers that do not overlap: 16-byte vector loads and stores, grid capped like the update's.  Every
+// bit crosses (NaN payloads, -0, denormals: nothing is computed), nothing at or beyond n is touched.
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+__global__ __launch_bounds__(256) void swap_fp32_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+  const long nv = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+    const u32x4 x = *(const u32x4*)(a + i * 4), y = *(const u32x4*)(b + i * 4);
+    *(u32x4*)(a + i * 4) = y; *(u32x4*)(b + i * 4) = x;
   }
 }
 
@@ -281,5 +420,78 @@ extern "C" int hriemo_adamw_flat_groups(float* p, const float* g, float* m, floa
   const size_t lds = (size_t)(S + 1) * sizeof(long long) + (size_t)G * 8 * sizeof(float) + (size_t)S;
   hipLaunchKernelGGL(adamw_flat_groups_kernel, dim3((int)gsz), dim3(256), lds, st, p, g, m, v, n, seg, seg_group, S, hyper, state, G);
   HRIEMO_LAUNCH_CHECK("adamw_flat_groups_kernel");
+  return 0;
+}
+
+// [x, x + bytes) and [y, y + bytes) share a byte
+static bool ranges_overlap(const void* x, const void* y, size_t bytes) {
+  const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+  return a < b ? b - a < bytes : a - b < bytes;
+}
+
+extern "C" int hriemo_optim_finalize_avg(const float* partial, int nblocks, const float* hyper, int G, const float* grad_scale,
+                                         const float* found_inf, float* state, const int* ctl, const float* avg_hyper, float* avg_state,
+                                         hipStream_t st) {
+  HRIEMO_CHECK(partial != nullptr && hyper != nullptr && state != nullptr, "optim_finalize_avg: partial, hyper and state are required");
+  HRIEMO_CHECK(nblocks > 0 && nblocks <= 4096, "optim_finalize_avg: nblocks=%d out of range (1..4096)", nblocks);
+  HRIEMO_CHECK(G >= 1 && G <= AG_MAX_GROUPS, "optim_finalize_avg: G=%d groups (1 .. %d)", G, (int)AG_MAX_GROUPS);
+  HRIEMO_CHECK(((uintptr_t)ctl % 4) == 0, "optim_finalize_avg: ctl is the int32 step-control block in device memory (or NULL)");
+  HRIEMO_CHECK(avg_hyper != nullptr && avg_state != nullptr && ((uintptr_t)avg_hyper % 4) == 0 && ((uintptr_t)avg_state % 4) == 0,
+               "optim_finalize_avg: avg_hyper and avg_state (fp32 [4] each, device memory) are required");
+  hipLaunchKernelGGL(optim_finalize_avg_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, hyper, G, grad_scale, found_inf, state, ctl,
+                     avg_hyper, avg_state);
+  HRIEMO_LAUNCH_CHECK("optim_finalize_avg_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_adamw_flat_dev_avg(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* state,
+                                         float* avg, const float* avg_state, hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0, "adamw_flat_dev_avg: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(p != nullptr && g != nullptr && m != nullptr && v != nullptr && avg != nullptr, "adamw_flat_dev_avg: p, g, m, v and avg are required");
+  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                   ((uintptr_t)avg % 16) == 0, "adamw_flat_dev_avg: unaligned buffer");
+  HRIEMO_CHECK(hyper != nullptr && state != nullptr && avg_state != nullptr, "adamw_flat_dev_avg: hyper, state and avg_state are required");
+  HRIEMO_CHECK(!ranges_overlap(avg, p, (size_t)n * 4) && !ranges_overlap(avg, g, (size_t)n * 4) && !ranges_overlap(avg, m, (size_t)n * 4) &&
+                   !ranges_overlap(avg, v, (size_t)n * 4), "adamw_flat_dev_avg: avg overlaps p, g, m or v");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  hipLaunchKernelGGL(adamw_flat_dev_avg_kernel, dim3((int)gsz), dim3(256), 0, st, p, g, m, v, n, hyper, state, avg, avg_state);
+  HRIEMO_LAUNCH_CHECK("adamw_flat_dev_avg_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_adamw_flat_groups_avg(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group,
+                                            int S, const float* hyper, const float* state, int G, float* avg, const float* avg_state,
+                                            hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0, "adamw_flat_groups_avg: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(p != nullptr && g != nullptr && m != nullptr && v != nullptr && avg != nullptr,
+               "adamw_flat_groups_avg: p, g, m, v and avg are required");
+  HRIEMO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                   ((uintptr_t)avg % 16) == 0, "adamw_flat_groups_avg: unaligned buffer");
+  HRIEMO_CHECK(hyper != nullptr && state != nullptr && avg_state != nullptr, "adamw_flat_groups_avg: hyper, state and avg_state are required");
+  HRIEMO_CHECK(G >= 1 && G <= AG_MAX_GROUPS, "adamw_flat_groups_avg: G=%d groups (1 .. %d)", G, (int)AG_MAX_GROUPS);
+  HRIEMO_CHECK(S >= 1 && S <= AG_MAX_SEGS, "adamw_flat_groups_avg: S=%d segments (1 .. %d)", S, (int)AG_MAX_SEGS);
+  HRIEMO_CHECK(seg != nullptr && seg_group != nullptr, "adamw_flat_groups_avg: seg (int64 [S + 1]) and seg_group (int32 [S]) are required");
+  HRIEMO_CHECK(((uintptr_t)seg % 8) == 0, "adamw_flat_groups_avg: seg (int64 [S + 1]) is not 8-byte aligned");
+  HRIEMO_CHECK(((uintptr_t)seg_group % 4) == 0, "adamw_flat_groups_avg: seg_group (int32 [S]) is not 4-byte aligned");
+  HRIEMO_CHECK(!ranges_overlap(avg, p, (size_t)n * 4) && !ranges_overlap(avg, g, (size_t)n * 4) && !ranges_overlap(avg, m, (size_t)n * 4) &&
+                   !ranges_overlap(avg, v, (size_t)n * 4), "adamw_flat_groups_avg: avg overlaps p, g, m or v");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  const size_t lds = (size_t)(S + 1) * sizeof(long long) + (size_t)G * 8 * sizeof(float) + (size_t)S;
+  hipLaunchKernelGGL(adamw_flat_groups_avg_kernel, dim3((int)gsz), dim3(256), lds, st, p, g, m, v, n, seg, seg_group, S, hyper, state, G, avg,
+                     avg_state);
+  HRIEMO_LAUNCH_CHECK("adamw_flat_groups_avg_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_swap_fp32(float* a, float* b, long n, hipStream_t st) {
+  HRIEMO_CHECK(n > 0 && n % 4 == 0, "swap_fp32: n=%ld must be a positive multiple of 4", n);
+  HRIEMO_CHECK(a != nullptr && b != nullptr && ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0, "swap_fp32: two 16-byte aligned buffers are required");
+  HRIEMO_CHECK(!ranges_overlap(a, b, (size_t)n * 4), "swap_fp32: the buffers overlap (or are one buffer)");
+  long gsz = (n / 4 + 255) / 256;
+  if (gsz > 4096) gsz = 4096;
+  hipLaunchKernelGGL(swap_fp32_kernel, dim3((int)gsz), dim3(256), 0, st, a, b, n);
+  HRIEMO_LAUNCH_CHECK("swap_fp32_kernel");
   return 0;
 }

@@ -1034,6 +1034,10 @@ class DataParallelStep(_RaggedStep):
         the update, the batch into the static state (load(ctl) -> bucket key: _load_packed or _load_store), the bucket graph
         picked -- or captured on the spot -- and replayed"""
         first, last = micro_flags(self._micro, self._pb.front.accum)
+        if self._optimizer is not None and self._optimizer._swapped is True:
+            # inside opt.averaged_weights(): a held micro-step uploads nothing (so _upload_hyper cannot refuse it), but its
+            # gradients must not come from the average either
+            self._optimizer._refuse_while_averaged("a training replay")
         if self._optimizer is not None and last:
             # the update of this group reads lr & co. as the scheduler left them after the previous update; a held micro-step
             # reads none of them (the finalize returns in front of hyper[], the update kernel in front of everything)

@@ -6,6 +6,8 @@ Adam moments the same layout -- every ``p.data`` becomes a view into a flat para
 is one elementwise kernel and the gradient norm one reduction, with the clip coefficient taken from device memory
 (no host synchronisation, safe between hipGraph replays).  Construct it BEFORE ``DataParallelStep.capture()``:
 it moves the parameter storage.  Results follow torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW (fp32)."""
+import contextlib
+
 import torch
 
 from . import _lib
@@ -52,6 +54,19 @@ class FusedClipAdamW:
 
 MAX_GROUPS = 16            # hriemo_adamw_flat_groups: rows of hyper / state
 MAX_SEGMENTS = 2048        # hriemo_adamw_flat_groups: entries of the segment table a block keeps in LDS
+AVERAGING_MODES = {"ema": 1.0, "swa": 2.0}     # avg_hyper[0] of hriemo_optim_finalize_avg (0: off)
+
+
+def is_averaging_step(t, avg_start, avg_every):
+    """does the real update that brings the step count to ``t`` fold the parameters into the average?  The rule the finalize kernel
+    evaluates on the device (host mirror: tests, logging)."""
+    return t > avg_start and (t - avg_start) % avg_every == 0
+
+
+def averaging_weight(mode, n_averaged, avg_decay):
+    """the weight ``w`` of ``avg += w * (p - avg)`` for an averaging update that finds ``n_averaged`` >= 1 earlier ones, in float64
+    (the device rounds ``1 - decay`` and ``1 / (n + 1)`` once, in fp32)"""
+    return 1.0 - avg_decay if mode == "ema" else 1.0 / (n_averaged + 1)
 
 
 def decay_groups(named_parameters, weight_decay, no_decay=lambda name, p: p.dim() < 2):
@@ -151,14 +166,30 @@ class DeviceAdamW(torch.optim.Optimizer):
       group's parameter count -- plus the moment shapes where the dict carries state: a dict with other counts is refused, one
       whose groups hold the same counts with members swapped between them is not detected.
     * ``grad_norm`` (pre-clip, unscaled), ``device_step`` and ``skipped`` are 0-dim device tensors (views: read them when wanted).
+    * ``averaging="ema"`` or ``"swa"`` keeps ``torch.optim.swa_utils.AveragedModel``'s running average of the parameters in one
+      more flat fp32 buffer, ``opt.avg`` (laid out like ``flat_p``, a bit copy of the parameters at construction), updated INSIDE the
+      update kernel: the step stays three launches and nothing is added behind a graph replay.  With ``t`` the device step count of
+      a real update (neither skipped nor held by an accumulation micro-step), the update averages iff ``t > avg_start`` and
+      ``(t - avg_start) % avg_every == 0`` -- the torch loop that calls ``update_parameters`` on exactly those steps: the first one
+      copies, a later one is ``avg += w * (p - avg)`` with ``w = 1 - avg_decay`` (``"ema"``, ``get_ema_multi_avg_fn(decay)``) or
+      ``1 / (n_averaged + 1)`` (``"swa"``, the default ``AveragedModel``).  A skipped or held step moves nothing of the average.
+      ``avg_decay``, ``avg_start`` and ``avg_every`` are host attributes uploaded with ``hyper``; ``n_averaged`` is a 0-dim device
+      view.  ``with opt.averaged_weights():`` exchanges parameters and average in place (one launch in, one out), so the eager
+      forward, ``EvalStep`` and everything built on them evaluate the average without a second model; no step, replay or state dict
+      is possible inside.  ``averaged_state_dict(model)`` is ``model.state_dict()`` with the averages in.  ``state_dict()`` gains one
+      top-level key ``"averaging"`` (torch's ``load_state_dict`` ignores it); loading a dict WITHOUT it -- a torch optimizer's --
+      restarts the average: ``n_averaged = 0`` and ``avg`` = the parameters as they are at that moment, so load the model first,
+      then the optimizer.
 
     Like FusedClipAdamW it re-homes every ``p.data`` into one flat fp32 buffer laid out like ``buckets.flat``: construct it BEFORE
     ``DataParallelStep.capture()``."""
 
     _step_supports_amp_scaling = True          # GradScaler.step: set opt.grad_scale / opt.found_inf and call step() directly
 
-    def __init__(self, buckets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=5.0, *, param_groups=None):
+    def __init__(self, buckets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=5.0, *, param_groups=None,
+                 averaging=None, avg_decay=0.999, avg_start=0, avg_every=1):
         flat_g = buckets.flat
+        self._check_averaging(averaging, avg_decay, avg_start, avg_every)
         if param_groups is None:
             _require_gpu(flat_g)
         self._check_scalars(lr, betas, eps, weight_decay, "")
@@ -189,7 +220,17 @@ class DeviceAdamW(torch.optim.Optimizer):
         self.nblocks = 1024
         self._partial = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
         # G rows of 8 words each, kept flat: row 0 of _state is the single-group state block word for word
-        self._hyper = torch.zeros(G * 8, dtype=torch.float32, device=dev)
+        self.averaging, self.avg_decay, self.avg_start, self.avg_every = averaging, avg_decay, avg_start, avg_every
+        self._swapped = False                       # inside averaged_weights(): flat_p holds the average, avg the parameters
+        if averaging is None:
+            self._hyper = torch.zeros(G * 8, dtype=torch.float32, device=dev)
+        else:
+            # avg_hyper[4] rides behind hyper[G][8] in ONE block: one pinned, stream-ordered copy uploads both
+            self._hyper_block = torch.zeros(G * 8 + 4, dtype=torch.float32, device=dev)
+            self._hyper, self._avg_hyper = self._hyper_block[:G * 8], self._hyper_block[G * 8:]
+            # device-written: n_averaged, w, flag, stamp (csrc/optim.hip)
+            self._avg_state = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.n_averaged = self._avg_state[0]
         self._state = torch.zeros(G * 8, dtype=torch.float32, device=dev)
         self._hyper_host = None                     # the image last uploaded
         if self._grouped:
@@ -213,11 +254,35 @@ class DeviceAdamW(torch.optim.Optimizer):
                     self.state[p] = {"step": self._state[0], "exp_avg": self.m[off:off + n].view_as(p),
                                      "exp_avg_sq": self.v[off:off + n].view_as(p)}
         self.grad_norm, self.device_step, self.skipped = self._state[6], self._state[0], self._state[7]
+        if averaging is not None:
+            self.avg = self.flat_p.clone()          # the bits of the parameters, zeros in the padding
 
     @staticmethod
     def _check_scalars(lr, betas, eps, weight_decay, where):
         if lr < 0 or eps < 0 or weight_decay < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
             raise ValueError(f"DeviceAdamW: lr, eps, weight_decay >= 0 and betas in [0, 1) are required{where}")
+
+    @staticmethod
+    def _check_averaging(averaging, avg_decay, avg_start, avg_every):
+        """the constructor's refusals (before any allocation) and _upload_hyper's, for attributes changed afterwards"""
+        if averaging is None:
+            if (avg_decay, avg_start, avg_every) != (0.999, 0, 1):
+                raise ValueError("DeviceAdamW: avg_decay / avg_start / avg_every are given without averaging= ('ema' or 'swa'): "
+                                 "nothing would be averaged")
+            return
+        if averaging not in AVERAGING_MODES:
+            raise ValueError(f"DeviceAdamW: averaging={averaging!r}; the modes are None, 'ema' and 'swa'")
+        if not (isinstance(avg_decay, (int, float)) and 0 <= avg_decay < 1):
+            raise ValueError(f"DeviceAdamW: avg_decay={avg_decay!r} must lie in [0, 1)")
+        for name, val, low in (("avg_start", avg_start, 0), ("avg_every", avg_every, 1)):
+            # whole numbers the device holds in fp32 next to the fp32 step count
+            if isinstance(val, bool) or not isinstance(val, int) or not low <= val < 2 ** 24:
+                raise ValueError(f"DeviceAdamW: {name}={val!r} must be an integer >= {low} (and below 2**24)")
+
+    def _refuse_while_averaged(self, what):
+        if self._swapped:
+            raise RuntimeError(f"DeviceAdamW: {what} inside `with opt.averaged_weights():` -- the parameter buffer holds the AVERAGE "
+                               "there; leave the block first")
 
     def add_param_group(self, param_group):
         if self.param_groups and not getattr(self, "_constructing", False):
@@ -228,7 +293,11 @@ class DeviceAdamW(torch.optim.Optimizer):
     # -- the step ---------------------------------------------------------------------------------
     def _upload_hyper(self):
         """hyper[] follows the param groups (a scheduler's lr included): one host -> device copy of the [G, 8] block (32 bytes per
-        group) when any group's image changed"""
+        group) when any group's image changed.  With averaging the 4 words of avg_hyper (mode, decay, start, every: the host
+        attributes avg_decay, avg_start, avg_every as they are now) ride behind it in the same block and the same copy.  Every step
+        and every replay that carries an update passes through here: inside ``averaged_weights()`` it raises before anything is
+        enqueued."""
+        self._refuse_while_averaged("step() / a replay that carries the update")
         img = []
         for g in self.param_groups:
             if g["amsgrad"] or g["maximize"]:
@@ -238,11 +307,16 @@ class DeviceAdamW(torch.optim.Optimizer):
                 raise RuntimeError("DeviceAdamW: the param groups carry different max_norm values; the clip is global")
             img += [float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                     float(mn) if mn else 0.0, 0.0, 0.0]
+        block = self._hyper
+        if self.averaging is not None:
+            self._check_averaging(self.averaging, self.avg_decay, self.avg_start, self.avg_every)
+            img += [AVERAGING_MODES[self.averaging], float(self.avg_decay), float(self.avg_start), float(self.avg_every)]
+            block = self._hyper_block
         img = tuple(img)
         if img != self._hyper_host:
             # pinned staging + an asynchronous copy in stream order: the host neither waits for the step in flight nor can a
             # later image overtake this one (torch's host allocator keeps the block until the copy has run)
-            self._hyper.copy_(torch.tensor(img, dtype=torch.float32).pin_memory(), non_blocking=True)
+            block.copy_(torch.tensor(img, dtype=torch.float32).pin_memory(), non_blocking=True)
             self._hyper_host = img
 
     def _enqueue(self, grad_scale=None, found_inf=None, ctl=None):
@@ -250,11 +324,25 @@ class DeviceAdamW(torch.optim.Optimizer):
         of a step captured with gradient accumulation (dp.capture_packed(grad_accum=k)): the finalize launch then holds the update
         on every micro-step whose ctl.last is 0 -- parameters, moments, step count, skipped and grad_norm stay as they are.
         Built with param_groups: the finalize for G groups and the one grouped update kernel take the places of the single-group
-        launches."""
+        launches.  Built with averaging: the averaging finalize (one entry for plain, ctl and groups) and the averaging form of the
+        update kernel -- still three launches."""
+        self._refuse_while_averaged("an update")
         g = self.buckets.flat
         n = g.numel()
         st = _stream()
         _lib.call("hriemo_sumsq_f32", _p(g), n, _p(self._partial), self.nblocks, st)
+        if self.averaging is not None:
+            G = len(self.param_groups)
+            _lib.call("hriemo_optim_finalize_avg", _p(self._partial), self.nblocks, _p(self._hyper), G, _p(grad_scale), _p(found_inf),
+                      _p(self._state), _p(ctl), _p(self._avg_hyper), _p(self._avg_state), st)
+            if self._grouped:
+                _lib.call("hriemo_adamw_flat_groups_avg", _p(self.flat_p), _p(g), _p(self.m), _p(self.v), n, _p(self._seg),
+                          _p(self._seg_group), self._seg_group.numel(), _p(self._hyper), _p(self._state), G, _p(self.avg),
+                          _p(self._avg_state), st)
+            else:
+                _lib.call("hriemo_adamw_flat_dev_avg", _p(self.flat_p), _p(g), _p(self.m), _p(self.v), n, _p(self._hyper), _p(self._state),
+                          _p(self.avg), _p(self._avg_state), st)
+            return
         if self._grouped:
             G = len(self.param_groups)
             _lib.call("hriemo_optim_finalize_groups", _p(self._partial), self.nblocks, _p(self._hyper), G, _p(grad_scale), _p(found_inf),
@@ -293,21 +381,79 @@ class DeviceAdamW(torch.optim.Optimizer):
         optimizer address the flat buffer, a detached .grad would silently drop out of both)"""
         self.buckets.zero_grad()
 
+    # -- the average ------------------------------------------------------------------------------
+    def _require_averaging(self, what):
+        if self.averaging is None:
+            raise RuntimeError(f"DeviceAdamW.{what}: built without averaging= ('ema' or 'swa'), there is no average")
+
+    def _swap_avg(self):
+        _lib.call("hriemo_swap_fp32", _p(self.flat_p), _p(self.avg), self.flat_p.numel(), _stream())
+        # through raw pointers, like the update: tell the bf16 weight shadows and EvalStep's stationary weight forms
+        _ops.bump_weights_epoch()
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with opt.averaged_weights():`` -- the model's parameters ARE the average inside the block: ``flat_p`` and ``avg`` are
+        exchanged in place by one launch (hriemo_swap_fp32, every bit crosses) and the weights epoch moves, so the eager forward,
+        ``EvalStep`` (default and ``stationary=True``), ``evaluate_packed`` / ``evaluate_store`` and the logs built on them see the
+        average without a second module.  The way out -- on an exception too -- exchanges them back: training continues from
+        bit-identical parameters.  Inside the block ``step()``, a captured replay that carries the update, ``state_dict()``,
+        ``load_state_dict()`` and a nested ``averaged_weights()`` raise."""
+        self._require_averaging("averaged_weights()")
+        self._refuse_while_averaged("a nested averaged_weights()")
+        self._swap_avg()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._swap_avg()
+
+    @torch.no_grad()
+    def averaged_state_dict(self, model):
+        """``model.state_dict()`` with a clone of the average in place of every parameter the buckets own (the models have no
+        buffers, so there is no counterpart of ``update_bn``): the reference's checkpoint format, loadable by the reference model"""
+        self._require_averaging("averaged_state_dict()")
+        self._refuse_while_averaged("averaged_state_dict()")
+        sd = model.state_dict()
+        for name, p in model.named_parameters():
+            off = self.buckets._offsets.get(id(p))
+            if off is not None and name in sd:
+                sd[name] = self.avg[off:off + p.numel()].view_as(p).clone()
+        return sd
+
     # -- checkpoints ------------------------------------------------------------------------------
     def state_dict(self):
         """torch.optim.AdamW's format.  The moments are the live views (as torch hands out its live state); every parameter gets
         its OWN copy of the step count, as torch keeps one per parameter: an optimizer that loads this and increments each entry
-        must not find them all aliasing one word."""
+        must not find them all aliasing one word.  With averaging ONE more top-level key, ``"averaging"``: mode, decay, start,
+        every, n_averaged (a 0-dim copy) and ``"avg"``, the per-parameter averages under the keys of ``"state"`` (live views, like
+        the moments).  ``torch.optim.AdamW.load_state_dict`` ignores the key."""
+        self._refuse_while_averaged("state_dict()")
         sd = super().state_dict()
         steps = self._state[0].expand(len(sd["state"])).clone().unbind(0)
         sd["state"] = {k: {**ent, "step": s} for (k, ent), s in zip(sd["state"].items(), steps)}
+        if self.averaging is not None:
+            keys = [k for g in sd["param_groups"] for k in g["params"]]
+            params = [p for g in self.param_groups for p in g["params"]]
+            sd["averaging"] = {"mode": self.averaging, "decay": self.avg_decay, "start": self.avg_start, "every": self.avg_every,
+                               "n_averaged": self._avg_state[0].clone(), "avg": {k: self._avg_view(p) for k, p in zip(keys, params)}}
         return sd
+
+    def _avg_view(self, p):
+        off = self.buckets._offsets[id(p)]
+        return self.avg[off:off + p.numel()].view_as(p)
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
         """takes a state dict of this class or of torch.optim.AdamW over the same parameters: values are copied INTO the flat
         buffers (the views stay), `step` comes from the per-parameter entries (all equal, or this raises), lr and the other
-        settings from the group"""
+        settings from the group.  The ``"averaging"`` block: a dict that carries one restores the average, ``n_averaged`` and the
+        host attributes decay / start / every (another mode, other keys or other shapes are refused; so is any such block when this
+        optimizer was built without averaging).  A dict WITHOUT one -- a torch optimizer's -- RESTARTS the average:
+        ``n_averaged = 0`` and ``avg`` becomes a copy of the parameters as they are now.  So load the model first, then the
+        optimizer."""
+        self._refuse_while_averaged("load_state_dict()")
         groups, state = state_dict["param_groups"], state_dict["state"]
         mine_groups = self.param_groups
         n_params = len(self.buckets.params)
@@ -334,6 +480,16 @@ class DeviceAdamW(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError(f"DeviceAdamW.load_state_dict: the parameters carry different step counts {sorted(steps)}; "
                              "one flat update has one step count")
+        av = state_dict.get("averaging")
+        if av is not None:
+            if av.get("mode") != self.averaging:
+                raise ValueError(f"DeviceAdamW.load_state_dict: the state dict's average is {av.get('mode')!r}, this optimizer was built "
+                                 f"with averaging={self.averaging!r}")
+            self._check_averaging(av["mode"], av["decay"], av["start"], av["every"])
+            if set(av["avg"]) != {key for key, _ in pairs} or any(tuple(av["avg"][key].shape) != tuple(p.shape) for key, p in pairs):
+                raise ValueError("DeviceAdamW.load_state_dict: the averages' shapes do not match the parameters (a different grouping "
+                                 "or another model)")
+        # nothing has been written up to here
         for key, p in pairs:
             ent = state.get(key)
             mine = self.state[p]
@@ -351,3 +507,16 @@ class DeviceAdamW(torch.optim.Optimizer):
                     group[k] = val
             group.setdefault("max_norm", self.defaults["max_norm"])    # a torch dict has none: the group keeps its own
         self._hyper_host = None
+        if self.averaging is not None:
+            if av is None:
+                self.avg.copy_(self.flat_p)                            # restart: the parameters as they are now
+                self._avg_state.zero_()
+            else:
+                for key, p in pairs:
+                    mine = self._avg_view(p)
+                    if av["avg"][key].data_ptr() != mine.data_ptr():
+                        mine.copy_(av["avg"][key])
+                self.avg_decay, self.avg_start, self.avg_every = av["decay"], av["start"], av["every"]
+                n_avg = float(av["n_averaged"])
+                self._avg_state.zero_()                                # no flag, no stamp: the next finalize decides anew
+                self._avg_state[0].fill_(n_avg)

@@ -549,6 +549,33 @@ int hriemo_optim_finalize_groups(const float* partial, int nblocks, const float*
                                  const float* found_inf, float* state, const int* ctl, hriemo_stream_t stream);
 int hriemo_adamw_flat_groups(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group, int S,
                              const float* hyper, const float* state, int G, hriemo_stream_t stream);
+/* Weight averaging inside the step (DeviceAdamW(averaging="ema" | "swa")): torch.optim.swa_utils.AveragedModel's running average
+ * as one more flat fp32 buffer `avg`, laid out like p, updated by the update kernel itself.  Two blocks beside hyper / state:
+ *   avg_hyper[4] (host-written fp32):   mode (0 off, 1 ema, 2 swa), decay, start, every (whole numbers below 2^24);
+ *   avg_state[4] (device-written fp32): n_averaged, w, flag (0 none, 1 averaging update, 2 first averaging update), stamp.
+ * hriemo_optim_finalize_avg is hriemo_optim_finalize_groups (G = 1 and ctl == NULL: hriemo_optim_finalize; G = 1 with ctl:
+ * hriemo_optim_finalize_ctl -- state comes out bit for bit) that also writes avg_state.  With t the step count a real update
+ * (neither skipped nor held) has just written: the update averages iff t > start and (t - start) % every == 0; then
+ * w = 1 - decay (ema) or 1 / (n_averaged + 1) (swa), in fp32, flag = 2 if n_averaged was 0 and 1 otherwise, n_averaged += 1,
+ * stamp = t.  A real update that does not average writes flag = 0 and stamp = t and leaves n_averaged and w alone.  A skipped or
+ * held step writes no word of avg_state.
+ * hriemo_adamw_flat_dev_avg / hriemo_adamw_flat_groups_avg are hriemo_adamw_flat_dev / hriemo_adamw_flat_groups -- p, m, v bit
+ * for bit -- that fold each freshly written 16-byte vector of p into avg when flag != 0 AND stamp == state[0] (a flag left by
+ * another step is no update): flag 2 stores the bits of p, flag 1 stores fmaf(w, p - avg, avg).  On every other step, skipped and
+ * held ones included, avg is neither loaded nor stored.  Nothing at or beyond element n is written.
+ * Refused besides what the plain entries refuse: NULL avg_hyper / avg_state / avg, avg not 16-byte aligned, avg overlapping p, g,
+ * m or v.
+ * hriemo_swap_fp32 exchanges a[0, n) and b[0, n) bit for bit (16-byte vectors; NaN payloads, -0 and denormals cross unchanged).
+ * Refused: n <= 0 or n % 4 != 0, NULL or unaligned buffers, buffers that overlap or are one buffer. */
+int hriemo_optim_finalize_avg(const float* partial, int nblocks, const float* hyper, int G, const float* grad_scale,
+                              const float* found_inf, float* state, const int* ctl, const float* avg_hyper, float* avg_state,
+                              hriemo_stream_t stream);
+int hriemo_adamw_flat_dev_avg(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* state, float* avg,
+                              const float* avg_state, hriemo_stream_t stream);
+int hriemo_adamw_flat_groups_avg(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group, int S,
+                                 const float* hyper, const float* state, int G, float* avg, const float* avg_state,
+                                 hriemo_stream_t stream);
+int hriemo_swap_fp32(float* a, float* b, long n, hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
