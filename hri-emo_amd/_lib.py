@@ -115,6 +115,8 @@ _SIGS = {
     "hriemo_adamw_flat_dev_avg": ("pppplppppp", "i"),
     "hriemo_adamw_flat_groups_avg": ("pppplppippippp", "i"),
     "hriemo_swap_fp32": ("pplp", "i"),
+    "hriemo_health_sweep": ("pppplpippipipp", "i"),
+    "hriemo_health_fold": ("ppiipppiipp", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),

@@ -139,6 +139,170 @@ def group_segments(buckets, param_groups):
     return seg, seg_group
 
 
+HEALTH_CHUNK = 32768       # elements per block of hriemo_health_sweep (one resident round of blocks at cfg 2)
+MAX_HEALTH_PARAMS = 4096   # hriemo_health_fold: parameters whose chunk ranges the one block keeps in LDS
+MAX_HEALTH_CAPACITY = 1 << 20
+
+
+def health_chunks(slots, chunk=HEALTH_CHUNK):
+    """The chunk table of hriemo_health_sweep / hriemo_health_fold: ``slots`` is one ``(start, length, group)`` per parameter in
+    flat-buffer order -- the parameter's slot of the flat buffers as GradBuckets lays it out (``start`` a multiple of 64 elements,
+    ``length`` the element count padded to 64) and the param group that owns it.  -> a list of ``(start, length, parameter, group)``
+    rows: every slot cut into pieces of at most ``chunk`` elements (a positive multiple of 1024), the pieces of one parameter
+    neighbours in ascending order, every element of every slot in exactly one row.  Pure host code."""
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1024 or chunk % 1024:
+        raise ValueError(f"health_chunks: chunk={chunk!r} must be a positive multiple of 1024")
+    rows, end = [], 0
+    for i, (start, length, group) in enumerate(slots):
+        if start % 64 or length % 64 or length <= 0 or start < end:
+            raise ValueError(f"health_chunks: slot {i} (start {start}, length {length}): slots start at multiples of 64 elements, are "
+                             "padded to 64 and ascend without overlap")
+        end = start + length
+        for off in range(0, length, chunk):
+            rows.append((start + off, min(chunk, length - off), i, group))
+    if not rows:
+        raise ValueError("health_chunks: no slots")
+    return rows
+
+
+def decode_health(image, n_params, capacity):
+    """One host image of the log's device buffer (int32 words, csrc/health.hip) -> the dict ``HealthLog.arrays()`` returns, without
+    the names: the records still in the ring in chronological order, oldest first."""
+    import numpy as np
+    img = np.ascontiguousarray(np.asarray(image, dtype=np.int32))
+    P, R = n_params, 4 + 4 * n_params
+    if img.shape != (4 + capacity * R,):
+        raise ValueError(f"decode_health: an image of {img.shape} words; {n_params} parameters and capacity {capacity} make {4 + capacity * R}")
+    n_recorded = int(img[0]) & 0xFFFFFFFF
+    kept = min(n_recorded, capacity)
+    ring = img[4:].reshape(capacity, R)
+    order = [(n_recorded - kept + i) % capacity for i in range(kept)]
+    recs = ring[order]
+    f32 = lambda a: np.ascontiguousarray(a).view(np.float32)  # noqa: E731
+    return {"n_recorded": n_recorded, "step": f32(recs[:, 0]), "kind": recs[:, 1].copy(), "grad_norm": f32(recs[:, 2]),
+            "grad_sq": f32(recs[:, 4:4 + P]), "nonfinite": recs[:, 4 + P:4 + 2 * P].copy(), "weight_sq": f32(recs[:, 4 + 2 * P:4 + 3 * P]),
+            "update_sq": f32(recs[:, 4 + 3 * P:4 + 4 * P])}
+
+
+class HealthLog:
+    """Per-parameter statistics of DeviceAdamW's steps, recorded by the step itself -- eagerly or inside any captured step -- into a
+    ring in device memory and read back once, when asked: ``DeviceAdamW(buckets, ..., health=HealthLog(capacity=64, every=1))``.
+
+    A step writes a **record** when its update was SKIPPED (always) or when it was a real update whose new step count ``t``
+    satisfies ``t % every == 0``; a held accumulation micro-step writes nothing.  A record holds ``step``, ``kind`` (0 real update,
+    1 skipped on a non-finite norm, 2 skipped on ``found_inf`` alone), ``grad_norm`` and, per parameter tensor in flat-buffer order,
+    ``grad_sq`` (sum of squares of the unscaled gradient over its finite elements), ``nonfinite`` (how many elements are NaN or
+    +-Inf, exact), ``weight_sq`` (the parameter after the update) and ``update_sq`` (the Adam term subtracted in this step); the last
+    two are zeros on a skipped record.  ``capacity`` records are kept, the newest overwrite the oldest.  ``capacity`` and ``every`` are
+    baked into captured graphs: they are fixed at construction.  The log is a diagnostic: it never enters ``state_dict()``.
+
+    ``arrays()`` is ONE device -> host copy; ``blame()`` and ``ratios()`` are built on it."""
+
+    def __init__(self, capacity=64, every=1):
+        for name, val, high in (("capacity", capacity, MAX_HEALTH_CAPACITY), ("every", every, 2 ** 24 - 1)):
+            if isinstance(val, bool) or not isinstance(val, int) or not 1 <= val <= high:
+                raise ValueError(f"HealthLog: {name}={val!r} must be an integer in 1 .. {high}")
+        self._capacity, self._every = capacity, every
+        self._opt = None
+        self.names = None
+
+    capacity = property(lambda self: self._capacity)
+    every = property(lambda self: self._every)
+
+    @capacity.setter
+    def capacity(self, value):
+        raise AttributeError("HealthLog.capacity is fixed at construction: captured graphs carry it (build a new log and optimizer)")
+
+    @every.setter
+    def every(self, value):
+        raise AttributeError("HealthLog.every is fixed at construction: captured graphs carry it (build a new log and optimizer)")
+
+    def _check_attach(self, buckets):
+        """DeviceAdamW's constructor, in front of its first allocation"""
+        if self._opt is not None:
+            raise ValueError("HealthLog: this log is already attached to an optimizer; every DeviceAdamW takes its own")
+        if len(buckets.params) > MAX_HEALTH_PARAMS:
+            raise ValueError(f"HealthLog: {len(buckets.params)} parameter tensors; the fold kernel takes at most {MAX_HEALTH_PARAMS}")
+
+    def _attach(self, opt, owner):
+        """owner: {id(p): group index}.  Builds the chunk table (uploaded here, once), the partials and the zeroed ring."""
+        buckets = opt.buckets
+        self._opt = opt
+        self._params = sorted(buckets.params, key=lambda q: buckets._offsets[id(q)])
+        self.n_params = len(self._params)
+        pad = lambda n: (n + 63) // 64 * 64  # noqa: E731
+        rows = health_chunks([(buckets._offsets[id(p)], pad(p.numel()), owner[id(p)]) for p in self._params])
+        dev = buckets.flat.device
+        self._chunks = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.n_chunks = len(rows)
+        self._partial = torch.zeros(self.n_chunks * 4, dtype=torch.float32, device=dev)
+        self._buf = torch.zeros(4 + self._capacity * (4 + 4 * self.n_params), dtype=torch.int32, device=dev)
+        self.names = [f"param{i}" for i in range(self.n_params)]
+
+    def _require_attached(self, what):
+        if self._opt is None:
+            raise RuntimeError(f"HealthLog.{what}: the log is not attached (DeviceAdamW(buckets, health=log))")
+
+    def _enqueue(self, opt, grad_scale, ctl):
+        """the two launches behind the update kernel, on the current stream"""
+        st = _stream()
+        g = opt.buckets.flat
+        G = len(opt.param_groups)
+        _lib.call("hriemo_health_sweep", _p(g), _p(opt.flat_p), _p(opt.m), _p(opt.v), g.numel(), _p(self._chunks), self.n_chunks,
+                  _p(opt._hyper), _p(opt._state), G, _p(ctl), self._every, _p(self._partial), st)
+        _lib.call("hriemo_health_fold", _p(self._partial), _p(self._chunks), self.n_chunks, self.n_params, _p(opt._state), _p(ctl),
+                  _p(grad_scale), self._every, self._capacity, _p(self._buf), st)
+
+    def name_parameters(self, named_parameters):
+        """names from ``model.named_parameters()``: parameters the optimizer does not own are ignored, a parameter of the optimizer
+        that gets no name raises (nothing is changed then)"""
+        self._require_attached("name_parameters()")
+        given = {id(p): name for name, p in named_parameters}
+        for i, p in enumerate(self._params):
+            if id(p) not in given:
+                raise ValueError(f"HealthLog.name_parameters: parameter {i} of the optimizer ({_describe(p)}) has no name")
+        self.names = [given[id(p)] for p in self._params]
+
+    def arrays(self):
+        """ONE read-back -> dict of numpy arrays, the records still in the ring oldest first: ``step`` [n], ``kind`` [n],
+        ``grad_norm`` [n], ``grad_sq`` / ``weight_sq`` / ``update_sq`` float32 [n, P], ``nonfinite`` int32 [n, P]; ``names`` (list of
+        P) and ``n_recorded``, the records ever written (it can exceed ``capacity``)"""
+        self._require_attached("arrays()")
+        out = decode_health(self._buf.cpu().numpy(), self.n_params, self._capacity)
+        out["names"] = list(self.names)
+        return out
+
+    def blame(self):
+        """the newest SKIPPED record still in the ring -> ``[(name, nonfinite_count), ...]`` of the parameters whose gradient holds
+        NaN or +-Inf, in flat-buffer order; ``[]`` when every gradient was finite (a ``found_inf``-only skip); ``None`` when the ring
+        holds no skipped record"""
+        a = self.arrays()
+        skipped = [i for i, k in enumerate(a["kind"]) if k != 0]
+        if not skipped:
+            return None
+        row = a["nonfinite"][skipped[-1]]
+        return [(name, int(c)) for name, c in zip(a["names"], row) if c != 0]
+
+    def ratios(self, record=-1):
+        """``{name: sqrt(update_sq / weight_sq)}`` -- the update-to-weight ratio of every parameter -- of a real-update record
+        (an index into ``arrays()``, default the newest record)"""
+        import numpy as np
+        a = self.arrays()
+        if len(a["kind"]) == 0:
+            raise IndexError("HealthLog.ratios: the ring holds no record")
+        if a["kind"][record] != 0:
+            raise ValueError(f"HealthLog.ratios: record {record} is a skipped step (kind {int(a['kind'][record])}): it carries no weight "
+                             "or update norms")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.sqrt(a["update_sq"][record].astype(np.float64) / a["weight_sq"][record].astype(np.float64))
+        return {name: float(x) for name, x in zip(a["names"], r)}
+
+    def reset(self):
+        """zeroes the counters (the next record goes to slot 0); the ring's old rows are unreachable afterwards"""
+        self._require_attached("reset()")
+        self._buf[:4].zero_()
+
+
 class DeviceAdamW(torch.optim.Optimizer):
     """FusedClipAdamW's update as a ``torch.optim.Optimizer`` whose every scalar lives in DEVICE memory -- what the reference's
     MOSEI trainer asks of its optimizer (scripts/fusion/train_mosei_fusion_seq_level_decoder.py:367-402, 564-584: AdamW under a
@@ -180,6 +344,12 @@ class DeviceAdamW(torch.optim.Optimizer):
       top-level key ``"averaging"`` (torch's ``load_state_dict`` ignores it); loading a dict WITHOUT it -- a torch optimizer's --
       restarts the average: ``n_averaged = 0`` and ``avg`` = the parameters as they are at that moment, so load the model first,
       then the optimizer.
+    * ``health=HealthLog(capacity=64, every=1)`` (or ``health=True``) attaches a health log, ``opt.health``: two more launches behind
+      the update kernel (``hriemo_health_sweep``, ``hriemo_health_fold``; they only read the buffers of the step) record the
+      per-parameter gradient norm, non-finite count, weight norm and update norm of every ``every``-th real update and of EVERY
+      skipped step into a ring in device memory -- eagerly and inside every captured step, with no read-back per step.
+      ``opt.health.blame()`` names the parameters whose gradient made the device skip an update, ``opt.health.ratios()`` gives the
+      update-to-weight ratios.  Without ``health=`` the launches are those of before; ``state_dict()`` never carries the log.
 
     Like FusedClipAdamW it re-homes every ``p.data`` into one flat fp32 buffer laid out like ``buckets.flat``: construct it BEFORE
     ``DataParallelStep.capture()``."""
@@ -187,9 +357,15 @@ class DeviceAdamW(torch.optim.Optimizer):
     _step_supports_amp_scaling = True          # GradScaler.step: set opt.grad_scale / opt.found_inf and call step() directly
 
     def __init__(self, buckets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=5.0, *, param_groups=None,
-                 averaging=None, avg_decay=0.999, avg_start=0, avg_every=1):
+                 averaging=None, avg_decay=0.999, avg_start=0, avg_every=1, health=None):
         flat_g = buckets.flat
         self._check_averaging(averaging, avg_decay, avg_start, avg_every)
+        if health is True:
+            health = HealthLog()
+        if health is not None:
+            if not isinstance(health, HealthLog):
+                raise ValueError(f"DeviceAdamW: health={health!r}; pass a HealthLog, True (HealthLog()) or None")
+            health._check_attach(buckets)
         if param_groups is None:
             _require_gpu(flat_g)
         self._check_scalars(lr, betas, eps, weight_decay, "")
@@ -256,6 +432,9 @@ class DeviceAdamW(torch.optim.Optimizer):
         self.grad_norm, self.device_step, self.skipped = self._state[6], self._state[0], self._state[7]
         if averaging is not None:
             self.avg = self.flat_p.clone()          # the bits of the parameters, zeros in the padding
+        self.health = health
+        if health is not None:
+            health._attach(self, {id(p): gi for gi, group in enumerate(self.param_groups) for p in group["params"]})
 
     @staticmethod
     def _check_scalars(lr, betas, eps, weight_decay, where):
@@ -320,6 +499,13 @@ class DeviceAdamW(torch.optim.Optimizer):
             self._hyper_host = img
 
     def _enqueue(self, grad_scale=None, found_inf=None, ctl=None):
+        """the step on the current stream (eagerly, or while a step is being captured): the three launches of _enqueue_update and,
+        with a health log attached, its two launches behind them -- in all four forms (plain, ctl, groups, averaging)"""
+        self._enqueue_update(grad_scale, found_inf, ctl)
+        if self.health is not None:
+            self.health._enqueue(self, grad_scale, ctl)
+
+    def _enqueue_update(self, grad_scale, found_inf, ctl):
         """the three launches on the current stream (eagerly, or while a step is being captured).  ctl: the int32 step-control block
         of a step captured with gradient accumulation (dp.capture_packed(grad_accum=k)): the finalize launch then holds the update
         on every micro-step whose ctl.last is 0 -- parameters, moments, step count, skipped and grad_norm stay as they are.

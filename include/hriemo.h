@@ -576,6 +576,42 @@ int hriemo_adamw_flat_groups_avg(float* p, const float* g, float* m, float* v, l
                                  const float* hyper, const float* state, int G, float* avg, const float* avg_state,
                                  hriemo_stream_t stream);
 int hriemo_swap_fp32(float* a, float* b, long n, hriemo_stream_t stream);
+/* The health log of the device-state optimizer (DeviceAdamW(health=HealthLog(capacity, every))): per-parameter statistics of a
+ * step, written by two launches BEHIND the update kernel into a ring in device memory.  They only read g, p, m, v, hyper, state
+ * and ctl; no existing launch changes.
+ *   chunks int64 [C][4] (host-written, once): {start, length, parameter, group} -- the parameters' slots of the flat buffers (start a
+ *                       multiple of 64 elements, length padded to 64, zeros in the padding of g, p, m, v) cut into pieces of at most
+ *                       `chunk` elements, in flat-buffer order: the chunks of one parameter are neighbours and ascend.
+ *                       1 <= C <= 2^20; parameter in [0, P), group in [0, G).
+ *   partial fp32 [C][4] (device-written):     {grad_sq, nonfinite (the bits of an int32), weight_sq, update_sq} of chunk c.
+ *   log int32 [4 + capacity * (4 + 4 P)]:     word 0 = n_recorded, the records ever written (words 1..3 spare); record r lives in
+ *                       slot r % capacity: {step (fp32 bits), kind, grad_norm (fp32 bits), spare}, grad_sq[P] (fp32 bits),
+ *                       nonfinite[P] (int32), weight_sq[P], update_sq[P] (fp32 bits).  1 <= P <= 4096, 1 <= capacity <= 2^20.
+ * Both kernels take the same block-uniform decision from state, ctl and every, in front of any barrier:
+ *   ctl != NULL and ctl[2] (last) == 0: a held micro-step records NOTHING -- every block returns with nothing loaded or stored;
+ *   state[1] (skip) != 0: ALWAYS a record, kind 1 if state[6] (grad_norm) is not finite, else kind 2 (found_inf alone); only g is
+ *                       read, weight_sq and update_sq are zeros;
+ *   otherwise (a real update, t = state[0]): a record of kind 0 iff t % every == 0; g, p, m and v are read.
+ * hriemo_health_sweep: one block of 256 threads per chunk.  grad_sq = sum of g^2 over the FINITE elements of the chunk (as the
+ * buffer holds them: still scaled by grad_scale), nonfinite = the number of NaN / +-Inf elements (exact), weight_sq = sum of p^2,
+ * update_sq = sum of (step_size * m / (sqrt(v) * isb2 + eps))^2 with step_size = state[group][3], isb2 = state[group][4],
+ * eps = hyper[group][3]: the Adam term the update kernel has just subtracted, from the moments it has just written.  Fixed-order
+ * sums: per thread over its vectors tid, tid + 256, ... element by element, the wave's xor butterfly, the four wave sums in index
+ * order; no floating-point atomics.  A row of the table is clamped before use (start into [0, n] and down to a multiple of 4, the
+ * length into [0, n - start] likewise, the group into [0, G)): a table that breaks its contract cannot make a buffer be read out of
+ * range.  The only store is partial[c].
+ * hriemo_health_fold: one block.  Adds the partials of every parameter in chunk order (the chunk range of a parameter is rebuilt
+ * from the table's parameter column, indices clamped to [0, P)), multiplies grad_sq by 1 / grad_scale^2 (grad_scale may be NULL:
+ * 1), writes the record into slot n_recorded % capacity and then n_recorded + 1: it is the only writer of the counter.  Nothing at
+ * or beyond the end of log is written whatever the table holds.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): n <= 0 or n % 4 != 0, C, P, G, capacity outside their ranges,
+ * every < 1, NULL or unaligned buffers (16 bytes: g, p, m, v, partial; 8: chunks; 4: ctl, log), partial overlapping g, p, m, v,
+ * chunks, hyper or state, log overlapping partial, chunks, state, ctl or grad_scale. */
+int hriemo_health_sweep(const float* g, const float* p, const float* m, const float* v, long n, const long long* chunks, int C,
+                        const float* hyper, const float* state, int G, const int* ctl, int every, float* partial,
+                        hriemo_stream_t stream);
+int hriemo_health_fold(const float* partial, const long long* chunks, int C, int P, const float* state, const int* ctl,
+                       const float* grad_scale, int every, int capacity, int* log, hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
