@@ -46,8 +46,8 @@ struct AttnArgs {
   // lane group g holds keys 4g..4g+3 of each 16-key subtile n).  NULL: the backward replays the hash.
   unsigned long long* mbits;
   // Packed (varlen) sequences: rows of sample b are cu_q[b] .. cu_q[b+1]-1 of Q / O / dO / dQ and cu_k[b] .. cu_k[b+1]-1 of
-  // K / V / dK / dV (int32 [B+1] each, both set or both NULL); Lq / Lk are then the LONGEST sequences (grid size, and the row
-  // stride of the lse / delta / mask-word side buffers, which keep their padded [B,H,Lq] indexing).  Every length >= 1.
+  // K / V / dK / dV (int32 [B+1] each, both set or both NULL); Lq / Lk are then upper bounds of the lengths that no sequence need
+  // reach (kernel form, grid size, and the slots of the lse / delta / mask-word side buffers: localize()).  Every length >= 1.
   const int* cu_q;
   const int* cu_k;
   // optional MX-fp8 copy of O for the out-projection GEMM (cfg 5's fp8 mode): bytes [B*Lq][ldoq] + E8M0 scales [H*HD/32][ldso];

@@ -144,11 +144,19 @@ int hriemo_attn_plan(int B, int H, int Lq, int Lk, int head_dim, int cus, int* f
 /* Packed (varlen) sequences, SURVEY 8(f) rank 4: the reference pads every sample to the batch maximum
  * (scripts/fusion/train_fusion_seq_level_decoder.py:191-232) and computes the PAD rows; here Q / O / dO / dQ hold the valid rows of
  * all samples back to back (sample b = rows cu_seqlens_q[b] .. cu_seqlens_q[b+1]-1) and K / V / dK / dV likewise with
- * cu_seqlens_k (int32 [B+1], device memory, every length >= 1).  max_len_q / max_len_k are the longest sequences: they size the
- * grid and are the row stride of lse / delta / drop_mask_bits and of the column-sum partials, which keep the padded indexing of
- * the functions above (so hriemo_attn_mask_bytes / *_colsum_rows are asked with the maxima).  Same arithmetic, same dropout
- * mask (it is keyed by position within the sequence), results on the valid rows identical to the padded call with a
- * key_padding_mask. */
+ * cu_seqlens_k (int32 [B+1], separate arrays in device memory, every length >= 1).  max_len_q / max_len_k are upper bounds of the
+ * lengths that NO sequence need reach (a captured step launches with the loader's padded length and appends its surplus rows as
+ * one more sequence): they choose the kernel form (hriemo_attn_plan at the maxima), size the grid -- blocks whose tile lies past
+ * their sample's end store nothing but zero column sums -- and size the side buffers, which are asked for with the maxima
+ * (hriemo_attn_mask_bytes / *_colsum_rows) and keep padded slots.  With bh = b * H + h:
+ *   lse, delta       element (b, h, q) at bh * max_len_q + q;
+ *   drop_mask_bits   a slot of max_len_q * ceil(max_len_k / 64) words per (b, h), filled COMPACTLY with the sample's own key-tile
+ *                    count: word (b, h, q, tile) at bh * max_len_q * ceil(max_len_k / 64) + q * ceil(len_k[b] / 64) + tile (the bits
+ *                    inside a word as above); the rest of the slot is not written;
+ *   partials         two-kernel form: row b * tiles(max_len) + tile on either side, single-pass forms: row b.
+ * Rows of Q / K / V / dO past cu_seqlens[B] are never read and rows of O / dQ / dK / dV past it never written.  Same arithmetic,
+ * same dropout mask (it is keyed by position within the sequence), results on the valid rows identical to the padded call with
+ * a key_padding_mask (tests/test_gpu_attention_variants_packed.py holds every kernel form to all of this). */
 /* hriemo_attn_fwd whose epilogue also writes the MX-fp8 form of O -- bytes Oq[B*Lq][ldoq], E8M0 scales So[H*hd/32][ldso] (ldso >=
  * B*Lq, a multiple of 256), bit-identical to hriemo_quant_mx8 of O -- for the out-projection GEMM of the fp8 mode.  head_dim % 32 == 0. */
 int hriemo_attn_fwd_q(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo,
