@@ -117,6 +117,10 @@ _SIGS = {
     "hriemo_swap_fp32": ("pplp", "i"),
     "hriemo_health_sweep": ("pppplpippipipp", "i"),
     "hriemo_health_fold": ("ppiipppiipp", "i"),
+    "hriemo_act_probe_rows": ("", "i"),
+    "hriemo_act_log_plan": ("iiiippppp", "i"),
+    "hriemo_act_probe": ("piiilppiippiiiippp", "i"),
+    "hriemo_act_log_fold": ("pppiiiipp", "i"),
     "hriemo_masked_mean_fwd": ("ppppiiip", "i"),
     "hriemo_rowsum_f32": ("ppilp", "i"),
     "hriemo_gate_input_pooled": ("pppiip", "i"),

@@ -108,12 +108,15 @@ class StepContext:
                      (form_stale), the step's weights pass keeps them fresh
       forms          a FormLog while such a step looks for the forms its forward asks for; None otherwise
       prologue       such a step's hand-over of the decoder's query prologue: prologue(decoder, B) -> the static (tgt, tgt32) layer 0
-                     starts its cross-attention on (models/emotion_decoder.py); None otherwise"""
-    __slots__ = ("capturing", "capture_origin", "seq_override", "join_scope", "half_reports", "stationary", "forms", "prologue")
+                     starts its cross-attention on (models/emotion_decoder.py); None otherwise
+      act_log        a train.ActivationLog whose probes the sub-layers launch (probe()); None: no launch anywhere"""
+    __slots__ = ("capturing", "capture_origin", "seq_override", "join_scope", "half_reports", "stationary", "forms", "prologue",
+                 "act_log")
 
     def __init__(self):
         self.capturing, self.capture_origin, self.seq_override, self.join_scope, self.half_reports = False, None, None, 0, {}
         self.stationary, self.forms, self.prologue = False, None, None
+        self.act_log = None
 
 
 CTX = StepContext()        # the context in force
@@ -134,6 +137,21 @@ class use_context:
         global CTX
         CTX = self.prev
         return False
+
+
+def probe(key, half, x, seq):
+    """A site of the activation log in force (train.ActivationLog): the statistics of x, whose rows are laid out as `seq`, go to the
+    forward (half 0) or gradient (half 1) half of the site `key` names -- a sub-layer's dropout site id, or the site's name.  One
+    launch of hriemo_act_probe on the current stream; nothing at all without a log or for a site the log does not keep.  No
+    autograd node: x is only read."""
+    log = CTX.act_log
+    if log is None or not log.open[half]:
+        # (no pass of the log is open: a sub-module called on its own inside log.watch(), or a backward behind close_backward() --
+        # a probe without its plan launch in front would run under the window of the pass before)
+        return
+    site = log.index.get(key)
+    if site is not None:
+        log.probe(site, half, x.detach(), seq)
 
 
 def fork(child, parent):
@@ -1912,6 +1930,7 @@ def _attn_ln_fwd(ctx, head, q, k, v, x2, x32v, ar, H, hd, sh, w_in16, w_out16, d
                               want_bits=attn_mask_bits(ar.B, H, ar.Lk, hd, ar.Lq), cu=ar.cu)
     g, y, y32, mean, rstd, mx = _proj_ln(o, sh, w_out, w_out16, b_out, x2, x32v, gamma, beta, p, seed, site + 1, b_off * ar.stride,
                                          ar.rows)
+    probe(site, 0, y, ctx.seq_q)
     probs = attn_probs(q, k, ar.B, H, ar.Lq, ar.Lk, hd, ar.kpm, lse, p, seed, site, b_off, ar.cu, out_l,
                        log=need_w if isinstance(need_w, LogSite) else None) if need_w else None
     ctx.save_for_backward(*head, o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits[0] if mbits else None)
@@ -1920,11 +1939,14 @@ def _attn_ln_fwd(ctx, head, q, k, v, x2, x32v, ar, H, hd, sh, w_in16, w_out16, d
     return tag_mx(y.view(shape), mx), (y32.view(shape) if y32 is not None else None), probs
 
 
-def _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site, row_off, rows, want_dx=True):
+def _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site, row_off, rows, want_dx=True, seq=None):
     """How every sub-layer's backward opens: the gradients of its output pair summed, the GradSink of `params` = (..., bias of the
     last Linear, gamma, beta), LayerNorm + residual + dropout backward into the sink's buffers.
-    -> (sink, dS: the residual path's gradient (None unless want_dx), dG: the last Linear's output gradient, dgamma, dbeta, dbias)"""
+    -> (sink, dS: the residual path's gradient (None unless want_dx), dG: the last Linear's output gradient, dgamma, dbeta, dbias)
+    seq: the Seq of the rows -- the summed gradient is the gradient half of the sub-layer's site in an activation log (probe)"""
     dy2 = _contig_bf16(_sum_grads(dy, dy32)).view(x2.shape)
+    if seq is not None:
+        probe(site - 1, 1, dy2, seq)
     sink = GradSink(params)
     return (sink,) + add_ln_bwd(dy2, g, x2, gamma, mean, rstd, p, seed, site, row_off, want_dx=want_dx,
                                 outs=(sink.buf(params[-2]), sink.buf(params[-1]), sink.buf(params[-3])),
@@ -1938,7 +1960,7 @@ def _attn_ln_bwd(ctx, params, dy, dy32, x2, x32v, tail, want_dx=True):
     o, lse, g, mean, rstd, w_in16, w_out16, gamma, mbits = tail
     p, seed, site, b_off = ctx.cfg[-4:]
     sink, ds, dg, dgamma, dbeta, db_out = _ln_bwd(params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site + 1,
-                                                  b_off * ctx.rows.stride, ctx.rows.rows, want_dx)
+                                                  b_off * ctx.rows.stride, ctx.rows.rows, want_dx, seq=ctx.seq_q)
     dw_out = sink.buf(params[-4])
     linear_dw(dg, o, dw_out, sink.fused)
     return sink, ds, linear_dx(dg, w_out16), dw_out, db_out, dgamma, dbeta
@@ -1966,6 +1988,7 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
         w_in16, w_out16 = sh.get(w_in), sh.get(w_out)
         ctx.cfg = (B, L, d, H, hd, p, seed, site, b_off)
         ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
+        ctx.seq_q = seq
         qkv = proj_fwd(Operand(x2, mx_of(x)), sh, w_in, w_in16, b_in)
         return _attn_ln_fwd(ctx, (x2, x32v, qkv), qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], x2, x32v, ar, H, hd, sh, w_in16,
                             w_out16, (p, seed, site, b_off), need_w, (seq.L, seq.L), (B, L, d))
@@ -1994,6 +2017,8 @@ class SelfAttnLN(_GradModeAware, torch.autograd.Function):
         if not folded:
             colsum(dqkv, db_in, acc)
         dx = linear_dx(dqkv, w_in16, epi=3, aux=ds).view(B, L, d) if want_dx else None
+        if CTX.act_log is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            probe(("input", site), 1, dx, ctx.seq_q)      # layer 0 only (the log's keys): x is the rows the encoder starts from
         sink.done()
         if site in FLUSH_SITES:
             _small_dw.flush()                 # the text branch's backward ends here: queued decoder / gate weight gradients go out now
@@ -2034,6 +2059,7 @@ class CrossAttnLN(_GradModeAware, torch.autograd.Function):
         x32v = xq32.view(B * Lq, d) if xq32 is not None else None
         ctx.cfg = (B, Lq, Lk, d, H, hd, p, seed, site, b_off)
         ctx.params = (w_in, b_in, w_out, b_out, gamma, beta)
+        ctx.seq_q = seq_q
         ctx.own_q, ctx.own_kv, ctx.slots, ctx.join_q = q_pre is None, kv_pre is None, slots, join_q
         w_out16 = sh.get(w_out)
         w_in16 = sh.get(w_in) if (ctx.own_q or ctx.own_kv) else None
@@ -2359,6 +2385,7 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
             _lib.call("hriemo_dropout_bf16", _p(h), _p(hd_), M, h.shape[1], float(p_mid), seed, _p(seed_word(h.device)),
                       site + 2, b_off * L, _stream())
         g, y, y32, mean, rstd, mx = _proj_ln(hd_, sh, w2, w2_16, b2, x2, x32v, gamma, beta, p, seed, site + 1, b_off * seq.L, seq.idx)
+        probe(site, 0, y, seq)
         ctx.save_for_backward(x2, x32v, h, hd_, g, mean, rstd, w1_16, w2_16, gamma)
         ctx.cfg = (B, L, d, p, p_mid, seed, site, b_off)
         ctx.seq = seq
@@ -2375,7 +2402,7 @@ class FFNLN(_GradModeAware, torch.autograd.Function):
         dev = x2.device
         p_w1, p_b1, p_w2 = ctx.params[:3]
         sink, ds, dg, dgamma, dbeta, db2 = _ln_bwd(ctx.params, dy, dy32, g, x2, x32v, gamma, mean, rstd, p, seed, site + 1,
-                                                   b_off * ctx.seq.L, ctx.seq.idx)
+                                                   b_off * ctx.seq.L, ctx.seq.idx, seq=ctx.seq)
         acc = sink.fused
         dw2 = sink.buf(p_w2)
         linear_dw(dg, hd_, dw2, acc)
@@ -2514,6 +2541,16 @@ def _gate_weights_bwd(part, Lp, dbeta2, w, hid, gin, a_pool, t_pool, cnt, w1_16,
     return da, dt, dw1, db1, dw2, db2
 
 
+def _fused_rows(sa, st, sf):
+    """the fused memory's layout as an activation log counts its rows: the packed plan as it is; padded, the rows both modalities
+    hold (the reference ORs the two padding masks cut to the fused length)"""
+    if sf.packed or (sa.kpm is None and st.kpm is None):
+        return sf
+    ma = sa.kpm[:, :sf.L] if sa.kpm is not None else None
+    m = ma.contiguous() if st.kpm is None else (st.kpm if ma is None else (ma | st.kpm))
+    return sf.with_kpm(m)
+
+
 class BetaGateFn(_GradModeAware, torch.autograd.Function):
     """(h_fusion, beta) = BetaGate(h_a, h_t, masks)  -- models/beta_gate_tacfn.py:68-118
     sa / st / sf: the Seq of h_a's rows, of h_t's rows and of the fused memory's -- all padded ([B, L_a, d], [B, L_t, d], h_fusion
@@ -2543,6 +2580,12 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         gin, a_pool, t_pool, cnt, hid, w, beta, w1_16, w2_16 = _gate_weights(pa, pt, sa, st, B, La, Lt, d, w1, b1, w2, b2, sh)
         H = torch.empty(sf.shape(d), dtype=BF16, device=dev)
         fuse_fwd(w, An, Tn, H, sf, d)
+        ctx.fused_rows = None
+        if CTX.act_log is not None and CTX.act_log.open[0]:
+            # (padded rows with masks: ONE elementwise launch of torch's, the OR of the two masks; the backward reuses the layout)
+            ctx.fused_rows = _fused_rows(sa, st, sf)
+            probe("gate.w", 0, w, Seq.padded(B, 1))
+            probe("gate.fused", 0, H, ctx.fused_rows)
         ctx.save_for_backward(xa, xt, An, Tn, mean_a, rstd_a, mean_t, rstd_t, gin, a_pool, t_pool, cnt, hid, w, w1_16,
                               w2_16, ga, gt, h_a32, h_t32)
         ctx.seqs = (sa, st, sf)
@@ -2564,6 +2607,8 @@ class BetaGateFn(_GradModeAware, torch.autograd.Function):
         # launches on the serial chain between the decoder's and the encoder's backward
         sink = GradSink(ctx.params)
         dH2 = _contig_bf16(dH) if dH is not None else torch.zeros(An.shape, dtype=BF16, device=dev)
+        if ctx.fused_rows is not None and dH is not None:
+            probe("gate.fused", 1, dH2, ctx.fused_rows)
         dbeta2 = dbeta.contiguous().float() if dbeta is not None else None
         part = torch.empty((B, _lib.lib().hriemo_pool_chunks(L), d), **f32)
         fuse_bwd_dw(dH2, An, Tn, part, sf, d)
@@ -3049,6 +3094,8 @@ class RowDotFn(_GradModeAware, torch.autograd.Function):
         bf = b.detach().float().contiguous()
         out = torch.empty(B * Ne, dtype=torch.float32, device=z.device)
         _lib.call("hriemo_rowdot_fwd", _p(z2), _p(z32v), _p(wf), _p(bf), _p(out), B * Ne, d, _stream())
+        if CTX.act_log is not None:
+            probe("logits", 0, out.view(B, Ne), Seq.padded(B, 1))
         ctx.save_for_backward(z2, z32v, wf)
         ctx.cfg = (B, Ne, d)
         ctx.params = (w, b)
@@ -3063,6 +3110,8 @@ class RowDotFn(_GradModeAware, torch.autograd.Function):
             dz32, dw, db = _fp32().rowdot_bwd(dl, z32v, wf, B, Ne, d)
             return None, dz32, dw.view_as(ctx.params[0]), db.view_as(ctx.params[1])
         dl2 = dl.contiguous().float().view(-1)
+        if CTX.act_log is not None:
+            probe("logits", 1, dl2.view(B, Ne), Seq.padded(B, 1))
         dz = torch.empty((B * Ne, d), dtype=BF16, device=z2.device)
         sink = GradSink(ctx.params)
         dw, db = sink.buf(ctx.params[0]), sink.buf(ctx.params[1])

@@ -728,6 +728,7 @@ class DataParallelStep(_RaggedStep):
         self._stats = None            # train.EpochStats fed by every executed (micro-)step (attach_stats)
         self._stats_scale = 1.0
         self._outputs = None          # with statistics attached: what the latest _fwd_bwd pass hands to _update_stats
+        self._act_log = None          # train.ActivationLog fed by every executed (micro-)step (attach_activations)
 
     @property
     def captured(self):
@@ -754,6 +755,23 @@ class DataParallelStep(_RaggedStep):
             raise RuntimeError("attach_stats() comes before capture() / capture_packed(): the update is part of the captured step "
                                "(release_graph() first to change it)")
         self._stats, self._stats_scale, self._outputs = stats, float(loss_scale), None
+
+    def attach_activations(self, log):
+        """Feed a ``train.ActivationLog`` from this step: every executed trainer step or micro-step -- a replay, an eager step, a
+        micro-batch of step_accumulated or of a captured accumulation group -- is one pass of the log: its plan launch at the top of
+        the forward in front of every fork, a probe behind every sub-layer the log keeps (forward) and at the top of its backward
+        (gradient), the forward fold at the end of the forward and the gradient fold behind backward, in front of the statistics
+        and the optimizer.  Nothing is read back.  Call it BEFORE capture() / capture_packed() / capture_store(), as attach_stats:
+        the launches are part of the captured step.  The warm-up passes of a capture -- those of a bucket graph met in the middle
+        of an epoch included -- run under the closed window and leave no trace.  After capture_packed(partial_batches=True) the
+        ghost utterances of a short batch never count.  log=None detaches.  Without a log attached every path launches exactly what
+        it launched before."""
+        if self.captured:
+            raise RuntimeError("attach_activations() comes before capture() / capture_packed(): the probes are part of the captured "
+                               "step (release_graph() first to change it)")
+        if log is not None:
+            log._guard()
+        self._act_log = self.ctx.act_log = log
 
     def _update_stats(self):
         """one hriemo_stats_update launch on the outputs of the latest _fwd_bwd pass (no-op without statistics attached)"""
@@ -791,6 +809,9 @@ class DataParallelStep(_RaggedStep):
             self.buckets._rebind()
         elif zero:
             self.buckets.zero_grad()
+        act = self._act_log
+        if act is not None:
+            act.n_valid = ctl[:1] if (ctl is not None and front.partial) else None
         if ragged is not None:
             logits, beta, _ = self.model.forward_packed(h_a, h_t, ragged[0], ragged[1], pad_to=ragged[2])
         elif front is not None:
@@ -812,6 +833,8 @@ class DataParallelStep(_RaggedStep):
             loss.backward(gradient=_ops.one(loss.device))      # the fused losses skip the multiply by this very tensor
         else:
             loss.backward()
+        if act is not None:
+            act.close_backward()              # the gradient half's fold: behind backward, in front of statistics and optimizer
         return loss.detach()
 
     @_in_step_context
@@ -1124,7 +1147,11 @@ class DataParallelStep(_RaggedStep):
         collectives = self._exchange_in_graph
 
         def warm():
-            self._fwd_bwd(*self._static)
+            if self._act_log is not None:
+                with self._act_log.paused():      # under the closed window: a warm-up pass leaves no trace in the log
+                    self._fwd_bwd(*self._static)
+            else:
+                self._fwd_bwd(*self._static)
             if collectives:
                 self.buckets.finish()         # the warm-up steps exchange eagerly (every rank alike) and leave the buckets reset
 
@@ -1249,10 +1276,16 @@ class _WeightsPass:
         self.seen, self.ptrs, self.forms = None, tuple(p.data_ptr() for p in self.params), {}
 
     def _body(self, entries, prologue):
-        with torch.no_grad():
-            for _, fn, args in entries:
-                fn(*args)
-            out = self.decoder.prologue(self.B) if prologue else None
+        from . import _ops
+        ctx = _ops.CTX
+        held, ctx.act_log = ctx.act_log, None     # the weights pass is no pass of an activation log: no probe in its graphs
+        try:
+            with torch.no_grad():
+                for _, fn, args in entries:
+                    fn(*args)
+                out = self.decoder.prologue(self.B) if prologue else None
+        finally:
+            ctx.act_log = held
         return None, out
 
     def eager(self):
@@ -1328,7 +1361,7 @@ class EvalStep(_RaggedStep):
     and the loop of scripts/infer/mosei_eval_infer.py.  An eager forward is ~150 launches issued from Python; one ``eval_packed``
     is the copies of the batch into the static buffers and one replay.
 
-    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False): loss_fn(logits, beta, y, n_valid=...) as
+    EvalStep(model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False, act_log=None): loss_fn(logits, beta, y, n_valid=...) as
     hri_emo_amd.train's losses; stats a ``train.EpochStats``, log a ``train.PredictionLog`` -- both are fed INSIDE the graph, one
     launch each, and never by a warm-up pass.  max_graphs: bucket graphs kept alive (default HRIEMO_VARLEN_MAX_GRAPHS), least
     recently replayed one released first.  The step has its own ``_ops.StepContext`` and its own graph pool, creates no gradient
@@ -1347,6 +1380,10 @@ class EvalStep(_RaggedStep):
     one family of bucket graphs serves the whole split.  Warm-up passes run with the closed window and leave the log bit-unchanged.
     Needs set_varlen_maps(True); varlen_maps() and mfma_maps() then join the switches recorded at capture.  ``return_attention``
     itself is not part of the captured step.
+    act_log: a ``train.ActivationLog`` -- every evaluation is one pass of it, forward half only: the log's plan launch at the top of
+    the model's forward (in front of every fork), a probe behind every sub-layer the log keeps, one fold at the forward's end; the
+    ghosts behind n_valid never count.  Warm-up passes run under the closed window.  A stationary step's dec0.self runs in the
+    weights pass, which is no pass of the log: that site stays absent.
 
     stationary=True: a bucket graph holds only what depends on the batch.  What depends on the parameters alone -- every weight
     form the forward asks for (bf16 shadows, concatenations, padded and MX-fp8 copies, the fp32 mode's splits) and the decoder's
@@ -1363,11 +1400,14 @@ class EvalStep(_RaggedStep):
 
     _label = "eval step"
 
-    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False):
+    def __init__(self, model, loss_fn=None, stats=None, log=None, max_graphs=None, attn_log=None, stationary=False, act_log=None):
         if max_graphs is not None and int(max_graphs) < 1:
             raise ValueError("EvalStep: max_graphs is a positive integer (or None)")
         super().__init__(model, loss_fn)
         self.stats, self.log, self.attn_log = stats, log, attn_log
+        if act_log is not None:
+            act_log._guard()
+        self.act_log = self.ctx.act_log = act_log
         self.max_graphs = None if max_graphs is None else int(max_graphs)
         self.stationary = bool(stationary)
         self._modes = None                 # _mode_switches() at capture
@@ -1476,6 +1516,13 @@ class EvalStep(_RaggedStep):
         """one evaluation on the static state, as every warm-up pass runs it and the capture records it; record: the pass feeds
         stats, log and attention log (the capture pass only; a warm-up pass runs the exports under the closed window)
         -> (loss | None, (logits, beta, z)), the form _record_graph takes"""
+        act = self.act_log
+        if act is not None and not record:
+            with act.paused():                    # the activation log's probes likewise
+                return self._pass_body(record)
+        return self._pass_body(record)
+
+    def _pass_body(self, record):
         from . import _ops
         pb = self._pb
         front = pb.front
@@ -1484,6 +1531,8 @@ class EvalStep(_RaggedStep):
         with torch.no_grad():
             _ops.seq_tables(front.lens.dev, pb.La, pb.Lt, rows=(seqs[0].N, seqs[1].N), cu=(pb.cu_a, pb.cu_t, pb.cu_f), masks=front.masks)
             n_valid = front.ctl.dev[:1]
+            if self.act_log is not None:
+                self.act_log.n_valid = n_valid
             if self.attn_log is not None:
                 self.attn_log.plan(front.lens.dev, n_valid, pb.B, record=record)
                 logits, beta, z = self.model._forward_rows(self._static[0], self._static[1], tuple(seqs), front.bool, (pb.La, pb.Lt),
@@ -1607,6 +1656,8 @@ class EvalStep(_RaggedStep):
         self.model.eval()
         try:
             with torch.no_grad():
+                if self.act_log is not None:
+                    self.act_log.n_valid = None
                 extra = {} if self.attn_log is None else {"attn_log": self.attn_log}
                 logits, beta, z = self.model.forward_packed(rows_a.to(dev, non_blocking=True), rows_t.to(dev, non_blocking=True), la, lt,
                                                             pad_to=(pb.La, pb.Lt), **extra)

@@ -184,6 +184,10 @@ class CrossModalTransformer(nn.Module):
                     (a, a32), (t, t32) = _ops.pack_pair(a, a32, plan[0]), _ops.pack_pair(t, t32, plan[1])
         if raw and plan is None:
             (a, a32), (t, t32) = _ops.ingest_pair(a, _ops.Seq.padded(B, La)), _ops.ingest_pair(t, _ops.Seq.padded(B, Lt))
+        if _ops.CTX.act_log is not None:          # the rows the encoder starts from (train.ActivationLog: input.audio, input.text)
+            s0 = plan[:2] if plan is not None else (_ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))
+            _ops.probe("input.audio", 0, a, s0[0])
+            _ops.probe("input.text", 0, t, s0[1])
         for i, layer in enumerate(self.layers):
             # (padded: every layer converts the masks itself, as it always did -- a view for bool masks)
             sa, st = plan[:2] if plan is not None else (_ops.Seq.padded(B, La, mask_a), _ops.Seq.padded(B, Lt, mask_t))

@@ -91,6 +91,8 @@ class FusionWithEmotionDecoder(nn.Module):
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
         h_a, h_t = self._ensure_3d(h_a), self._ensure_3d(h_t)
+        if _ops.CTX.act_log is not None:
+            _ops.CTX.act_log._guard()          # an activation log in fp32 precision: refused before anything is enqueued
         # one cast at the boundary; between the sub-modules activations travel as (bf16, fp32-twin) pairs
         # (_ops.INGEST_ROWS: the pairs are made by the encoder's entry, one launch each, packed where it packs)
         raw = _ops.ingestible(h_a, h_t)
@@ -128,6 +130,8 @@ class FusionWithEmotionDecoder(nn.Module):
         _check_attn_log(self, attn_log, return_attention, pad)
         if attn_log is not None and not _ops.varlen_maps():
             raise ValueError("forward_packed: attention maps of packed rows need set_varlen_maps(True)")
+        if _ops.CTX.act_log is not None:
+            _ops.CTX.act_log._guard()          # an activation log in fp32 precision: refused before anything is enqueued
         a, a32 = _ops.ingest_pair(rows_a, plan[0], src_packed=True)
         t, t32 = _ops.ingest_pair(rows_t, plan[1], src_packed=True)
         return self._run(a, a32, t, t32, masks[0], masks[1], pad[1], rows_a.dtype, return_attention, plan=plan,
@@ -143,6 +147,11 @@ class FusionWithEmotionDecoder(nn.Module):
             # (B: the plan's real samples -- a bucket plan's filler sequence has no map)
             enc_sites, dec_sites = attn_log.sites(plan[0].Breal)
             need, need_enc, need_dec = True, enc_sites or False, dec_sites or False
+        act_log = _ops.CTX.act_log
+        if act_log is not None:
+            # a train.ActivationLog: its plan launch comes in front of every fork of the pass (the only writer of the window the
+            # probes of the sub-layers read), its forward fold behind every join
+            act_log.begin_pass()
         _ops.begin_step()
         # the decoder's memory mask needs the two padding masks only (L_fused = T_t, beta_gate_tacfn.py:98-116): built here, not on
         # the decoder's serial chain behind the gate
@@ -167,6 +176,8 @@ class FusionWithEmotionDecoder(nn.Module):
             sm = sm.with_kpm(fused_early if (fused_early is not None and h_fusion.size(1) == Lt) else
                              self._build_fused_mask(mask_a, mask_t, h_fusion.size(1)))
         z, logits, decoder_attns = self.emotion_decoder._fwd(h_fusion, sm, need_dec, out_dtype)
+        if act_log is not None:
+            act_log.end_forward()
         if return_attention:
             return logits, beta, z, {"encoder": encoder_attns, "decoder": decoder_attns}
         return logits, beta, z

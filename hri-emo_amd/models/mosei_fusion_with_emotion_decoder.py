@@ -29,6 +29,8 @@ class MoseiFusionWithEmotionDecoder(nn.Module):
         self.backbone.set_batch_offset(offset)
 
     def forward(self, h_a, h_t, mask_a=None, mask_t=None, return_attention=False):
+        if _ops.CTX.act_log is not None:
+            _ops.CTX.act_log._guard()          # refused before the projections are enqueued
         h_a_proj = _ops.LinearFn.apply(h_a, self.audio_proj.weight, self.audio_proj.bias, self._sh)   # :63
         h_t_proj = _ops.LinearFn.apply(h_t, self.text_proj.weight, self.text_proj.bias, self._sh)     # :65
         return self.backbone(h_a_proj, h_t_proj, mask_a, mask_t, return_attention=return_attention)   # :68-79
@@ -51,6 +53,8 @@ class MoseiFusionWithEmotionDecoder(nn.Module):
         plan.N rows of each source -- all of them for a batch's own plan; for a bucket plan the bucket's row count, a slice that is
         static per bucket graph (the caller keeps the rows between the batch's last row and plan.N finite: their gradient is zero,
         and zero times a NaN would not be)"""
+        if _ops.CTX.act_log is not None:
+            _ops.CTX.act_log._guard()          # refused before the projections are enqueued
         a = _ops.LinearFn.apply(rows_a[:plan[0].N], self.audio_proj.weight, self.audio_proj.bias, self._sh)
         t = _ops.LinearFn.apply(rows_t[:plan[1].N], self.text_proj.weight, self.text_proj.bias, self._sh)
         return self.backbone._forward_rows(a, t, plan, masks, pad, return_attention, attn_log)

@@ -610,6 +610,288 @@ class AttentionLog:
         return out
 
 
+ACT_HALVES = ("forward", "gradient")
+ACT_PROBE_ROWS = 32            # rows per chunk of hriemo_act_probe (hriemo_act_probe_rows())
+_ACT_ENC = ("audio_self", "text_self", "audio_cross", "audio_ffn", "text_cross", "text_ffn")      # CrossModalBlock._site order
+_ACT_DEC = ("self", "cross", "ffn")                                                               # ExplainableDecoderLayer._site order
+_ACT_FIELDS = ("have", "n_rows", "n_bad", "first_bad_row", "absmax", "sumsq")
+
+
+def activation_site_names(num_layers_fusion, num_layers_decoder):
+    """the sites of an ActivationLog in forward order (23 for two encoder and two decoder layers)"""
+    names = ["input.audio", "input.text"]
+    names += [f"enc{i}.{s}" for i in range(int(num_layers_fusion)) for s in _ACT_ENC]
+    names += ["gate.w", "gate.fused"]
+    names += [f"dec{j}.{s}" for j in range(int(num_layers_decoder)) for s in _ACT_DEC]
+    return names + ["logits"]
+
+
+class ActivationLog:
+    """Activation-side blame for a step that runs inside a graph: per sub-layer, the statistics of its output (forward half) and of
+    the summed gradient that arrives at its backward for that output (gradient half) -- n_rows, n_bad (non-finite elements),
+    first_bad_row, absmax and sumsq over the finite elements of the rows that count -- written by the pass itself into a ring of
+    `capacity` records in device memory (csrc/actlog.hip), read back once when asked.  Where ``optim.HealthLog.blame()`` names the
+    parameters whose gradient was not finite, ``blame()`` here names the sub-layer, sample and position where a non-finite value
+    first appeared.
+
+    ``ActivationLog.for_model(model, capacity=16, every=1, sites=None, device=None, max_rows=65536)`` builds the site table of a
+    FusionWithEmotionDecoder or its MOSEI wrapper (``activation_site_names``): input.audio, input.text (the rows the encoder starts
+    from); per encoder layer enc{i}.audio_self, .text_self, .audio_cross, .audio_ffn, .text_cross, .text_ffn and per decoder layer
+    dec{j}.self, .cross, .ffn (each sub-layer's LayerNorm output); gate.w (the gate vector [B, d]), gate.fused (the decoder's
+    memory); logits.  sites: names or fnmatch patterns -- only those launch a probe; the record keeps every site's words, the
+    others with have = 0.  every: pass p of the run records iff p % every == 0.  max_rows sizes the per-site partial sums: the
+    largest row count of one activation buffer a pass may probe.
+
+    Rows that count: those of the real sequences of the batch inside their lengths -- PAD rows, the filler sequence and surplus rows
+    of a bucket plan and the ghost utterances of a short batch (n_valid) never do, whatever they hold.  The gradient half of a site
+    no backward node receives a gradient for keeps have = 0: gate.w, the input.* sites when the inputs need no gradient, every site of an
+    evaluation pass.  Under a
+    ``GradScaler`` the gradient half holds the statistics of the SCALED gradients (the log sits in front of the unscale).
+
+    Use: eagerly ``with log.watch(): out = model(...); loss.backward(); log.close_backward()``; in a captured trainer step
+    ``dp.DataParallelStep.attach_activations(log)`` before capture; in a captured evaluation ``dp.EvalStep(..., act_log=log)``
+    (forward half only).  Warm-up passes of a capture never record.  bf16 precision only (both GEMM modes): under
+    ``set_precision("fp32")`` a pass with a log installed raises NotImplementedError.
+
+    arrays(): one read-back -> {"sites", "n_passes", "n_recorded", "pass" [n], "halves" [n], "forward": {field: [n, S]},
+    "gradient": {field: [n, S]}}, records oldest first, fields have, n_rows, n_bad, first_bad_row, absmax, sumsq and rms =
+    sqrt(sumsq / (n_rows * d)) formed here in float64.  blame(record=-1): None if the record holds no non-finite element, else
+    {"half", "site", "sample", "position", "n_bad"}: the first site in forward order whose forward half has n_bad > 0; if the
+    forward is clean, the first site in backward (reverse) order whose gradient half has.  reset() clears the ring.
+    ``decode`` and ``blame_of`` are the same rules on a host image of the state: the CPU mirror."""
+
+    HEADER = 8                 # counters int32 [4] | window int32 [4]
+    REC_HEADER, ENTRY = 4, 8
+
+    def __init__(self, names, widths, keys=None, capacity=16, every=1, sites=None, device="cuda", max_rows=65536):
+        import fnmatch
+        if int(capacity) < 1 or int(every) < 1 or int(max_rows) < 1:
+            raise ValueError("ActivationLog: capacity, every and max_rows are positive")
+        self.names, self.widths = list(names), [int(w) for w in widths]
+        if len(self.names) != len(self.widths) or not self.names:
+            raise ValueError("ActivationLog: one width per site, at least one site")
+        self.capacity, self.every, self.max_rows = int(capacity), int(every), int(max_rows)
+        self.device = torch.device(device)
+        S = self.S = len(self.names)
+        if sites is None:
+            chosen = set(self.names)
+        else:
+            chosen = set()
+            for pat in ([sites] if isinstance(sites, str) else list(sites)):
+                hit = fnmatch.filter(self.names, pat)
+                if not hit:
+                    raise ValueError(f"ActivationLog: no site matches {pat!r}; the sites are {', '.join(self.names)}")
+                chosen.update(hit)
+        self.selected = [n for n in self.names if n in chosen]
+        # key -> site index, selected sites only: what _ops.probe looks up (a sub-layer's dropout site id, or the site's name)
+        by_name = {n: i for i, n in enumerate(self.names)}
+        self.index = {k: by_name[n] for k, n in (keys or {}).items() if n in chosen}
+        self.index.update({n: by_name[n] for n in self.selected})
+        self.row_len = [None] * S          # rows per sample of the site's buffer, noted by its first probe: first_bad_row -> (sample, position)
+        self.recording = True              # False: the passes are warm-up passes (paused())
+        self.open = [False, False]         # a pass's forward / gradient half is open: begin_pass .. end_forward / close_backward
+        self.n_valid = None                # the step's device word: the ghosts behind it never count
+        self.chunk_cap = (self.max_rows + ACT_PROBE_ROWS - 1) // ACT_PROBE_ROWS
+        self._counts_at = self.HEADER
+        self._ring_at = self.HEADER + (2 * S + 3) // 4 * 4
+        self.rec_words = self.REC_HEADER + 2 * S * self.ENTRY
+        # counters | window | counts | ring: ONE buffer, one read-back
+        self._small = torch.zeros(self._ring_at + self.capacity * self.rec_words, dtype=torch.int32, device=self.device)
+        self.counters, self.window = self._small[:4], self._small[4:8]
+        self.counts, self.ring = self._small[self._counts_at:self._counts_at + 2 * S], self._small[self._ring_at:]
+        self.partial = None
+        if self.device.type == "cuda":
+            from . import _lib
+            if _lib.lib().hriemo_act_probe_rows() != ACT_PROBE_ROWS:
+                raise RuntimeError("ActivationLog: the library's chunk of rows is not this module's")
+            self.partial = torch.zeros(2 * S * self.chunk_cap * 8, dtype=torch.float32, device=self.device)
+
+    @classmethod
+    def for_model(cls, model, capacity=16, every=1, sites=None, device=None, max_rows=65536):
+        core = getattr(model, "backbone", model)
+        if not (hasattr(core, "cross_modal") and hasattr(core, "beta_gate") and hasattr(core, "emotion_decoder")
+                and hasattr(core, "_run")):
+            raise NotImplementedError(f"ActivationLog.for_model: {type(model).__name__} is not served (FusionWithEmotionDecoder and "
+                                      "MoseiFusionWithEmotionDecoder are; FusionClassifier and the legacy block and gate are open)")
+        enc, dec = core.cross_modal.layers, core.emotion_decoder.layers
+        names = activation_site_names(len(enc), len(dec))
+        d, ne = core.emotion_decoder.d_model, core.emotion_decoder.num_emotions
+        widths = [ne if n == "logits" else d for n in names]
+        keys = {}
+        for i, layer in enumerate(enc):
+            keys.update({layer._site[j]: f"enc{i}.{s}" for j, s in enumerate(_ACT_ENC)})
+        # the gradient of the encoder's input rows is what layer 0's self-attentions return for them
+        keys.update({("input", enc[0]._site[0]): "input.audio", ("input", enc[0]._site[1]): "input.text"})
+        for j, layer in enumerate(dec):
+            keys.update({layer._site[k]: f"dec{j}.{s}" for k, s in enumerate(_ACT_DEC)})
+        if device is None:
+            device = next(core.parameters()).device
+        return cls(names, widths, keys, capacity, every, sites, device, max_rows)
+
+    @property
+    def nbytes(self):
+        return self._small.numel() * 4 + (self.partial.numel() * 4 if self.partial is not None else 0)
+
+    def reset(self):
+        self._small.zero_()
+
+    # ---- the pass
+    def _guard(self):
+        from . import _ops
+        if _ops.precision() == "fp32":
+            raise NotImplementedError('ActivationLog: set_precision("fp32") is not served (the fp32 sub-layers have no probes); '
+                                      'detach the log or switch to set_precision("bf16")')
+
+    def watch(self):
+        """``with log.watch():`` -- the log is installed on the step context in force: every pass of a served model inside the block
+        plans, probes and folds its forward half; ``close_backward()`` behind ``loss.backward()`` folds the gradient half.  Only a
+        pass of the whole model is a pass of the log: a sub-module called on its own inside the block (``model.cross_modal(...)``,
+        ``model.beta_gate(...)``) has no plan launch in front and launches no probe; a backward that runs behind
+        ``close_backward()`` launches none either.  Entering the block forgets the n_valid word of a step the log served before."""
+        return _ActWatch(self)
+
+    def paused(self):
+        """``with log.paused():`` -- the passes inside are warm-up passes: they run under the closed window and leave no trace"""
+        return _ActPaused(self)
+
+    def begin_pass(self):
+        """the top of a pass, in front of every fork: ONE launch (hriemo_act_log_plan)"""
+        self._guard()
+        from . import _lib, _ops
+        p = _ops._p
+        _lib.call("hriemo_act_log_plan", 1 if self.recording else 0, self.every, self.capacity, self.S, p(self.counters), p(self.window),
+                  p(self.counts), p(self.ring), _ops._stream())
+        self.open = [True, True]
+
+    def _fold(self, half):
+        from . import _lib, _ops
+        p = _ops._p
+        _lib.call("hriemo_act_log_fold", p(self.partial), p(self.counts), p(self.window), half, self.S, self.chunk_cap, self.capacity,
+                  p(self.ring), _ops._stream())
+
+    def end_forward(self):
+        """the end of the forward, behind every join: the forward half's fold"""
+        self._fold(0)
+        self.open[0] = False
+
+    def close_backward(self):
+        """behind ``loss.backward()``: the gradient half's fold"""
+        self._fold(1)
+        self.open[1] = False
+
+    def probe(self, site, half, x, seq):
+        """hriemo_act_probe of x (rows laid out as the _ops.Seq `seq`) for site index `site` on the current stream"""
+        from . import _lib, _ops
+        p = _ops._p
+        if x.dtype not in (torch.bfloat16, torch.float32) or x.device != self._small.device:
+            raise TypeError(f"ActivationLog: a {x.dtype} activation on {x.device} at site {self.names[site]}")
+        d = x.shape[-1]
+        x2 = x.reshape(-1, d)
+        if x2.stride(1) != 1 or x2.data_ptr() != x.data_ptr():
+            raise ValueError(f"ActivationLog: site {self.names[site]} handed rows that are not dense")
+        n_rows = x2.shape[0]
+        if n_rows != seq.N:
+            raise ValueError(f"ActivationLog: site {self.names[site]}: {n_rows} rows, the layout has {seq.N}")
+        if n_rows > self.max_rows:
+            raise ValueError(f"ActivationLog: site {self.names[site]} has {n_rows} rows; the log was sized for max_rows={self.max_rows}")
+        self.row_len[site] = seq.L
+        kpm = None
+        if not seq.packed and seq.kpm is not None:
+            kpm = seq.kpm if seq.kpm.is_contiguous() else seq.kpm.contiguous()
+        _lib.call("hriemo_act_probe", p(x2), 0 if x.dtype == torch.bfloat16 else 1, n_rows, d, x2.stride(0), p(seq.cu) if seq.packed else None,
+                  p(kpm), seq.Breal, seq.L, p(self.n_valid), p(self.window), site, half, self.S, self.chunk_cap, p(self.partial),
+                  p(self.counts), _ops._stream())
+
+    # ---- read-back
+    @classmethod
+    def decode(cls, image, names, widths, capacity):
+        """The records of a host image of the state (counters | window | counts | ring, int32), oldest first.  Closed passes leave
+        no record; a ring that wrapped holds the latest `capacity` records."""
+        img = np.ascontiguousarray(np.asarray(image, dtype=np.int32))
+        S, cap = len(names), int(capacity)
+        ring_at = cls.HEADER + (2 * S + 3) // 4 * 4
+        rw = cls.REC_HEADER + 2 * S * cls.ENTRY
+        if img.size != ring_at + cap * rw:
+            raise ValueError(f"ActivationLog.decode: an image of {img.size} words; {S} sites and capacity {cap} make {ring_at + cap * rw}")
+        n_passes, n_rec = int(img[0]), int(img[1])
+        n = min(max(n_rec, 0), cap)
+        order = [(n_rec - n + i) % cap for i in range(n)]
+        recs = img[ring_at:].reshape(cap, rw)[order] if n else np.zeros((0, rw), np.int32)
+        ent = recs[:, cls.REC_HEADER:].reshape(n, 2, S, cls.ENTRY)
+        out = {"sites": list(names), "n_passes": n_passes, "n_recorded": n_rec, "pass": recs[:, 0].copy(), "halves": recs[:, 1].copy()}
+        w = np.asarray(widths, dtype=np.float64)[None, :]
+        for h, half in enumerate(ACT_HALVES):
+            e = ent[:, h]
+            f = {k: e[:, :, i].copy() for i, k in enumerate(_ACT_FIELDS[:4])}
+            f["absmax"] = e[:, :, 4].copy().view(np.float32)
+            f["sumsq"] = e[:, :, 5].copy().view(np.float32)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rms = np.sqrt(f["sumsq"].astype(np.float64) / (f["n_rows"].astype(np.float64) * w))
+            f["rms"] = np.where((f["have"] == 1) & (f["n_rows"] > 0), rms, np.nan)
+            out[half] = f
+        return out
+
+    @staticmethod
+    def blame_of(arr, row_len, record=-1):
+        """the blame rule on decoded records: forward before gradient, forward order, reverse order for the gradients"""
+        n = len(arr["pass"])
+        if n == 0:
+            return None
+        r = range(n)[record]
+        S = len(arr["sites"])
+        for half, order in (("forward", range(S)), ("gradient", range(S - 1, -1, -1))):
+            f = arr[half]
+            for s in order:
+                if f["have"][r, s] == 1 and f["n_bad"][r, s] > 0:
+                    row, L = int(f["first_bad_row"][r, s]), row_len[s]
+                    if L is None or L < 1 or row < 0:
+                        sample = position = None
+                    else:
+                        sample, position = row // L, row % L
+                    return {"half": half, "site": arr["sites"][s], "sample": sample, "position": position, "n_bad": int(f["n_bad"][r, s])}
+        return None
+
+    def arrays(self):
+        return self.decode(self._small.cpu().numpy(), self.names, self.widths, self.capacity)
+
+    def blame(self, record=-1):
+        return self.blame_of(self.arrays(), self.row_len, record)
+
+    @property
+    def n_recorded(self):
+        return int(self._small[1].item())
+
+
+class _ActWatch:
+    def __init__(self, log):
+        self.log, self.prev = log, None
+
+    def __enter__(self):
+        from . import _ops
+        self.log._guard()
+        self.ctx = _ops.CTX
+        self.log.n_valid, self.log.open = None, [False, False]
+        self.prev, self.ctx.act_log = self.ctx.act_log, self.log
+        return self.log
+
+    def __exit__(self, *exc):
+        self.ctx.act_log, self.log.open = self.prev, [False, False]
+        return False
+
+
+class _ActPaused:
+    def __init__(self, log):
+        self.log, self.prev = log, True
+
+    def __enter__(self):
+        self.prev, self.log.recording = self.log.recording, False
+        return self.log
+
+    def __exit__(self, *exc):
+        self.log.recording = self.prev
+        return False
+
+
 def evaluate_packed(model, batches, loss_fn, stats, pad_to=None, step=None):
     """The reference's evaluate() bodies (train_fusion_seq_level_decoder.py:342-372, train_mosei_fusion_seq_level_decoder.py:432-495)
     on ragged batches: model.eval() under torch.no_grad(); for every data.collate_seq_packed batch (rows_a, lengths_a, rows_t,

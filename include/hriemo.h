@@ -620,6 +620,51 @@ int hriemo_health_sweep(const float* g, const float* p, const float* m, const fl
                         hriemo_stream_t stream);
 int hriemo_health_fold(const float* partial, const long long* chunks, int C, int P, const float* state, const int* ctl,
                        const float* grad_scale, int every, int capacity, int* log, hriemo_stream_t stream);
+/* Activation log in device memory (csrc/actlog.hip; train.ActivationLog): per-site statistics of the activations of a pass and of
+ * the gradients that arrive at them, written by the pass itself, so that a captured step can say in which sub-layer, sample and
+ * position a non-finite value first appeared.  S sites, two halves (0: forward, 1: gradient).  State, owned by the caller:
+ *   counters int32 [4]    {n_passes, n_recorded, 0, 0}; zeroed to reset
+ *   window   int32 [4]    {open, slot, pass, 0}: written by the plan, read by every probe and fold behind it
+ *   counts   int32 [2 S]  the chunk count of the latest probe of (half, site), at half * S + site
+ *   partial  fp32 [2 S][chunk_cap][8]  one row per chunk of hriemo_act_probe_rows() rows: {sumsq, absmax, n_bad (int32 bits),
+ *                         first_bad_row (int32 bits, -1: none), n_rows (int32 bits), 0, 0, 0}
+ *   ring     int32        `capacity` records of 4 + 16 S words: {pass, halves (bit 0: forward folded, bit 1: gradient folded), 0, 0},
+ *                         then for (half, site), at word 4 + (half * S + site) * 8: {have, n_rows, n_bad, first_bad_row,
+ *                         absmax (fp32 bits), sumsq (fp32 bits), 0, 0}; record r of the run lives in slot r % capacity
+ * hriemo_act_log_plan: ONE block, recorded once at the top of a pass, in front of every fork; the only writer of counters and
+ * window.  record = 0 (a warm-up pass): writes the closed window {0, 0, 0, 0} and touches nothing else.  record = 1: the pass is
+ * counted (pass = n_passes, n_passes += 1); if pass % every == 0 the window {1, n_recorded % capacity, pass, 0} opens, that record
+ * is cleared (every have 0, header {pass, 0, 0, 0}), counts is cleared and n_recorded += 1; otherwise the window closes.
+ * hriemo_act_probe: the sweep over one activation buffer x [n_rows, d] with leading dimension ld (dtype 0: bf16, 1: fp32), one
+ * block of 256 threads per chunk of rows.  A block that finds the window closed returns before its first load of x and before any
+ * barrier.  Which rows count, with nv = clamp(*n_valid, 1, B) (n_valid NULL: B):
+ *   cu_seqlens != NULL (packed rows, int32 [B + 1] or longer): row r counts iff it lies in a sequence b < nv of the B real ones,
+ *                         cu[b] <= r < cu[b + 1], at a position l = r - cu[b] < L; its index is b * L + l
+ *   otherwise (padded rows [B, L], n_rows <= B * L): row r = b * L + l counts iff b < nv and (kpm == NULL or kpm[r] == 0)
+ * so the filler sequence of a bucket plan, surplus rows behind the last sequence, PAD rows and the ghost utterances of a short
+ * batch never count and may hold anything.  Per chunk: sumsq = the sum of x^2 over the FINITE elements of the counted rows (fp32,
+ * fmaf, fixed order: per thread over its vectors tid, tid + 256, ... of the chunk element by element, the wave's xor butterfly,
+ * the four wave sums in index order), absmax over the same elements, n_bad = the number of NaN / +-Inf elements (exact),
+ * first_bad_row = the smallest index b * L + l of a counted row that holds one, n_rows = the counted rows.  Block 0 also stores
+ * the launch's chunk count.  d % 8 == 0 (bf16) or d % 4 == 0 (fp32) with ld likewise and x 16-byte aligned reads 16-byte vectors,
+ * anything else element by element.  Whatever cu_seqlens holds, x is read at rows below n_rows only.
+ * hriemo_act_log_fold: once per half, one block per site; returns if the window is closed.  Folds the site's chunk partials (sum,
+ * max, integer sums, min; fixed order: per thread over the chunks tid, tid + 256, ..., butterfly, four wave sums) and writes the
+ * site's entry of the open record with have = 1; a site whose chunk count is 0 keeps have = 0.  Thread 0 of site 0 writes the
+ * record's pass and sets the half's bit.  The slot is clamped into [0, capacity) and a chunk count into [0, chunk_cap] before
+ * they address anything.  No floating-point atomics anywhere: the same pass from the same state gives the same bits.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): record, half or dtype outside {0, 1}, every, capacity, n_sites,
+ * chunk_cap, B, L, n_rows or d < 1 (or above their limits), ld < d, B * L >= 2^31, site outside [0, n_sites), more chunks than
+ * chunk_cap, padded rows beyond B * L, cu_seqlens together with kpm, NULL or misaligned state pointers (16 bytes: counters,
+ * window, partial, ring; 4: counts, cu_seqlens, n_valid), state blocks that overlap each other or x. */
+int hriemo_act_probe_rows(void);
+int hriemo_act_log_plan(int record, int every, int capacity, int n_sites, int* counters, int* window, int* counts, int* ring,
+                        hriemo_stream_t stream);
+int hriemo_act_probe(const void* x, int dtype, int n_rows, int d, long ld, const int* cu_seqlens, const unsigned char* kpm, int B, int L,
+                     const int* n_valid, const int* window, int site, int half, int n_sites, int chunk_cap, float* partial, int* counts,
+                     hriemo_stream_t stream);
+int hriemo_act_log_fold(const float* partial, const int* counts, const int* window, int half, int n_sites, int chunk_cap, int capacity,
+                        int* ring, hriemo_stream_t stream);
 /* Launch-boundary reduce.  hriemo_add_ln_bwd with dgamma == NULL and hriemo_colsum_bf16 with out == NULL stop after
  * their per-block partial sums ([hriemo_add_ln_bwd_partial_rows(M,d)][3*d] resp. [hriemo_colsum_partial_rows(M,N)][N]
  * fp32 at the start of the caller's workspace); hriemo_colreduce_batch finishes any number of such jobs in one launch
