@@ -115,6 +115,10 @@ _SIGS = {
     "hriemo_adamw_flat_dev_avg": ("pppplppppp", "i"),
     "hriemo_adamw_flat_groups_avg": ("pppplppippippp", "i"),
     "hriemo_swap_fp32": ("pplp", "i"),
+    "hriemo_sumsq_units": ("plpipp", "i"),
+    "hriemo_optim_finalize_units": ("pippipipppppppp", "i"),
+    "hriemo_adamw_flat_units": ("pppplpppippipip", "i"),
+    "hriemo_adamw_flat_units_avg": ("pppplpppippipippp", "i"),
     "hriemo_health_sweep": ("pppplpippipipp", "i"),
     "hriemo_health_fold": ("ppiipppiipp", "i"),
     "hriemo_act_probe_rows": ("", "i"),

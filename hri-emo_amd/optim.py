@@ -165,6 +165,73 @@ def health_chunks(slots, chunk=HEALTH_CHUNK):
     return rows
 
 
+CLIP_MODES = ("global", "group", "parameter")     # DeviceAdamW(clip=...)
+
+
+def clip_units(buckets, param_groups, mode):
+    """The tables of the unit clip modes (``DeviceAdamW(clip="group" | "parameter")``: hriemo_sumsq_units,
+    hriemo_optim_finalize_units, hriemo_adamw_flat_units) for these groups over ``buckets.flat`` -- a dict of host integers:
+
+    * ``seg`` [S + 1], ``seg_group`` [S]: the segment table of the update kernel.  ``mode="group"``: ``group_segments``' table
+      (neighbours of one group merged).  ``mode="parameter"``: ONE segment per parameter slot, neighbours never merged.
+    * ``seg_unit`` [S]: the clip unit of every segment -- the group index, or the parameter's index in flat-buffer order.
+    * ``unit_group`` [U]: the group whose ``max_norm`` clips unit u.
+    * ``chunks``: rows ``(start, length, unit, group)`` -- every segment cut the way ``health_chunks`` cuts a slot (pieces of at
+      most 32768 elements, starts at 64-element boundaries), ordered by unit, then by start; every element of the flat buffer lies in
+      exactly one row.  ``unit_chunks`` [U + 1]: unit u owns rows ``unit_chunks[u] .. unit_chunks[u + 1] - 1``.
+
+    Pure host code: works on buckets in host memory.  ValueError (by name, before anything is allocated) for groups that do not
+    partition ``buckets.params``, more than 16 groups, a group without parameters, more than 2048 units or 2048 segments."""
+    if mode not in ("group", "parameter"):
+        raise ValueError(f"clip_units: mode={mode!r}; the unit modes are 'group' and 'parameter'")
+    groups = _materialise(param_groups)
+    owner = _group_of_params(buckets, groups)
+    for gi, g in enumerate(groups):
+        if not g["params"]:
+            raise ValueError(f"DeviceAdamW: param_groups[{gi}] holds no parameter: with clip={mode!r} it would be a clip unit of nothing")
+    n = buckets.flat.numel()
+    if mode == "group":
+        seg, seg_group = group_segments(buckets, groups)
+        seg_unit, unit_group = list(seg_group), list(range(len(groups)))
+    else:
+        order = sorted(buckets.params, key=lambda q: buckets._offsets[id(q)])
+        seg = [buckets._offsets[id(p)] for p in order] + [n]
+        seg_group = [owner[id(p)] for p in order]
+        seg_unit, unit_group = list(range(len(order))), list(seg_group)
+    S, U = len(seg_group), len(unit_group)
+    if U > MAX_SEGMENTS:
+        raise ValueError(f"DeviceAdamW: clip={mode!r} makes {U} clip units; the unit kernels take at most {MAX_SEGMENTS}")
+    if S > MAX_SEGMENTS:
+        raise ValueError(f"DeviceAdamW: the groups cut the flat buffer into {S} segments; the grouped update kernel takes at most "
+                         f"{MAX_SEGMENTS} (group neighbouring parameters together)")
+    chunks, unit_chunks = unit_chunk_table(seg, seg_unit, unit_group)
+    return {"seg": seg, "seg_group": seg_group, "seg_unit": seg_unit, "unit_group": unit_group, "chunks": chunks, "unit_chunks": unit_chunks}
+
+
+def unit_chunk_table(seg, seg_unit, unit_group):
+    """``(chunks, unit_chunks)`` of ``clip_units`` from a segment table: every segment cut by ``health_chunks``, the rows
+    ``(start, length, unit, group)`` ordered by unit, then by start.  The table addresses the gradient buffer, so it is checked
+    here, where it is built: the rows tile ``[0, seg[-1])`` exactly once, start and end at 64-element boundaries, hold at most
+    32768 elements, and every unit owns at least one row (ValueError otherwise)."""
+    S, U, n = len(seg_unit), len(unit_group), seg[-1]
+    if len(seg) != S + 1 or any(not 0 <= u < U for u in seg_unit):
+        raise ValueError(f"unit_chunk_table: {len(seg)} offsets for {S} segments, or a segment's unit outside 0 .. {U - 1}")
+    cut = health_chunks([(seg[s], seg[s + 1] - seg[s], seg_unit[s]) for s in range(S)])
+    chunks = sorted(((start, length, unit, unit_group[unit]) for start, length, _, unit in cut), key=lambda r: (r[2], r[0]))
+    unit_chunks = [0] * (U + 1)
+    for row in chunks:
+        unit_chunks[row[2] + 1] += 1
+    for u in range(U):
+        unit_chunks[u + 1] += unit_chunks[u]
+    covered = sorted((start, start + length) for start, length, _, _ in chunks)
+    if (covered[0][0] != 0 or covered[-1][1] != n or any(a[1] != b[0] for a, b in zip(covered, covered[1:]))
+            or any(start % 64 or length % 64 or not 0 < length <= HEALTH_CHUNK for start, length, _, _ in chunks)
+            or any(unit_chunks[u + 1] <= unit_chunks[u] for u in range(U))):
+        raise ValueError("unit_chunk_table: the chunks do not tile the flat buffer once, or a unit owns none (segments start at "
+                         "64-element boundaries, without gaps, and every unit owns a segment)")
+    return chunks, unit_chunks
+
+
 def decode_health(image, n_params, capacity):
     """One host image of the log's device buffer (int32 words, csrc/health.hip) -> the dict ``HealthLog.arrays()`` returns, without
     the names: the records still in the ring in chronological order, oldest first."""
@@ -321,6 +388,20 @@ class DeviceAdamW(torch.optim.Optimizer):
       global -- one norm over all groups, as ``clip_grad_norm_(model.parameters())`` -- and so are the skip decision, the step
       count and ``skipped``; a group that names another ``max_norm`` is refused.  ``LambdaLR(opt, [f0, f1])`` drives the groups.
       Without ``param_groups`` there is one group and the three single-group launches run, bit for bit as before.
+    * ``clip="global"`` (default) is that one clip.  ``clip="group"`` makes every param group a CLIP UNIT, clipped by its own norm
+      against its own ``max_norm`` (group key ``"max_norm"``; a missing key takes the constructor's, ``<= 0`` or ``None`` leaves the
+      group unclipped): ``for g in groups: clip_grad_norm_(g["params"], g["max_norm"])``.  ``clip="parameter"`` makes every
+      parameter tensor a unit, clipped against its group's ``max_norm``: ``clip_grad_norm_([p], g["max_norm"])`` per parameter.
+      Per unit ``norm_u = sqrt(sum g^2) / grad_scale`` and ``coef_u = (max_norm > 0 ? min(1, max_norm / (norm_u + 1e-6)) : 1) /
+      grad_scale``.  The step stays three launches (``hriemo_sumsq_units``, ``hriemo_optim_finalize_units``,
+      ``hriemo_adamw_flat_units``; tables from ``optim.clip_units``), eagerly and inside every captured step, with averaging, a
+      health log and ``GradScaler``, with or without ``param_groups``.  What stays global: the skip decision (any non-finite norm,
+      or ``found_inf``), the step count, ``skipped``, the hold of accumulation micro-steps and ``grad_norm`` -- the norm over
+      everything, formed as the fixed-order sum of the unit sums.  Word 2 of the state block (``coef``) holds the SMALLEST unit
+      coefficient in these modes.  ``clip_state[U][2]`` = ``norm_u, coef_u`` lives on the device: a real update writes both, a
+      skipped step the norms only (the non-finite unit shows without a health log), a held micro-step nothing;
+      ``opt.clip_arrays()`` reads it back once.  ``state_dict()`` gains a top-level ``"clip"`` key in the unit modes (a dict of
+      another mode is refused by name; a dict without the key -- ``torch.optim.AdamW``'s -- loads as ever).
     * A step whose gradient norm is not finite, or in which ``GradScaler`` found an inf, is SKIPPED on the device: parameters,
       moments and the step count stay bit-identical, ``skipped`` counts it.  ``max_norm=None`` disables the clip, not the norm.
     * ``GradScaler.step(opt)`` hands ``grad_scale`` / ``found_inf`` over as device tensors (``_step_supports_amp_scaling``):
@@ -356,9 +437,13 @@ class DeviceAdamW(torch.optim.Optimizer):
 
     _step_supports_amp_scaling = True          # GradScaler.step: set opt.grad_scale / opt.found_inf and call step() directly
 
-    def __init__(self, buckets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=5.0, *, param_groups=None,
-                 averaging=None, avg_decay=0.999, avg_start=0, avg_every=1, health=None):
+    def __init__(self, buckets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=5.0, *, clip="global",
+                 param_groups=None, averaging=None, avg_decay=0.999, avg_start=0, avg_every=1, health=None):
         flat_g = buckets.flat
+        if clip not in CLIP_MODES:
+            raise ValueError(f"DeviceAdamW: clip={clip!r}; the modes are 'global', 'group' and 'parameter'")
+        if clip != "global" and param_groups is None:
+            param_groups = [{"params": list(buckets.params)}]      # one group: its units share the constructor's max_norm
         self._check_averaging(averaging, avg_decay, avg_start, avg_every)
         if health is True:
             health = HealthLog()
@@ -370,17 +455,25 @@ class DeviceAdamW(torch.optim.Optimizer):
             _require_gpu(flat_g)
         self._check_scalars(lr, betas, eps, weight_decay, "")
         # every refusal comes before the first allocation and before any p.data moves
-        groups, seg, seg_group = None, None, None
+        groups, seg, seg_group, units = None, None, None, None
         if param_groups is not None:
             groups = _materialise(param_groups)          # generators are read here, once; everything below sees lists
-            seg, seg_group = group_segments(buckets, groups)
+            if clip == "global":
+                seg, seg_group = group_segments(buckets, groups)
+            else:
+                units = clip_units(buckets, groups, clip)
+                seg, seg_group = units["seg"], units["seg_group"]
             if len(seg_group) > MAX_SEGMENTS:
                 raise ValueError(f"DeviceAdamW: the groups cut the flat buffer into {len(seg_group)} segments; the grouped update "
                                  f"kernel takes at most {MAX_SEGMENTS} (group neighbouring parameters together)")
             for gi, g in enumerate(groups):
-                if "max_norm" in g and g["max_norm"] != max_norm:
+                if clip == "global" and "max_norm" in g and g["max_norm"] != max_norm:
                     raise ValueError(f"DeviceAdamW: param_groups[{gi}] names max_norm={g['max_norm']!r}, the optimizer {max_norm!r}: "
-                                     "the clip is global (one norm over all groups), per-group clipping is not built")
+                                     "the clip is global (one norm over all groups); clip='group' or clip='parameter' gives every "
+                                     "group its own max_norm")
+                mn = g.get("max_norm")
+                if clip != "global" and mn is not None and (isinstance(mn, bool) or not isinstance(mn, (int, float)) or mn != mn):
+                    raise ValueError(f"DeviceAdamW: param_groups[{gi}] names max_norm={mn!r}; a number (<= 0 or None: no clipping)")
                 self._check_scalars(g.get("lr", lr), g.get("betas", betas), g.get("eps", eps), g.get("weight_decay", weight_decay),
                                     f" (param_groups[{gi}])")
                 if "betas" in g:
@@ -394,7 +487,9 @@ class DeviceAdamW(torch.optim.Optimizer):
         self.m = torch.zeros_like(flat_g)
         self.v = torch.zeros_like(flat_g)
         self.nblocks = 1024
-        self._partial = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
+        self.clip = clip
+        # the unit modes keep one partial per chunk of their own table instead of one per block of the fixed grid
+        self._partial = torch.zeros(self.nblocks if units is None else len(units["chunks"]), dtype=torch.float32, device=dev)
         # G rows of 8 words each, kept flat: row 0 of _state is the single-group state block word for word
         self.averaging, self.avg_decay, self.avg_start, self.avg_every = averaging, avg_decay, avg_start, avg_every
         self._swapped = False                       # inside averaged_weights(): flat_p holds the average, avg the parameters
@@ -412,6 +507,16 @@ class DeviceAdamW(torch.optim.Optimizer):
         if self._grouped:
             self._seg = torch.tensor(seg, dtype=torch.int64, device=dev)
             self._seg_group = torch.tensor(seg_group, dtype=torch.int32, device=dev)
+        if units is not None:
+            # uploaded here, once; clip_state[U][2] = norm_u, coef_u is written by the finalize launch alone
+            self._seg_unit = torch.tensor(units["seg_unit"], dtype=torch.int32, device=dev)
+            self._unit_group = torch.tensor(units["unit_group"], dtype=torch.int32, device=dev)
+            self._unit_chunks = torch.tensor(units["unit_chunks"], dtype=torch.int32, device=dev)
+            self._chunks = torch.tensor(units["chunks"], dtype=torch.int64, device=dev)
+            self._unit_group_host = list(units["unit_group"])
+            self._clip_state = torch.zeros(2 * len(units["unit_group"]), dtype=torch.float32, device=dev)
+            self._clip_params = sorted(buckets.params, key=lambda q: buckets._offsets[id(q)])
+            self._clip_names = None
         # the group's keys are torch.optim.AdamW's (a state dict travels both ways) plus max_norm
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                         capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True, max_norm=max_norm)
@@ -482,7 +587,7 @@ class DeviceAdamW(torch.optim.Optimizer):
             if g["amsgrad"] or g["maximize"]:
                 raise RuntimeError("DeviceAdamW: amsgrad / maximize are not built; there is no fallback to torch.optim.AdamW")
             mn = g["max_norm"]
-            if mn != self.param_groups[0]["max_norm"]:
+            if self.clip == "global" and mn != self.param_groups[0]["max_norm"]:
                 raise RuntimeError("DeviceAdamW: the param groups carry different max_norm values; the clip is global")
             img += [float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                     float(mn) if mn else 0.0, 0.0, 0.0]
@@ -516,6 +621,22 @@ class DeviceAdamW(torch.optim.Optimizer):
         g = self.buckets.flat
         n = g.numel()
         st = _stream()
+        if self.clip != "global":
+            # the unit modes: per-chunk sums of squares, ONE finalize for plain / ctl / averaging, the update with per-unit coef
+            G, S, U, C = len(self.param_groups), self._seg_group.numel(), self._unit_group.numel(), self._partial.numel()
+            avg = self.averaging is not None
+            _lib.call("hriemo_sumsq_units", _p(g), n, _p(self._chunks), C, _p(self._partial), st)
+            _lib.call("hriemo_optim_finalize_units", _p(self._partial), C, _p(self._unit_chunks), _p(self._unit_group), U, _p(self._hyper), G,
+                      _p(grad_scale), _p(found_inf), _p(self._state), _p(ctl), _p(self._clip_state),
+                      _p(self._avg_hyper) if avg else None, _p(self._avg_state) if avg else None, st)
+            if avg:
+                _lib.call("hriemo_adamw_flat_units_avg", _p(self.flat_p), _p(g), _p(self.m), _p(self.v), n, _p(self._seg), _p(self._seg_group),
+                          _p(self._seg_unit), S, _p(self._hyper), _p(self._state), G, _p(self._clip_state), U, _p(self.avg),
+                          _p(self._avg_state), st)
+            else:
+                _lib.call("hriemo_adamw_flat_units", _p(self.flat_p), _p(g), _p(self.m), _p(self.v), n, _p(self._seg), _p(self._seg_group),
+                          _p(self._seg_unit), S, _p(self._hyper), _p(self._state), G, _p(self._clip_state), U, st)
+            return
         _lib.call("hriemo_sumsq_f32", _p(g), n, _p(self._partial), self.nblocks, st)
         if self.averaging is not None:
             G = len(self.param_groups)
@@ -566,6 +687,36 @@ class DeviceAdamW(torch.optim.Optimizer):
         """zeroes the flat gradient buffer; the gradients stay views into it whatever set_to_none says (the kernels and the
         optimizer address the flat buffer, a detached .grad would silently drop out of both)"""
         self.buckets.zero_grad()
+
+    # -- the clip units ---------------------------------------------------------------------------
+    def _require_units(self, what):
+        if self.clip == "global":
+            raise RuntimeError(f"DeviceAdamW.{what}: built with clip='global', there are no clip units (grad_norm is the one norm)")
+
+    def name_parameters(self, named_parameters):
+        """names for ``clip_arrays()["unit"]`` in parameter mode, from ``model.named_parameters()``: parameters the optimizer does
+        not own are ignored, a parameter of the optimizer that gets no name raises (nothing is changed then)"""
+        self._require_units("name_parameters()")
+        given = {id(p): name for name, p in named_parameters}
+        for i, p in enumerate(self._clip_params):
+            if id(p) not in given:
+                raise ValueError(f"DeviceAdamW.name_parameters: parameter {i} of the optimizer ({_describe(p)}) has no name")
+        self._clip_names = [given[id(p)] for p in self._clip_params]
+
+    def clip_arrays(self):
+        """ONE read-back of ``clip_state`` -> ``{"mode", "unit", "norm", "coef", "max_norm"}``: per clip unit the pre-clip, unscaled
+        gradient norm and the coefficient (``1 / grad_scale`` folded in) of the last real update -- after a skipped step ``norm`` is
+        that step's and ``coef`` still the last real update's -- and the ``max_norm`` of the unit's group as the host holds it.
+        ``unit``: the group indices in group mode; in parameter mode the names attached by ``name_parameters``, else the parameters'
+        indices in flat-buffer order."""
+        self._require_units("clip_arrays()")
+        img = self._clip_state.cpu().numpy().reshape(-1, 2)
+        if self.clip == "parameter" and self._clip_names is not None:
+            unit = list(self._clip_names)
+        else:
+            unit = list(range(img.shape[0]))
+        max_norm = [self.param_groups[gi]["max_norm"] for gi in self._unit_group_host]
+        return {"mode": self.clip, "unit": unit, "norm": img[:, 0].copy(), "coef": img[:, 1].copy(), "max_norm": max_norm}
 
     # -- the average ------------------------------------------------------------------------------
     def _require_averaging(self, what):
@@ -624,6 +775,8 @@ class DeviceAdamW(torch.optim.Optimizer):
             params = [p for g in self.param_groups for p in g["params"]]
             sd["averaging"] = {"mode": self.averaging, "decay": self.avg_decay, "start": self.avg_start, "every": self.avg_every,
                                "n_averaged": self._avg_state[0].clone(), "avg": {k: self._avg_view(p) for k, p in zip(keys, params)}}
+        if self.clip != "global":
+            sd["clip"] = {"mode": self.clip}        # the groups carry their max_norm; clip_state is a diagnostic and stays out
         return sd
 
     def _avg_view(self, p):
@@ -638,7 +791,8 @@ class DeviceAdamW(torch.optim.Optimizer):
         host attributes decay / start / every (another mode, other keys or other shapes are refused; so is any such block when this
         optimizer was built without averaging).  A dict WITHOUT one -- a torch optimizer's -- RESTARTS the average:
         ``n_averaged = 0`` and ``avg`` becomes a copy of the parameters as they are now.  So load the model first, then the
-        optimizer."""
+        optimizer.  The ``"clip"`` key: a dict that carries one must name this optimizer's ``clip`` mode (another mode is refused by
+        name); a dict without one loads in every mode, each group keeping the ``max_norm`` the dict gives it, or its own."""
         self._refuse_while_averaged("load_state_dict()")
         groups, state = state_dict["param_groups"], state_dict["state"]
         mine_groups = self.param_groups
@@ -649,7 +803,11 @@ class DeviceAdamW(torch.optim.Optimizer):
                              % (len(groups), [len(a["params"]) for a in groups], len(mine_groups), [len(b["params"]) for b in mine_groups]))
         if any(src.get("amsgrad") or src.get("maximize") for src in groups):
             raise ValueError("DeviceAdamW.load_state_dict: amsgrad / maximize states cannot be continued here")
-        if any("max_norm" in src and src["max_norm"] != groups[0].get("max_norm") for src in groups):
+        cl = state_dict.get("clip")
+        if cl is not None and cl.get("mode") != self.clip:
+            raise ValueError(f"DeviceAdamW.load_state_dict: the state dict was written with clip={cl.get('mode')!r}, this optimizer was "
+                             f"built with clip={self.clip!r}")
+        if self.clip == "global" and any("max_norm" in src and src["max_norm"] != groups[0].get("max_norm") for src in groups):
             raise ValueError("DeviceAdamW.load_state_dict: the groups carry different max_norm values; the clip is global")
         if len(state) not in (0, n_params):
             raise ValueError("DeviceAdamW.load_state_dict: state for %d of %d parameters" % (len(state), n_params))

@@ -584,6 +584,44 @@ int hriemo_adamw_flat_groups_avg(float* p, const float* g, float* m, float* v, l
                                  const float* hyper, const float* state, int G, float* avg, const float* avg_state,
                                  hriemo_stream_t stream);
 int hriemo_swap_fp32(float* a, float* b, long n, hriemo_stream_t stream);
+/* Per-group and per-parameter gradient clipping (DeviceAdamW(clip="group" | "parameter")): every CLIP UNIT -- a param group, or one
+ * parameter tensor -- is clipped by its own norm against its group's max_norm, hyper[g][5] of EVERY row (<= 0: that group's units
+ * are not clipped).  Still three launches: hriemo_sumsq_units -> hriemo_optim_finalize_units -> hriemo_adamw_flat_units(_avg).
+ *   chunks int64 [C][4] (host-written, once): {start, length, unit, group} -- the segments cut into pieces of at most 32768 elements
+ *                       (start a multiple of 64 elements, length a multiple of 64), rows ordered by unit, then by start; the
+ *                       kernels read start and length only.  1 <= C <= 2^20.
+ *   unit_chunks int32 [U+1]:   unit u owns the rows unit_chunks[u] .. unit_chunks[u+1]-1; unit_chunks[0] = 0, unit_chunks[U] = C.
+ *   unit_group int32 [U]:      the group in [0, G) whose max_norm clips unit u.  1 <= U <= 2048.
+ *   seg_unit int32 [S]:        the unit in [0, U) of segment s, beside seg / seg_group of the grouped update.
+ *   clip_state fp32 [U][2] (device-written): norm_u = sqrt(sum of g^2 over the unit) / grad_scale and
+ *                       coef_u = (max_norm_g > 0 ? min(1, max_norm_g / (norm_u + 1e-6)) : 1) / grad_scale.
+ * hriemo_sumsq_units: one block of 256 threads per chunk, partial[c] = the chunk's sum of squares in one fixed order (16-byte loads;
+ * per thread fmaf over its vectors in ascending order, the xor butterfly over the wave, the four wave sums in index order; no
+ * atomics).  Nothing is masked: a NaN / Inf element makes its chunk's partial NaN / Inf.  Rows are clamped into [0, n) before use.
+ * hriemo_optim_finalize_units is hriemo_optim_finalize_groups (ctl may be NULL; HOLD as there) and, with avg_hyper / avg_state given
+ * (both or neither), hriemo_optim_finalize_avg: one entry for every form.  It adds each unit's partials in ONE order that depends on
+ * the tables alone (lane l of a wave adds the unit's partials l, l + 64, ... ascending, then the xor butterfly), forms the global
+ * sum as the fixed-order sum of the unit sums, and decides the skip from it as before (any non-finite unit makes it non-finite).
+ * A real update writes both columns of clip_state and state[0][2] (coef) = the SMALLEST unit coefficient; a skipped step writes the
+ * norms only (which unit was not finite can be read without a health log); a held step writes no word of clip_state.  Everything
+ * else of state[G][8] is as hriemo_optim_finalize_groups leaves it.
+ * hriemo_adamw_flat_units / _avg are hriemo_adamw_flat_groups / _avg whose every 16-byte vector takes coef from clip_state of its
+ * segment's unit instead of state[0][2]: the same inline arithmetic, so a unit's elements equal hriemo_adamw_flat_dev run with the
+ * group's hyper row and a state block whose coef is coef_u, bit for bit.  LDS grows by 4 U + 2 S bytes.  seg_unit only selects a
+ * scalar and is clamped to [0, U).
+ * Refused besides what the grouped entries refuse: U outside 1..2048 (or U > S, U > C), C outside 1..2^20 or more chunks /
+ * segments than 16-byte vectors in n, NULL or misaligned chunks / unit_chunks / unit_group / seg_unit / clip_state / partial,
+ * partial or clip_state overlapping the buffers read beside them, one of avg_hyper / avg_state without the other. */
+int hriemo_sumsq_units(const float* g, long n, const long long* chunks, int C, float* partial, hriemo_stream_t stream);
+int hriemo_optim_finalize_units(const float* partial, int C, const int* unit_chunks, const int* unit_group, int U, const float* hyper,
+                                int G, const float* grad_scale, const float* found_inf, float* state, const int* ctl, float* clip_state,
+                                const float* avg_hyper, float* avg_state, hriemo_stream_t stream);
+int hriemo_adamw_flat_units(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group,
+                            const int* seg_unit, int S, const float* hyper, const float* state, int G, const float* clip_state, int U,
+                            hriemo_stream_t stream);
+int hriemo_adamw_flat_units_avg(float* p, const float* g, float* m, float* v, long n, const long long* seg, const int* seg_group,
+                                const int* seg_unit, int S, const float* hyper, const float* state, int G, const float* clip_state, int U,
+                                float* avg, const float* avg_state, hriemo_stream_t stream);
 /* The health log of the device-state optimizer (DeviceAdamW(health=HealthLog(capacity, every))): per-parameter statistics of a
  * step, written by two launches BEHIND the update kernel into a ring in device memory.  They only read g, p, m, v, hyper, state
  * and ctl; no existing launch changes.
