@@ -86,6 +86,7 @@ _SIGS = {
     "hriemo_ingest_rows": ("pilpiiiiipppplpp", "i"),
     "hriemo_seq_tables": ("ppiiiiippppppp", "i"),
     "hriemo_gather_rows": ("plppiplp", "i"),
+    "hriemo_gather_rows_aug": ("piippipllQIiIIiIIfp", "i"),
     "hriemo_dropout_bf16": ("pplifQpIlp", "i"),
     "hriemo_gemm_ln_supported": ("i", "i"),
     "hriemo_gemm_ln_fwd": ("iiiplplppppppppppffQpIlpp", "i"),

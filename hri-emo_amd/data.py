@@ -9,6 +9,7 @@ masks (True = PAD), plus what the reference leaves on the table (SURVEY.md 8f ra
   GEMM / LayerNorm / attention of the path) stays small.
 """
 import itertools
+import math
 import weakref
 
 import torch
@@ -91,6 +92,98 @@ def length_bucketed_batches(lengths, batch_size, shuffle=True, generator=None, b
         perm = torch.randperm(len(batches), generator=generator).tolist()
         batches = [batches[i] for i in perm]
     return batches
+
+
+class StoreAugment:
+    """Seeded train-time augmentation of the rows a ``DeviceFeatureStore`` hands to a TRAINER step, applied inside the gather
+    (hriemo_gather_rows_aug, csrc/store.hip): no buffer, no upload, nothing inside the captured graphs changes.
+
+    ``time_mask=dict(spans=1..4, max_width=W >= 1, max_frac=0 < f <= 1)`` (one dict for both modalities, or a pair (audio, text)
+    whose entries may be None): per utterance `spans` spans of rows become zero, each of a width uniform in [0, min(W, f * L)] at
+    a uniform place (SpecAugment's time mask on frames).  ``noise_std=(sigma_a, sigma_t)``: zero-mean noise of that standard
+    deviation is added to every kept element (a sum of four 8-bit uniforms: bounded by 3.45 sigma).  ``modality_drop=(p_a, p_t)``:
+    with probability p_a an utterance's audio rows are all zero, with p_t its text rows -- never both (one draw decides), so
+    p_a + p_t < 1.  Noise first, then the zeros.
+
+    Everything is a function of (seed, draw, modality, the utterance's id in the store, row, column) through the counter hash of
+    csrc/common.h: not of the batch an utterance is in, its position there, or the data-parallel shard that holds it
+    (tests/augment_reference.py is the host replica).  ``draw`` is a host int that starts at 0: ``step_store`` uses it and adds one
+    per accepted call (every micro-step of an accumulation group is a draw of its own); ``fetch`` reads it and never advances it.
+    A caller that resumes sets it, e.g. ``aug.draw = epoch * steps_per_epoch + step``.  Data parallel: every rank constructs the same
+    object and steps in lockstep -- ``seed`` and ``draw`` MUST agree across ranks; then a sample's augmentation does not depend
+    on which rank holds it.  Evaluation is never augmented: EvalStep and train.evaluate_store take no augment."""
+
+    NOISE_VAR = 21845.0              # variance of the sum of four uniform bytes: 4 * (256^2 - 1) / 12
+
+    def __init__(self, seed, time_mask=None, noise_std=None, modality_drop=None):
+        seed = int(seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError(f"StoreAugment: seed {seed} (an unsigned 64-bit integer)")
+        if time_mask is None or isinstance(time_mask, dict):
+            time_mask = (time_mask, time_mask)
+        if len(time_mask) != 2:
+            raise ValueError("StoreAugment: time_mask is one dict(spans=, max_width=, max_frac=) or a pair (audio, text) of them")
+        masks = []
+        for name, tm in zip(("audio", "text"), time_mask):
+            if tm is None:
+                masks.append((0, 0, 0.0))
+                continue
+            if not isinstance(tm, dict) or set(tm) != {"spans", "max_width", "max_frac"}:
+                raise ValueError(f"StoreAugment: time_mask ({name}) is dict(spans=, max_width=, max_frac=)")
+            spans, width, frac = tm["spans"], tm["max_width"], float(tm["max_frac"])
+            if int(spans) != spans or not 1 <= spans <= 4:
+                raise ValueError(f"StoreAugment: time_mask ({name}) spans = {spans!r} (1 .. 4)")
+            if int(width) != width or not 1 <= width < 1 << 31:
+                raise ValueError(f"StoreAugment: time_mask ({name}) max_width = {width!r} (an integer >= 1)")
+            if not 0.0 < frac <= 1.0:
+                raise ValueError(f"StoreAugment: time_mask ({name}) max_frac = {frac!r} (0 < max_frac <= 1)")
+            masks.append((int(spans), int(width), frac))
+        sigma = (0.0, 0.0) if noise_std is None else tuple(float(v) for v in noise_std)
+        if len(sigma) != 2 or not all(0.0 <= v < float("inf") for v in sigma):
+            raise ValueError(f"StoreAugment: noise_std = {noise_std!r} (a pair (audio, text) of finite sigma >= 0)")
+        drop = (0.0, 0.0) if modality_drop is None else tuple(float(v) for v in modality_drop)
+        if len(drop) != 2 or not all(v >= 0.0 for v in drop) or not drop[0] + drop[1] < 1.0:
+            raise ValueError(f"StoreAugment: modality_drop = {modality_drop!r} (a pair p_a, p_t >= 0 with p_a + p_t < 1)")
+        if not any(m[0] for m in masks) and not any(sigma) and not any(drop):
+            raise ValueError("StoreAugment: no transform is enabled (time_mask, noise_std and modality_drop are all off): "
+                             "an augment that does nothing is refused; pass augment=None")
+        self.seed, self.draw = seed, 0
+        self.time_mask, self.noise_std, self.modality_drop = tuple(masks), sigma, drop
+
+    @staticmethod
+    def _thr16(p):
+        """round(p * 65536) in [0, 65535], as make_drop (csrc/common.h) counts a dropout rate"""
+        return max(0, min(65535, int(p * 65536.0 + 0.5)))
+
+    def config(self):
+        """the configuration as plain Python values (what state_dict carries beside seed and draw)"""
+        return {"time_mask": [list(m) for m in self.time_mask], "noise_std": list(self.noise_std), "modality_drop": list(self.modality_drop)}
+
+    def state_dict(self):
+        return {"seed": self.seed, "draw": self.draw, "config": self.config()}
+
+    def load_state_dict(self, state):
+        """seed and draw of a saved run; a dict saved from another configuration is refused (ValueError), nothing is changed then"""
+        if state.get("config") != self.config():
+            raise ValueError(f"StoreAugment.load_state_dict: the state was saved with another configuration ({state.get('config')!r}; "
+                             f"this object has {self.config()!r})")
+        seed, draw = int(state["seed"]), int(state["draw"])
+        if seed < 0 or seed >= 1 << 64 or draw < 0:
+            raise ValueError(f"StoreAugment.load_state_dict: seed {seed}, draw {draw}")
+        self.seed, self.draw = seed, draw
+
+    def launch_args(self, which, draw=None):
+        """the scalar arguments of hriemo_gather_rows_aug behind max_rows for the audio (which = 0) or the text (1) launch:
+        (seed, draw, modality, thr_lo, thr_hi, spans, max_width, frac16, noise_scale); the draw is taken modulo 2^32"""
+        draw = self.draw if draw is None else int(draw)
+        if draw < 0:
+            raise ValueError(f"StoreAugment: draw = {draw} (a counter >= 0)")
+        thr_a, thr_t = self._thr16(self.modality_drop[0]), self._thr16(self.modality_drop[1])
+        lo, hi = ((0, thr_a), (thr_a, thr_a + thr_t))[which]
+        spans, width, frac = self.time_mask[which]
+        frac16 = min(65536, int(frac * 65536.0 + 0.5))
+        scale = torch.tensor(self.noise_std[which] / math.sqrt(self.NOISE_VAR), dtype=torch.float64).float().item()      # fp32(sigma / sqrt(var))
+        return (self.seed, draw & 0xFFFFFFFF, which + 1, lo, hi, spans, min(width, 0xFFFFFFFF), frac16, scale)
 
 
 class DeviceFeatureStore:
@@ -248,11 +341,27 @@ class DeviceFeatureStore:
             words += ids + list(itertools.accumulate(lens, initial=0)) + [0] * (stride - 2 * n - 1)
         return words
 
-    def gather_into(self, plan_dev, stride, n, dst_a, rows_a, dst_t, rows_t, dst_y):
+    _DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+    def _check_augment(self, who, augment):
+        """the refusals of an augment, before anything is allocated or enqueued"""
+        if not isinstance(augment, StoreAugment):
+            raise TypeError(f"{who}: augment is a data.StoreAugment (or None)")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{who}: augment= on a store that lives on {self.device}: the augmentation is part of the gather kernel "
+                               "(hriemo_gather_rows_aug) and has no CPU fallback; the lengths do not change, so the host needs nothing from it")
+        if max(self.pad_to) >= 65536:
+            raise ValueError(f"{who}: augment= on a store with an utterance of {max(self.pad_to)} rows (the span arithmetic is 16-bit: < 65536)")
+
+    def gather_into(self, plan_dev, stride, n, dst_a, rows_a, dst_t, rows_t, dst_y, augment=None, draw=None):
         """The batch of a plan block on the device (plan_words(ids, stride), n = len(ids)) into three destinations on the current
         stream: rows 0 .. rows_a of dst_a and 0 .. rows_t of dst_t (the batch's rows, zeros behind them), the first n rows of dst_y
-        (None: no targets wanted).  One hriemo_gather_rows launch each; no allocation, no synchronisation."""
+        (None: no targets wanted).  One hriemo_gather_rows launch each; no allocation, no synchronisation.  augment (a
+        StoreAugment; draw None: its own counter, which is never advanced here): the audio and the text rows go through
+        hriemo_gather_rows_aug instead, the targets stay with the plain kernel."""
         from . import _lib
+        if augment is not None:
+            self._check_augment("DeviceFeatureStore.gather_into", augment)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         base = plan_dev.data_ptr()
         for p, (src, off, dst, rows) in enumerate(((self.rows_a, self.off_a, dst_a, rows_a), (self.rows_t, self.off_t, dst_t, rows_t),
@@ -263,15 +372,22 @@ class DeviceFeatureStore:
             if dst.dtype != src.dtype or dst[0].numel() * dst.element_size() != row_bytes or dst.shape[0] < rows or not dst.is_contiguous():
                 raise ValueError(f"DeviceFeatureStore.gather_into: destination {tuple(dst.shape)} / {dst.dtype} for {rows} rows of "
                                  f"{tuple(src.shape[1:])} / {src.dtype}")
+            if augment is not None and p < 2:
+                _lib.call("hriemo_gather_rows_aug", src.data_ptr(), src[0].numel(), self._DTYPE_CODES[src.dtype], off.data_ptr(),
+                          base + 4 * p * stride, n, dst.data_ptr(), rows, self.pad_to[p], *augment.launch_args(p, draw), stream)
+                continue
             _lib.call("hriemo_gather_rows", src.data_ptr(), row_bytes, off.data_ptr(), base + 4 * p * stride, n, dst.data_ptr(), rows, stream)
 
     # ---- batches
-    def fetch(self, ids):
+    def fetch(self, ids, augment=None, draw=None):
         """-> (rows_a, lengths_a, rows_t, lengths_t, y): exactly what collate_seq_packed gives for the samples `ids` (after the
         store's mask / sanitise / crop / cast), as fresh tensors with rows and targets on the store's device.  The two lengths
         tensors stay int64 HOST tensors, as the collate makes them: every consumer (forward_packed, step_packed, eval_packed) wants
         them on the host and refuses device lengths.  On a GPU the rows come through hriemo_gather_rows, on a CPU device through
-        torch indexing."""
+        torch indexing.  augment (a StoreAugment): the rows as a trainer step with that augment sees them at `draw` (None:
+        ``augment.draw``, which fetch never advances); GPU stores only (RuntimeError on a CPU device)."""
+        if augment is not None:
+            self._check_augment("DeviceFeatureStore.fetch", augment)
         ids = self.check_ids(ids)
         la, lt = [self.lengths_a[i] for i in ids], [self.lengths_t[i] for i in ids]
         len_a, len_t = torch.tensor(la, dtype=torch.int64), torch.tensor(lt, dtype=torch.int64)
@@ -285,7 +401,7 @@ class DeviceFeatureStore:
         y = torch.empty((n,) + tuple(self.y.shape[1:]), dtype=self.y.dtype, device=self.device)
         stride = 2 * n + 1
         plan = torch.tensor(self.plan_words(ids, stride), dtype=torch.int32).to(self.device)
-        self.gather_into(plan, stride, n, rows_a, rows_a.shape[0], rows_t, rows_t.shape[0], y)
+        self.gather_into(plan, stride, n, rows_a, rows_a.shape[0], rows_t, rows_t.shape[0], y, augment, draw)
         return rows_a[:na], len_a, rows_t[:nt], len_t, y
 
     def batches(self, batch_size, shuffle=True, generator=None, bucket_mult=50):

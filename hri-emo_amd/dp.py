@@ -475,11 +475,13 @@ class _StoreFeed:
     capture, and the plan block -- int32 [3, 2B + 1]: {ids[n], dst_cu[n + 1]} for the audio rows, the text rows and the targets, zero
     padded -- with its pinned twin (_HostBlock), uploaded once per batch.  The gather itself is three eager launches on the step's
     stream in front of the replay; the captured graphs do not know where their static rows came from.  While the feed is alive the
-    store refuses append()."""
-    __slots__ = ("store", "version", "B", "pad", "stride", "block", "__weakref__")
+    store refuses append().  augment: the data.StoreAugment of a trainer step (None: the plain gather, always so for an evaluation);
+    every fill gathers at ``augment.draw`` as it stands, the step that owns the feed advances it."""
+    __slots__ = ("store", "version", "B", "pad", "stride", "block", "augment", "__weakref__")
 
-    def __init__(self, store, B, pad, device):
+    def __init__(self, store, B, pad, device, augment=None):
         self.store, self.version, self.B, self.pad = store, store.version, int(B), (int(pad[0]), int(pad[1]))
+        self.augment = augment
         self.stride = 2 * self.B + 1
         self.block = _HostBlock([0] * (3 * self.stride), device)
         store._holders.add(self)
@@ -503,7 +505,8 @@ class _StoreFeed:
         the head of each source and zeros up to the bucket's end in the same launch, the targets into the first n rows of y"""
         def fill(static, n_utt, own, key):
             self.block.upload(self.store.plan_words(ids, self.stride))
-            self.store.gather_into(self.block.dev, self.stride, n_utt, static[0], key[0], static[1], key[1], static[4] if targets else None)
+            self.store.gather_into(self.block.dev, self.stride, n_utt, static[0], key[0], static[1], key[1], static[4] if targets else None,
+                                   self.augment)
         return fill
 
 
@@ -659,7 +662,7 @@ class _RaggedStep:
         y_static = torch.zeros((len(ids),) + tuple(store.y.shape[1:]), dtype=store.y.dtype, device=dev) if targets else None
         return ids, la, lt, (La, Lt), y_static
 
-    def _capture_ragged(self, begin, widths, dtype, y_static, la, lt, pad, load, store=None, partial=True, accum=1, ctl=True):
+    def _capture_ragged(self, begin, widths, dtype, y_static, la, lt, pad, load, store=None, partial=True, accum=1, ctl=True, augment=None):
         """What every capture from ragged batches does behind its entry's checks: begin() -- the old step goes (behind the refusals
         that need it untouched) and the subclass's facts of the new one are set --, the static state is built (_ragged_state), a
         step that reads `store` gets its _StoreFeed (made after the old step and its feed have gone), the first batch is loaded by
@@ -670,7 +673,7 @@ class _RaggedStep:
         self._pb, self._static = _ragged_state(self.model, len(la), pad, widths, dtype, y_static, partial, accum, ctl)
         try:
             if store is not None:
-                self._feed = _StoreFeed(store, len(la), pad, self._static[0].device)
+                self._feed = _StoreFeed(store, len(la), pad, self._static[0].device, augment)
             self._packed_graph(load())
         except BaseException:
             self.release_graph()          # a failed capture leaves no graph behind -- and no feed that would keep the store from growing
@@ -995,7 +998,7 @@ class DataParallelStep(_RaggedStep):
         self._micro = 0
 
     @_in_step_context
-    def capture_store(self, store, ids, pad_to=None, optimizer=None, collectives=False, partial_batches=False, grad_accum=1):
+    def capture_store(self, store, ids, pad_to=None, optimizer=None, collectives=False, partial_batches=False, grad_accum=1, augment=None):
         """capture_packed() for batches that are lists of utterance ids of a ``data.DeviceFeatureStore`` on this step's device: the
         batch `ids` fixes B, pad_to = (L_a, L_t) defaults to ``store.pad_to`` (the store's longest utterances).  Everything behind the
         static row sources is capture_packed unchanged -- bucket graphs and their LRU cap, ghosts and the control block
@@ -1006,12 +1009,20 @@ class DataParallelStep(_RaggedStep):
         step's stream in front of the replay; the kernel writes the zero tail up to the bucket's end as well.  No row crosses
         PCIe, nothing is read back, no device memory is allocated.
         While the step is captured the store refuses ``append``.  Data parallel: every rank holds the whole store (a few GB) and
-        passes ITS slice of the global batch's ids (``shard_bounds``); ``set_batch_offset`` / ``set_global_batch`` are untouched."""
+        passes ITS slice of the global batch's ids (``shard_bounds``); ``set_batch_offset`` / ``set_global_batch`` are untouched.
+
+        augment (a ``data.StoreAugment``): the audio and text gathers of every ``step_store`` become hriemo_gather_rows_aug launches
+        -- time masks, noise, modality dropout, all seeded by (augment.seed, augment.draw, store id) -- and nothing else changes: the
+        graphs, the plan block and the targets gather are the same.  The warm-up and capture fills here use ``augment.draw`` as it
+        stands and leave it alone.  Every rank passes an augment with the same seed and keeps the same draw (lockstep); a sample's
+        augmentation then does not depend on the rank that holds it.  Evaluation takes no augment."""
         self._check_ragged_capture("capture_store", partial_batches, grad_accum)
         ids, la, lt, pad, y_static = self._store_capture("capture_store", store, ids, pad_to)
+        if augment is not None:
+            store._check_augment("capture_store", augment)
         self._capture_ragged(lambda: self._begin_ragged("capture_store", optimizer, collectives), store.widths, store.dtype, y_static, la, lt,
                              pad, lambda: self._load_store(ids, la, lt), store, partial=partial_batches, accum=grad_accum,
-                             ctl=partial_batches or grad_accum > 1)
+                             ctl=partial_batches or grad_accum > 1, augment=augment)
         self._end_capture()
 
     @_in_step_context
@@ -1023,15 +1034,23 @@ class DataParallelStep(_RaggedStep):
         inside it, n <= B (n == B without partial_batches), lengths inside pad_to (ValueError) -- and nothing is enqueued when one
         fails.  Then: plan block up, at most three hriemo_gather_rows launches, lengths (and control) block up, replay.  After
         use_graph(False) this is the eager step_packed on ``store.fetch(ids)``.  Micro-steps, flush_accumulated() and the
-        optimizer in the graph behave as after capture_packed."""
+        optimizer in the graph behave as after capture_packed.
+        After capture_store(augment=aug) the rows are gathered with ``draw = aug.draw`` -- captured, or eager through
+        ``store.fetch(ids, augment=aug)``: both see identical rows -- and ``aug.draw`` goes up by one per call that got through (every
+        micro-step is a draw of its own); a refused call leaves it alone.  Ghost utterances are not in the plan and stay zero rows."""
         feed = self._feed
         if feed is None or self._pb is None or self._pb.front is None:
             raise RuntimeError("step_store needs capture_store() first")
         ids, la, lt = feed.batch(ids, self._pb.front.partial or not self._replaying, "step_store")
+        aug = feed.augment
         if self._replaying:
-            return self._replay_ragged(lambda ctl: self._load_store(ids, la, lt, ctl=ctl))
-        rows_a, _, rows_t, _, y = feed.store.fetch(ids)
-        return self._eager_ragged(rows_a, rows_t, la, lt, y)
+            loss = self._replay_ragged(lambda ctl: self._load_store(ids, la, lt, ctl=ctl))
+        else:
+            rows_a, _, rows_t, _, y = feed.store.fetch(ids, augment=aug)
+            loss = self._eager_ragged(rows_a, rows_t, la, lt, y)
+        if aug is not None:
+            aug.draw += 1
+        return loss
 
     @_in_step_context
     def step_packed(self, rows_a, rows_t, lengths_a, lengths_t, y):

@@ -317,6 +317,28 @@ int hriemo_seq_tables(const int* lengths_a, const int* lengths_t, int B, int La,
  * plan that is not 4-byte or offsets that are not 8-byte aligned. */
 int hriemo_gather_rows(const void* store, long row_bytes, const long long* offsets, const int* plan, int n, void* dst, long dst_rows,
                        hriemo_stream_t stream);
+/* hriemo_gather_rows with seeded train-time augmentation of the rows it moves (data.StoreAugment): same store / offsets / plan /
+ * dst / zero tail / clamps, but typed: rows of row_elems elements of dtype (0 fp32, 1 bf16, 2 fp16), store and dst aligned to the
+ * element.  max_rows: the host's bound on the rows of any utterance of the store (the kernel cannot read it without a round trip).
+ * Everything random is the counter hash of csrc/common.h keyed by the utterance's STORE id u = ids[i], so it depends neither on the
+ * batch's composition nor on the data-parallel shard; L = the utterance's rows, AUG_SITE = 0x41554700:
+ *   ku = fmix32(site_key(seed, AUG_SITE + modality, draw) + u * DROP_CA), modality 1 = audio, 2 = text;
+ *   modality drop: rd = fmix32(site_key(seed, AUG_SITE, draw) + u * DROP_CA) & 0xffff: all rows of the utterance are zero iff
+ *     thr_lo <= rd < thr_hi (audio launch [0, thr_a), text launch [thr_a, thr_a + thr_t): never both);
+ *   time spans j = 0 .. spans-1: h = fmix32(ku + (j+1) * DROP_CB), W = min(max_width, (L * frac16) >> 16),
+ *     w = ((h & 0xffff) * (W+1)) >> 16, s = ((h >> 16) * (L - w + 1)) >> 16: rows [s, s+w) are zero;
+ *   noise (noise_scale != 0): element (r, c) of the utterance: h = mix24(fmix32(ku + 0x27d4eb2f) + r * DROP_CA + c * DROP_CB),
+ *     k = sum of the four bytes of h - 510 (mean 0, variance 21845), out = rne_dtype(x + noise_scale * k) with the product and the
+ *     sum each rounded to fp32 (no FMA).  The caller passes noise_scale = sigma / sqrt(21845).
+ * Noise first, then the zeros (+0.0 bits; masked rows are not read).  With noise_scale == 0 kept elements are bit copies.
+ * Refused (non-zero, hriemo_last_error set, nothing launched): a null pointer; n < 1 or n > 512; a dtype code outside 0..2;
+ * row_elems outside 1..65535; dst_rows < 1; max_rows >= 65536; modality outside {1, 2}; thr_lo > thr_hi or thr_hi > 65536;
+ * spans outside 0..4; frac16 > 65536; a negative or non-finite noise_scale; a plan that is not 4-byte or offsets that are not
+ * 8-byte aligned; store or dst not aligned to the element. */
+int hriemo_gather_rows_aug(const void* store, int row_elems, int dtype, const long long* offsets, const int* plan, int n, void* dst,
+                           long dst_rows, long max_rows, unsigned long long seed, unsigned draw, int modality, unsigned thr_lo,
+                           unsigned thr_hi, int spans, unsigned max_width, unsigned frac16, float noise_scale,
+                           hriemo_stream_t stream);
 long hriemo_add_ln_bwd_workspace_bytes(int M, int d);
 int hriemo_add_ln_bwd(const void* dY, const void* G, const void* X, const float* X32, const float* gamma, const float* mean,
                       const float* rstd, void* dX, void* dG, float* dgamma, float* dbeta, float* dbias, int accumulate,
