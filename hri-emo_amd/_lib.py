@@ -143,6 +143,8 @@ _SIGS = {
     "hriemo_stats_counts": ("ppiippipp", "i"),
     "hriemo_stats_auc_tiles": ("i", "i"),
     "hriemo_stats_auc": ("ppiipppp", "i"),
+    "hriemo_stats_rank": ("ppiippp", "i"),
+    "hriemo_stats_confusion": ("pppipiipp", "i"),
     "hriemo_scalar_gate_dx":("pipippppiiip", "i"),
     "hriemo_fuse_bwd_dw": ("ppppiiip", "i"),
     "hriemo_gate_dpre": ("pippp" + "iip", "i"),

@@ -6,6 +6,11 @@
 //                         samples to the epoch's log, adds to the sums and counters
 //   hriemo_stats_counts   tp / fp / fn per class and threshold over the log                     (once per epoch)
 //   hriemo_stats_auc      2 [p_i > p_j] + [p_i == p_j] over all (positive i, negative j) pairs   (once per epoch, the O(N^2) part)
+//   hriemo_stats_rank     per logged sample the number of positives / negatives with p_j >= p_i: average precision, PR and ROC
+//                         curves of the reference's reporting layer (tools/mosei_export_per_class_metrics.py,
+//                         scripts/infer/mosei_plot_metrics.py) from integers                    (on demand, O(N^2) as well)
+//   hriemo_stats_confusion  one block behind hriemo_stats_update of a single-label step: the confusion matrix of the epoch
+//                         (macro / weighted F1, recall per class: train_text_baseline.py:59-61, linear_probe_baseline.py:132-133)
 // and the products of the reference's inference driver (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy):
 //   hriemo_predict_log    one block behind the forward of a (captured) evaluation step: appends the batch's probabilities (sigmoid
 //                         or softmax), its per-sample mean beta and -- single-label -- its argmax to a log that needs no targets
@@ -337,6 +342,92 @@ __global__ __launch_bounds__(256) void stats_auc_kernel(const float* __restrict_
   }
 }
 
+// The ranks of one class: for entry i < n, rank[c, 0, i] = #{j < n : truth_j != 0, p_j >= p_i} and rank[c, 1, i] the same over
+// truth_j == 0 (entry i counts itself in its own plane).  Grid (ceil(capacity / 256), C): a thread owns entry i, the block walks
+// every j through LDS 256 at a time as stats_auc_kernel does -- the positives in one array, the negatives in the other, NaN where
+// the entry is of the other kind (both comparisons with NaN are false; a NaN p_i gets 0 / 0).  Entries at or past the cursor are
+// never read.  Two uint32 per thread (<= capacity), ordinary stores of the thread's own two results, no atomics; elements at or
+// past n are stored as 0, so every element of rank is written by every launch.  A block wholly past the cursor stores its zeros
+// and leaves before the first barrier.
+__global__ __launch_bounds__(256) void stats_rank_kernel(const float* __restrict__ probs, const unsigned char* __restrict__ truth,
+                                                         int capacity, const int* __restrict__ counters, int* __restrict__ rank) {
+  __shared__ float qp[AUC_TILE];
+  __shared__ float qn[AUC_TILE];
+  const int n = min(max(counters[SC_CURSOR], 0), capacity);
+  const int c = blockIdx.y;
+  const int i = blockIdx.x * AUC_TILE + threadIdx.x;
+  int* r_pos = rank + (long)c * 2 * capacity;
+  int* r_neg = r_pos + capacity;
+  if ((int)blockIdx.x * AUC_TILE >= n) {
+    if (i < capacity) {
+      r_pos[i] = 0;
+      r_neg[i] = 0;
+    }
+    return;
+  }
+  const float* pc = probs + (long)c * capacity;
+  const unsigned char* tc = truth + (long)c * capacity;
+  const float pi = i < n ? pc[i] : __builtin_nanf("");
+  unsigned int ge_pos = 0, ge_neg = 0;
+  for (int j0 = 0; j0 < n; j0 += AUC_TILE) {
+    const int j = j0 + threadIdx.x;
+    float vp = __builtin_nanf(""), vn = __builtin_nanf("");
+    if (j < n) {
+      const float v = pc[j];
+      if (tc[j] != 0) vp = v;
+      else vn = v;
+    }
+    __syncthreads();                                 // the previous chunk has been read
+    qp[threadIdx.x] = vp;
+    qn[threadIdx.x] = vn;
+    __syncthreads();
+    const int m = min(AUC_TILE, n - j0);
+    for (int k = 0; k < m; ++k) {
+      ge_pos += qp[k] >= pi ? 1u : 0u;
+      ge_neg += qn[k] >= pi ? 1u : 0u;
+    }
+  }
+  if (i < capacity) {
+    r_pos[i] = i < n ? (int)ge_pos : 0;
+    r_neg[i] = i < n ? (int)ge_neg : 0;
+  }
+}
+
+// cm[C * C + 2] (int32) of one epoch: the confusion matrix, rows = label, columns = prediction, then {n_ignored, n_bad}
+#define CONFUSION_MAX_CLASSES 64
+#define CONFUSION_IGNORE (-100LL)
+
+// One block of 256 behind stats_update_kernel<true> of the same step: the only writer of cm (stream order), so the final adds are
+// ordinary read-modify-writes by one thread per cell.  The same nv, the same skip on a non-finite loss, the same first-maximum
+// rule (a NaN counts as maximal).  The block's counts are formed in LDS with integer atomics -- integer sums do not depend on the
+// order -- and then added to cm in cell order.  A label outside [0, C) indexes nothing: -100 (the criterion's ignore_index) counts
+// in cm[C * C], anything else in cm[C * C + 1].
+__global__ __launch_bounds__(256) void stats_confusion_kernel(const float* __restrict__ x, const long long* __restrict__ label,
+                                                              const float* __restrict__ loss, int skip_nonfinite,
+                                                              const int* __restrict__ n_valid, int B, int C, int* __restrict__ cm) {
+  __shared__ int acc[CONFUSION_MAX_CLASSES * CONFUSION_MAX_CLASSES + 2];
+  if (skip_nonfinite && !isfinite(loss[0])) return;  // block-uniform: in front of every barrier
+  const int nv = n_valid != nullptr ? min(max(n_valid[0], 1), B) : B;
+  const int cells = C * C + 2;
+  for (int k = threadIdx.x; k < cells; k += 256) acc[k] = 0;
+  __syncthreads();
+  for (int b = threadIdx.x; b < nv; b += 256) {
+    const float* xr = x + (long)b * C;
+    int best = 0;
+    float bv = xr[0];
+    for (int c = 1; c < C; ++c) {
+      const float v = xr[c];
+      if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
+    }
+    const long long lab = label[b];
+    const int cell = (lab >= 0 && lab < (long long)C) ? (int)lab * C + best : (lab == CONFUSION_IGNORE ? C * C : C * C + 1);
+    atomicAdd(&acc[cell], 1);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < cells; k += 256)
+    if (acc[k] != 0) cm[k] += acc[k];
+}
+
 extern "C" int hriemo_stats_update(const float* logits, const float* targets, const long long* labels, const float* loss, float loss_scale,
                                    const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int skip_nonfinite,
                                    float* probs, unsigned char* truth, int capacity, int* counters, double* sums, hipStream_t st) {
@@ -429,5 +520,26 @@ extern "C" int hriemo_stats_auc(const float* probs, const unsigned char* truth, 
   HRIEMO_CHECK(C <= 65535 && ((uintptr_t)partial % 8) == 0, "stats_auc: %d classes / partial not 8-byte aligned", C);
   hipLaunchKernelGGL(stats_auc_kernel, dim3(hriemo_stats_auc_tiles(capacity), C), dim3(256), 0, st, probs, truth, capacity, counters, partial, npn);
   HRIEMO_LAUNCH_CHECK("stats_auc_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_stats_rank(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters, int* rank,
+                                 hipStream_t st) {
+  HRIEMO_CHECK(capacity >= 1 && C >= 1 && C <= 65535, "stats_rank: capacity = %d (>= 1), C = %d (1 .. 65535)", capacity, C);
+  HRIEMO_CHECK(probs != nullptr && truth != nullptr && counters != nullptr && rank != nullptr, "stats_rank: probs, truth, counters and rank are required");
+  HRIEMO_CHECK(((uintptr_t)counters % 4) == 0 && ((uintptr_t)rank % 4) == 0 && ((uintptr_t)probs % 4) == 0,
+               "stats_rank: probs / counters / rank are not 4-byte aligned");
+  hipLaunchKernelGGL(stats_rank_kernel, dim3((capacity + AUC_TILE - 1) / AUC_TILE, C), dim3(256), 0, st, probs, truth, capacity, counters, rank);
+  HRIEMO_LAUNCH_CHECK("stats_rank_kernel");
+  return 0;
+}
+
+extern "C" int hriemo_stats_confusion(const float* logits, const long long* labels, const float* loss, int skip_nonfinite,
+                                      const int* n_valid, int B, int C, int* cm, hipStream_t st) {
+  HRIEMO_CHECK(B >= 1 && C >= 1 && C <= CONFUSION_MAX_CLASSES, "stats_confusion: B = %d (>= 1), C = %d (1 .. %d)", B, C, CONFUSION_MAX_CLASSES);
+  HRIEMO_CHECK(logits != nullptr && labels != nullptr && loss != nullptr && cm != nullptr, "stats_confusion: logits, labels, loss and cm are required");
+  HRIEMO_CHECK(((uintptr_t)n_valid % 4) == 0 && ((uintptr_t)cm % 4) == 0, "stats_confusion: n_valid / cm are not 4-byte aligned");
+  hipLaunchKernelGGL(stats_confusion_kernel, dim3(1), dim3(256), 0, st, logits, labels, loss, skip_nonfinite, n_valid, B, C, cm);
+  HRIEMO_LAUNCH_CHECK("stats_confusion_kernel");
   return 0;
 }

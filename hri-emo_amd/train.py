@@ -72,6 +72,8 @@ def mosei_step_loss(logits, beta, targets, pos_weight=None, beta_entropy=0.0, gr
 SWEEP = tuple(float(t) for t in np.linspace(0.05, 0.95, 19))        # calibrate_thresholds' grid (:165)
 _MAX_THRESHOLDS = 64          # STATS_MAX_THRESHOLDS of csrc/metrics.hip
 _CTR = ("cursor", "n_samples", "n_batches", "n_skipped", "n_correct", "n_nonfinite", "overflow")
+_MAX_CONFUSION_CLASSES = 64   # CONFUSION_MAX_CLASSES of csrc/metrics.hip
+_IGNORE_INDEX = -100          # nn.CrossEntropyLoss's ignore_index: such a sample has no label
 
 
 def thresholds_up(thresholds):
@@ -89,6 +91,23 @@ def _f1(tp, fp, fn):
     """2 tp / (2 tp + fp + fn) in float64, 0 where the denominator is 0 (f1_score(..., zero_division=0))"""
     tp, den = np.asarray(tp, dtype=np.float64), 2.0 * np.asarray(tp, dtype=np.float64) + np.asarray(fp, dtype=np.float64) + np.asarray(fn, dtype=np.float64)
     return np.where(den > 0, 2.0 * tp / np.where(den > 0, den, 1.0), 0.0)
+
+
+def _calibrate(sweep_counts, sweep, per_class):
+    """calibrate_thresholds' choice from the sweep's integers [C, S, 3]: per class the FIRST grid point of strictly greater F1 (start
+    0.5 / -1) and the F1 there -> (thresholds float32 [C], F1 float64 [C]); without a sweep: 0.5 and the F1 at 0.5.  The one place
+    the selection rule lives: result() and per_class_table() both read it."""
+    C, S = sweep_counts.shape[0], sweep_counts.shape[1]
+    f1_sweep = _f1(sweep_counts[:, :, 0], sweep_counts[:, :, 1], sweep_counts[:, :, 2])          # [C, S]
+    chosen, f1_cal = np.full(C, 0.5, dtype=np.float32), np.zeros(C)
+    for c in range(C):
+        best, best_t = -1.0, 0.5
+        for s in range(S):
+            if f1_sweep[c, s] > best:
+                best, best_t = float(f1_sweep[c, s]), sweep[s]
+        chosen[c] = best_t
+        f1_cal[c] = best if S > 0 else per_class[c]
+    return chosen, f1_cal
 
 
 class EpochStats:
@@ -119,26 +138,47 @@ class EpochStats:
     counts at the chosen grid points, while the reference compares a second time against those rounded values.  The two differ
     only where a probability lies within one fp32 ulp of a grid threshold.
 
+    confusion=True (single_label only): update() enqueues hriemo_stats_confusion right behind hriemo_stats_update -- same n_valid,
+    loss and skip_nonfinite -- and result() gains confusion (int64 [C, C], rows = label, columns = first argmax), n_ignored (labels
+    equal to the criterion's ignore_index -100), per_class_f1, per_class_recall, macro_f1 (over the classes that occur as a label or
+    a prediction: f1_score(average="macro")), weighted_f1 and uar (mean recall over the classes with support), all float64 from the
+    integers with zero_division = 0; the matrix lives in the buffer result() reads back, so it stays ONE read-back.  ValueError if a
+    label was neither in [0, C) nor -100.  What the four-class trainers report (train_text_baseline.py:59-61,
+    linear_probe_baseline.py:132-133).
+
+    ranking() / pr_curve(c) / roc_curve(c) / per_class_table() (multi_label): average precision and the precision-recall and ROC
+    curves of the reporting layer (tools/mosei_export_per_class_metrics.py, scripts/infer/mosei_plot_metrics.py) from two integers
+    per logged sample (hriemo_stats_rank), ratios in float64 on the host; see ranking().
+
     CPU tensors take the same definitions in plain torch / numpy (the log lives in host memory).  Statistics are per rank."""
 
-    def __init__(self, num_outputs, capacity, kind="multi_label", skip_nonfinite=False, device="cuda"):
+    def __init__(self, num_outputs, capacity, kind="multi_label", skip_nonfinite=False, device="cuda", confusion=False):
         if kind not in ("multi_label", "single_label"):
             raise ValueError("EpochStats: kind is 'multi_label' or 'single_label'")
         if int(num_outputs) < 1 or int(capacity) < 1:
             raise ValueError("EpochStats: num_outputs and capacity are positive")
+        if confusion and kind != "single_label":
+            raise ValueError("EpochStats: confusion=True needs kind='single_label': a confusion matrix is defined for one label per sample "
+                             "(the multi-label kind reports tp / fp / fn per class)")
+        if confusion and int(num_outputs) > _MAX_CONFUSION_CLASSES:
+            raise ValueError(f"EpochStats: confusion=True takes at most {_MAX_CONFUSION_CLASSES} classes")
+        self.confusion = bool(confusion)
         self.C, self.capacity, self.kind, self.skip_nonfinite = int(num_outputs), int(capacity), kind, bool(skip_nonfinite)
         self.device = torch.device(device)
         self.multi = kind == "multi_label"
         C, dev = self.C, self.device
         self.tiles = (self.capacity + 255) // 256            # hriemo_stats_auc_tiles
         # everything result() reads back is ONE buffer: counters int32[8] | sums float64[4] | npn int32[C, 2] | counts
-        # int32[C, 64, 3] | auc partials uint64[C, tiles]; every part starts 8-byte aligned
+        # int32[C, 64, 3] | auc partials uint64[C, tiles] | cm int32[C * C + 2] (confusion=True); every part starts 8-byte aligned
         o_npn = 64
         o_cnt = o_npn + 8 * C
         o_auc = o_cnt + 4 * C * _MAX_THRESHOLDS * 3
-        self._small = torch.zeros(o_auc + 8 * C * self.tiles, dtype=torch.uint8, device=dev)
-        self._parts = (o_npn, o_cnt, o_auc)
+        o_cm = o_auc + 8 * C * self.tiles
+        self._small = torch.zeros(o_cm + (4 * (C * C + 2) if self.confusion else 0), dtype=torch.uint8, device=dev)
+        self._parts = (o_npn, o_cnt, o_auc, o_cm)
         self.counters, self.sums, self._npn, self._counts, self._partial = self._views(self._small)
+        self.cm = self._cm_view(self._small)         # {confusion matrix [C, C] (row = label), n_ignored, n_bad}, or None
+        self._rank = None                            # int32 [C, 2, capacity], allocated by the first ranking()
         if self.multi:
             self.probs = torch.zeros(C, self.capacity, dtype=torch.float32, device=dev)
             self.truth = torch.zeros(C, self.capacity, dtype=torch.uint8, device=dev)
@@ -147,13 +187,19 @@ class EpochStats:
         self._thr = torch.zeros(_MAX_THRESHOLDS, dtype=torch.float32, device=dev)
 
     def _views(self, buf):
-        o_npn, o_cnt, o_auc = self._parts
+        o_npn, o_cnt, o_auc, o_cm = self._parts
         return (buf[:32].view(torch.int32), buf[32:64].view(torch.float64), buf[o_npn:o_cnt].view(torch.int32).view(self.C, 2),
-                buf[o_cnt:o_auc].view(torch.int32), buf[o_auc:].view(torch.int64).view(self.C, self.tiles))
+                buf[o_cnt:o_auc].view(torch.int32), buf[o_auc:o_cm].view(torch.int64).view(self.C, self.tiles))
+
+    def _cm_view(self, buf):
+        return buf[self._parts[3]:].view(torch.int32) if self.confusion else None
 
     def reset(self):
-        """a new epoch: counters and sums to zero (the log needs no clearing: only entries in front of the cursor are ever read)"""
+        """a new epoch: counters, sums and the confusion matrix to zero (the log needs no clearing: only entries in front of the
+        cursor are ever read)"""
         self._small[:64].zero_()
+        if self.confusion:
+            self.cm.zero_()
 
     # ---- update
     def _check(self, logits, beta, targets, loss):
@@ -184,6 +230,8 @@ class EpochStats:
         _lib.call("hriemo_stats_update", p(x), p(y) if self.multi else None, None if self.multi else p(y), p(lv), float(loss_scale),
                   p(bt), bt.numel() // B if bt is not None else 0, p(nv), B, self.C, int(self.skip_nonfinite), p(self.probs), p(self.truth),
                   self.capacity, p(self.counters), p(self.sums), _ops._stream())
+        if self.confusion:
+            _lib.call("hriemo_stats_confusion", p(x), p(y), p(lv), int(self.skip_nonfinite), p(nv), B, self.C, p(self.cm), _ops._stream())
 
     def _update_cpu(self, logits, beta, targets, loss, n_valid, loss_scale, B):
         import math
@@ -207,7 +255,14 @@ class EpochStats:
             else:
                 ctr[6] = 1
         else:
-            ctr[4] += int((x.argmax(dim=1) == targets.detach()[:nv]).sum())
+            pred, lab = x.argmax(dim=1).numpy(), targets.detach()[:nv].to(torch.int64).numpy()
+            ctr[4] += int((pred == lab).sum())
+            if self.confusion:
+                cm, C = self.cm.numpy(), self.C
+                ok = (lab >= 0) & (lab < C)
+                np.add.at(cm, lab[ok] * C + pred[ok], 1)
+                cm[C * C] += int((lab == _IGNORE_INDEX).sum())
+                cm[C * C + 1] += int((~ok & (lab != _IGNORE_INDEX)).sum())
         ctr[1] += nv
         ctr[2] += 1
         self.sums[0] += lv * loss_scale * nv
@@ -249,9 +304,11 @@ class EpochStats:
                               p(self._counts), _ops._stream())
                     _lib.call("hriemo_stats_auc", p(self.probs), p(self.truth), self.capacity, self.C, p(self.counters), p(self._partial),
                               p(self._npn), _ops._stream())
-            ctr, sums, npn, counts, partial = self._views(self._small.cpu())          # the epoch's one read-back
+            host = self._small.cpu()                                                  # the epoch's one read-back
+            ctr, sums, npn, counts, partial = self._views(host)
+            cm = self._cm_view(host)
         else:
-            ctr, sums = self.counters, self.sums
+            ctr, sums, cm = self.counters, self.sums, self.cm
         ctr, sums = [int(v) for v in ctr.tolist()], [float(v) for v in sums.tolist()]
         out = dict(zip(_CTR[1:5], ctr[1:5]))
         n = out["n_samples"]
@@ -259,6 +316,8 @@ class EpochStats:
         out["accuracy"] = out["n_correct"] / n if n > 0 else 0.0
         out["mean_beta"] = sums[1] / sums[2] if sums[2] > 0 else 0.0
         if not self.multi:
+            if self.confusion:
+                out.update(self._confusion_metrics(cm.numpy().astype(np.int64)))
             return out
         if ctr[6]:
             raise RuntimeError(f"EpochStats: the log of {self.capacity} samples overflowed ({n} samples were offered); size capacity for the epoch")
@@ -274,20 +333,140 @@ class EpochStats:
         per_class = _f1(tp, fp, fn)
         both = (npn[:, 0] > 0) & (npn[:, 1] > 0)
         auc = two_u[both].astype(np.float64) / (2.0 * npn[both, 0].astype(np.float64) * npn[both, 1].astype(np.float64))
-        f1_sweep = _f1(counts[:, 1:, 0], counts[:, 1:, 1], counts[:, 1:, 2])          # [C, S - 1]
-        chosen, f1_cal = np.full(self.C, 0.5, dtype=np.float32), np.zeros(self.C)
-        for c in range(self.C):
-            best, best_t = -1.0, 0.5
-            for s in range(S - 1):
-                if f1_sweep[c, s] > best:
-                    best, best_t = float(f1_sweep[c, s]), sweep[s]
-            chosen[c] = best_t
-            f1_cal[c] = best if S > 1 else per_class[c]
+        chosen, f1_cal = _calibrate(counts[:, 1:], sweep, per_class)
         out.update(n_logged=n_log, micro_f1=float(_f1(tp.sum(), fp.sum(), fn.sum())), macro_f1=float(per_class.mean()),
                    per_class_f1=per_class, macro_auc=float(auc.mean()) if auc.size else 0.0, calibrated_thresholds=chosen,
                    macro_f1_calibrated=float(f1_cal.mean()), tp=tp, fp=fp, fn=fn, sweep_counts=counts[:, 1:], auc_2u=two_u,
                    n_pos=npn[:, 0], n_neg=npn[:, 1])
         return out
+
+    # ---- single-label: the confusion matrix
+    def _confusion_metrics(self, cm):
+        """the keys result() gains with confusion=True, in float64 from the integers cm [C * C + 2] (zero_division = 0 throughout)"""
+        C = self.C
+        n_ignored, n_bad = int(cm[C * C]), int(cm[C * C + 1])
+        if n_bad:
+            raise ValueError(f"EpochStats: {n_bad} labels outside [0, {C}) that are not the ignore_index {_IGNORE_INDEX}")
+        m = cm[:C * C].reshape(C, C).copy()
+        tp, support, predicted = np.diag(m), m.sum(axis=1), m.sum(axis=0)
+        f1 = _f1(tp, predicted - tp, support - tp)
+        recall = np.where(support > 0, tp / np.where(support > 0, support, 1).astype(np.float64), 0.0)
+        present = (support + predicted) > 0              # f1_score(labels=None): the classes that occur as a label or a prediction
+        n = float(support.sum())
+        return {"confusion": m, "n_ignored": n_ignored, "per_class_f1": f1, "per_class_recall": recall,
+                "macro_f1": float(f1[present].mean()) if present.any() else 0.0,
+                "weighted_f1": float((f1 * support).sum() / n) if n > 0 else 0.0,
+                "uar": float(recall[support > 0].mean()) if (support > 0).any() else 0.0}
+
+    # ---- multi-label: ranking metrics
+    def _ranks_cpu(self, n):
+        """ge_pos / ge_neg [C, n] of the first n log entries by sorting: the kernel's definition (hriemo_stats_rank) in numpy"""
+        pr, t = self.probs[:, :n].numpy(), self.truth[:, :n].numpy() != 0
+        ge = np.zeros((2, self.C, n), dtype=np.int64)
+        for c in range(self.C):
+            for plane, kind in enumerate((t[c], ~t[c])):
+                q = np.sort(pr[c][kind])
+                ge[plane, c] = q.size - np.searchsorted(q, pr[c], "left")
+        return ge[0], ge[1]
+
+    def ranking(self):
+        """The ranking metrics of the reference's reporting layer (tools/mosei_export_per_class_metrics.py,
+        scripts/infer/mosei_plot_metrics.py) from integers: one launch (hriemo_stats_rank) plus hriemo_stats_auc over the log, then
+        the read-back of the small block, the ranks and the first n_logged columns of the log.  multi_label only.  Returns
+        ge_pos, ge_neg (int64 [C, n]: per logged sample the number of positives / negatives of its class with p_j >= p_i, itself
+        included), probs (fp32 [C, n]), truth (bool [C, n]), n_pos, n_neg, per_class_auc (float64 [C], nan where a class lacks one
+        kind), macro_auc (result()'s), average_precision (float64 [C]: the mean over the positives of ge_pos / (ge_pos + ge_neg) --
+        sklearn's average_precision_score, ties included; 0.0 for a class without positives, as mosei_plot_metrics.py:47,135) and
+        macro_ap (mean over the classes with a positive, 0.0 without one).  RuntimeError / ValueError as result()."""
+        if not self.multi:
+            raise ValueError("EpochStats.ranking: ranking metrics belong to the multi_label kind (single_label keeps no log)")
+        C = self.C
+        if self.device.type == "cuda":
+            from . import _lib, _ops
+            p = _ops._p
+            with torch.cuda.device(self.device):
+                if self._rank is None:
+                    self._rank = torch.zeros(C, 2, self.capacity, dtype=torch.int32, device=self.device)
+                _lib.call("hriemo_stats_rank", p(self.probs), p(self.truth), self.capacity, C, p(self.counters), p(self._rank), _ops._stream())
+                _lib.call("hriemo_stats_auc", p(self.probs), p(self.truth), self.capacity, C, p(self.counters), p(self._partial),
+                          p(self._npn), _ops._stream())
+            ctr, _, npn, _, partial = self._views(self._small.cpu())
+        else:
+            ctr = self.counters
+        ctr = [int(v) for v in ctr.tolist()]
+        if ctr[6]:
+            raise RuntimeError(f"EpochStats: the log of {self.capacity} samples overflowed ({ctr[1]} samples were offered); size capacity for the epoch")
+        if ctr[5]:
+            raise ValueError(f"EpochStats: {ctr[5]} non-finite logits were logged; ranking metrics of this epoch are undefined")
+        n = min(max(ctr[0], 0), self.capacity)
+        if self.device.type == "cuda":
+            rank = self._rank[:, :, :n].cpu().numpy().astype(np.int64)
+            ge_pos, ge_neg = rank[:, 0], rank[:, 1]
+            two_u, npn = partial.numpy().sum(axis=1), npn.numpy().astype(np.int64)
+            probs, truth = self.probs[:, :n].cpu().numpy(), self.truth[:, :n].cpu().numpy() != 0
+        else:
+            ge_pos, ge_neg = self._ranks_cpu(n)
+            _, two_u, npn = self._integers_cpu(np.zeros(1, dtype=np.float32), n)
+            probs, truth = self.probs[:, :n].numpy().copy(), self.truth[:, :n].numpy() != 0
+        n_pos, n_neg = npn[:, 0], npn[:, 1]
+        both = (n_pos > 0) & (n_neg > 0)
+        auc = np.full(C, np.nan)
+        auc[both] = two_u[both].astype(np.float64) / (2.0 * n_pos[both].astype(np.float64) * n_neg[both].astype(np.float64))
+        ap = np.zeros(C)
+        for c in range(C):
+            if n_pos[c] > 0:
+                gp, gn = ge_pos[c][truth[c]].astype(np.float64), ge_neg[c][truth[c]].astype(np.float64)
+                ap[c] = float((gp / (gp + gn)).sum() / float(n_pos[c]))
+        return {"ge_pos": ge_pos, "ge_neg": ge_neg, "probs": probs, "truth": truth, "n_pos": n_pos, "n_neg": n_neg, "n_logged": n,
+                "per_class_auc": auc, "macro_auc": float(auc[both].mean()) if both.any() else 0.0, "average_precision": ap,
+                "macro_ap": float(ap[n_pos > 0].mean()) if (n_pos > 0).any() else 0.0}
+
+    @staticmethod
+    def _distinct(rk, c):
+        """per distinct probability of class c, ascending: (probability, ge_pos, ge_neg) -- tied samples share their two counts"""
+        thr, first = np.unique(rk["probs"][c], return_index=True)
+        return thr, rk["ge_pos"][c][first].astype(np.float64), rk["ge_neg"][c][first].astype(np.float64)
+
+    def pr_curve(self, c, ranking=None):
+        """(precision, recall, thresholds) of class c in sklearn.metrics.precision_recall_curve's layout: one point per distinct
+        probability in ascending order, precision = ge_pos / (ge_pos + ge_neg), recall = ge_pos / n_pos, then the point (1, 0).
+        Pure host arithmetic on a ranking() result (taken now when none is passed).  ValueError for a class without positives."""
+        rk = self.ranking() if ranking is None else ranking
+        if int(rk["n_pos"][c]) == 0:
+            raise ValueError(f"EpochStats.pr_curve: class {c} has no positive sample; its recall is undefined")
+        thr, gp, gn = self._distinct(rk, c)
+        return np.append(gp / (gp + gn), 1.0), np.append(gp / float(rk["n_pos"][c]), 0.0), thr
+
+    def roc_curve(self, c, ranking=None):
+        """(fpr, tpr, thresholds) of class c in sklearn.metrics.roc_curve(..., drop_intermediate=False)'s layout: the point (0, 0)
+        with threshold inf, then one point per distinct probability in descending order, fpr = ge_neg / n_neg, tpr = ge_pos / n_pos.
+        Pure host arithmetic on a ranking() result.  ValueError for a class that lacks positives or negatives."""
+        rk = self.ranking() if ranking is None else ranking
+        if int(rk["n_pos"][c]) == 0 or int(rk["n_neg"][c]) == 0:
+            raise ValueError(f"EpochStats.roc_curve: class {c} has {int(rk['n_pos'][c])} positives and {int(rk['n_neg'][c])} negatives; "
+                             "the curve needs both kinds")
+        thr, gp, gn = self._distinct(rk, c)
+        return (np.append(0.0, gn[::-1] / float(rk["n_neg"][c])), np.append(0.0, gp[::-1] / float(rk["n_pos"][c])),
+                np.append(np.inf, thr[::-1].astype(np.float64)))
+
+    def per_class_table(self, names=None, thresholds=None):
+        """The reference's per-class table (tools/mosei_export_per_class_metrics.py:10-17) from one result(thresholds) and one
+        ranking(): a list of dicts class_, prevalence (n_pos / n), auc (nan where a class lacks one kind), auprc (average
+        precision), f1_raw (p >= 0.5), f1_cal (the sweep's F1 at the chosen grid point, as macro_f1_calibrated), thr."""
+        names = [str(c) for c in range(self.C)] if names is None else list(names)
+        if len(names) != self.C:
+            raise ValueError(f"EpochStats.per_class_table: {len(names)} names for {self.C} classes")
+        res, rk = self.result(thresholds), self.ranking()
+        sweep = np.asarray(SWEEP if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        _, f1_cals = _calibrate(res["sweep_counts"], sweep, res["per_class_f1"])           # result()'s own rule on result()'s integers
+        n = max(1, res["n_logged"])
+        rows = []
+        for c in range(self.C):
+            f1_cal = float(f1_cals[c])
+            rows.append({"class_": names[c], "prevalence": float(res["n_pos"][c]) / n, "auc": float(rk["per_class_auc"][c]),
+                         "auprc": float(rk["average_precision"][c]), "f1_raw": float(res["per_class_f1"][c]), "f1_cal": f1_cal,
+                         "thr": float(res["calibrated_thresholds"][c])})
+        return rows
 
 
 # ------------------------------------------------------------------------------------------------------------------ prediction log

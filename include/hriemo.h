@@ -446,7 +446,25 @@ int hriemo_fusion_loss_ce_n(const float* logits, const long long* labels, const 
  * threshold rounded UP to fp32 and the decisions are the same.
  * hriemo_stats_auc: per class, 2U = sum over (positive i, negative j) of 2 [p_i > p_j] + [p_i == p_j], as partial sums
  * partial uint64 [C, hriemo_stats_auc_tiles(capacity)] (256 rows i per tile; every tile is stored, tiles past the cursor as 0;
- * the caller adds them), and npn int32 [C, 2] = {n_pos, n_neg}.  AUC = 2U / (2 n_pos n_neg), formed on the host. */
+ * the caller adds them), and npn int32 [C, 2] = {n_pos, n_neg}.  AUC = 2U / (2 n_pos n_neg), formed on the host.
+ * hriemo_stats_rank: the ranking metrics of the reference's reporting layer (tools/mosei_export_per_class_metrics.py:10-17,
+ * scripts/infer/mosei_plot_metrics.py:44-80,130-148: average precision, precision-recall and ROC curves) as integers.  With
+ * n = clamp(cursor, 0, capacity), rank int32 [C, 2, capacity]: for i < n, rank[c, 0, i] = the number of j < n with truth[c, j] != 0
+ * and probs[c, j] >= probs[c, i], rank[c, 1, i] the same over truth[c, j] == 0; entry i counts itself in the plane of its own kind.
+ * Elements n <= i < capacity of both planes are stored as 0: every element of rank is written by every call.  Log entries at or
+ * past the cursor are never read (they may hold NaN); a NaN probs[c, i] compares false with everything and gets 0 / 0.  No sort, no
+ * floating-point sum and no atomics on the device; the host forms precision = ge_pos / (ge_pos + ge_neg), recall = ge_pos / n_pos,
+ * fpr = ge_neg / n_neg at every distinct probability, and average precision = sum over the positives of their precision / n_pos.
+ * Refused (non-zero, nothing launched): capacity < 1, C < 1 or C > 65535 (the grid's second dimension), a NULL pointer, probs /
+ * counters / rank not 4-byte aligned.
+ * hriemo_stats_confusion: ONE block of 256, meant to be recorded directly behind hriemo_stats_update of the same single-label step
+ * (stream order makes it the only writer of cm).  cm int32 [C * C + 2], owned by the caller, zeroed to reset: the confusion matrix
+ * (row = label, column = prediction), then {n_ignored, n_bad}.  nv = clamp(*n_valid, 1, B) (NULL: B); rows b >= nv are never read.
+ * skip_nonfinite != 0 and a NaN / Inf loss[0]: cm is left untouched (the batch hriemo_stats_update only counts in n_skipped).
+ * Otherwise, for each of the first nv samples, pred = the first maximal logit's index (a NaN counts as maximal: the rule of
+ * hriemo_stats_update) and cm[label * C + pred] += 1 for 0 <= label < C; label == -100 (the criterion's ignore_index): cm[C * C]
+ * += 1; any other label: cm[C * C + 1] += 1, and nothing is indexed with it.  Refused (non-zero, nothing launched): B < 1, C < 1
+ * or C > 64, NULL logits / labels / loss / cm, n_valid / cm not 4-byte aligned. */
 int hriemo_stats_update(const float* logits, const float* targets, const long long* labels, const float* loss, float loss_scale,
                         const float* beta, int beta_per_sample, const int* n_valid, int B, int C, int skip_nonfinite,
                         float* probs, unsigned char* truth, int capacity, int* counters, double* sums, hriemo_stream_t stream);
@@ -455,6 +473,10 @@ int hriemo_stats_counts(const float* probs, const unsigned char* truth, int capa
 int hriemo_stats_auc_tiles(int capacity);
 int hriemo_stats_auc(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters,
                      unsigned long long* partial, int* npn, hriemo_stream_t stream);
+int hriemo_stats_rank(const float* probs, const unsigned char* truth, int capacity, int C, const int* counters, int* rank,
+                      hriemo_stream_t stream);
+int hriemo_stats_confusion(const float* logits, const long long* labels, const float* loss, int skip_nonfinite, const int* n_valid,
+                           int B, int C, int* cm, hriemo_stream_t stream);
 /* Prediction log in device memory (csrc/metrics.hip): the products of the reference's inference driver
  * (scripts/infer/mosei_eval_infer.py: {split}_y_prob.npy, {split}_beta_mean.npy) without targets and without a read-back per batch.
  * State, owned by the caller, counters zeroed to reset:
